@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native X-as-Supervision training step (BASELINE.json north_star).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One "step" = the reference's hot-loop body (train.py:160-190): discriminator forward/backward/Adam, then
@@ -9,10 +9,18 @@ generator forward/backward/Adam, on one synthetic batch of the workload HM36_Mul
 256x256, multi-hypothesis detector), B = 32 samples per GPU, fp32, inputs resident in HBM.  One sample
 = 4 real + 4 pseudo images = 8 input images; the step runs 12 detector forwards and 8 detector backwards
 per sample.  Rank 0 prints ONE JSON line (metric = images/s over the whole job).
+
+A plain run sets up, warms up, times K steps and prints the headline.  --full adds everything else, after the
+timed region and untimed by the headline: HIP-event kernel times of the last timed step (roofline), an extra step
+without stream overlap, the exact-fp32 and dedupe figures, the precision cross-checks, the data-parallel exchange
+figures and replica checksums (N > 1) and the CPU oracle baseline.  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
+import math
 import os
+import re
 import sys
 import time
 
@@ -161,6 +169,58 @@ def train_step_variant_check(step, x, model, disc, opt_det, opt_disc, xl, precis
             'grad_arena_rel_diff': gr, 'grad_arena_norm_f32': {k: float(v.double().norm()) for k, v in gb.items()}}
 
 
+DUMP_BYTES = 63 * 2**20      # --dump-outputs: array data at most (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(path, result, opt_det, opt_disc, seed=0):
+    """--dump-outputs: what the last timed step hands its caller - its return values (loss_disc, loss_kp, total, info) and the
+    parameter arenas the two Adam updates left - as <path>/<name>.npy, float64 where the tensor is float64, else float32.
+    The budget of DUMP_BYTES is shared out smallest first; a tensor larger than its share is written as a fixed sample of its
+    flattened elements, at sorted indices drawn from a CPU generator seeded with (seed, element count): the same positions in
+    every run and every build.  -> {name: (shape, elements written)}."""
+    import numpy as np
+    loss_disc, loss_kp, total, info = result
+    arrays = []
+
+    def add(name, v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                add('%s.%s' % (name, k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, e in enumerate(v):
+                add('%s.%d' % (name, i), e)
+        elif isinstance(v, torch.Tensor):
+            arrays.append((re.sub(r'[^A-Za-z0-9_.-]', '_', name), v.detach()))
+        elif isinstance(v, (bool, int, float)):
+            arrays.append((re.sub(r'[^A-Za-z0-9_.-]', '_', name), torch.tensor(float(v), dtype=torch.float64)))
+
+    add('loss_disc', loss_disc)
+    add('loss_kp', loss_kp)
+    add('total', total)
+    add('info', info)
+    add('params.detector', opt_det.param_arena)
+    if opt_disc is not None:
+        add('params.discriminator', opt_disc.param_arena)
+    os.makedirs(path, exist_ok=True)
+    budget, left, written = DUMP_BYTES, len(arrays), {}
+    for name, t in sorted(arrays, key=lambda a: a[1].numel()):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        size = 8 if dt == torch.float64 else 4
+        n = t.numel()
+        k = min(n, budget // left // size)
+        flat = t.reshape(-1)
+        if k < n:
+            g = torch.Generator().manual_seed(seed * 1000003 + n)
+            idx = torch.randint(0, n, (k,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.to(dt).cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a if k < n else a.reshape(tuple(t.shape)))
+        written[name] = (tuple(t.shape), k)
+        budget -= k * size
+        left -= 1
+    return written
+
+
 def launch_ranks(n):
     """Run this script as n ranks of a single-node torchrun job (child process; no exec, no GPU use here)."""
     import socket
@@ -207,7 +267,16 @@ def main():
     ap.add_argument('--ref-n1', type=float, default=None,
                     help='samples/s of the SAME build at N = 1 (a previous run of this script): adds comm.per_rank_over_n1 to the line')
     ap.add_argument('--shape-report', default=None, help='write a per-conv-shape timing table to this file')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline, after the timed region: per-kernel / roofline figures (HIP events in the '
+                         'last timed step, one extra step without stream overlap), the exact-fp32 and dedupe figures, the precision '
+                         'cross-checks, the exchange figures and replica checksums (N > 1) and the CPU oracle baseline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed (losses, info, updated parameters; a fixed sample where large, '
+                         '64 MB at most) as DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full and (args.shape_report or args.ref_n1):
+        ap.error('--shape-report and --ref-n1 report figures of --full runs: add --full')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: this parent has not touched the GPU; it starts N fresh ranks (one per GPU, RCCL)
@@ -264,17 +333,21 @@ def main():
         torch.cuda.synchronize()
         log('warmup step %d: %.1f ms' % (i, (time.perf_counter() - tw) * 1e3))
     sync()
-    # HIP events bracket every conv-family launch of the LAST timed step (1 818 launches): bracketing all K steps cost
+    # --full: HIP events bracket every conv-family launch of the LAST timed step (1 818 launches): bracketing all K steps cost
     # ~4 % of the headline (two event packets per launch on the queue), one step costs < 1 %.
     from xas_amd.prof import CONV_ENTRIES
     HEAD = ('xas_head_softargmax_fwd', 'xas_head_softargmax_from_partials', 'xas_head_softargmax_bwd', 'xas_head_softargmax_bwd_amax')
     from xas_amd.prof import BN_ENTRIES
     timer = KernelTimer(CONV_ENTRIES + HEAD + BN_ENTRIES)
+    result = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         if i == args.steps - 1:
-            with timer:
-                step(x)
+            if args.full:
+                with timer:
+                    result = step(x)
+            else:
+                result = step(x)
         else:
             step(x)
     sync()
@@ -286,6 +359,44 @@ def main():
     dt = float(t.item())
     log('timed %d steps: %.1f ms/step' % (args.steps, dt / args.steps * 1e3))
     log('memory: peak allocated %.1f GB, reserved %.1f GB' % (torch.cuda.max_memory_allocated() / 2**30, torch.cuda.memory_reserved() / 2**30))
+    if args.dump_outputs and rank == 0 and result is not None:
+        written = dump_outputs(args.dump_outputs, result, opt_det, opt_disc)
+        log('outputs of the last timed step: %d arrays in %s (%d sampled)'
+            % (len(written), args.dump_outputs, sum(1 for s, k in written.values() if k < math.prod(s))))
+    result = None
+
+    per_sample = IMAGES_PER_SAMPLE['MPI' if args.workload.startswith('MPI') else 'HM36']
+    samples = world * args.batch * args.steps
+    line = {
+        'metric': 'images/sec %s 256px bs%d (full disc+gen training step)' % (args.workload, args.batch),
+        'value': samples * per_sample / dt, 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None,
+        'dtype': {'f32': 'f32 (exact fp32 MFMA)', 'bf16x6': 'f32 (bf16x6 split, f32 accumulate)',
+                  'f16x3': 'f32 (f16x3 split: every fp32 operand as two fp16 pieces, three products; f32 accumulate)',
+                  'bf16': 'bf16 products, f32 accumulate (variant: NOT fp32 accurate, not the headline)'}[args.precision],
+        'data': 'synthetic',
+        'config': {'workload': args.workload, 'batch_per_gpu': args.batch, 'cameras': len(cams),
+                   'image': '256x256', 'images_per_sample': per_sample, 'parallelism': 'dp%d' % world,
+                   'samples_per_s': samples / dt, 'ranks': world,
+                   'samples_per_s_per_rank': samples / dt / world,
+                   'detector_forwards_per_s': samples * (2 if args.dedupe else 3) * len(cams) / dt,
+                   'precision': args.precision,
+                   'dedupe': bool(args.dedupe), 'full': bool(args.full)},
+    }
+    if args.full:
+        full_figures(args, line, dt, rank, world, dev, model, disc, opt_det, opt_disc, step, x, cams, timer, timed_steps, sync, log)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_figures(args, line, dt, rank, world, dev, model, disc, opt_det, opt_disc, step, x, cams, timer, timed_steps, sync, log):
+    """--full: every figure and check beside the headline, after the timed region (untimed by it); adds to `line` on rank 0."""
+    from xas_amd import _lib as _xl
+    from xas_amd.prof import KernelTimer
 
     # N > 1: one extra, UNTIMED step with the data-parallel exchanges instrumented (xas_amd/dp.py comm_stats): what the step waits
     # for - the exposed part of the gradient buckets, the host-visible time of the SyncBatchNorm exchanges - and what it sends
@@ -432,24 +543,11 @@ def main():
                         ':f16x3': 'igemm_x6_kernel<.,.,.,2> / igemm_x6t_kernel<.,.,2> (fwd / dgrad) + wgrad_x6_kernel<.,.,2> / wgrad_x6t_kernel<.,2>: f16x3 MFMA implicit-GEMM conv family',
                         ':bf16': 'igemm_x6_kernel<.,.,.,1> + wgrad_x6_kernel<.,.,1>: bf16 MFMA implicit-GEMM conv family',
                         ':f32': 'igemm_buf_kernel + wgrad_buf_kernel (+ stem_fwd_kernel): exact-fp32 MFMA implicit-GEMM conv family'}
-        line = {
-            'metric': 'images/sec %s 256px bs%d (full disc+gen training step)' % (args.workload, args.batch),
-            'value': samples * per_sample / dt, 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None,
-            'dtype': {'f32': 'f32 (exact fp32 MFMA)', 'bf16x6': 'f32 (bf16x6 split, f32 accumulate)',
-                      'f16x3': 'f32 (f16x3 split: every fp32 operand as two fp16 pieces, three products; f32 accumulate)',
-                      'bf16': 'bf16 products, f32 accumulate (variant: NOT fp32 accurate, not the headline)'}[args.precision],
-            'data': 'synthetic',
-            'config': {'workload': args.workload, 'batch_per_gpu': args.batch, 'cameras': len(cams),
-                       'image': '256x256', 'images_per_sample': per_sample, 'parallelism': 'dp%d' % world,
-                       'samples_per_s': samples / dt, 'ranks': world,
-                       **({'param_checksum_per_rank': checksums, 'replicas_identical': all(c == checksums[0] for c in checksums)}
-                          if checksums else {}),
-                       'samples_per_s_per_rank': samples / dt / world,
-                       'detector_forwards_per_s': samples * (2 if args.dedupe else 3) * len(cams) / dt,
-                       'precision': args.precision,
-                       'dedupe': bool(args.dedupe), **({'variant_check': variant_check} if variant_check else {})},
+        if checksums:
+            line['config'].update(param_checksum_per_rank=checksums, replicas_identical=all(c == checksums[0] for c in checksums))
+        if variant_check:
+            line['config']['variant_check'] = variant_check
+        line.update({
             'roofline': {'bound': 'mfma', 'achieved': cl[dom]['achieved'], 'peak': cl[dom]['peak'], 'unit': 'TFLOP/s',
                          'frac': cl[dom]['frac'], 'traffic': traffic, 'traffic_source': tsrc,
                          'kernel': kernel_names[dom],
@@ -482,7 +580,7 @@ def main():
                          'families': {k: {'launches': v['launches'] // timed_steps, 'ms_per_step': v['ms'] / timed_steps,
                                           'tflops': (v['flops'] / (v['ms'] * 1e-3) / 1e12) if v['ms'] > 0 else 0.0}
                                       for k, v in summ.items()}},
-        }
+        })
         if comm is not None:
             if args.ref_n1:
                 comm['per_rank_over_n1'] = (samples / dt / world) / args.ref_n1
@@ -545,10 +643,6 @@ def main():
             log('timing the CPU oracle (B=2: 3 warm-up + 5 timed steps; B=8: 1 + 3) on %d host threads' % threads)
             line['cpu_baseline'] = cpu_baseline(args.workload, threads, B=2, warm=3, timed=5)
             line['cpu_baseline_b8'] = cpu_baseline(args.workload, threads, B=8, warm=1, timed=3)
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

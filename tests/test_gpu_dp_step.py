@@ -96,7 +96,7 @@ def test_bench_two_rank_rehearsal():
     from _ranks import release_gpu_memory
     release_gpu_memory()                     # the child needs the card's memory, not this process's cache
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--batch', '4', '--steps', '2',
-                        '--warmup', '1', '--f32-steps', '0', '--no-cpu-baseline', '--ref-n1', '100.0'], capture_output=True, text=True,
+                        '--warmup', '1', '--f32-steps', '0', '--no-cpu-baseline', '--ref-n1', '100.0', '--full'], capture_output=True, text=True,
                        timeout=200, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
