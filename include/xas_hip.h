@@ -27,18 +27,36 @@ extern "C" {
 #endif
 
 const char* xas_last_error(void);
-/* Kernel-variant selectors kept for coverage tests (tests/test_gpu_nn.py::test_conv_kernel_variants): 0 = the shipped
- * configuration; results agree to accumulation-order noise under every flag.  The first group only concerns the exact-fp32
- * kernels (XAS_PREC_F32).
- *   32      plain K-loop in fwd / dgrad instead of the pipelined one      524288  same for the weight gradient
- *   64      global-load fwd / dgrad kernels (the >= 2 GiB fallback)       128     same for the weight gradient
- *   8192    plain (not XCD-grouped) weight-gradient block order
- *   32768 / 65536 / 98304  column-reduce slab target 512 / 128 / 64       262144  86-VGPR build of the backward column sums
- * and two that concern the bf16-split kernels (tests/test_gpu_tap_kernels.py compares both settings):
- *   4194304 (bit 22)  no tap re-use kernels: stride-1 3x3 layers on the implicit-GEMM kernels (forward, data and weight gradient)
- *   8388608 (bit 23)  no 64 x 256 tiles for layers whose output channels are a multiple of 256
- *   16777216 (bit 24) the general weight-gradient kernel for the 7x7 stem instead of stem_wgrad_kernel
- *   33554432 (bit 25) the exact-fp32 stem forward kernel in the f16x3 mode too */
+/* Kernel-variant selectors (xas_set_tuning flags) kept for coverage tests and A/B runs: 0 = the shipped configuration; results
+ * agree to accumulation-order noise under every flag (tests/test_gpu_nn.py::test_conv_kernel_variants,
+ * tests/test_gpu_tap_kernels.py, tests/test_gpu_persistent_gemm.py).  xas_amd/_lib.py mirrors the table as TUNE_*. */
+enum {
+  /* not a caller's flag: the launcher of the bf16-split weight-gradient kernel sets it in the kernel's own copy of the flags */
+  XAS_TUNE_WGRAD_SPLIT_XCD = 1,              /* all tiles of a pixel split on one XCD (split count a multiple of 8) */
+  /* exact-fp32 kernels (XAS_PREC_F32) */
+  XAS_TUNE_PLAIN_KLOOP = 32,                 /* plain K-loop in fwd / dgrad instead of the pipelined one */
+  XAS_TUNE_GLOBAL_LOAD = 64,                 /* global-load fwd / dgrad kernels (the >= 2 GiB fallback) */
+  XAS_TUNE_WGRAD_GLOBAL_LOAD = 128,          /* the same for the weight gradient */
+  XAS_TUNE_WGRAD_ALT_ORDER = 8192,           /* the weight-gradient block order that is not shipped: plain instead of XCD-grouped
+                                              * (buffer-load kernel), one pixel split per XCD instead of plain (global-load kernel) */
+  XAS_TUNE_WGRAD_PLAIN_KLOOP = 524288,       /* plain K-loop in the weight gradient */
+  /* batch-norm / column-sum reductions */
+  XAS_TUNE_SLAB_SHIFT = 15,                  /* bits 15-16: slab target of the column reduction, (flags >> SHIFT) & MASK ... */
+  XAS_TUNE_SLAB_MASK = 3,
+  XAS_TUNE_SLAB_512 = 32768,                 /* ... 0 = 256 (shipped), 1 = 512, */
+  XAS_TUNE_SLAB_128 = 65536,                 /* 2 = 128, */
+  XAS_TUNE_SLAB_64 = 98304,                  /* 3 = 64 */
+  XAS_TUNE_COL_REDUCE_LEAN = 262144,         /* the <= 64-VGPR build of the backward column sums instead of the 86-VGPR one */
+  /* bf16-split kernels (XAS_PREC_F16X3 / XAS_PREC_BF16X6) */
+  XAS_TUNE_GENERAL_KERNELS = 1 << 22,        /* two effects: no tap re-use kernels (stride-1 3x3 layers on the implicit-GEMM kernels:
+                                              * forward, data and weight gradient) AND no streaming batch-norm apply / backward-apply
+                                              * kernels (every layer on the general ones) */
+  XAS_TUNE_NO_WIDE_TILES = 1 << 23,          /* no 64 x 256 tiles for layers whose output channels are a multiple of 256 */
+  XAS_TUNE_NO_STEM_WGRAD = 1 << 24,          /* the general weight-gradient kernel for the 7x7 stem instead of stem_wgrad_kernel */
+  XAS_TUNE_STEM_FWD_F32 = 1 << 25,           /* the exact-fp32 stem forward kernel in the f16x3 mode too */
+  XAS_TUNE_NO_X6P = 1 << 26,                 /* no persistent 1x1 kernel (igemm_x6p_kernel): one 64 x 256 tile per block */
+  XAS_TUNE_X6P_ANY_K = 1 << 27               /* persistent 1x1 kernel for every K, also above the build's XAS_X6P_MAX_K */
+};
 int xas_set_tuning(int flags);
 /* Arithmetic of the MFMA convolutions (forward, data gradient, weight gradient).  All modes keep fp32 activations, fp32
  * master weights and fp32 accumulation; they differ in how a product of two fp32 operands is formed:

@@ -72,6 +72,19 @@ def test_exports_and_signatures():
     assert sub * stride == ops_nn.AMAX_SLOT_FLOATS and stride * 4 == 128
 
 
+def test_tuning_flags_match_the_header():
+    """Every XAS_TUNE_* of the header has an equal _lib.TUNE_*, and the reverse."""
+    from xas_amd import _lib
+    src = open(os.path.join(ROOT, 'include', 'xas_hip.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    header = {}
+    for name, base, shift in re.findall(r'\bXAS_(TUNE_\w+)\s*=\s*(\d+)(?:\s*<<\s*(\d+))?\s*[,}\n]', src):
+        header[name] = int(base) << int(shift or 0)
+    mirror = {k: v for k, v in vars(_lib).items() if k.startswith('TUNE_')}
+    assert len(header) >= 10 and len(header) == len(re.findall(r'\bXAS_TUNE_\w+\s*=', src))
+    assert header == mirror
+
+
 def test_no_cpu_fallback():
     import torch
     from xas_amd import ops_head

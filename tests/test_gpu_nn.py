@@ -7,6 +7,7 @@ import torch.nn.functional as TF
 
 import inputs as gi
 from conftest import golden
+from xas_amd import _lib
 
 pytestmark = pytest.mark.gpu
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a))
@@ -60,13 +61,15 @@ def test_conv2d_fwd_bwd(n, cin, h, w, cout, k, stride, pad):
     assert rel(m.bias.grad, bc.grad) < 3e-6
 
 
-@pytest.mark.parametrize('tune,what', [(32, 'plain K-loop, buffer loads'), (64 | 128, 'global-load kernels (>= 2 GiB fallback)'),
-                                       (64 | 128 | 32, 'global-load kernels, plain loop'), (524288, 'plain weight-gradient loop'),
-                                       (8192, 'plain (not XCD-grouped) weight-gradient block order')])
+@pytest.mark.parametrize('tune,what', [
+    (_lib.TUNE_PLAIN_KLOOP, 'plain K-loop, buffer loads'),
+    (_lib.TUNE_GLOBAL_LOAD | _lib.TUNE_WGRAD_GLOBAL_LOAD, 'global-load kernels (>= 2 GiB fallback)'),
+    (_lib.TUNE_GLOBAL_LOAD | _lib.TUNE_WGRAD_GLOBAL_LOAD | _lib.TUNE_PLAIN_KLOOP, 'global-load kernels, plain loop'),
+    (_lib.TUNE_WGRAD_PLAIN_KLOOP, 'plain weight-gradient loop'),
+    (_lib.TUNE_WGRAD_ALT_ORDER, 'plain (not XCD-grouped) weight-gradient block order')])
 def test_conv_kernel_variants(tune, what):
     """Every conv kernel variant that stays in the library (fallbacks for tensors the 32-bit buffer offsets cannot
     address, the non-pipelined loops, the alternative block order) gives the same results as the shipped ones."""
-    from xas_amd import _lib
     try:
         _lib.query('xas_set_precision', _lib.PREC_F32)     # the selectors concern the exact-fp32 kernels
         _lib.query('xas_set_tuning', tune)
@@ -136,10 +139,10 @@ def test_linear(rows, cin, cout):
 @pytest.mark.parametrize('n,c,h,act,res', [(4, 64, 16, 1, False), (2, 256, 9, 1, True), (3, 32, 8, 2, False),
                                            (2, 2048, 4, 0, False), (2, 128, 7, 0, True)])
 def test_batch_norm_train(n, c, h, act, res, lean, request):
-    """lean: the <= 64-register build of the backward sums (tuning bit 18; shipped in r04, kept as a variant)."""
+    """lean: the <= 64-register build of the backward sums (TUNE_COL_REDUCE_LEAN; shipped in r04, kept as a variant)."""
     from xas_amd import layers as L
     from xas_amd._lib import query
-    query('xas_set_tuning', (1 << 18) if lean else 0)
+    query('xas_set_tuning', _lib.TUNE_COL_REDUCE_LEAN if lean else 0)
     request.addfinalizer(lambda: query('xas_set_tuning', 0))
     g = torch.Generator().manual_seed(c + h)
     x = torch.randn(n, c, h, h, generator=g) * 2 + 3            # mean >> 0 exercises the pivoted variance

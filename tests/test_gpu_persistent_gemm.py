@@ -2,19 +2,20 @@
 outputs in the f16x3 arithmetic - a block walks over several M-tiles and its loads run ahead into the next tile.
 
 Checked two ways through the C ABI: (1) against float64 evaluated from the operands on sampled outputs (the bar of every conv
-kernel, 3e-6); (2) BIT-IDENTICAL to igemm_x6_kernel<64, 256> (tuning bit 26 switches the persistent kernel off): same
+kernel, 3e-6); (2) BIT-IDENTICAL to igemm_x6_kernel<64, 256> (TUNE_NO_X6P switches the persistent kernel off): same
 fragments, same MFMA order, same epilogue - for tile counts that are / are not multiples of the tiles per block, one and several
 N-tiles, the norm-statistics epilogue and the accumulate-and-mask epilogue.
 reference: modules/integral_base_modules/resnet.py:16-47 (torchvision Bottleneck conv1 / conv3), deconv_head.py:34-35."""
 import pytest
 import torch
 
+from xas_amd import _lib
 from test_gpu_bench_kernels import _dgrad_samples, _fwd_samples, _gen, _operands, _rel, _shape
 
 pytestmark = pytest.mark.gpu
 
-NO_PERSIST = 1 << 26
-ANY_K = 1 << 27          # the dispatch keeps K > 128 on the one-tile kernel (no gain there): the tests run those shapes through
+NO_PERSIST = _lib.TUNE_NO_X6P
+ANY_K = _lib.TUNE_X6P_ANY_K     # the dispatch keeps K > 128 on the one-tile kernel (no gain there): the tests run those shapes through
                         # the persistent kernel as well
 
 

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+from xas_amd import _lib
+
 pytestmark = pytest.mark.gpu
 
 
@@ -51,12 +53,14 @@ def test_large_problem_kernels_vs_float64(n, cin, h, w, cout, k):
 
 
 def test_tap_and_wide_tile_kernels_equal_the_implicit_gemm():
-    """The same problems with the tap re-use kernels and the 64 x 256 tiles switched off (tune bits 22 / 23): results agree to
+    """The same problems with the tap re-use kernels and the 64 x 256 tiles switched off (TUNE_GENERAL_KERNELS - which also takes
+    batch norms off their streaming kernels - and TUNE_NO_WIDE_TILES): results agree to
     accumulation-order noise; the kernel class the library reports does not change."""
     from xas_amd import layers as L
     from xas_amd._lib import query
     outs = {}
-    for tune in (0, (1 << 22) | (1 << 23)):
+    off = _lib.TUNE_GENERAL_KERNELS | _lib.TUNE_NO_WIDE_TILES
+    for tune in (0, off):
         query('xas_set_tuning', tune)
         try:
             res = []
@@ -74,7 +78,7 @@ def test_tap_and_wide_tile_kernels_equal_the_implicit_gemm():
             outs[tune] = res
         finally:
             query('xas_set_tuning', 0)
-    for a, b in zip(outs[0], outs[(1 << 22) | (1 << 23)]):
+    for a, b in zip(outs[0], outs[off]):
         for ta, tb in zip(a, b):
             assert rel(ta, tb) < 2e-6
 
@@ -106,7 +110,7 @@ def test_batched_weight_preparation_is_bit_identical(monkeypatch):
 
 
 def test_stem_weight_gradient_kernel_equals_the_general_kernel():
-    """stem_wgrad_kernel (LDS patches, tune bit 24 switches it off) against the general weight-gradient kernel and float64."""
+    """stem_wgrad_kernel (LDS patches, TUNE_NO_STEM_WGRAD switches it off) against the general weight-gradient kernel and float64."""
     from xas_amd import layers as L
     from xas_amd._lib import query
     g = torch.Generator().manual_seed(11)
@@ -117,7 +121,7 @@ def test_stem_weight_gradient_kernel_equals_the_general_kernel():
     gy = torch.randn(yc.shape, generator=g)
     (yc * gy.double()).sum().backward()
     res = {}
-    for tune in (0, 1 << 24):
+    for tune in (0, _lib.TUNE_NO_STEM_WGRAD):
         query('xas_set_tuning', tune)
         try:
             m = L.Conv2d(3, 64, 7, 2, 3, bias=False).cuda()
@@ -129,13 +133,13 @@ def test_stem_weight_gradient_kernel_equals_the_general_kernel():
             res[tune] = m.weight.grad.clone()
         finally:
             query('xas_set_tuning', 0)
-    assert rel(res[0], wc.grad) < 3e-6 and rel(res[1 << 24], wc.grad) < 3e-6
-    assert rel(res[0], res[1 << 24]) < 2e-6
+    assert rel(res[0], wc.grad) < 3e-6 and rel(res[_lib.TUNE_NO_STEM_WGRAD], wc.grad) < 3e-6
+    assert rel(res[0], res[_lib.TUNE_NO_STEM_WGRAD]) < 2e-6
 
 
 def test_stem_forward_f16x3_kernel_against_float64_and_the_fp32_kernel():
     """stem_fwd_f16_kernel (default mode: two fp16 planes of patch and weights, K laid out as 7 filter rows x 24) against a
-    float64 convolution and against stem_fwd_kernel (tune bit 25), on an image size with ragged tiles."""
+    float64 convolution and against stem_fwd_kernel (TUNE_STEM_FWD_F32), on an image size with ragged tiles."""
     from xas_amd import layers as L
     from xas_amd._lib import query
     g = torch.Generator().manual_seed(13)
@@ -146,7 +150,7 @@ def test_stem_forward_f16x3_kernel_against_float64_and_the_fp32_kernel():
     with torch.no_grad():
         m.weight.copy_(wt)
     res = {}
-    for tune in (0, 1 << 25):
+    for tune in (0, _lib.TUNE_STEM_FWD_F32):
         query('xas_set_tuning', tune)
         try:
             with torch.no_grad():
@@ -156,4 +160,4 @@ def test_stem_forward_f16x3_kernel_against_float64_and_the_fp32_kernel():
     for tune, y in res.items():
         e = float((y - ref).norm() / ref.norm())
         assert e < 1e-6, (tune, e)
-    assert float((res[0] - res[1 << 25]).abs().max()) < 2e-5
+    assert float((res[0] - res[_lib.TUNE_STEM_FWD_F32]).abs().max()) < 2e-5

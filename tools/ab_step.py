@@ -12,7 +12,7 @@ model, disc, od, odisc = engine.prepare_model(cfg)
 model.cuda().train(); disc.cuda().train()
 step = engine.TrainStep(cfg, model, disc, od, odisc)
 x = synthetic_batch(32, cfg['model_params']['cam_id_list'], torch.device('cuda'), seed=1)
-# variants: an integer = xas_set_tuning flags; NAME=VALUE = module attribute of xas_amd.ops_nn (e.g. FUSE_DGRAD_BN=0),
+# variants: an integer = xas_set_tuning flags (XAS_TUNE_* of include/xas_hip.h, or-ed); NAME=VALUE = module attribute of xas_amd.ops_nn (e.g. FUSE_DGRAD_BN=0),
 # interleaved in ONE process so that box-to-box and clock drift cancel
 def parse(a):
     if '=' in a:
@@ -29,7 +29,7 @@ def select(sel):
         setattr(ops_nn, sel[1], sel[2] if sel[1].startswith('_') else bool(sel[2]))      # _NAME=int, NAME=0/1
 
 
-variants = [parse(a) for a in (sys.argv[1:] or ['0', '8192'])]
+variants = [parse(a) for a in (sys.argv[1:] or ['0', str(_lib.TUNE_WGRAD_ALT_ORDER)])]
 for name, sel in variants:
     select(sel)
     step(x)

@@ -5,6 +5,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'x-as-supervision_amd')]
 import torch
+from xas_amd import _lib
 from xas_amd._lib import call, ptr
 
 
@@ -57,7 +58,7 @@ def conv_cases():
         t = timed(lambda: call('xas_conv_fwd_bnstats', ptr(x), ptr(w), ptr(y), shp, G, None, ptr(mean), ptr(var), cout, None,
                                ptr(ws), None, None, 0.1))
         print('conv_fwd_bnstats  %s  %.3f ms  %.1f TF  %.2f TB/s' % ((n, cin, h, cout, k), t * 1e3, fl / t / 1e12, byts / t / 1e12))
-        for tune in (4, 32, 8388608 | 16777216):
+        for tune in (_lib.TUNE_PLAIN_KLOOP, _lib.TUNE_NO_WIDE_TILES | _lib.TUNE_NO_STEM_WGRAD):
             query('xas_set_tuning', tune)
             t = timed(lambda: call('xas_conv_fwd', ptr(x), ptr(w), None, ptr(y), shp))
             print('   tune %-9d      %.3f ms  %.1f TF' % (tune, t * 1e3, fl / t / 1e12))

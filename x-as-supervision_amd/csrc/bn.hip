@@ -30,8 +30,8 @@ static int col_geom(long M, int C, int G, ColGeom* g) {
   while (cb < 64 && C % (cb * 2) == 0) cb *= 2;
   g->CB = cb; g->G = G; g->Mg = M / G;
   g->TX = g->CB / 4; g->TY = 256 / g->TX; g->ncb = C / g->CB;
-  static const long kWant[4] = {256, 512, 128, 64};           // tune bits 15-16 (experiment)
-  long want = kWant[(tune_flags() >> 15) & 3] * (G > 1 ? 2 : 1) / ((long)g->ncb * G);   // ~1-2 blocks per CU in total
+  static const long kWant[4] = {256, 512, 128, 64};           // XAS_TUNE_SLAB_* (experiment)
+  long want = kWant[(tune_flags() >> XAS_TUNE_SLAB_SHIFT) & XAS_TUNE_SLAB_MASK] * (G > 1 ? 2 : 1) / ((long)g->ncb * G);   // ~1-2 blocks per CU in total
   long maxslab = cdiv(g->Mg, (long)g->TY * 8);   // at least 8 rows per thread
   if (want > maxslab) want = maxslab;
   if (want < 1) want = 1;
@@ -109,11 +109,7 @@ __device__ __forceinline__ float4 load_wt(__amdgpu_buffer_rsrc_t r, unsigned byt
 // loads of the reduction passes: PLAIN since r05.  r03/r04 shipped non-temporal loads here like for every streamed operand
 // (measured with the weight gradients sharing the chip); on ONE stream the apply kernel that follows reads
 // the same x and dy again and finds part of them in the caches when the reduction did not mark them for early eviction:
-// -0.7 ms/step (in-box, interleaved, 3 rounds: 124.8 -> 124.1).  XAS_BN_REDUCE_NT=1 brings the hint back.
-#ifndef XAS_BN_REDUCE_NT
-#define XAS_BN_REDUCE_NT 0
-#endif
-__device__ __forceinline__ float4 red_load(const float4* p) { return XAS_BN_REDUCE_NT ? stream_load(p) : *p; }
+// -0.7 ms/step (in-box, interleaved, 3 rounds: 124.8 -> 124.1).
 
 template <int MODE, int UNR = 4, int FL = 4>   // 0: stats of x around pivot ; 1: bn backward sums ; 2: plain column sums of x ;
                       // 3: bn backward sums WITHOUT x: xhat = (z - beta)/gamma with z recovered from y (act != 0)
@@ -164,8 +160,8 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
 #pragma unroll UNR
   for (long r = r0 + ty; r < r1; r += g.TY) {
     if (MODE == 3) {
-      float4 g4 = red_load(reinterpret_cast<const float4*>(dy + r * C + c));
-      const float4 yv = red_load(reinterpret_cast<const float4*>(y + r * C + c));
+      float4 g4 = *reinterpret_cast<const float4*>(dy + r * C + c);
+      const float4 yv = *reinterpret_cast<const float4*>(y + r * C + c);
       const float neg = act == 1 ? 0.f : 0.01f, up = act == 1 ? 0.f : 100.f;
       float4 z;                                            // pre-activation value
       z.x = yv.x > 0.f ? yv.x : yv.x * up; z.y = yv.y > 0.f ? yv.y : yv.y * up;
@@ -177,9 +173,9 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
       s2.z = fmaf(g4.z, (z.z - p0.z) * p1.z, s2.z); s2.w = fmaf(g4.w, (z.w - p0.w) * p1.w, s2.w);
       continue;
     }
-    const float4 xv = red_load(reinterpret_cast<const float4*>(x + r * C + c));
+    const float4 xv = *reinterpret_cast<const float4*>(x + r * C + c);
     if (MODE == 4) {
-      float4 g4 = red_load(reinterpret_cast<const float4*>(dy + r * C + c));
+      float4 g4 = *reinterpret_cast<const float4*>(dy + r * C + c);
       const float neg = act == 1 ? 0.f : 0.01f;
       g4.x *= bn_affine(xv.x, p0.x, rsg.x, bt.x) > 0.f ? 1.f : neg; g4.y *= bn_affine(xv.y, p0.y, rsg.y, bt.y) > 0.f ? 1.f : neg;
       g4.z *= bn_affine(xv.z, p0.z, rsg.z, bt.z) > 0.f ? 1.f : neg; g4.w *= bn_affine(xv.w, p0.w, rsg.w, bt.w) > 0.f ? 1.f : neg;
@@ -195,14 +191,14 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
       s1.x += a0; s1.y += b; s1.z += cc; s1.w += d;
       s2.x = fmaf(a0, a0, s2.x); s2.y = fmaf(b, b, s2.y); s2.z = fmaf(cc, cc, s2.z); s2.w = fmaf(d, d, s2.w);
     } else {
-      float4 g4 = red_load(reinterpret_cast<const float4*>(dy + r * C + c));
+      float4 g4 = *reinterpret_cast<const float4*>(dy + r * C + c);
       if (act && a.mask) {
         const unsigned mb = a.mask[(r * C + c) >> 2];
         const float neg = act == 1 ? 0.f : 0.01f;
         g4.x *= (mb & 1u) ? 1.f : neg; g4.y *= (mb & 2u) ? 1.f : neg;
         g4.z *= (mb & 4u) ? 1.f : neg; g4.w *= (mb & 8u) ? 1.f : neg;
       } else if (act) {
-        const float4 yv = red_load(reinterpret_cast<const float4*>(y + r * C + c));
+        const float4 yv = *reinterpret_cast<const float4*>(y + r * C + c);
         const float neg = act == 1 ? 0.f : 0.01f;
         g4.x *= yv.x > 0.f ? 1.f : neg; g4.y *= yv.y > 0.f ? 1.f : neg;
         g4.z *= yv.z > 0.f ? 1.f : neg; g4.w *= yv.w > 0.f ? 1.f : neg;
@@ -240,10 +236,8 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
     const int last = old == total - 1u;
     if (last) {
       __hip_atomic_store(a.ticket + blockIdx.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for re-use
-#ifndef XAS_BN_NO_ACQUIRE
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");    // drop this CU's stale L1 lines (other blocks' partials)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     }
     s_last = last;
   }
@@ -383,22 +377,18 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
 
 template <int MODE>
 __global__ __launch_bounds__(256) void col_reduce_kernel(ColArgs a) {
-#ifdef XAS_BN_PRIO
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-#endif
   col_reduce_body<MODE, 4, 4>(a);
 }
 
 // Same kernel compiled for at most 64 VGPRs: shipped for the backward sums in r04, when they ran beside two weight-gradient
 // blocks per CU (which leave 112 VGPRs per SIMD lane - room for two lean waves instead of one).  On ONE stream (r05) the
 // 86-register build above is 0.7 ms/step faster (in-box, interleaved, 5 rounds: 126.95 -> 126.24) and is the shipped one;
-// tune bit 18 selects this build.
+// XAS_TUNE_COL_REDUCE_LEAN selects this build.
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void col_reduce_lean_kernel(ColArgs a) {
-#ifdef XAS_BN_PRIO
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-#endif
   col_reduce_body<MODE, 2, 2>(a);
 }
 
@@ -547,9 +537,7 @@ __global__ __launch_bounds__(256) void bn_apply_stream_kernel(const float4* __re
                                                              float eps, long n4g, int C4, float4* __restrict__ y,
                                                              uint8_t* __restrict__ mask_out, float* __restrict__ amax_out) {
   float amx = 0.f;                                     // max |y| of this thread (amax_out != null: xas_bn_apply_amax)
-#ifdef XAS_BN_PRIO
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-#endif
   const long goff = (long)blockIdx.y * n4g;
   const long stride = (long)gridDim.x * blockDim.x;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -568,11 +556,7 @@ __global__ __launch_bounds__(256) void bn_apply_stream_kernel(const float4* __re
       mask_out[goff + k] = (uint8_t)((o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) | (o.w > 0.f ? 8u : 0u));
     o.x = act_fwd(o.x, ACT); o.y = act_fwd(o.y, ACT); o.z = act_fwd(o.z, ACT); o.w = act_fwd(o.w, ACT);
     amx = amax4(amx, o);
-#ifdef XAS_BN_APPLY_PLAIN_STORE
-    y[goff + k] = o;
-#else
     stream_store(y + goff + k, o);
-#endif
   };
   const float4 z4 = make_float4(0, 0, 0, 0);
   for (; i + 3 * stride < n4g; i += 4 * stride) {
@@ -594,9 +578,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_stream_kernel(
     const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ sums, float eps, long n4g, int C4, float inv_count, float4* __restrict__ dx,
     float4* __restrict__ dres, const uint8_t* __restrict__ mask, float* __restrict__ amax_out) {
-#ifdef XAS_BN_PRIO
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-#endif
   float amx = 0.f;                                     // max |dx| of this thread (amax_out != null: xas_bn_bwd_apply_amax)
   const long goff = (long)blockIdx.y * n4g;
   const long stride = (long)gridDim.x * blockDim.x;
@@ -635,11 +617,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_stream_kernel(
     o.z = g.z * is.z * (dz.z - a.z * inv_count - xh.z * b.z * inv_count);
     o.w = g.w * is.w * (dz.w - a.w * inv_count - xh.w * b.w * inv_count);
     amx = fmaxf(fmaxf(amx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-#ifdef XAS_BN_BWD_PLAIN_STORE
-    dx[goff + k] = o;
-#else
     stream_store(dx + goff + k, o);
-#endif
   };
   const float4 z4 = make_float4(0, 0, 0, 0);
   constexpr bool NEEDX = XH || SIGN == 2, NEEDY = SIGN == 1 || !XH;
@@ -649,13 +627,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_stream_kernel(
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long k = goff + i + u * stride;
-#ifdef XAS_BN_BWD_PLAIN_LOAD
-      dv[u] = dy[k];
-      xv[u] = NEEDX ? x[k] : z4;
-#else
       dv[u] = stream_load(dy + k);
       xv[u] = NEEDX ? stream_load(x + k) : z4;
-#endif
       yv[u] = NEEDY ? stream_load(y + k) : z4;
       mb[u] = SIGN == 3 ? mask[k] : 0u;
     }
@@ -997,7 +970,7 @@ extern "C" int xas_bn_apply_amax(const float* x, const float* mean, const float*
     unsigned gx = ew_grid_g(n4g, groups);
     const bool pow2 = (C4 & (C4 - 1)) == 0;
     if (pow2 && C4 > 256) gx = (gx + (C4 / 256) - 1) / (C4 / 256) * (C4 / 256);
-    if (pow2 && ((long)gx * 256) % C4 == 0 && !(tune_flags() & (1 << 22))) {
+    if (pow2 && ((long)gx * 256) % C4 == 0 && !(tune_flags() & XAS_TUNE_GENERAL_KERNELS)) {
       const dim3 grid(gx, groups);
       const float4* x4 = reinterpret_cast<const float4*>(x);
       const float4* r4 = reinterpret_cast<const float4*>(residual);
@@ -1058,7 +1031,7 @@ extern "C" int xas_bn_bwd_reduce(const float* x, const float* y, const float* dy
               "bn_bwd_reduce: null buffer (an activation needs y, or x with gamma and beta)");
   XAS_REQUIRE(x || (act != 0 && y && gamma && beta), "bn_bwd_reduce: without x the layer needs an activation, y, gamma, beta");
   XAS_REQUIRE((dbeta_acc == nullptr) == (dgamma_acc == nullptr), "bn_bwd_reduce: gradient accumulators come in pairs");
-  const bool lean = (tune_flags() & 262144) != 0;      // shipped: the 86-VGPR build (tune bit 18 selects the <= 64-VGPR one: see col_reduce_lean_kernel)
+  const bool lean = (tune_flags() & XAS_TUNE_COL_REDUCE_LEAN) != 0;      // shipped: the 86-VGPR build (the flag selects the <= 64-VGPR one: see col_reduce_lean_kernel)
   ColArgs a{};
   if (col_args(&a, g, M, C, workspace)) return 1;
   a.dy = dy; a.mean = mean; a.var = var_biased; a.eps = eps; a.act = act;
@@ -1117,7 +1090,7 @@ extern "C" int xas_bn_bwd_apply_amax(const float* x, const float* y, const float
     else if (act == 2 && !x && y && !dresidual) mode = 2;
     else if (act == 1 && x && y && !mask) mode = dresidual ? 3 : 4;
     else if (act == 1 && x && mask) mode = dresidual ? 5 : 6;
-    if (mode >= 0 && pow2 && ((long)gx * 256) % C4 == 0 && !(tune_flags() & (1 << 22))) {
+    if (mode >= 0 && pow2 && ((long)gx * 256) % C4 == 0 && !(tune_flags() & XAS_TUNE_GENERAL_KERNELS)) {
       const dim3 grid(gx, groups);
       const float4* x4 = reinterpret_cast<const float4*>(x);
       const float4* y4 = reinterpret_cast<const float4*>(y);

@@ -549,9 +549,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
   // cuts the kernel's HBM fetch 2-7x, yet the step is 3 % SLOWER (the tiles of a split then hammer the same L2
   // lines at the same time); the plain order below is the shipped one.
   int split, tile;
-  if (!(p.tune & 8192)) {                    // default: tiles fastest, dealt round-robin over the XCDs
+  if (!(p.tune & XAS_TUNE_WGRAD_ALT_ORDER)) {  // default: tiles fastest, dealt round-robin over the XCDs
     tile = blockIdx.x % p.ntiles; split = blockIdx.x / p.ntiles;
-  } else {                                   // experiment (bit13): one split per XCD - 2-7x less HBM traffic (PMC) but slower
+  } else {                                   // experiment: one split per XCD - 2-7x less HBM traffic (PMC) but slower
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
     split = xcd + 8 * (q / p.ntiles);
     tile = q - (q / p.ntiles) * p.ntiles;
@@ -709,7 +709,7 @@ __global__ __launch_bounds__(256) void wgrad_buf_kernel(WgradParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / C::WAVES_N, wn = wave % C::WAVES_N;
   int tile, split;
-  if (p.tune & 8192) {                       // experiment (bit13): tiles fastest, dealt round-robin over the XCDs
+  if (p.tune & XAS_TUNE_WGRAD_ALT_ORDER) {     // experiment: tiles fastest, dealt round-robin over the XCDs
     tile = blockIdx.x % p.ntiles; split = blockIdx.x / p.ntiles;
   } else {
     // XCD-grouped order.  A group = the KK-tiles of one (pixel split, Cout tile): they read the SAME dy tile and the
@@ -1113,7 +1113,6 @@ __global__ __launch_bounds__(256) void stem_fwd_f16_kernel(const float* __restri
         b0[pc] = *reinterpret_cast<const uint4*>(wp + i * STH_WROW);
         b1[pc] = *reinterpret_cast<const uint4*>(wp + (32 + i) * STH_WROW);
       }
-      frag_regs(a); frag_regs(b0); frag_regs(b1);
 #pragma unroll
       for (int t = 0; t < 3; ++t) {                    // a2 b1, a1 b2, a1 b1 (smallest first)
         const int pa = t == 0 ? 1 : 0, pb = t == 1 ? 1 : 0;
@@ -1558,7 +1557,7 @@ static bool igemm_fits(const IgemmParams& p) {
 }
 
 // Exact-fp32 MFMA path: buffer-load kernel unless its offset scheme cannot address the tensor or a coverage test asks for
-// the global-load kernel (tune bit6 = 64); tune bit5 (32): plain K-loop instead of the pipelined one.
+// the global-load kernel (XAS_TUNE_GLOBAL_LOAD); XAS_TUNE_PLAIN_KLOOP: plain K-loop instead of the pipelined one.
 template <int BM, int BN, int MODE>
 static int launch_tile(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
   const bool fits = igemm_fits(p);
@@ -1572,11 +1571,11 @@ static int launch_tile(const IgemmParams& p, int Mrows_max, int phases, hipStrea
   // nothing to look ahead to (they re-load the last step) - the plain loop is 18 % faster there (0.608 -> 0.497 ms for
   // 64 -> 256 channels at 256 x 64 x 64, r02)
   const bool short_k = p.stride == 1 && (long)p.R * p.S * p.Cs <= 2 * BK;
-  if (fits && !(p.tune & 64)) {
-    if ((p.tune & 32) || short_k) return launch_igemm_buf<BM, BN, MODE, false>(p, Mrows_max, phases, st);
+  if (fits && !(p.tune & XAS_TUNE_GLOBAL_LOAD)) {
+    if ((p.tune & XAS_TUNE_PLAIN_KLOOP) || short_k) return launch_igemm_buf<BM, BN, MODE, false>(p, Mrows_max, phases, st);
     return launch_igemm_buf<BM, BN, MODE, true>(p, Mrows_max, phases, st);
   }
-  if (p.tune & 32) return launch_igemm<BM, BN, MODE, 2, false>(p, Mrows_max, phases, st);
+  if (p.tune & XAS_TUNE_PLAIN_KLOOP) return launch_igemm<BM, BN, MODE, 2, false>(p, Mrows_max, phases, st);
   return launch_igemm<BM, BN, MODE, 2, true>(p, Mrows_max, phases, st);
 }
 
@@ -1681,9 +1680,9 @@ static int fwd_stats_tile_rows(const xas_conv_shape* s, int groups) {
   pick_tile(s->Cout, M, 1, &bm, &bn);
   // the bf16-split kernels use 64 x 256 tiles for wide layers, unless the tap re-use kernel (128-row patches) takes the shape
   const bool x6 = precision_of(s) != XAS_PREC_F32;
-  const bool tap = x6 && bm == 128 && !(g_tune & (1 << 22)) &&
+  const bool tap = x6 && bm == 128 && !(g_tune & XAS_TUNE_GENERAL_KERNELS) &&
                    tap_tile_ok(s->R, s->S, s->stride, s->pad, s->Hi, s->Wi, s->Ho, s->Wo, s->Cin, s->N);
-  if (x6 && !tap && !(g_tune & (1 << 23))) pick_tile(s->Cout, M, 1, &bm, &bn, true);
+  if (x6 && !tap && !(g_tune & XAS_TUNE_NO_WIDE_TILES)) pick_tile(s->Cout, M, 1, &bm, &bn, true);
   if (Mg % bm) return 0;
   if ((M / bm) * 2 * (long)s->Cout * 4 >= 0x7fffff00l) return 0;
   return bm;
@@ -1712,8 +1711,8 @@ static int conv_fwd_impl(const float* x, const float* w_packed, const float* bia
   hipStream_t st = as_stream(stream);
   if (s->Cin == 3 && s->R == 7 && s->S == 7 && s->stride == 2 && s->pad == 3 && s->Cout == ST_CO && bias == nullptr) {
     const int tiles = (int)(cdiv(s->Ho, ST_TH) * cdiv(s->Wo, ST_TW));
-    // f16x3 needs max |image| (the scale of the split); without it - and under tune bit 25 - the exact-fp32 stem kernel
-    if (precision_of(s) == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & (1 << 25)))
+    // f16x3 needs max |image| (the scale of the split); without it - and under XAS_TUNE_STEM_FWD_F32 - the exact-fp32 stem kernel
+    if (precision_of(s) == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & XAS_TUNE_STEM_FWD_F32))
       hipLaunchKernelGGL(stem_fwd_f16_kernel, dim3((unsigned)cdiv(tiles, STH_TPB), s->N), dim3(256), 0, st, x, w_packed, y, s->N, s->Hi,
                          s->Wi, s->Ho, s->Wo, s->grad_amax);
     else
@@ -1800,7 +1799,7 @@ extern "C" int xas_conv_kernel_class(const xas_conv_shape* s, int pass) {
   if (thin) return 0;
   if (pass == 0) {
     if (s->Cin == 3 && s->R == 7 && s->S == 7 && s->stride == 2 && s->pad == 3 && s->Cout == ST_CO)              // stem kernels
-      return (prec == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & (1 << 25))) ? 4 : 1;
+      return (prec == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & XAS_TUNE_STEM_FWD_F32)) ? 4 : 1;
     return (s->Cin % BK == 0 && s->Cout >= 16) ? split : 0;
   }
   if (pass == 1) return (s->Cout % BK == 0 && s->Cin >= 16) ? split : 0;
@@ -2000,7 +1999,7 @@ static inline unsigned slab_threads() { return XAS_SLAB_THREADS; }
 // does the weight gradient of this shape run on the bf16-split kernel (conv_x6.hip)?  32-bit byte offsets (tensors below
 // 2 GiB), whole float4s inside one filter tap, at most one carry per coordinate in the per-thread pixel decode
 static bool wgrad_on_x6(const xas_conv_shape* s, const float* x) {
-  if (precision_of(s) == XAS_PREC_F32 || (g_tune & 128)) return false;
+  if (precision_of(s) == XAS_PREC_F32 || (g_tune & XAS_TUNE_WGRAD_GLOBAL_LOAD)) return false;
   const long xbytes = ((long)s->N * s->Hi * s->Wi + (long)s->pad * s->Wi + s->pad) * s->Cin * 4;
   const long dybytes = (long)s->N * s->Ho * s->Wo * s->Cout * 4;
   return s->Cin % 4 == 0 && s->Cout % 4 == 0 && s->Cout >= 16 && (x == nullptr || ((uintptr_t)x & 15) == 0) &&
@@ -2028,7 +2027,7 @@ static void wgrad_plan(const xas_conv_shape* s, bool x6, int* bm, int* bn, int* 
   if (sp > maxsp) sp = maxsp;
   if (sp < 1) sp = 1;
   if (x6 && sp >= 8) sp -= sp % 8;                 // bf16-split kernel: whole pixel splits per XCD (wgrad_x6_kernel)
-  else if (x6 || !(g_tune & 8192)) {               // XCD-grouped order: (splits x Cout tiles) groups, 8 XCDs -> keep them balanced
+  else if (x6 || !(g_tune & XAS_TUNE_WGRAD_ALT_ORDER)) {   // XCD-grouped order: (splits x Cout tiles) groups, 8 XCDs -> keep them balanced
     const long nct = cdiv(s->Cout, *bm);
     while (sp > 1 && (sp * nct) % 8 != 0 && (sp * nct) > 8) --sp;
   }
@@ -2081,7 +2080,7 @@ static int launch_wgrad(const WgradParams& p, int splits, hipStream_t st) {
 
 template <int BM, int BN, int T, bool PIPE = true>
 static int launch_wgrad_buf_t(const WgradParams& p, int splits, hipStream_t st) {
-  if (PIPE && (g_tune & 524288)) return launch_wgrad_buf_t<BM, BN, T, false>(p, splits, st);   // tune bit19: plain K-loop
+  if (PIPE && (g_tune & XAS_TUNE_WGRAD_PLAIN_KLOOP)) return launch_wgrad_buf_t<BM, BN, T, false>(p, splits, st);
   size_t lds = (size_t)2 * WBK * ((BM + 4) + (BN + 32)) * sizeof(float);
   static size_t attr_set_dev[kMaxDevices] = {};
   size_t& attr_set = attr_set_dev[current_device()];
@@ -2095,7 +2094,7 @@ static int launch_wgrad_buf_t(const WgradParams& p, int splits, hipStream_t st) 
   q.ntiles = q.nct * (int)cdiv(p.KK, BN);
   q.nsplits = splits;
   q.tune = g_tune;
-  dim3 grid((unsigned)((g_tune & 8192) ? splits * q.ntiles : 8 * cdiv((long)splits * q.nct, 8) * (q.ntiles / q.nct)));
+  dim3 grid((unsigned)((g_tune & XAS_TUNE_WGRAD_ALT_ORDER) ? splits * q.ntiles : 8 * cdiv((long)splits * q.nct, 8) * (q.ntiles / q.nct)));
   hipLaunchKernelGGL((wgrad_buf_kernel<BM, BN, T, PIPE>), grid, dim3(256), lds, st, q);
   XAS_LAUNCH_CHECK();
   return 0;
@@ -2192,7 +2191,7 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dw_packed, fl
     XAS_LAUNCH_CHECK();
     return 0;
   }
-  if (stem_wgrad_ok(s) && !(g_tune & (1 << 24))) {    // (tune bit 24: the general kernel)
+  if (stem_wgrad_ok(s) && !(g_tune & XAS_TUNE_NO_STEM_WGRAD)) {    // (the flag: the general kernel)
     const int patches = s->N * (s->Ho / ST_TH) * (s->Wo / ST_TW);
     const int ppb = (int)cdiv(patches, kStemWgradBlocks), blocks = (int)cdiv(patches, ppb);
     hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, dy, workspace, s->N, s->Hi, s->Wi,
@@ -2221,12 +2220,12 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dw_packed, fl
   const bool vec = (s->Cin % 4 == 0) && (((uintptr_t)x & 15) == 0);
   int rc;
   // buffer-load kernel: 32-bit byte offsets (tensors < 2 GiB) and at most one carry per coordinate in the per-thread
-  // pixel decode (31 / Wo + 1 <= Ho); tune bit7 (128) forces the old kernel
+  // pixel decode (31 / Wo + 1 <= Ho); XAS_TUNE_WGRAD_GLOBAL_LOAD forces the old kernel
   const long xbytes = ((long)s->N * s->Hi * s->Wi + (long)s->pad * s->Wi + s->pad) * s->Cin * 4;
   const long dybytes = (long)p.M * s->Cout * 4;
-  const bool buf_ok = vec && s->Cin % 32 == 0 && xbytes < 0x7fffff00l && dybytes < 0x7fffff00l && 31 / s->Wo + 1 <= s->Ho && !(g_tune & 128);
+  const bool buf_ok = vec && s->Cin % 32 == 0 && xbytes < 0x7fffff00l && dybytes < 0x7fffff00l && 31 / s->Wo + 1 <= s->Ho && !(g_tune & XAS_TUNE_WGRAD_GLOBAL_LOAD);
   int tbm = 0, tsplits = 0, tpps = 0;
-  if (x6 && !(g_tune & (1 << 22)) &&                  // tune bit 22: no tap re-use kernels
+  if (x6 && !(g_tune & XAS_TUNE_GENERAL_KERNELS) &&   // (the flag: no tap re-use kernels)
       wgrad_x6t_plan(s->N, s->Hi, s->Wi, s->Cin, s->Cout, s->R, s->S, s->stride, s->pad, s->Ho, s->Wo, &tbm, &tsplits, &tpps)) {
     splits = tsplits;
     p.out = (splits == 1 && !oihw) ? dw_packed : workspace;

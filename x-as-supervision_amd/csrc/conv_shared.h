@@ -37,7 +37,7 @@ struct IgemmParams {
   int R, S, stride, pad;
   FastDiv div_hw, div_w;   // row -> (n, a, b) decode over the row grid
   int Hrow, Wrow;          // row grid (fwd: Ho x Wo; dgrad: per-phase grid, set in kernel)
-  int tune;                // kernel-variant selectors kept for coverage tests (xas_set_tuning): bit5 plain K-loop, bit6 global-load kernel
+  int tune;                // xas_set_tuning value: kernel-variant selectors kept for coverage tests (XAS_TUNE_* in xas_hip.h)
   int nMt, nNt, mt_per_xcd;   // tile counts and M-tiles per XCD for the XCD-aware block order
   int t2d_tw;                 // != 0: the rows of a 128-row tile are an 8 x t2d_tw pixel patch of one image (t2d_tw = 16) or of two
                               // images (t2d_tw = 8) instead of 128 consecutive pixels (igemm_x6t_kernel); the epilogue maps rows with tile_row()
@@ -180,13 +180,7 @@ template <int P> __device__ __forceinline__ float4 sub_piece4(float4 v, uint2 q)
 template <int P> __device__ __forceinline__ Pieces<P> split_pieces(float4 r, float s) {
   Pieces<P> o;
   if constexpr (P == 2) {
-#ifdef XAS_F16_SPLIT_GENERIC                       // (A/B builds: the compiler's 14-instruction form)
-    r.x *= s; r.y *= s; r.z *= s; r.w *= s;
-    o.q[0] = pack_f16x4(r);
-    o.q[1] = pack_f16x4(sub_f16x4(r, o.q[0]));
-#else
     split_f16x4(r, s, o.q[0], o.q[1]);
-#endif
   } else {
 #pragma unroll
     for (int pc = 0; pc < P; ++pc) {
@@ -201,115 +195,19 @@ template <int P> struct Products;
 template <> struct Products<3> { static constexpr int N = 6; static constexpr int A[6] = {2, 0, 1, 1, 0, 0}; static constexpr int B[6] = {0, 2, 1, 0, 1, 0}; };
 template <> struct Products<2> { static constexpr int N = 3; static constexpr int A[3] = {1, 0, 0}; static constexpr int B[3] = {0, 1, 0}; };
 template <> struct Products<1> { static constexpr int N = 1; static constexpr int A[1] = {0}; static constexpr int B[1] = {0}; };
-// XAS_FRAG_AGPR (experiment, r05): a matrix-instruction operand fragment is moved to the ACCUMULATION half of the register file
-// once, where it is formed; the K-doubled matrix instructions then read their 128-bit A / B operands from there.  With the
-// operands read from AGPRs the multi-stream hazard of DESIGN.md section 5 did not show (0 / 500 steps on the three-stream schedule,
-// shipped build on the same lease 11 / 200: profiles/r05_hazard_census_agpr.txt).
-__device__ __forceinline__ uint4 frag_reg(uint4 v) {
-#ifdef XAS_FRAG_AGPR
-  typedef unsigned u32x4v_ __attribute__((ext_vector_type(4)));
-  u32x4v_ t = {v.x, v.y, v.z, v.w}, o;
-  asm("" : "=a"(o) : "0"(t));
-  return make_uint4(o[0], o[1], o[2], o[3]);
-#else
-  return v;
-#endif
-}
-template <int A_, int B_>
-__device__ __forceinline__ void frag_regs(uint4 (&f)[A_][B_]) {
-#ifdef XAS_FRAG_AGPR
-#pragma unroll
-  for (int i = 0; i < A_; ++i)
-#pragma unroll
-    for (int j = 0; j < B_; ++j) f[i][j] = frag_reg(f[i][j]);
-#endif
-}
-template <int A_>
-__device__ __forceinline__ void frag_regs(uint4 (&f)[A_]) {
-#ifdef XAS_FRAG_AGPR
-#pragma unroll
-  for (int i = 0; i < A_; ++i) f[i] = frag_reg(f[i]);
-#endif
-}
 
+// One K = 16 matrix instruction on a pair of operand fragments (P = 2: fp16 pieces, else bf16 pieces).
 template <int P>
 __device__ __forceinline__ f32x16 mfma_piece(uint4 a, uint4 b, f32x16 c) {
-#ifdef XAS_MFMA_X8
-  // diagnosis build: the K = 16 matrix instructions of gfx950 replaced by two K = 8 ones of the previous generation (the low /
-  // high 64 bits of each lane's operand pair up the same k indices on both sides, so every dot product has the same terms)
-  typedef short s16x4v __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-  const uint2 alo = make_uint2(a.x, a.y), ahi = make_uint2(a.z, a.w), blo = make_uint2(b.x, b.y), bhi = make_uint2(b.z, b.w);
-  if constexpr (P == 2) {
-    c = __builtin_amdgcn_mfma_f32_32x32x8f16(__builtin_bit_cast(f16x4v, alo), __builtin_bit_cast(f16x4v, blo), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x8f16(__builtin_bit_cast(f16x4v, ahi), __builtin_bit_cast(f16x4v, bhi), c, 0, 0, 0);
-  } else {
-    c = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(__builtin_bit_cast(s16x4v, alo), __builtin_bit_cast(s16x4v, blo), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(__builtin_bit_cast(s16x4v, ahi), __builtin_bit_cast(s16x4v, bhi), c, 0, 0, 0);
-  }
-#endif
-#ifdef XAS_MFMA_16X16
-  // diagnosis build (WRONG RESULTS ON PURPOSE - only run-to-run reproducibility is looked at): gfx950's other new shape,
-  // 16x16x32, in place of 32x32x16 - four of them, one per quarter of the accumulator, on the same operand registers.  Every
-  // accumulator element still receives a 32-term dot product of operand values of the right scale, so the step stays finite.
-  {
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4v t = {c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]};
-      if constexpr (P == 2) t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), t, 0, 0, 0);
-      else t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), t, 0, 0, 0);
-      c[4 * q] = t[0]; c[4 * q + 1] = t[1]; c[4 * q + 2] = t[2]; c[4 * q + 3] = t[3];
-    }
-    return c;
-  }
-#endif
-#ifdef XAS_MFMA_AGPR_OPERANDS
-  // diagnosis build: the A / B operands of the matrix instruction come from ACCUMULATION registers (the unified file's upper
-  // half; copied there by v_accvgpr_write): does the multi-stream hazard depend on where the K-doubled instruction reads its
-  // 128-bit operands from?  (A production form would load the fragments straight into AGPRs - ds_read / buffer_load can.)
-  {
-    typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-    u32x4v av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w}, aa, ab;
-    asm volatile("" : "=a"(aa) : "0"(av));
-    asm volatile("" : "=a"(ab) : "0"(bv));
-    a = make_uint4(aa[0], aa[1], aa[2], aa[3]);
-    b = make_uint4(ab[0], ab[1], ab[2], ab[3]);
-  }
-#endif
-#ifdef XAS_MFMA_AGPR_DUMMY
-  // diagnosis control for XAS_MFMA_AGPR_OPERANDS: the same eight copies into accumulation registers before every matrix
-  // instruction, but the instruction still reads the ORIGINAL (vector-register) operands: is it the copies or the operand source?
-  {
-    typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-    u32x4v av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w}, aa, ab;
-    asm volatile("" : "=a"(aa) : "0"(av));
-    asm volatile("" : "=a"(ab) : "0"(bv));
-    asm volatile("" :: "a"(aa), "a"(ab));
-  }
-#endif
-#ifdef XAS_MFMA_X16_TWICE
-  // diagnosis control for XAS_MFMA_X8: the K = 16 instruction issued TWICE (second result thrown away): the timing of the K = 8
-  // build with the instruction of the shipped one
-  {
-    f32x16 waste = c;
-    if constexpr (P == 2) waste = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), waste, 0, 0, 0);
-    else waste = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), waste, 0, 0, 0);
-    asm volatile("" :: "v"(waste));
-  }
-#endif
-#ifdef XAS_MFMA_NOP
-  // diagnosis build: XAS_MFMA_NOP idle issue slots of the wave after every matrix instruction (is it the issue density?)
   if constexpr (P == 2) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
   else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+#ifdef XAS_MFMA_NOP
+  // spaced build: XAS_MFMA_NOP idle issue slots of the wave after every matrix instruction
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_nop %0" :: "n"(XAS_MFMA_NOP));
   __builtin_amdgcn_sched_barrier(0);
-  return c;
-#else
-  if constexpr (P == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 #endif
+  return c;
 }
 
 // dgrad epilogue with the batch-norm backward reduction folded in (see IgemmParams::bnb_x).  Stride 1: output row = m.
@@ -549,11 +447,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x16 (&ac
           v.x += (mb & 1u) ? o.x : 0.f; v.y += (mb & 2u) ? o.y : 0.f;
           v.z += (mb & 4u) ? o.z : 0.f; v.w += (mb & 8u) ? o.w : 0.f;
         }
-#ifdef XAS_CONV_ROWS_PLAIN_STORE
-        *reinterpret_cast<float4*>(p.out + orow * p.Cd + nn) = v;
-#else
         stream_store(reinterpret_cast<float4*>(p.out + orow * p.Cd + nn), v);
-#endif
       }
     }
     if constexpr (HEAD && MODE == 0 && BM == 64 && BNH == 64) {

@@ -44,9 +44,6 @@ namespace xas {
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef short s16x8_t __attribute__((ext_vector_type(8)));
 
-#ifndef XAS_X6_ABL
-#define XAS_X6_ABL 0               // timing ablations of igemm_x6_kernel (results wrong): tools/gpu/r3_abl3.sh
-#endif
 constexpr int XH = 16;             // k per half-step
 constexpr int XLDH = XH;           // igemm LDS row in halfwords: 32 B, unpadded.  The two 16-byte halves of rows 8..15 (mod 16) are
                                    // swapped (xswz): the 8-byte stores of a half-wave (8 rows x 32 B) and the 16-byte fragment reads
@@ -127,7 +124,6 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
   constexpr int HBUF = P * PLANE;               // halfwords per half-buffer
   constexpr int AP = BM / 64;                   // activation float4 per thread per half-step (4 threads x 16 B per row)
   constexpr int NT = Products<P>::N;            // partial products
-  constexpr int TILES = C::MI * C::NI, NMF = NT * TILES;
   extern __shared__ __align__(16) float lds[];
   unsigned short* S = reinterpret_cast<unsigned short*>(lds);     // [2][P][BM][XLDH]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -265,76 +261,29 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
     unsigned short* sb = S + buf * HBUF;
 #pragma unroll
     for (int j = 0; j < AP; ++j) {
-      float4 r = ra[h * AP + j];
-#if !(XAS_X6_ABL & (32 | 64))
-      const Pieces<P> pcs = split_pieces<P>(r, f16_sa);       // (P = 2: both fp16 pieces in eight instructions, conv_shared.h)
+      const Pieces<P> pcs = split_pieces<P>(ra[h * AP + j], f16_sa);   // (P = 2: both fp16 pieces in eight instructions, conv_shared.h)
 #pragma unroll
       for (int pc = 0; pc < P; ++pc)
         *reinterpret_cast<uint2*>(sb + pc * PLANE + (arow + 64 * j) * XLDH + xswz(arow, kq4 >> 1) + (kq4 & 1) * 4) = pcs.q[pc];
-#else
-      if (P == 2) { r.x *= f16_sa; r.y *= f16_sa; r.z *= f16_sa; r.w *= f16_sa; }
-#pragma unroll
-      for (int pc = 0; pc < P; ++pc) {
-        uint2 q = (XAS_X6_ABL & 32) ? make_uint2(__float_as_uint(r.x) + pc, __float_as_uint(r.z)) : pack_piece4<P>(r);
-#if XAS_X6_ABL & 64
-        {                                              // twice the conversion work, same stores
-          const unsigned z = (unsigned)p.tune & 0x40000000u;          // runtime zero
-          float4 r2 = make_float4(r.x * 1.0000002f, r.y * 1.0000002f, r.z * 1.0000002f, r.w * 1.0000002f);
-          const uint2 q2 = pack_bf16x4(r2);
-          const float4 r3 = sub_bf16x4(r2, q2);
-          q.x |= (q2.x ^ __float_as_uint(r3.x) ^ __float_as_uint(r3.y)) & z; q.y |= (q2.y ^ __float_as_uint(r3.z) ^ __float_as_uint(r3.w)) & z;
-        }
-#endif
-        *reinterpret_cast<uint2*>(sb + pc * PLANE + (arow + 64 * j) * XLDH + xswz(arow, kq4 >> 1) + (kq4 & 1) * 4) = q;
-        if (pc + 1 < P && !(XAS_X6_ABL & 32)) r = sub_piece4<P>(r, q);
-      }
-#endif
     }
   };
   const int i = lane & 31, hh = lane >> 5;
-#if XAS_X6_ABL & 16
-  uint4 fa[P][C::MI];
-#pragma unroll
-  for (int pc = P - 1; pc >= 0; --pc)
-#pragma unroll
-    for (int mi = 0; mi < C::MI; ++mi)
-      fa[pc][mi] = *reinterpret_cast<const uint4*>(S + pc * PLANE + (wm * C::WM + mi * 32 + i) * XLDH + xswz(i, hh));
-#endif
   auto compute = [&](int buf, const uint4 (&gb)[P][C::NI]) {
     const unsigned short* sb = S + buf * HBUF;
-#if !(XAS_X6_ABL & 16)
     uint4 fa[P][C::MI];
 #pragma unroll
     for (int pc = P - 1; pc >= 0; --pc)              // smallest pieces first: they feed the first products
 #pragma unroll
       for (int mi = 0; mi < C::MI; ++mi)
         fa[pc][mi] = *reinterpret_cast<const uint4*>(sb + pc * PLANE + (wm * C::WM + mi * 32 + i) * XLDH + xswz(i, hh));
-#else
-    (void)sb;
-#endif
-#ifdef XAS_FRAG_AGPR
-    uint4 gq[P][C::NI];
-#pragma unroll
-    for (int pc = 0; pc < P; ++pc)
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni) gq[pc][ni] = frag_reg(gb[pc][ni]);
-    frag_regs(fa);
-#else
-    const uint4 (&gq)[P][C::NI] = gb;
-#endif
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int mi = 0; mi < C::MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < C::NI; ++ni)
-          acc[mi][ni] = mfma_piece<P>(gq[Products<P>::B[t]][ni], fa[Products<P>::A[t]][mi], acc[mi][ni]);
+          acc[mi][ni] = mfma_piece<P>(gb[Products<P>::B[t]][ni], fa[Products<P>::A[t]][mi], acc[mi][ni]);
   };
-  (void)NMF;
-#define SYNC() do { if (!(XAS_X6_ABL & 8)) __syncthreads(); } while (0)
-#define LOADB(g, h) do { if (!(XAS_X6_ABL & 1)) load_b(g, h); } while (0)
-#define LOADA(r) do { if (!(XAS_X6_ABL & 2)) load_a(r); } while (0)
-#define STORE(b, h, r) do { if (!(XAS_X6_ABL & 4)) split_store(b, h, r); } while (0)
   uint4 gb_0[P][C::NI], gb_1[P][C::NI];              // weight fragments of even / odd half-steps
   if (nk > 0) {
     load_a(ra_0);                                      // K-step 0
@@ -344,24 +293,24 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
     split_store(0, 0, ra_0);
     int ks = 0;
     for (; ks + 1 < nk; ks += 2) {
-      SYNC();
+      __syncthreads();
       compute(0, gb_0);                                // half-step 2 ks
-      LOADB(gb_0, 0);                                 // weights of half-step 2 ks + 2
-      STORE(1, 1, ra_0);
-      SYNC();
-      LOADA(ra_0);                                    // activations of K-step ks + 2: set 0 is free
+      load_b(gb_0, 0);                                 // weights of half-step 2 ks + 2
+      split_store(1, 1, ra_0);
+      __syncthreads();
+      load_a(ra_0);                                    // activations of K-step ks + 2: set 0 is free
       compute(1, gb_1);                                // half-step 2 ks + 1
-      LOADB(gb_1, 1);                                 // weights of half-step 2 ks + 3
-      STORE(0, 0, ra_1);
-      SYNC();
+      load_b(gb_1, 1);                                 // weights of half-step 2 ks + 3
+      split_store(0, 0, ra_1);
+      __syncthreads();
       compute(0, gb_0);                                // half-step 2 ks + 2
-      LOADB(gb_0, 0);                                 // weights of half-step 2 ks + 4
-      STORE(1, 1, ra_1);
-      SYNC();
-      LOADA(ra_1);                                    // K-step ks + 3
+      load_b(gb_0, 0);                                 // weights of half-step 2 ks + 4
+      split_store(1, 1, ra_1);
+      __syncthreads();
+      load_a(ra_1);                                    // K-step ks + 3
       compute(1, gb_1);                                // half-step 2 ks + 3
-      LOADB(gb_1, 1);                                 // weights of half-step 2 ks + 5
-      STORE(0, 0, ra_0);                         // K-step ks + 2, first half (never computed when ks + 2 == nk)
+      load_b(gb_1, 1);                                 // weights of half-step 2 ks + 5
+      split_store(0, 0, ra_0);                         // K-step ks + 2, first half (never computed when ks + 2 == nk)
     }
     if (ks < nk) {                                     // one K-step left: in set 0, its first half is in buffer 0
       __syncthreads();
@@ -380,9 +329,6 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
         for (int e = 0; e < 16; ++e) acc[mi][ni][e] *= f16_desc;
   }
   igemm_epilogue<BM, BN, MODE, BNB, (BN >= 128 ? BN / 64 : 1)>(p, acc, acc2, m0, n0, wm, wn, lane, Mrows, HW, Wrow, ph, pw, lds);
-#ifdef XAS_DRAIN_AT_END
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
 }
 
 // ------------------------------------------------------------------------------------
@@ -471,23 +417,13 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
 #pragma unroll
       for (int mi = 0; mi < C::MI; ++mi)
         fa[pc][mi] = *reinterpret_cast<const uint4*>(sb + pc * PLANE + (mi * 32 + i) * XLDH + xswz(i, hh));
-#ifdef XAS_FRAG_AGPR
-    uint4 gq[P][C::NI];
-#pragma unroll
-    for (int pc = 0; pc < P; ++pc)
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni) gq[pc][ni] = frag_reg(gb[pc][ni]);
-    frag_regs(fa);
-#else
-    const uint4 (&gq)[P][C::NI] = gb;
-#endif
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int mi = 0; mi < C::MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < C::NI; ++ni)
-          acc[mi][ni] = mfma_piece<P>(gq[Products<P>::B[t]][ni], fa[Products<P>::A[t]][mi], acc[mi][ni]);
+          acc[mi][ni] = mfma_piece<P>(gb[Products<P>::B[t]][ni], fa[Products<P>::A[t]][mi], acc[mi][ni]);
   };
   uint4 gb_0[P][C::NI], gb_1[P][C::NI];
   load_a(ra_0);                                          // tile 0: K-steps 0 and 1
@@ -680,20 +616,7 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
       for (int mi = 0; mi < C::MI; ++mi)
         fa[pc][mi] = *reinterpret_cast<const uint4*>(S + pc * plane_b + fbase[mi] + tapoff);
   };
-  auto mfmas = [&](const uint4 (&fa_)[P][C::MI], const uint4 (&gb_)[P][C::NI]) {
-#ifdef XAS_FRAG_AGPR
-    uint4 fa[P][C::MI], gb[P][C::NI];
-#pragma unroll
-    for (int pc = 0; pc < P; ++pc) {
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi) fa[pc][mi] = frag_reg(fa_[pc][mi]);
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni) gb[pc][ni] = frag_reg(gb_[pc][ni]);
-    }
-#else
-    const uint4 (&fa)[P][C::MI] = fa_;
-    const uint4 (&gb)[P][C::NI] = gb_;
-#endif
+  auto mfmas = [&](const uint4 (&fa)[P][C::MI], const uint4 (&gb)[P][C::NI]) {
 #pragma unroll
     for (int t = 0; t < Products<P>::N; ++t)
 #pragma unroll
@@ -738,9 +661,6 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
         for (int e = 0; e < 16; ++e) acc[mi][ni][e] *= f16_desc;
   }
   igemm_epilogue<BM, BN, MODE, false, (BN == 128 ? 2 : 1)>(p, acc, acc2, m0, n0, wm, wn, lane, Mrows, H * W, W, 0, 0, lds);
-#ifdef XAS_DRAIN_AT_END
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
 }
 
 template <int BN>
@@ -752,7 +672,7 @@ constexpr size_t igemm_x6t_lds(int P) {
 
 // does the tap-reuse kernel take this problem?  (stride-1 3x3, same-size maps, 128-row tiles that are whole patches)
 static bool x6t_takes(const IgemmParams& p, int bm, int phases) {
-  if (p.tune & (1 << 22)) return false;                // tune bit 22: implicit-GEMM kernel for every shape
+  if (p.tune & XAS_TUNE_GENERAL_KERNELS) return false;   // implicit-GEMM kernel for every shape
   if (bm != 128 || phases != 1 || p.bnb_x) return false;
   return tap_tile_ok(p.R, p.S, p.stride, p.pad, p.Hs, p.Ws, p.Hd, p.Wd, p.Cs, p.N);
 }
@@ -783,9 +703,6 @@ constexpr size_t igemm_x6_lds(int P, bool bnb) {
   size_t b = ((size_t)BM * (BN / (BN >= 128 ? BN / 64 : 1) + 4) + 2 * 256) * sizeof(float);   // epilogue staging (64-column passes for BN >= 128) + partial-combine area
   size_t c = bnb ? ((size_t)2 * TileCfg<BM, BN>::WAVES_M * 32 * (BN + 4) + 2 * 256) * sizeof(float) : 0;   // bn-backward epilogue staging
   a = a > b ? (a > c ? a : c) : (b > c ? b : c);
-#ifdef XAS_X6_LDS_FLOOR                              // ablation builds: same blocks per CU for every variant
-  a = a > XAS_X6_LDS_FLOOR ? a : XAS_X6_LDS_FLOOR;
-#endif
   return a;
 }
 
@@ -840,7 +757,7 @@ static int launch_igemm_x6t(const IgemmParams& p, int Mrows_max, hipStream_t st)
   return 0;
 }
 
-// pure GEMM with an even number of K-steps: what igemm_x6p_kernel is written for (tune bit 26: never).
+// pure GEMM with an even number of K-steps: what igemm_x6p_kernel is written for (XAS_TUNE_NO_X6P: never).
 // Measured alone at 384 / 256 images (r05): K = 64: 505 -> 437 us forward (4.6 TB/s), 427 -> 362 us data gradient; K = 128:
 // -5 % / -9 %; K >= 256: +-2 % either way.  In the step (in-box, interleaved, 3 rounds) taking every K is 0.2-0.3 ms better
 // than stopping at 128: XAS_X6P_MAX_K bounds it for experiments.
@@ -848,8 +765,8 @@ static int launch_igemm_x6t(const IgemmParams& p, int Mrows_max, hipStream_t st)
 #define XAS_X6P_MAX_K 4096
 #endif
 static bool x6p_takes(const IgemmParams& p, int mode, int phases) {
-  if (p.tune & (1 << 26)) return false;
-  if (p.Cs > XAS_X6P_MAX_K && !(p.tune & (1 << 27))) return false;
+  if (p.tune & XAS_TUNE_NO_X6P) return false;
+  if (p.Cs > XAS_X6P_MAX_K && !(p.tune & XAS_TUNE_X6P_ANY_K)) return false;
   const int hr = mode == 0 ? p.Hrow : p.Hd, wr = mode == 0 ? p.Wrow : p.Wd;
   return p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && phases == 1 && p.Cs % (2 * BK) == 0 && p.Hs == hr && p.Ws == wr &&
          !p.t2d_tw && !p.bnb_x && p.a_amax != nullptr && (p.Cd & 3) == 0;
@@ -908,7 +825,7 @@ static int launch_igemm_x6_p(const IgemmParams& p, int Mrows_max, int phases, hi
       return launch_igemm_x6_t<128, 32, 1, P, true>(p, Mrows_max, phases, st);
     }
   }
-  if (!(p.tune & (1 << 23))) {                         // tune bit 23: no 64 x 256 tiles
+  if (!(p.tune & XAS_TUNE_NO_WIDE_TILES)) {
     pick_tile(p.Cd, Mrows_max, phases, &bm, &bn, true);
     if constexpr (P == 2) {
       if (bn == 256 && x6p_takes(p, MODE, phases)) return launch_igemm_x6p<MODE>(p, Mrows_max, st);
@@ -969,7 +886,7 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
   const int nkt = p.ntiles / p.nct;
   const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
   int split, tile;
-  if (p.tune & 1) {                                  // ALL tiles of a pixel split on one XCD (splits a multiple of 8): x and dy
+  if (p.tune & XAS_TUNE_WGRAD_SPLIT_XCD) {           // ALL tiles of a pixel split on one XCD (splits a multiple of 8): x and dy
     split = xcd + 8 * (qb / p.ntiles);               // of the split are fetched into ONE L2; KK-tiles of a Cout tile adjacent
     const int t = qb - (qb / p.ntiles) * p.ntiles;
     tile = (t / nkt) + (t - (t / nkt) * nkt) * p.nct;
@@ -983,9 +900,6 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
   const int co0 = (tile % p.nct) * BM, nn0 = (tile / p.nct) * BN;
   const int mbeg = split * p.m_per_split, mend = min(p.M, mbeg + p.m_per_split);
   const int HWo = p.Ho * p.Wo;
-#ifdef XAS_WGRAD_PRIO
-  __builtin_amdgcn_s_setprio(XAS_WGRAD_PRIO);
-#endif
   float f16_sd = kF16AScale, f16_sx = kF16AScale, f16_desc = 1.f;      // P == 2: scales of dy and of x, scale of the result
   if (P == 2) {                                        // (each operand from its maximum; the launchers insist on both)
     float id = 1.f / kF16AScale, ix = 1.f / kF16AScale;
@@ -1101,8 +1015,6 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
         fb[pc][ni] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       }
     }
-    frag_regs(fa);
-    frag_regs(fb);
 #pragma unroll
     for (int t = 0; t < Products<P>::N; ++t)
 #pragma unroll
@@ -1158,9 +1070,6 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
         if (nn < p.KK) slab[(size_t)co * p.KK + nn] = P == 2 ? acc[mi][ni][reg] * f16_desc : acc[mi][ni][reg];
       }
     }
-#ifdef XAS_DRAIN_AT_END
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
 }
 
 // ------------------------------------------------------------------------------------
@@ -1299,7 +1208,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
       const s16x4_t hi = tr_read(sb, fragA + pc * XH * SA + 4 * SA);
       fa[pc] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
     }
-    frag_regs(fa);
     // halo pixel of the slice's first pixel for tap (0, 0) offset: row ks (two rows 2 (ks & 3) of image ks >> 2 when 8-wide)
     const int wbase = tw == 16 ? (ks + 1) * hw + 1 : (ks >> 2) * npix_img + (2 * (ks & 3) + 1) * hw + 1;
 #pragma unroll
@@ -1315,7 +1223,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
           const s16x4_t hi = tr_read(SX, xo + pc * xplane + 4 * XPB);
           fb[pc] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
         }
-        frag_regs(fb);
 #pragma unroll
         for (int k = 0; k < Products<P>::N; ++k)
           acc[ti] = mfma_piece<P>(fa[Products<P>::A[k]], fb[Products<P>::B[k]], acc[ti]);
@@ -1353,9 +1260,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
       }
     }
   }
-#ifdef XAS_DRAIN_AT_END
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
 }
 
 // plan of the tap-reuse weight gradient; false: the shape is not taken (wgrad_x6_kernel does it)
@@ -1424,7 +1328,7 @@ static int launch_wgrad_x6_t(const WgradParams& p, int splits, hipStream_t st) {
   q.nct = (int)cdiv(p.Cout, BM);
   q.ntiles = q.nct * (int)cdiv(p.KK, BN);
   q.nsplits = splits;
-  q.tune = (splits % 8 == 0) ? 1 : 0;                // wgrad_plan rounds the split count to a multiple of 8 when it can
+  q.tune = (splits % 8 == 0) ? XAS_TUNE_WGRAD_SPLIT_XCD : 0;   // wgrad_plan rounds the split count to a multiple of 8 when it can
   dim3 grid(q.tune ? (unsigned)(splits * q.ntiles) : (unsigned)(8 * cdiv((long)splits * q.nct, 8) * (q.ntiles / q.nct)));
   hipLaunchKernelGGL((wgrad_x6_kernel<BM, BN, P>), grid, dim3(256), lds, st, q);
   XAS_LAUNCH_CHECK();

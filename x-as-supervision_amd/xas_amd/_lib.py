@@ -5,7 +5,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('XAS_HIP_LIB') or os.path.join(_HERE, 'libxas_hip.so')   # override: ablation / A-B builds (tools/build_abl.py, tools/gpu/ab_lib.sh)
+LIB_PATH = os.environ.get('XAS_HIP_LIB') or os.path.join(_HERE, 'libxas_hip.so')   # override: A/B builds (tools/build_variant.py, tools/gpu/ab_lib.sh)
 _lib = None
 ABI_VERSION = 3          # include/xas_hip.h / csrc/abi.hip: xas_abi_version()
 
@@ -24,6 +24,18 @@ class ConvShape(ctypes.Structure):
 # xas_hip.h XAS_PREC_*: arithmetic of the MFMA convolutions.  ConvShape.mode = 0 (process default) or 1 + one of these.
 PREC_F32, PREC_BF16, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3
 PREC_NAMES = {'f32': PREC_F32, 'bf16': PREC_BF16, 'bf16x6': PREC_BF16X6, 'f16x3': PREC_F16X3}
+
+# xas_hip.h XAS_TUNE_*: flags of xas_set_tuning (kernel variants for coverage tests and A/B runs; 0 = shipped).  The header
+# documents each one; tests/test_abi.py keeps the two tables equal.
+TUNE_WGRAD_SPLIT_XCD = 1
+TUNE_PLAIN_KLOOP, TUNE_GLOBAL_LOAD, TUNE_WGRAD_GLOBAL_LOAD = 32, 64, 128
+TUNE_WGRAD_ALT_ORDER, TUNE_WGRAD_PLAIN_KLOOP = 8192, 524288
+TUNE_SLAB_SHIFT, TUNE_SLAB_MASK = 15, 3
+TUNE_SLAB_512, TUNE_SLAB_128, TUNE_SLAB_64 = 32768, 65536, 98304
+TUNE_COL_REDUCE_LEAN = 262144
+TUNE_GENERAL_KERNELS = 1 << 22       # no tap re-use conv kernels AND no streaming batch-norm kernels
+TUNE_NO_WIDE_TILES, TUNE_NO_STEM_WGRAD, TUNE_STEM_FWD_F32 = 1 << 23, 1 << 24, 1 << 25
+TUNE_NO_X6P, TUNE_X6P_ANY_K = 1 << 26, 1 << 27
 
 
 # name -> (argument codes, return code).  's' = pointer to ConvShape.  Last 'p' is the stream
