@@ -152,6 +152,30 @@ int xas_patch_to_world_bwd(const float* kps, const float* grad_world, const floa
                            float rect_width, int flags, float* grad_kps, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * World -> patch geometry (the other direction), all hypotheses in one launch.
+ * Replaces modules/util.py:155-168 -> :116-125 (world -> image) and :98-113 (image -> patch), and with
+ * pre_rot / pelvis_origin the front of project_smpl_to_patch_kps (:376-382: torch.bmm(joints, global_rot) * 1000
+ * + convert_pelvis_to_world, :343-352, whose batched torch.linalg.inv becomes a closed-form adjugate).
+ * pts [B][Hy][K][3]; pre_rot [B][3][3] or NULL: p <- (p . pre_rot[b]) * pre_scale (row vector times matrix);
+ * pelvis_origin != 0: p <- p + inv(rot_world)(pelvis - trans_world); camera arrays as xas_patch_to_world_fwd;
+ * out [B][Hy][K][3].  No clamps: a camera-space depth <= 0 gives what IEEE division gives.
+ * flags: XAS_GEO_NORM (normalised patch coordinates), XAS_GEO_IMAGE (stop after world -> image: u px, v px, depth mm),
+ * XAS_GEO_WORLD (stop after the rotation / pelvis shift: world mm - convert_verts, :367-373, and :343-352 itself).
+ * Backward: grad_pts, and with pre_rot grad_pre_rot [B][3][3] (sum over the Hy*K points of a sample, one block per
+ * sample, fixed order, no atomics: bit-reproducible).  Camera arrays receive no gradient.
+ * ---------------------------------------------------------------------------------- */
+#define XAS_GEO_WORLD 16
+int xas_world_to_patch_fwd(const float* pts, const float* pre_rot, float pre_scale, int pelvis_origin,
+                           const float* trans_image, const float* k_mat, const float* pelvis,
+                           const float* rot_world, const float* trans_world, int B, int Hy, int K,
+                           float image_size, float rect_width, int flags, float* out, void* stream);
+int xas_world_to_patch_bwd(const float* pts, const float* grad_out, const float* pre_rot, float pre_scale,
+                           int pelvis_origin, const float* trans_image, const float* k_mat, const float* pelvis,
+                           const float* rot_world, const float* trans_world, int B, int Hy, int K,
+                           float image_size, float rect_width, int flags, float* grad_pts, float* grad_pre_rot,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Line-mask renderer fused with the max over lines.
  * Replaces modules/util.py:21-59 (about 25 ATen kernels, 419 MB intermediates) plus
  * torch.max(dim=1) at modules/model.py:94,96.

@@ -2,6 +2,8 @@
 //
 // patch_to_world : modules/util.py:128-152 -> :61-95, all hypotheses in one launch, with
 //                  closed-form 2x2 / 3x3 inverses instead of two batched LU solves.
+// world_to_patch : modules/util.py:155-168 -> :116-125, :98-113, the other direction, with the optional row-vector
+//                  rotation, scale and pelvis shift of project_smpl_to_patch_kps (:356-383, :343-352) in front of it.
 // draw_lines_max : modules/util.py:21-59 + torch.max(dim=1) at modules/model.py:94,96.
 //                  max_l exp(e_l) == exp(max_l e_l): one exp per pixel, nothing but the
 //                  [B,1,S,S] mask ever reaches HBM (the reference keeps ten 419 MB
@@ -119,6 +121,154 @@ __global__ void patch_to_world_bwd_kernel(const float* __restrict__ kps, const f
     }
   }
   gk[i * 3] = d0; gk[i * 3 + 1] = d1; gk[i * 3 + 2] = d2;
+}
+
+// ------------------------------------------------------------------ world -> patch
+struct ProjParams {
+  float a00, a01, a10, a11, t0, t1;   // crop affine (forward)
+  float fx, fy, cx, cy, pz;           // intrinsics, pelvis depth
+  float r[9];                         // rot_world row-major
+  float tw[3];
+  float pw[3];                        // pelvis in world coordinates (pelvis_origin), else 0
+  float g[9];                         // pre_rot row-major (has_rot)
+};
+
+__device__ __forceinline__ ProjParams load_proj(const float* pre_rot, int pelvis_origin, const float* ti, const float* km,
+                                                const float* pv, const float* rw, const float* tw, int b, int flags) {
+  ProjParams c;
+  const float* R = rw + b * 9;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) c.r[e] = R[e];
+  c.tw[0] = tw[b * 3]; c.tw[1] = tw[b * 3 + 1]; c.tw[2] = tw[b * 3 + 2];
+  const float* Kc = km + b * 9;
+  c.fx = Kc[0]; c.fy = Kc[4]; c.cx = Kc[2]; c.cy = Kc[5];
+  c.a00 = c.a11 = 1.f; c.a01 = c.a10 = c.t0 = c.t1 = 0.f; c.pz = 0.f;
+  if (!(flags & (XAS_GEO_IMAGE | XAS_GEO_WORLD))) {
+    const float* A = ti + b * 6;
+    c.a00 = A[0]; c.a01 = A[1]; c.t0 = A[2]; c.a10 = A[3]; c.a11 = A[4]; c.t1 = A[5];
+    c.pz = pv[b * 3 + 2];
+  }
+  c.pw[0] = c.pw[1] = c.pw[2] = 0.f;
+  if (pelvis_origin) {                                 // inv(rot_world) (pelvis - trans_world), adjugate / determinant (util.py:350)
+    const float m00 = R[4] * R[8] - R[5] * R[7], m01 = R[2] * R[7] - R[1] * R[8], m02 = R[1] * R[5] - R[2] * R[4];
+    const float m10 = R[5] * R[6] - R[3] * R[8], m11 = R[0] * R[8] - R[2] * R[6], m12 = R[2] * R[3] - R[0] * R[5];
+    const float m20 = R[3] * R[7] - R[4] * R[6], m21 = R[1] * R[6] - R[0] * R[7], m22 = R[0] * R[4] - R[1] * R[3];
+    const float d3 = R[0] * m00 + R[1] * m10 + R[2] * m20;
+    const float q0 = pv[b * 3] - c.tw[0], q1 = pv[b * 3 + 1] - c.tw[1], q2 = pv[b * 3 + 2] - c.tw[2];
+    c.pw[0] = m00 / d3 * q0 + m01 / d3 * q1 + m02 / d3 * q2;
+    c.pw[1] = m10 / d3 * q0 + m11 / d3 * q1 + m12 / d3 * q2;
+    c.pw[2] = m20 / d3 * q0 + m21 / d3 * q1 + m22 / d3 * q2;
+  }
+  if (pre_rot) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) c.g[e] = pre_rot[b * 9 + e];
+  }
+  return c;
+}
+
+// steps 1-2: (p . pre_rot) * pre_scale + pelvis_world  (row vector times matrix, torch.bmm(joints, global_rot), util.py:376-380)
+__device__ __forceinline__ void to_world(const ProjParams& c, bool has_rot, float scale, float& p0, float& p1, float& p2) {
+  if (has_rot) {
+    const float q0 = (p0 * c.g[0] + p1 * c.g[3] + p2 * c.g[6]) * scale;
+    const float q1 = (p0 * c.g[1] + p1 * c.g[4] + p2 * c.g[7]) * scale;
+    const float q2 = (p0 * c.g[2] + p1 * c.g[5] + p2 * c.g[8]) * scale;
+    p0 = q0; p1 = q1; p2 = q2;
+  }
+  p0 += c.pw[0]; p1 += c.pw[1]; p2 += c.pw[2];
+}
+
+__global__ void world_to_patch_fwd_kernel(const float* __restrict__ pts, const float* pre_rot, float pre_scale,
+                                          int pelvis_origin, const float* ti, const float* km, const float* pv,
+                                          const float* rw, const float* tw, int B, int HK, float S, float rect, int flags,
+                                          float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * HK) return;
+  const int b = i / HK;
+  const ProjParams c = load_proj(pre_rot, pelvis_origin, ti, km, pv, rw, tw, b, flags);
+  float p0 = pts[i * 3], p1 = pts[i * 3 + 1], p2 = pts[i * 3 + 2];
+  to_world(c, pre_rot != nullptr, pre_scale, p0, p1, p2);
+  if (flags & XAS_GEO_WORLD) {                         // world mm (convert_verts, convert_pelvis_to_world)
+    out[i * 3] = p0; out[i * 3 + 1] = p1; out[i * 3 + 2] = p2;
+    return;
+  }
+  const float c0 = c.r[0] * p0 + c.r[1] * p1 + c.r[2] * p2 + c.tw[0];
+  const float c1 = c.r[3] * p0 + c.r[4] * p1 + c.r[5] * p2 + c.tw[1];
+  const float c2 = c.r[6] * p0 + c.r[7] * p1 + c.r[8] * p2 + c.tw[2];
+  const float u = c0 / c2 * c.fx + c.cx, v = c1 / c2 * c.fy + c.cy;      // no clamp: c2 <= 0 gives what IEEE division gives
+  if (flags & XAS_GEO_IMAGE) {                         // world -> image only (u px, v px, depth mm), util.py:116-125
+    out[i * 3] = u; out[i * 3 + 1] = v; out[i * 3 + 2] = c2;
+    return;
+  }
+  float z = (c2 - c.pz) / (1.0f / S * rect);
+  float x = c.a00 * u + c.a01 * v + c.t0;
+  float y = c.a10 * u + c.a11 * v + c.t1;
+  if (flags & XAS_GEO_NORM) {
+    x = x / (S - 1.f) * 2.f - 1.f;
+    y = y / (S - 1.f) * 2.f - 1.f;
+    z = z / (S - 1.f);
+  }
+  out[i * 3] = x; out[i * 3 + 1] = y; out[i * 3 + 2] = z;
+}
+
+// One block per sample: its threads walk the sample's Hy*K points (grad_pts), and the nine sums of grad_pre_rot are formed
+// in a FIXED order (per-thread strided sum, butterfly wave sum, waves in order through LDS) - no floating-point atomics, so
+// the op is bit-reproducible run to run.
+constexpr int kProjBwdThreads = 256;
+
+__global__ __launch_bounds__(kProjBwdThreads) void world_to_patch_bwd_kernel(
+    const float* __restrict__ pts, const float* __restrict__ go, const float* pre_rot, float pre_scale, int pelvis_origin,
+    const float* ti, const float* km, const float* pv, const float* rw, const float* tw, int HK, float S, float rect,
+    int flags, float* __restrict__ gp, float* __restrict__ grot) {
+  __shared__ float sm[20];
+  const int b = blockIdx.x;
+  const ProjParams c = load_proj(pre_rot, pelvis_origin, ti, km, pv, rw, tw, b, flags);
+  const bool has_rot = pre_rot != nullptr;
+  float acc[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) acc[e] = 0.f;
+  for (int n = threadIdx.x; n < HK; n += kProjBwdThreads) {
+    const size_t i = (size_t)b * HK + n;
+    const float s0 = pts[i * 3], s1 = pts[i * 3 + 1], s2 = pts[i * 3 + 2];
+    float g0 = go[i * 3], g1 = go[i * 3 + 1], g2 = go[i * 3 + 2];
+    float d0, d1, d2;                                  // gradient w.r.t. the world point
+    if (flags & XAS_GEO_WORLD) {
+      d0 = g0; d1 = g1; d2 = g2;
+    } else {
+      float p0 = s0, p1 = s1, p2 = s2;
+      to_world(c, has_rot, pre_scale, p0, p1, p2);
+      const float c0 = c.r[0] * p0 + c.r[1] * p1 + c.r[2] * p2 + c.tw[0];
+      const float c1 = c.r[3] * p0 + c.r[4] * p1 + c.r[5] * p2 + c.tw[1];
+      const float c2 = c.r[6] * p0 + c.r[7] * p1 + c.r[8] * p2 + c.tw[2];
+      if (!(flags & XAS_GEO_IMAGE)) {
+        if (flags & XAS_GEO_NORM) { g0 = g0 * 2.f / (S - 1.f); g1 = g1 * 2.f / (S - 1.f); g2 = g2 / (S - 1.f); }
+        const float e0 = c.a00 * g0 + c.a10 * g1, e1 = c.a01 * g0 + c.a11 * g1;
+        g0 = e0; g1 = e1;
+        g2 = g2 / (1.0f / S * rect);
+      }
+      const float k0 = g0 * c.fx / c2, k1 = g1 * c.fy / c2;             // d/dc0, d/dc1
+      const float k2 = g2 - (k0 * c0 + k1 * c1) / c2;                   // d/dc2
+      d0 = c.r[0] * k0 + c.r[3] * k1 + c.r[6] * k2;
+      d1 = c.r[1] * k0 + c.r[4] * k1 + c.r[7] * k2;
+      d2 = c.r[2] * k0 + c.r[5] * k1 + c.r[8] * k2;
+    }
+    if (has_rot) {
+      d0 *= pre_scale; d1 *= pre_scale; d2 *= pre_scale;
+      acc[0] += s0 * d0; acc[1] += s0 * d1; acc[2] += s0 * d2;
+      acc[3] += s1 * d0; acc[4] += s1 * d1; acc[5] += s1 * d2;
+      acc[6] += s2 * d0; acc[7] += s2 * d1; acc[8] += s2 * d2;
+      const float e0 = c.g[0] * d0 + c.g[1] * d1 + c.g[2] * d2;
+      const float e1 = c.g[3] * d0 + c.g[4] * d1 + c.g[5] * d2;
+      const float e2 = c.g[6] * d0 + c.g[7] * d1 + c.g[8] * d2;
+      d0 = e0; d1 = e1; d2 = e2;
+    }
+    gp[i * 3] = d0; gp[i * 3 + 1] = d1; gp[i * 3 + 2] = d2;
+  }
+  if (!has_rot) return;                                // uniform over the block
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    const float r = block_sum(acc[e], sm);
+    if (threadIdx.x == 0) grot[b * 9 + e] = r;
+  }
 }
 
 // ------------------------------------------------------------------ line renderer
@@ -305,6 +455,44 @@ extern "C" int xas_patch_to_world_bwd(const float* kps, const float* grad_world,
   hipLaunchKernelGGL(patch_to_world_bwd_kernel, dim3(cdiv(n, 128)), dim3(128), 0, as_stream(stream), kps, grad_world,
                      trans_image, k_mat, pelvis, rot_world, trans_world, B, Hy * K, image_size, rect_width, flags,
                      grad_kps);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_world_to_patch_fwd(const float* pts, const float* pre_rot, float pre_scale, int pelvis_origin,
+                                      const float* trans_image, const float* k_mat, const float* pelvis,
+                                      const float* rot_world, const float* trans_world, int B, int Hy, int K,
+                                      float image_size, float rect_width, int flags, float* out, void* stream) {
+  XAS_REQUIRE(pts && out && k_mat && rot_world && trans_world, "world_to_patch: null buffer");
+  XAS_REQUIRE((flags & (XAS_GEO_IMAGE | XAS_GEO_WORLD)) || (trans_image && pelvis), "world_to_patch: null crop / pelvis buffer");
+  XAS_REQUIRE(!pelvis_origin || pelvis, "world_to_patch: pelvis_origin needs the pelvis");
+  XAS_REQUIRE(!(flags & ~(XAS_GEO_NORM | XAS_GEO_IMAGE | XAS_GEO_WORLD)), "world_to_patch: unknown flag in %d", flags);
+  XAS_REQUIRE(B > 0 && Hy > 0 && K > 0 && (long)B * Hy * K <= 0x7fffffffL / 3, "world_to_patch: bad shape B=%d Hy=%d K=%d",
+              B, Hy, K);
+  const int n = B * Hy * K;
+  hipLaunchKernelGGL(world_to_patch_fwd_kernel, dim3(cdiv(n, 128)), dim3(128), 0, as_stream(stream), pts, pre_rot,
+                     pre_scale, pelvis_origin, trans_image, k_mat, pelvis, rot_world, trans_world, B, Hy * K, image_size,
+                     rect_width, flags, out);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_world_to_patch_bwd(const float* pts, const float* grad_out, const float* pre_rot, float pre_scale,
+                                      int pelvis_origin, const float* trans_image, const float* k_mat, const float* pelvis,
+                                      const float* rot_world, const float* trans_world, int B, int Hy, int K,
+                                      float image_size, float rect_width, int flags, float* grad_pts, float* grad_pre_rot,
+                                      void* stream) {
+  XAS_REQUIRE(pts && grad_out && grad_pts && k_mat && rot_world && trans_world, "world_to_patch bwd: null buffer");
+  XAS_REQUIRE((flags & (XAS_GEO_IMAGE | XAS_GEO_WORLD)) || (trans_image && pelvis),
+              "world_to_patch bwd: null crop / pelvis buffer");
+  XAS_REQUIRE(!pelvis_origin || pelvis, "world_to_patch bwd: pelvis_origin needs the pelvis");
+  XAS_REQUIRE(!pre_rot == !grad_pre_rot, "world_to_patch bwd: grad_pre_rot goes with pre_rot");
+  XAS_REQUIRE(!(flags & ~(XAS_GEO_NORM | XAS_GEO_IMAGE | XAS_GEO_WORLD)), "world_to_patch bwd: unknown flag in %d", flags);
+  XAS_REQUIRE(B > 0 && Hy > 0 && K > 0 && (long)B * Hy * K <= 0x7fffffffL / 3,
+              "world_to_patch bwd: bad shape B=%d Hy=%d K=%d", B, Hy, K);
+  hipLaunchKernelGGL(world_to_patch_bwd_kernel, dim3(B), dim3(kProjBwdThreads), 0, as_stream(stream), pts, grad_out,
+                     pre_rot, pre_scale, pelvis_origin, trans_image, k_mat, pelvis, rot_world, trans_world, Hy * K,
+                     image_size, rect_width, flags, grad_pts, grad_pre_rot);
   XAS_LAUNCH_CHECK();
   return 0;
 }

@@ -3,8 +3,11 @@
 Built here: `draw_lines` (+ the fused `draw_lines_max` the model actually consumes),
 `convert_patch_to_world` (all hypotheses in one launch, closed-form 2x2 / 3x3 inverses),
 `make_coordinate_grid`, `smpl_to_h36m`, and for the evaluation path `convert_patch_to_image`,
-`triangulation` / `batch_triangulate` (device DLT, no batched SVD).  The reference's dead code
-(rule_transformation, my_truncated_normal, project_smpl_to_patch_kps has no caller) is not rebuilt.
+`triangulation` / `batch_triangulate` (device DLT, no batched SVD), and the SMPL side of the geometry:
+`project_smpl_to_patch_kps`, `convert_pelvis_to_world` (one world->patch launch, ops_head.world_to_patch) and `flip_3D`.
+`convert_world_to_patch` / `convert_world_to_image` / `convert_image_to_patch` stay the reference's (the device version is
+ops_head.world_to_patch).  The reference's dead code (rule_transformation, my_truncated_normal) is not rebuilt
+(SURVEY 2, row 6).
 """
 import torch
 
@@ -82,6 +85,29 @@ def smpl_to_h36m(verts, h36m_regressor):
     return j - j[:, 0:1]
 
 
+def convert_pelvis_to_world(x, mode):
+    """Pelvis of camera `mode` in world coordinates, inv(rot_world) (pelvis - trans_world), [B,1,3] (util.py:343-352)."""
+    pelvis = x['{}_pelvis'.format(mode)]
+    zero = torch.zeros(pelvis.shape[0], 1, 3, device=pelvis.device, dtype=torch.float32)
+    return ops_head.world_to_patch(zero, x, mode, pelvis_origin=True, stop_at_world=True)
+
+
+def project_smpl_to_patch_kps(global_rot_params, pose_params, shape_params,
+                              smpl_layer, h36m_regressor, x, mode, convert_verts=False):
+    """SMPL parameters -> the 18 H36M joints in the patch of camera `mode`, pixels [B,18,3] (util.py:356-383); with
+    `convert_verts` the vertices in world mm instead.  The global rotation is applied after the layer (row vector times
+    `global_rot_params` [B,3,3]), so the layer runs with a zero root rotation.  SMPL skinning, the joint regression and
+    one world->patch launch (rotation, m -> mm, pelvis shift, projection); differentiable in the three parameter sets."""
+    full_pose = torch.cat([pose_params.new_zeros(pose_params.shape[0], 3), pose_params], dim=1)
+    verts, _ = smpl_layer(full_pose, shape_params)
+    if convert_verts:
+        return ops_head.world_to_patch(verts, x, mode, pre_rot=global_rot_params, pre_scale=1000.0, pelvis_origin=True,
+                                       stop_at_world=True)
+    joints = smpl_to_h36m(verts, h36m_regressor)
+    return ops_head.world_to_patch(joints, x, mode, is_norm=False, pre_rot=global_rot_params, pre_scale=1000.0,
+                                   pelvis_origin=True)
+
+
 def random_rotation_3D(keypoints):
     """Random rotation about z in [-pi/4, pi/4] per sample (util.py:389-407; only with use_aug).  The angles are drawn
     from the CPU generator exactly as the reference does (torch.rand(B, 1)): same seed, same augmentation."""
@@ -90,6 +116,17 @@ def random_rotation_3D(keypoints):
     c, s, z, o = torch.cos(ang), torch.sin(ang), torch.zeros_like(ang), torch.ones_like(ang)
     rot = torch.stack([c, -s, z, s, c, z, z, z, o], dim=1).view(B, 3, 3)
     return torch.bmm(keypoints, rot.to(keypoints.dtype))
+
+
+def flip_3D(keypoints):
+    """Swap left and right of the legs (joints 1-3 / 4-6) or of the arms (11-13 / 14-16), chosen by one torch.rand(1) of the
+    CPU generator as the reference does (util.py:409-416)."""
+    order = list(range(keypoints.shape[1]))
+    if torch.rand(1) < 0.5:
+        order[1:7] = [4, 5, 6, 1, 2, 3]
+    else:
+        order[11:17] = [14, 15, 16, 11, 12, 13]
+    return keypoints[:, order]
 
 
 # names this mirror does not replace resolve, lazily, to the reference module behind it on sys.path

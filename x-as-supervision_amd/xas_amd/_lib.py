@@ -58,6 +58,8 @@ SIGNATURES = {
     'xas_head_softargmax_bwd_amax': ('ppppiiiiipppp', 'i'),
     'xas_patch_to_world_fwd': ('ppppppiiiffipp', 'i'),
     'xas_patch_to_world_bwd': ('pppppppiiiffipp', 'i'),
+    'xas_world_to_patch_fwd': ('ppfipppppiiiffipp', 'i'),
+    'xas_world_to_patch_bwd': ('pppfipppppiiiffippp', 'i'),
     'xas_lines_nblk': ('i', 'i'),
     'xas_draw_lines_max_fwd': ('plliippiufipp', 'i'),
     'xas_draw_lines_max_bwd': ('plliippiufipppp', 'i'),

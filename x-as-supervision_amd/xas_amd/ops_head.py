@@ -1,4 +1,4 @@
-"""Soft-argmax head, patch->world geometry and line-mask renderer as autograd ops over the C ABI."""
+"""Soft-argmax head, patch->world / world->patch geometry and line-mask renderer as autograd ops over the C ABI."""
 import torch
 
 from . import _lib
@@ -7,6 +7,7 @@ from ._lib import call, ptr, query
 HEAD_STATS = 16
 peak_probe = None        # measurement hook (tests): called with the int64 depth-peak indices [B,K,Hy] of every head forward
 GEO_NORM, GEO_MONO, GEO_PATCH = 1, 2, 4
+GEO_IMAGE, GEO_WORLD = 8, 16
 
 
 def _nhwc_storage(logits):
@@ -121,6 +122,55 @@ def patch_to_world(kps, trans_image, k_mat, pelvis, rot_world, trans_world, imag
         kps = kps.unsqueeze(1)
     flags = (GEO_NORM if is_norm else 0) | (GEO_MONO if mono else 0) | (GEO_PATCH if patch else 0)
     out = _PatchToWorld.apply(kps, trans_image, k_mat, pelvis, rot_world, trans_world, image_size, rect_width, flags)
+    return out.squeeze(1) if squeeze else out
+
+
+class _WorldToPatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts, pre_rot, ti, km, pv, rw, tw, pre_scale, pelvis_origin, image_size, rect_width, flags):
+        pts = pts.contiguous()
+        B, Hy, K, _ = pts.shape
+        rot = pre_rot.contiguous() if pre_rot is not None else None
+        cams = [t.contiguous().float() for t in (ti, km, pv, rw, tw)]
+        out = torch.empty_like(pts)
+        call('xas_world_to_patch_fwd', ptr(pts), ptr(rot), float(pre_scale), int(pelvis_origin), *[ptr(c) for c in cams],
+             B, Hy, K, float(image_size), float(rect_width), flags, ptr(out))
+        ctx.save_for_backward(pts, *cams, *(() if rot is None else (rot,)))
+        ctx.cfg = (float(pre_scale), int(pelvis_origin), float(image_size), float(rect_width), flags)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        pts, ti, km, pv, rw, tw, *rot = ctx.saved_tensors
+        rot = rot[0] if rot else None
+        B, Hy, K, _ = pts.shape
+        scale, origin, S, rect, flags = ctx.cfg
+        gp = torch.empty_like(pts)
+        grot = torch.empty_like(rot) if rot is not None else None
+        call('xas_world_to_patch_bwd', ptr(pts), ptr(go.contiguous()), ptr(rot), scale, origin, ptr(ti), ptr(km), ptr(pv),
+             ptr(rw), ptr(tw), B, Hy, K, S, rect, flags, ptr(gp), ptr(grot))
+        return (gp, grot) + (None,) * 10
+
+
+def world_to_patch(points, params, mode, is_norm=True, RECT_WIDTH=2000, pre_rot=None, pre_scale=1.0, pelvis_origin=False,
+                   stop_at_image=False, stop_at_world=False):
+    """World mm -> patch coordinates of camera `mode` of the batch dict (modules/util.py:155-168), points [B,K,3] or
+    [B,Hy,K,3].  With `pre_rot` [B,3,3] the points are first turned and scaled, (p . pre_rot) * pre_scale, and with
+    `pelvis_origin` moved to the pelvis in world coordinates (the front of project_smpl_to_patch_kps, util.py:376-380) - all
+    in the one launch.  `stop_at_image`: (u px, v px, depth mm) of util.py:116-125; `stop_at_world`: the world points
+    themselves.  Differentiable in `points` and `pre_rot`; the camera arrays are constants."""
+    squeeze = points.dim() == 3
+    if squeeze:
+        points = points.unsqueeze(1)
+    if points.dim() != 4 or points.shape[-1] != 3:
+        raise RuntimeError('world_to_patch: points must be [B,K,3] or [B,Hy,K,3]')
+    if pre_rot is not None and tuple(pre_rot.shape) != (points.shape[0], 3, 3):
+        raise RuntimeError('world_to_patch: pre_rot must be [B,3,3]')
+    flags = (GEO_NORM if is_norm else 0) | (GEO_IMAGE if stop_at_image else 0) | (GEO_WORLD if stop_at_world else 0)
+    key = lambda name: params['{}_{}'.format(mode, name)]
+    out = _WorldToPatch.apply(points.float(), None if pre_rot is None else pre_rot.float(), key('trans_image'), key('k_mat'),
+                              key('pelvis'), key('rot_world'), key('trans_world'), pre_scale, bool(pelvis_origin),
+                              key('img').shape[-1], RECT_WIDTH, flags)
     return out.squeeze(1) if squeeze else out
 
 
