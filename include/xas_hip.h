@@ -99,7 +99,10 @@ int xas_abi_version(void);
  * Replaces keypoint_detector_integral_multi.py:69-88 (softmax, six marginal sums, peak
  * pick, topk, two avg_pool1d, two gathers) and keypoint_detector_integral.py:48-63.
  *
- * logits  [B][H][W][K*D] (NHWC storage of the reference's [B, K*D, H, W]); D==H==W.
+ * logits  [B][H][W][K*D] (NHWC storage of the reference's [B, K*D, H, W]); D==H==W, the heat-map is a cube.
+ *          Accepted: D % 4 == 0 and 4 <= D <= 128 (input patches of side 4*D up to 512).  D in {4,8,16,32,64} runs on
+ *          the power-of-two kernel family (head.hip), every other D on the general one (head_any.hip); anything else
+ *          is refused with status 1 (xas_head_workspace_floats: 0) and a message that names this range.
  * num_hypo >= 1 with neighbor > 0 : multi-hypothesis head; num_hypo == 1 and
  * neighbor == 0 : single-hypothesis head (plain expectation along depth).
  * kps      [B][num_hypo][K][3]   normalised to [-1,1)
@@ -107,7 +110,7 @@ int xas_abi_version(void);
  * depth_prob_map [groups][K][D]  (depth marginal of the FIRST sample of each of `groups` equal sub-batches:
  *                                 sample 0 for groups = 1, multi.py:45; one per camera in a camera-batched pass)
  * stats    [B][K][XAS_HEAD_STATS] saved for backward (lse, X, Y, Z_h, S_h ...)
- * partial  workspace, xas_head_workspace_floats(B,K,D) floats
+ * partial  workspace, xas_head_workspace_floats(B,K,D) floats: [B][nchunk][K][3 + D] first-pass records
  * ---------------------------------------------------------------------------------- */
 #define XAS_HEAD_STATS 16
 size_t xas_head_workspace_floats(int B, int K, int D);

@@ -12,6 +12,7 @@
 // Pass 2 (head_finalize): one wave per (b,k): merge chunks, normalise, pick the depth
 // peaks (value desc, index asc), windowed expectation, write kps / indices / stats.
 #include "common.h"
+#include "head_any.h"
 
 namespace xas {
 
@@ -20,9 +21,13 @@ struct HeadGeom {
   int wshift;                                     // log2(W): W is a power of two, so pix -> (h, w) is shift/mask
 };
 
+// Power-of-two sides up to 64 keep the kernels of this file; every other size goes to the general family (head_any.hip).
+static bool pow2_family(int D) { return D >= 4 && D <= 64 && (D & (D - 1)) == 0; }
+
 static int make_geom(int B, int K, int D, HeadGeom* g) {
-  XAS_REQUIRE(B > 0 && K > 0 && D >= 4 && D <= 64 && (D & (D - 1)) == 0,
-              "head: need power-of-two depth_dim in [4,64], got B=%d K=%d D=%d", B, K, D);
+  // (the launchers send every other depth_dim that is a multiple of 4 in [4,128] to head_any.hip)
+  XAS_REQUIRE(B > 0 && K > 0 && pow2_family(D),
+              "head: depth_dim must be a multiple of 4 in [4,128] (heat-map cube D == H == W), got B=%d K=%d D=%d", B, K, D);
   g->B = B; g->K = K; g->D = D; g->W = D; g->HW = D * D;
   g->wshift = 0;
   while ((1 << g->wshift) < D) ++g->wshift;
@@ -252,6 +257,7 @@ __global__ void head_bwd_kernel(const float4* __restrict__ logits, const float* 
 using namespace xas;
 
 extern "C" size_t xas_head_workspace_floats(int B, int K, int D) {
+  if (!pow2_family(D)) return head_any_workspace_floats(B, K, D);
   HeadGeom g;
   if (make_geom(B, K, D, &g)) return 0;
   return (size_t)B * g.nchunk * K * g.rec;
@@ -260,6 +266,8 @@ extern "C" size_t xas_head_workspace_floats(int B, int K, int D) {
 extern "C" int xas_head_softargmax_fwd(const float* logits, int B, int K, int D, int num_hypo, int neighbor,
                                        float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                        float* partial, void* stream) {
+  if (!pow2_family(D))
+    return head_any_fwd(logits, B, K, D, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, partial, stream);
   HeadGeom g;
   if (make_geom(B, K, D, &g)) return 1;
   XAS_REQUIRE(logits && kps && depth_prob_map && stats && partial, "head fwd: null buffer");
@@ -286,6 +294,8 @@ extern "C" int xas_head_softargmax_fwd(const float* logits, int B, int K, int D,
 extern "C" int xas_head_softargmax_from_partials(const float* partial, int B, int K, int D, int nchunk, int num_hypo, int neighbor,
                                                  float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                                  void* stream) {
+  if (!pow2_family(D))
+    return head_any_from_partials(partial, B, K, D, nchunk, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, stream);
   HeadGeom g;
   if (make_geom(B, K, D, &g)) return 1;
   XAS_REQUIRE(partial && kps && depth_prob_map && stats && nchunk >= 1, "head from partials: null buffer");
@@ -309,6 +319,8 @@ extern "C" int xas_head_softargmax_bwd(const float* logits, const float* stats, 
 extern "C" int xas_head_softargmax_bwd_amax(const float* logits, const float* stats, const int64_t* z_idx,
                                             const float* grad_kps, int B, int K, int D, int num_hypo, int neighbor,
                                             float* grad_logits, float* coef, float* amax_out, void* stream) {
+  if (!pow2_family(D))
+    return head_any_bwd(logits, stats, z_idx, grad_kps, B, K, D, num_hypo, neighbor, grad_logits, coef, amax_out, stream);
   HeadGeom g;
   if (make_geom(B, K, D, &g)) return 1;
   XAS_REQUIRE(logits && stats && grad_kps && grad_logits && coef, "head bwd: null buffer");

@@ -13,15 +13,18 @@ class KPDetector3D(nn.Module):
         cfg.depth_dim = depth_dim
         cfg.num_layers = num_layers
         self.num_kp = num_kp
+        self.depth_dim = depth_dim
         self.net = get_pose_net(cfg, num_joints=num_kp)
         self.name = name
 
     def forward(self, x):
+        ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3D')
         kps, depth_prob_map = ops_head.softargmax_single(self.net(x), self.num_kp)
         return kps, depth_prob_map          # kps [B, 1, num_kp, 3], aligned with the multi-hypothesis layout
 
     def forward_groups(self, x, groups):
         """`groups` consecutive reference calls as one camera-batched pass (see KPDetector3DMulti.forward_groups)."""
+        ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3D')
         with ops_nn.bn_groups(groups):
             heatmap = self.net(x)
         return ops_head.softargmax_single(heatmap, self.num_kp, groups=groups)

@@ -1,6 +1,7 @@
 """Multi-hypothesis 3-D key-point detector (reference: modules/keypoint_detector_integral_multi.py:7-88).
 
-`net` (ResNet-50 + deconv head) produces logits [B, K*D, 64, 64] with NHWC storage; the softmax over
+`net` (ResNet-50 + deconv head) produces logits [B, K*D, D, D] with NHWC storage, D = depth_dim = input side / 4 (64 for
+the 256^2 patches of the shipped configurations; any multiple of 4 up to 128 is taken); the softmax over
 D*H*W, the three marginals, the depth-peak top-k and the windowed expectations run as ONE fused HIP
 reduction that reads the logits once (xas_head_softargmax_fwd) instead of ~15 ATen kernels and five
 passes over a 604 MB tensor.  Ties between equal peak scores resolve to the lower depth bin.
@@ -20,6 +21,7 @@ class KPDetector3DMulti(nn.Module):
         self.num_hypo = num_hypo
         self.neighbor_size = neighbor_size
         self.num_kp = num_kp
+        self.depth_dim = depth_dim
         self.net = get_pose_net(cfg, num_joints=num_kp)
         self.name = name
         # the final 1x1 convolution writes the head's first-pass records from its epilogue (forward half)
@@ -29,6 +31,7 @@ class KPDetector3DMulti(nn.Module):
         self.last_peak_indices = None      # int64 [B, K, num_hypo] of the latest forward (diagnostics / tests)
 
     def forward(self, x):
+        ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3DMulti')
         heatmap = self.net(x)
         kps, depth_prob_map, idx = ops_head.softargmax_multi(heatmap, self.num_kp, self.num_hypo, self.neighbor_size)
         self.last_peak_indices = idx
@@ -42,6 +45,7 @@ class KPDetector3DMulti(nn.Module):
         detector pass, model.py:231).  `x` is then the TAIL view [(G-P)*B, ...] of one image buffer [G*B, ...] whose
         first P*B images are those calls' inputs; -> (kps of the G-P graph calls, depth maps [G, K, D], kps of the prefix
         calls [P*B, Hy, K, 3], no graph)."""
+        ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3DMulti')
         if not prefix_groups:
             with ops_nn.bn_groups(groups):
                 heatmap = self.net(x)

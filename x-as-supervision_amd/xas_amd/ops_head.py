@@ -19,6 +19,14 @@ def _nhwc_storage(logits):
     return logits
 
 
+def check_patch_size(x, depth_dim, who):
+    """The detectors' heat-map is a quarter of the input patch per side and must be a cube: depth_dim == S / 4."""
+    if x.dim() != 4 or x.shape[-1] != x.shape[-2] or x.shape[-1] != 4 * depth_dim:
+        raise RuntimeError('%s(depth_dim=%d) takes square input patches of side 4 * depth_dim = %d, got input %s: build the '
+                           'detector with depth_dim = patch size / 4 (a multiple of 4, at most 128: patches up to 512)'
+                           % (who, depth_dim, 4 * depth_dim, tuple(x.shape)))
+
+
 class _SoftArgmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, num_kp, num_hypo, neighbor, groups):
@@ -29,7 +37,8 @@ class _SoftArgmax(torch.autograd.Function):
         B, C, H, W = logits.shape
         D = C // num_kp
         if not (C == num_kp * D and D == H == W):
-            raise RuntimeError('soft-argmax head needs D == H == W (got C=%d K=%d H=%d W=%d)' % (C, num_kp, H, W))
+            raise RuntimeError('soft-argmax head needs a heat-map cube D == H == W with D a multiple of 4 in [4,128] '
+                               '(got C=%d K=%d H=%d W=%d)' % (C, num_kp, H, W))
         dev = logits.device
         kps = torch.empty(B, num_hypo, num_kp, 3, device=dev, dtype=torch.float32)
         z_idx = torch.empty(B, num_kp, num_hypo, device=dev, dtype=torch.int64)

@@ -68,10 +68,14 @@ CONFIG_NAMES = ('HM36_Multi_SurS1', 'HM36_Multi_SurS2', 'HM36_Multi_SynthS1', 'H
                 'MPI_Multi_SurS1', 'MPI_Multi_SurS2', 'MPI_Multi_SynthS2')
 
 
-def model_config(name='HM36_Multi_SurS1'):
+def model_config(name='HM36_Multi_SurS1', patch=256):
     """dataset / model / train parameters of the shipped YAMLs (config/HM36_Multi_SurS1.yaml:1-106 and its six
     siblings, which differ only in the fields set below; asserted equal to the YAML contents in
-    tests/test_configs.py).  Real runs load the YAML itself (train.py); benchmarks and tests have no config dir."""
+    tests/test_configs.py).  Real runs load the YAML itself (train.py); benchmarks and tests have no config dir.
+    `patch`: side of the square input patch (the YAMLs' 256): sets patch_width / patch_height and depth_dim = patch / 4."""
+    if patch % 32 or not 32 <= patch <= 512:
+        raise ValueError('patch=%r: the detector takes square patches whose side is a multiple of 32, at most 512 '
+                         '(depth_dim = patch / 4 <= 128)' % (patch,))
     if name not in CONFIG_NAMES:
         raise KeyError('unknown config %r (known: %s)' % (name, ', '.join(CONFIG_NAMES)))
     mpi, s2, synth = name.startswith('MPI'), name.endswith('S2'), 'Synth' in name
@@ -85,7 +89,7 @@ def model_config(name='HM36_Multi_SurS1'):
     adv = (1.0 if mpi else 0.5) if s2 else 0.0
     lc['smpl_disc_loss'] = {'weight': adv, 'update_interval': 1}
     lc['smpl_gen_loss'] = {'weight': adv}
-    mp = {'detector_params': {'name': 'resnet_multi', 'num_kp': 18, 'depth_dim': 64, 'num_hypo': 3, 'neighbor_size': 15},
+    mp = {'detector_params': {'name': 'resnet_multi', 'num_kp': 18, 'depth_dim': patch // 4, 'num_hypo': 3, 'neighbor_size': 15},
           'smpl_disc_params': {'name': 'res_sage_gcn_decouple', 'input_dim': 128, 'hidden_dim': 128, 'output_dim': 128,
                                'num_node': 18, 'disc_sup_dim': 3, 'num_layers': 2, 'use_self_loop': True, 'use_pe': True},
           'smpl_layer_params': {'model_path': 'data/smpl_models'},
@@ -100,7 +104,7 @@ def model_config(name='HM36_Multi_SurS1'):
         epochs = 80 if mpi else 50
     tp = {'num_epochs': epochs, 'batch_size': 32, 'epoch_milestones': [70] if name == 'MPI_Multi_SurS1' else [40],
           'lr_kp_detector': 1.0e-4 if s2 else 2.0e-4, 'lr_discriminator': 1.0e-4 if s2 else 2.0e-4,
-          'checkpoint_freq': 2 if s2 else 20, 'patch_width': 256, 'patch_height': 256,
+          'checkpoint_freq': 2 if s2 else 20, 'patch_width': patch, 'patch_height': patch,
           'rect_3d_width': 2000, 'rect_3d_height': 2000,
           'aug': {'scale_factor': 0.0, 'rot_factor': 0, 'color_factor': 0.0, 'rot_aug_rate': 0.0, 'flip_aug_rate': 0.0,
                   'do_flip_aug': False}}
