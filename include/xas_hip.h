@@ -48,9 +48,10 @@ enum {
   XAS_TUNE_SLAB_64 = 98304,                  /* 3 = 64 */
   XAS_TUNE_COL_REDUCE_LEAN = 262144,         /* the <= 64-VGPR build of the backward column sums instead of the 86-VGPR one */
   /* bf16-split kernels (XAS_PREC_F16X3 / XAS_PREC_BF16X6) */
-  XAS_TUNE_GENERAL_KERNELS = 1 << 22,        /* two effects: no tap re-use kernels (stride-1 3x3 layers on the implicit-GEMM kernels:
-                                              * forward, data and weight gradient) AND no streaming batch-norm apply / backward-apply
-                                              * kernels (every layer on the general ones) */
+  XAS_TUNE_GENERAL_KERNELS = 1 << 22,        /* three effects: no tap re-use kernels (stride-1 3x3 layers on the implicit-GEMM kernels:
+                                              * forward, data and weight gradient), no streaming batch-norm apply / backward-apply
+                                              * kernels (every layer on the general ones) AND the soft-argmax head's general
+                                              * policy for power-of-two cube sides too (the workspace query follows) */
   XAS_TUNE_NO_WIDE_TILES = 1 << 23,          /* no 64 x 256 tiles for layers whose output channels are a multiple of 256 */
   XAS_TUNE_NO_STEM_WGRAD = 1 << 24,          /* the general weight-gradient kernel for the 7x7 stem instead of stem_wgrad_kernel */
   XAS_TUNE_STEM_FWD_F32 = 1 << 25,           /* the exact-fp32 stem forward kernel in the f16x3 mode too */
@@ -100,8 +101,8 @@ int xas_abi_version(void);
  * pick, topk, two avg_pool1d, two gathers) and keypoint_detector_integral.py:48-63.
  *
  * logits  [B][H][W][K*D] (NHWC storage of the reference's [B, K*D, H, W]); D==H==W, the heat-map is a cube.
- *          Accepted: D % 4 == 0 and 4 <= D <= 128 (input patches of side 4*D up to 512).  D in {4,8,16,32,64} runs on
- *          the power-of-two kernel family (head.hip), every other D on the general one (head_any.hip); anything else
+ *          Accepted: D % 4 == 0 and 4 <= D <= 128 (input patches of side 4*D up to 512).  One kernel family (head.hip):
+ *          D in {4,8,16,32,64} runs on its power-of-two policy, every other D on the general one; anything else
  *          is refused with status 1 (xas_head_workspace_floats: 0) and a message that names this range.
  * num_hypo >= 1 with neighbor > 0 : multi-hypothesis head; num_hypo == 1 and
  * neighbor == 0 : single-hypothesis head (plain expectation along depth).

@@ -1,5 +1,8 @@
 """GPU parity: soft-argmax head, patch->world, line-mask renderer (HIP, through the C ABI)
-against the CPU oracle and the reference-import goldens."""
+against the CPU oracle and the reference-import goldens.  The head's cases of power-of-two cube side run twice: on the
+power-of-two policy of csrc/head.hip (shipped) and, under TUNE_GENERAL_KERNELS, on its general policy, at the same bars."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -22,7 +25,19 @@ def close(a, b, atol, rtol=0.0):
     np.testing.assert_allclose(a, b, atol=atol, rtol=rtol)
 
 
-def test_head_small_vs_golden_and_oracle():
+@contextlib.contextmanager
+def general_policy():
+    """TUNE_GENERAL_KERNELS: power-of-two cube sides on the head's general policy too; reset on the way out."""
+    from xas_amd import _lib
+    _lib.query('xas_set_tuning', _lib.TUNE_GENERAL_KERNELS)
+    try:
+        yield
+    finally:
+        _lib.query('xas_set_tuning', 0)
+
+
+def _head_small():
+    """-> peak indices"""
     from xas_amd import ops_head
     g = golden('head_small')
     lg = dev(g['logits']).requires_grad_(True)
@@ -35,9 +50,22 @@ def test_head_small_vs_golden_and_oracle():
     k1, d1 = ops_head.softargmax_single(dev(g['logits']), 2)
     close(k1, g['kps_single'], 1e-5)
     close(d1, g['depth_prob_map_single'], 1e-6)
+    return idx.cpu().numpy()
 
 
-def test_head_full_size_vs_golden():
+def test_head_small_vs_golden_and_oracle():
+    _head_small()
+
+
+def test_head_small_on_the_general_policy():
+    """K = 2, D = 16: G = 4 lanes per joint reduced through LDS instead of the xor tree."""
+    shipped = _head_small()
+    with general_policy():
+        assert np.array_equal(_head_small(), shipped)
+
+
+def _head_full():
+    """-> peak indices"""
     from xas_amd import ops_head
     g = golden('head_full')
     lg, _ = gi.planted_logits(1, 18, 64, seed=12)
@@ -46,39 +74,81 @@ def test_head_full_size_vs_golden():
     close(kps, g['kps'], 2e-5)
     close(dmap, g['depth_prob_map'], 1e-6)
     close(ops_head.softargmax_single(dev(lg), 18)[0], g['kps_single'], 2e-5)
+    return idx.cpu().numpy()
 
 
-@pytest.mark.parametrize('B,K,D,hy,nb', [(3, 18, 64, 3, 15), (2, 5, 32, 2, 7), (1, 18, 64, 1, 0), (4, 3, 16, 3, 15)])
-def test_head_vs_oracle_random(B, K, D, hy, nb):
+def test_head_full_size_vs_golden():
+    _head_full()
+
+
+def test_head_full_size_on_the_general_policy():
+    """1 x 18 x 64: G = 16, 288 channel quads x 2 pixel slots."""
+    shipped = _head_full()
+    with general_policy():
+        assert np.array_equal(_head_full(), shipped)
+
+
+def _head_vs_oracle(B, K, D, hy, nb, policies):
+    """The oracle's forward and backward once, then the HIP head on each policy (a context manager) against it."""
     from oracle import head as ohead
     from xas_amd import ops_head
     lg_np, _ = gi.planted_logits(B, K, D, seed=100 + B)
     gw = torch.randn(B, hy, K, 3, generator=torch.Generator().manual_seed(1))
     lc = T(lg_np).requires_grad_(True)
-    lgpu = dev(lg_np).requires_grad_(True)
     if nb:
         ko, do, io = ohead.softargmax_multi(lc, K, hy, nb)
-        kg, dg, ig = ops_head.softargmax_multi(lgpu, K, hy, nb)
-        assert np.array_equal(io.numpy(), ig.cpu().numpy())
     else:
         ko, do = ohead.softargmax_single(lc, K)
-        kg, dg = ops_head.softargmax_single(lgpu, K)
-    close(kg, ko, 2e-5)
-    close(dg, do, 1e-6)
     (ko * gw).sum().backward()
-    (kg * gw.cuda()).sum().backward()
-    close(lgpu.grad, lc.grad, 2e-7, 2e-4)
-    # size independent property: softmax gradient sums to zero per (b,k)
-    s = lgpu.grad.reshape(B, K, -1).sum(-1).abs().max().item()
-    assert s < 1e-5
+    for policy in policies:
+        with policy():
+            lgpu = dev(lg_np).requires_grad_(True)
+            if nb:
+                kg, dg, ig = ops_head.softargmax_multi(lgpu, K, hy, nb)
+                assert np.array_equal(io.numpy(), ig.cpu().numpy())       # every policy equals the oracle, hence each other
+            else:
+                kg, dg = ops_head.softargmax_single(lgpu, K)
+            close(kg, ko, 2e-5)
+            close(dg, do, 1e-6)
+            (kg * gw.cuda()).sum().backward()
+            close(lgpu.grad, lc.grad, 2e-7, 2e-4)
+            # size independent property: softmax gradient sums to zero per (b,k)
+            s = lgpu.grad.reshape(B, K, -1).sum(-1).abs().max().item()
+            assert s < 1e-5
 
 
-def test_head_flat_logits_tie_rule():
-    """All-equal logits: every inner bin is a 'peak' with equal value -> lowest indices first."""
+@pytest.mark.parametrize('B,K,D,hy,nb', [(3, 18, 64, 3, 15), (2, 5, 32, 2, 7), (1, 18, 64, 1, 0), (4, 3, 16, 3, 15)])
+def test_head_vs_oracle_random(B, K, D, hy, nb):
+    _head_vs_oracle(B, K, D, hy, nb, [contextlib.nullcontext])
+
+
+@pytest.mark.parametrize('B,K,D,hy,nb', [(2, 5, 32, 2, 7), (4, 3, 16, 3, 15), (1, 18, 64, 1, 0)])
+def test_head_vs_oracle_random_on_the_general_policy(B, K, D, hy, nb):
+    """D = 64 with K = 18 and D = 16 with K = 3: G = 16 and G = 4; D = 32 with K = 5: a block of 40 channel quads, not a multiple
+    of a wave (the case the shuffle tree needs R = 64 / gcd(C4, 64) for)."""
+    _head_vs_oracle(B, K, D, hy, nb, [contextlib.nullcontext, general_policy])
+
+
+def test_head_d8_on_both_policies():
+    """B = 2, K = 3, D = 8, single hypothesis: the smallest G >= 2, rows (8 pixels) shorter than a slot stride."""
+    _head_vs_oracle(2, 3, 8, 1, 0, [contextlib.nullcontext, general_policy])
+
+
+def _flat_logits():
     from xas_amd import ops_head
     kps, _, idx = ops_head.softargmax_multi(torch.zeros(1, 2 * 16, 16, 16, device='cuda'), 2, 3, 15)
     assert idx.cpu().tolist() == [[[1, 2, 3], [1, 2, 3]]]
     assert torch.isfinite(kps).all()
+
+
+def test_head_flat_logits_tie_rule():
+    """All-equal logits: every inner bin is a 'peak' with equal value -> lowest indices first."""
+    _flat_logits()
+
+
+def test_head_flat_logits_tie_rule_on_the_general_policy():
+    with general_policy():
+        _flat_logits()
 
 
 def test_patch_to_world():

@@ -1,4 +1,4 @@
-"""Soft-argmax head at cube sides other than 16/32/64 (the general kernel family, csrc/head_any.hip) on the GPU, against the
+"""Soft-argmax head at cube sides other than 16/32/64 (the general policy of csrc/head.hip) on the GPU, against the
 reference-generated golden `head_sizes.npz` (tests/golden/make_golden_head_sizes.py) and against float64 autograd through
 the restatement of tests/golden/head_sizes_inputs.py (evaluated here, in float64 on the device).
 
@@ -187,7 +187,7 @@ def test_forward_and_backward_are_bit_reproducible(name):
 @pytest.mark.selfcheck
 @pytest.mark.parametrize('name', ['d24', 'd96'])
 def test_from_partials_reproduces_the_one_call_forward(name):
-    """xas_head_softargmax_from_partials over the records that the general family's own first pass left in the workspace."""
+    """xas_head_softargmax_from_partials over the records that the general policy's own first pass left in the workspace."""
     from xas_amd import ops_head
     from xas_amd._lib import call, ptr
     D, K, B, hy, nb, seed = hs.CASES[name]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Soft-argmax head kernels alone at the BASELINE size (B=32, K=18, D=H=W=64): achieved HBM GB/s.
-usage: bench_head.py [B] [--depth D]      D: cube side (64; e.g. 96 for 384^2 patches - the general kernel family)"""
+usage: bench_head.py [B] [--depth D]      D: cube side (64; e.g. 96 for 384^2 patches - the head's general policy)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'x-as-supervision_amd')]

@@ -11,112 +11,195 @@
 // Pass 1 (head_partial): per (b, pixel chunk) -> per joint {max, sum e*w, sum e*h, pz[D]}.
 // Pass 2 (head_finalize): one wave per (b,k): merge chunks, normalise, pick the depth
 // peaks (value desc, index asc), windowed expectation, write kps / indices / stats.
+//
+// One kernel family, two policies (template parameter POW2 of the partial and backward kernels):
+//   * power of two, D in {4,8,16,32,64}: pix -> (h, w) is shift/mask; the G = D/4 lanes of one (slot, joint) sit inside one
+//     wave (R is a multiple of 64 / gcd(C4, 64)) and reduce with an xor-shuffle tree; one block holds all K joints;
+//   * general, every other D % 4 == 0 up to 128: one division per thread before the loop, then the thread walks (h, w) by
+//     its pixel stride (rh rows + rw columns, one carry); the G lanes reduce through LDS in lane order (G = 3, 10, 24 ... have
+//     no xor tree), wherever the group falls inside a wave; a block holds the channel quads of KT joints (all K when
+//     K*G <= 1024, else the joints are tiled over gridDim.z).
+// XAS_TUNE_GENERAL_KERNELS puts the power-of-two sides on the general policy too (coverage: pow2_policy is the one rule).
 #include "common.h"
-#include "head_any.h"
 
 namespace xas {
 
 struct HeadGeom {
-  int B, K, D, HW, W, C4, G, R, P, nchunk, rec;  // rec = 3 + D floats per (b,chunk,k)
-  int wshift;                                     // log2(W): W is a power of two, so pix -> (h, w) is shift/mask
+  int B, K, D, HW, W, C4, G, rec;   // rec = 3 + D floats per (b,chunk,k)
+  int KT, ntile, C4t;               // joints per block, joint tiles (gridDim.z), channel quads per block and pixel
+  int R, rh, rw, wshift;            // pixel slots per block; R = rh * W + rw: a thread's step in (h, w); log2(W) (POW2 only)
+  int P, nchunk;                    // pixels per block, blocks per image
 };
 
-// Power-of-two sides up to 64 keep the kernels of this file; every other size goes to the general family (head_any.hip).
-static bool pow2_family(int D) { return D >= 4 && D <= 64 && (D & (D - 1)) == 0; }
+// The dispatch rule: which policy a cube side runs on.
+static bool pow2_policy(int D) {
+  return D >= 4 && D <= 64 && (D & (D - 1)) == 0 && !(tune_flags() & XAS_TUNE_GENERAL_KERNELS);
+}
 
-static int make_geom(int B, int K, int D, HeadGeom* g) {
-  // (the launchers send every other depth_dim that is a multiple of 4 in [4,128] to head_any.hip)
-  XAS_REQUIRE(B > 0 && K > 0 && pow2_family(D),
+static int make_geom(int B, int K, int D, bool pow2, HeadGeom* g) {
+  XAS_REQUIRE(B > 0 && K > 0, "head: need B > 0 and K > 0, got B=%d K=%d D=%d", B, K, D);
+  XAS_REQUIRE(D >= 4 && D <= 128 && D % 4 == 0,
               "head: depth_dim must be a multiple of 4 in [4,128] (heat-map cube D == H == W), got B=%d K=%d D=%d", B, K, D);
   g->B = B; g->K = K; g->D = D; g->W = D; g->HW = D * D;
+  g->G = D / 4;
+  g->C4 = K * g->G;
+  g->rec = 3 + D;
+  const int ktmax = 1024 / g->G;                  // >= 32 joints
+  g->ntile = pow2 ? 1 : (K + ktmax - 1) / ktmax;
+  g->KT = (K + g->ntile - 1) / g->ntile;
+  g->C4t = g->KT * g->G;
+  int R = 1;
+  if (pow2) {                                     // a lane group never straddles a wave: R is a multiple of 64 / gcd(C4, 64)
+    int gcd = 1;
+    while (gcd < 64 && (g->C4 % (gcd * 2)) == 0) gcd *= 2;
+    R = 64 / gcd;
+  }
+  while ((long)g->C4t * R * 2 <= 640 && R * 2 <= g->HW) R *= 2;
+  XAS_REQUIRE((long)g->C4t * R <= 1024, "head: K*D=%d too wide for one workgroup", K * D);
+  g->R = R; g->rh = R / g->W; g->rw = R % g->W;
   g->wshift = 0;
   while ((1 << g->wshift) < D) ++g->wshift;
-  g->C4 = K * D / 4;
-  g->G = D / 4;
-  int gcd = 1;
-  while (gcd < 64 && (g->C4 % (gcd * 2)) == 0) gcd *= 2;
-  int rstep = 64 / gcd;                       // R must be a multiple of this
-  int R = rstep;
-  while ((long)g->C4 * R * 2 <= 640 && R * 2 <= g->HW) R *= 2;
-  XAS_REQUIRE((long)g->C4 * R <= 1024, "head: K*D=%d too wide for one workgroup", K * D);
-  g->R = R;
   g->P = R > 128 ? R : 128;       // pixels per workgroup: 128 amortises the block-level merge (64: 3.8 TB/s)
   if (g->P > g->HW) g->P = g->HW;
   g->P = (g->P / R) * R;
   XAS_REQUIRE(g->P >= R, "head: heat-map too small");
   g->nchunk = (g->HW + g->P - 1) / g->P;
-  g->rec = 3 + D;
   return 0;
 }
 
+// ---- what the two policies supply ----------------------------------------------------------------------------------------
+// (h, w) of the pixels a thread visits, as floats.  POW2: from the pixel index.  General: the thread starts at `pix` and
+// every call steps by g.R pixels, so it must be called once per visited pixel, in order.
+template <bool POW2>
+struct PixelWalk {
+  int h, w;
+  __device__ PixelWalk(const HeadGeom& g, int pix) {
+    if constexpr (!POW2) { h = pix / g.W; w = pix - h * g.W; }   // the only division
+  }
+  __device__ void next(const HeadGeom& g, int pix, float* fh, float* fw) {
+    if constexpr (POW2) {
+      *fw = (float)(pix & (g.W - 1)); *fh = (float)(pix >> g.wshift);
+    } else {
+      *fw = (float)w; *fh = (float)h;
+      w += g.rw; h += g.rh;
+      if (w >= g.W) { w -= g.W; ++h; }
+    }
+  }
+};
+
+// Maximum over the G lanes of this thread's (slot, joint); `lead` is the group's first thread.  General: through s[blockDim.x].
+template <bool POW2>
+__device__ float group_max(float v, int G, float* s, int lead) {
+  if constexpr (POW2) {
+    for (int o = G >> 1; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+  } else {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    float gm = -INFINITY;
+    for (int j = 0; j < G; ++j) gm = fmaxf(gm, s[lead + j]);
+    return gm;
+  }
+}
+// Sums of x and y over the same lanes (valid in the group's first thread): xor tree, or LDS in lane order.
+template <bool POW2>
+__device__ void group_sum2(float& x, float& y, int G, float* s_x, float* s_y, int lead) {
+  if constexpr (POW2) {
+    for (int o = G >> 1; o > 0; o >>= 1) { x += __shfl_xor(x, o, 64); y += __shfl_xor(y, o, 64); }
+  } else {
+    s_x[threadIdx.x] = x;
+    s_y[threadIdx.x] = y;
+    __syncthreads();
+    if ((int)threadIdx.x == lead) {
+      x = 0.f; y = 0.f;
+      for (int j = 0; j < G; ++j) { x += s_x[lead + j]; y += s_y[lead + j]; }
+    }
+  }
+}
+
+static size_t partial_lds_bytes(const HeadGeom& g, bool pow2) {
+  return ((size_t)g.R * g.KT * g.rec + (pow2 ? 0 : 3 * (size_t)g.C4t * g.R)) * sizeof(float);
+}
+
+template <bool POW2>
 __global__ void head_partial_kernel(const float4* __restrict__ logits, float* __restrict__ partial, HeadGeom g) {
-  extern __shared__ float smem[];            // [R][K][3 + D]
+  extern __shared__ float smem[];            // [R][KT][3 + D] records; general: then per thread max, sx, sy
+  const int KT = POW2 ? g.K : g.KT, C4t = POW2 ? g.C4 : g.C4t;
+  float* s_m = smem + (size_t)g.R * KT * g.rec;
+  float* s_x = s_m + blockDim.x;
+  float* s_y = s_x + blockDim.x;
   const int tid = threadIdx.x;
-  const int c4 = tid % g.C4, slot = tid / g.C4;
-  const int k = c4 / g.G, dq = c4 % g.G;
+  const int c4t = tid % C4t, slot = tid / C4t;
+  const int kt = c4t / g.G, dq = c4t % g.G;
+  const int k0 = POW2 ? 0 : blockIdx.z * KT, k = k0 + kt;
+  const bool live = POW2 || k < g.K;         // the last joint tile may be ragged
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int pix0 = chunk * g.P;
   const int pend = min(g.P, g.HW - pix0);
-  const float4* base = logits + ((size_t)b * g.HW + pix0) * g.C4 + c4;
 
   float m = -INFINITY, sx = 0.f, sy = 0.f, z0 = 0.f, z1 = 0.f, z2 = 0.f, z3 = 0.f;
-  // four pixels per trip: one running-max update (one rescale exp) per 16 values keeps the loop-carried
-  // dependency short; the 4 loads are issued back to back
-  int p = slot;
-  for (; p + 3 * g.R < pend; p += 4 * g.R) {
-    float4 v[4];
+  if (live) {
+    const float4* base = logits + ((size_t)b * g.HW + pix0) * g.C4 + (k * g.G + dq);
+    PixelWalk<POW2> walk(g, pix0 + slot);
+    // four pixels per trip: one running-max update (one rescale exp) per 16 values keeps the loop-carried
+    // dependency short; the 4 loads are issued back to back
+    int p = slot;
+    for (; p + 3 * g.R < pend; p += 4 * g.R) {
+      float4 v[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = stream_load(base + (size_t)(p + u * g.R) * g.C4);
-    float mn = m;
+      for (int u = 0; u < 4; ++u) v[u] = stream_load(base + (size_t)(p + u * g.R) * g.C4);
+      float mn = m;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) mn = fmaxf(mn, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
-    const float sc = __expf(m - mn);          // exp(-inf) = 0 on the first trip
-    m = mn;
-    z0 *= sc; z1 *= sc; z2 *= sc; z3 *= sc; sx *= sc; sy *= sc;
+      for (int u = 0; u < 4; ++u) mn = fmaxf(mn, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
+      const float sc = __expf(m - mn);          // exp(-inf) = 0 on the first trip
+      m = mn;
+      z0 *= sc; z1 *= sc; z2 *= sc; z3 *= sc; sx *= sc; sy *= sc;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int pix = pix0 + p + u * g.R;
-      const float fw = (float)(pix & (g.W - 1)), fh = (float)(pix >> g.wshift);
-      const float e0 = __expf(v[u].x - mn), e1 = __expf(v[u].y - mn), e2 = __expf(v[u].z - mn), e3 = __expf(v[u].w - mn);
+      for (int u = 0; u < 4; ++u) {
+        float fh, fw;
+        walk.next(g, pix0 + p + u * g.R, &fh, &fw);
+        const float e0 = __expf(v[u].x - mn), e1 = __expf(v[u].y - mn), e2 = __expf(v[u].z - mn), e3 = __expf(v[u].w - mn);
+        const float es = (e0 + e1) + (e2 + e3);
+        z0 += e0; z1 += e1; z2 += e2; z3 += e3;
+        sx = fmaf(es, fw, sx);
+        sy = fmaf(es, fh, sy);
+      }
+    }
+    for (; p < pend; p += g.R) {
+      const float4 v = stream_load(base + (size_t)p * g.C4);
+      float fh, fw;
+      walk.next(g, pix0 + p, &fh, &fw);
+      const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+      const float sc = __expf(m - mn);
+      m = mn;
+      const float e0 = __expf(v.x - mn), e1 = __expf(v.y - mn), e2 = __expf(v.z - mn), e3 = __expf(v.w - mn);
       const float es = (e0 + e1) + (e2 + e3);
-      z0 += e0; z1 += e1; z2 += e2; z3 += e3;
-      sx = fmaf(es, fw, sx);
-      sy = fmaf(es, fh, sy);
+      z0 = z0 * sc + e0; z1 = z1 * sc + e1; z2 = z2 * sc + e2; z3 = z3 * sc + e3;
+      sx = sx * sc + es * fw;
+      sy = sy * sc + es * fh;
     }
   }
-  for (; p < pend; p += g.R) {
-    const float4 v = base[(size_t)p * g.C4];
-    const int pix = pix0 + p;
-    const float fw = (float)(pix & (g.W - 1)), fh = (float)(pix >> g.wshift);
-    const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
-    const float sc = __expf(m - mn);
-    m = mn;
-    const float e0 = __expf(v.x - mn), e1 = __expf(v.y - mn), e2 = __expf(v.z - mn), e3 = __expf(v.w - mn);
-    const float es = (e0 + e1) + (e2 + e3);
-    z0 = z0 * sc + e0; z1 = z1 * sc + e1; z2 = z2 * sc + e2; z3 = z3 * sc + e3;
-    sx = sx * sc + es * fw;
-    sy = sy * sc + es * fh;
-  }
   // unify the running max over the G lanes of this (slot, joint), then sum sx / sy
-  float gm = m;
-  for (int o = g.G >> 1; o > 0; o >>= 1) gm = fmaxf(gm, __shfl_xor(gm, o, 64));
+  const int lead = tid - dq;                  // first thread of the group
+  const float gm = group_max<POW2>(m, g.G, s_m, lead);
   const float sc = (m == -INFINITY) ? 0.f : __expf(m - gm);
   z0 *= sc; z1 *= sc; z2 *= sc; z3 *= sc; sx *= sc; sy *= sc;
-  for (int o = g.G >> 1; o > 0; o >>= 1) { sx += __shfl_xor(sx, o, 64); sy += __shfl_xor(sy, o, 64); }
-  float* rec = smem + ((size_t)slot * g.K + k) * g.rec;
+  group_sum2<POW2>(sx, sy, g.G, s_x, s_y, lead);
+  float* rec = smem + ((size_t)slot * KT + kt) * g.rec;
   if (dq == 0) { rec[0] = gm; rec[1] = sx; rec[2] = sy; }
   rec[3 + 4 * dq + 0] = z0; rec[3 + 4 * dq + 1] = z1; rec[3 + 4 * dq + 2] = z2; rec[3 + 4 * dq + 3] = z3;
   __syncthreads();
-  // merge the R slots; thread t handles entry t of the [K][rec] record table
-  float* out = partial + ((size_t)b * g.nchunk + chunk) * g.K * g.rec;
-  for (int e = tid; e < g.K * g.rec; e += blockDim.x) {
+  // merge the R slots; thread t handles entry t of this tile's [joints][rec] record table
+  const int kn = POW2 ? g.K : min(KT, g.K - k0);
+  float* out = partial + (((size_t)b * g.nchunk + chunk) * g.K + k0) * g.rec;
+  for (int e = tid; e < kn * g.rec; e += blockDim.x) {
     const int kk = e / g.rec, f = e % g.rec;
     float M = -INFINITY;
-    for (int s = 0; s < g.R; ++s) M = fmaxf(M, smem[((size_t)s * g.K + kk) * g.rec]);
+    for (int s = 0; s < g.R; ++s) M = fmaxf(M, smem[((size_t)s * KT + kk) * g.rec]);
     if (f == 0) { out[e] = M; continue; }
     float acc = 0.f;
     for (int s = 0; s < g.R; ++s) {
-      const float* r = smem + ((size_t)s * g.K + kk) * g.rec;
+      const float* r = smem + ((size_t)s * KT + kk) * g.rec;
       const float ms = r[0];
       acc += (ms == -INFINITY) ? 0.f : r[f] * __expf(ms - M);
     }
@@ -124,36 +207,43 @@ __global__ void head_partial_kernel(const float4* __restrict__ logits, float* __
   }
 }
 
+// One wave per (b,k); lane l keeps depth bins l and l + 64 (the second one is dead for D <= 64: it holds 0 and scores -1).
 __global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom g, int num_hypo, int neighbor,
                                      float* __restrict__ kps, int64_t* __restrict__ z_idx,
                                      float* __restrict__ depth_prob_map, int dmap_every, float* __restrict__ stats) {
   const int b = blockIdx.x / g.K, k = blockIdx.x % g.K;
-  const int d = threadIdx.x;                  // one wave; lane = depth bin
-  const bool live = d < g.D;
+  const int lane = threadIdx.x;
+  const int d0 = lane, d1 = lane + 64;
+  const bool live0 = d0 < g.D, live1 = d1 < g.D;
   const float* p0 = partial + ((size_t)b * g.nchunk * g.K + k) * g.rec;
   const size_t cstride = (size_t)g.K * g.rec;
   float M = -INFINITY;
   for (int c = 0; c < g.nchunk; ++c) M = fmaxf(M, p0[c * cstride]);
-  float sd = 0.f, SX = 0.f, SY = 0.f;
+  float sd0 = 0.f, sd1 = 0.f, SX = 0.f, SY = 0.f;
   for (int c = 0; c < g.nchunk; ++c) {
     const float* r = p0 + c * cstride;
     const float sc = __expf(r[0] - M);
-    if (live) sd += r[3 + d] * sc;
+    if (live0) sd0 += r[3 + d0] * sc;
+    if (live1) sd1 += r[3 + d1] * sc;
     SX += r[1] * sc;
     SY += r[2] * sc;
   }
-  const float S = wave_sum(live ? sd : 0.f);
-  const float pz = live ? sd / S : 0.f;
+  const float S = wave_sum(sd0 + sd1);        // dead bins hold 0
+  const float pz0 = live0 ? sd0 / S : 0.f, pz1 = live1 ? sd1 / S : 0.f;
   const float X = SX / S, Y = SY / S;
   float* st = stats + ((size_t)b * g.K + k) * XAS_HEAD_STATS;
-  if (b % dmap_every == 0 && live) depth_prob_map[((size_t)(b / dmap_every) * g.K + k) * g.D + d] = pz;
+  if (b % dmap_every == 0) {
+    float* dm = depth_prob_map + ((size_t)(b / dmap_every) * g.K + k) * g.D;
+    if (live0) dm[d0] = pz0;
+    if (live1) dm[d1] = pz1;
+  }
   const float fD = (float)g.D;
   const float xn = X / fD * 2.f - 1.f, yn = Y / fD * 2.f - 1.f;
-  if (d == 0) { st[0] = M + __logf(S); st[1] = X; st[2] = Y; }
+  if (lane == 0) { st[0] = M + __logf(S); st[1] = X; st[2] = Y; }
 
   if (neighbor == 0) {                        // single hypothesis: plain expectation
-    const float Z = wave_sum(pz * (float)d);
-    if (d == 0) {
+    const float Z = wave_sum(pz0 * (float)d0 + pz1 * (float)d1);
+    if (lane == 0) {
       float* o = kps + ((size_t)b * g.K + k) * 3;
       o[0] = xn; o[1] = yn; o[2] = Z / fD * 2.f - 1.f;
       st[3] = Z;
@@ -161,20 +251,29 @@ __global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom
     }
     return;
   }
-  const float left = __shfl_up(pz, 1, 64), right = __shfl_down(pz, 1, 64);
-  const bool inner = d >= 1 && d <= g.D - 2;
-  float score = inner ? ((pz >= left && pz >= right) ? pz : 0.f) : -1.f;
+  // neighbours: bin 63's right one is bin 64 (lane 0's second bin), bin 64's left one is bin 63 (lane 63's first bin)
+  float left0 = __shfl_up(pz0, 1, 64), right0 = __shfl_down(pz0, 1, 64);
+  float left1 = __shfl_up(pz1, 1, 64), right1 = __shfl_down(pz1, 1, 64);
+  const float bin64 = __shfl(pz1, 0, 64), bin63 = __shfl(pz0, 63, 64);
+  if (lane == 63) right0 = bin64;
+  if (lane == 0) left1 = bin63;
+  const bool inner0 = d0 >= 1 && d0 <= g.D - 2, inner1 = d1 <= g.D - 2;   // (bin 127's right neighbour is never read)
+  float score0 = inner0 ? ((pz0 >= left0 && pz0 >= right0) ? pz0 : 0.f) : -1.f;
+  float score1 = inner1 ? ((pz1 >= left1 && pz1 >= right1) ? pz1 : 0.f) : -1.f;
   const int r = neighbor / 2;
   for (int h = 0; h < num_hypo; ++h) {
-    const float best = wave_max(score);
-    const unsigned long long cand = __ballot(score == best);
-    const int idx = __ffsll((long long)cand) - 1;   // lowest bin among equal scores
-    if (d == idx) score = -2.f;
-    const bool inwin = live && (d >= idx - r) && (d <= idx + r);
-    const float sw = wave_sum(inwin ? pz : 0.f);
-    const float swd = wave_sum(inwin ? pz * (float)d : 0.f);
+    const float best = wave_max(fmaxf(score0, score1));
+    const unsigned long long cand0 = __ballot(score0 == best), cand1 = __ballot(score1 == best);
+    // lowest bin among equal scores: every first bin (0..63) sorts before every second bin (64..127)
+    const int idx = cand0 ? __ffsll((long long)cand0) - 1 : 64 + __ffsll((long long)cand1) - 1;
+    if (d0 == idx) score0 = -2.f;
+    if (d1 == idx) score1 = -2.f;
+    const bool in0 = live0 && (d0 >= idx - r) && (d0 <= idx + r);
+    const bool in1 = live1 && (d1 >= idx - r) && (d1 <= idx + r);
+    const float sw = wave_sum((in0 ? pz0 : 0.f) + (in1 ? pz1 : 0.f));
+    const float swd = wave_sum((in0 ? pz0 * (float)d0 : 0.f) + (in1 ? pz1 * (float)d1 : 0.f));
     const float Z = swd / sw;
-    if (d == 0) {
+    if (lane == 0) {
       float* o = kps + (((size_t)b * num_hypo + h) * g.K + k) * 3;
       o[0] = xn; o[1] = yn; o[2] = Z / fD * 2.f - 1.f;
       z_idx[((size_t)b * g.K + k) * num_hypo + h] = idx;
@@ -184,7 +283,7 @@ __global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom
   }
 }
 
-// per (b,k): {cx, cy, c0, lse, gz[D]}
+// per (b,k): {cx, cy, c0, lse, gz[D]}; thread = depth bin (64 threads for D <= 64, else 128; nothing crosses lanes here)
 __global__ void head_bwd_coef_kernel(const float* __restrict__ stats, const int64_t* __restrict__ z_idx,
                                      const float* __restrict__ grad_kps, HeadGeom g, int num_hypo, int neighbor,
                                      float* __restrict__ coef) {
@@ -214,42 +313,72 @@ __global__ void head_bwd_coef_kernel(const float* __restrict__ stats, const int6
   if (d < g.D) o[4 + d] = gz;
 }
 
+template <bool POW2>
 __global__ void head_bwd_kernel(const float4* __restrict__ logits, const float* __restrict__ coef, HeadGeom g,
                                 float4* __restrict__ grad, float* __restrict__ amax_out) {
   __shared__ unsigned s_amax;                          // amax_out != null: max |grad| of the block (bit pattern), then of the launch
   if (threadIdx.x == 0) s_amax = 0u;
   if (amax_out) __syncthreads();
   float amx = 0.f;
+  const int KT = POW2 ? g.K : g.KT, C4t = POW2 ? g.C4 : g.C4t;
   const int tid = threadIdx.x;
-  const int c4 = tid % g.C4, slot = tid / g.C4;
-  const int k = c4 / g.G, dq = c4 % g.G;
+  const int c4t = tid % C4t, slot = tid / C4t;
+  const int kt = c4t / g.G, dq = c4t % g.G;
+  const int bz = POW2 ? 0 : blockIdx.z;
+  const int k = bz * KT + kt;
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int pix0 = chunk * g.P;
   const int pend = min(g.P, g.HW - pix0);
-  const float* cf = coef + ((size_t)b * g.K + k) * (4 + g.D);
-  const float cx = cf[0], cy = cf[1], c0 = cf[2], lse = cf[3];
-  const float4 gz = *reinterpret_cast<const float4*>(cf + 4 + 4 * dq);
-  const size_t off = ((size_t)b * g.HW + pix0) * g.C4 + c4;
+  if (POW2 || k < g.K) {
+    const float* cf = coef + ((size_t)b * g.K + k) * (4 + g.D);
+    const float cx = cf[0], cy = cf[1], c0 = cf[2], lse = cf[3];
+    const float4 gz = *reinterpret_cast<const float4*>(cf + 4 + 4 * dq);
+    const size_t off = ((size_t)b * g.HW + pix0) * g.C4 + (k * g.G + dq);
+    PixelWalk<POW2> walk(g, pix0 + slot);
 #pragma unroll 4
-  for (int p = slot; p < pend; p += g.R) {
-    const float4 v = stream_load(logits + off + (size_t)p * g.C4);
-    const int pix = pix0 + p;
-    const float lin = cx * (float)(pix & (g.W - 1)) + cy * (float)(pix >> g.wshift) + c0;
-    float4 o;
-    o.x = __expf(v.x - lse) * (lin + gz.x);
-    o.y = __expf(v.y - lse) * (lin + gz.y);
-    o.z = __expf(v.z - lse) * (lin + gz.z);
-    o.w = __expf(v.w - lse) * (lin + gz.w);
-    amx = fmaxf(fmaxf(amx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    stream_store(grad + off + (size_t)p * g.C4, o);
+    for (int p = slot; p < pend; p += g.R) {
+      const float4 v = stream_load(logits + off + (size_t)p * g.C4);
+      float fh, fw;
+      walk.next(g, pix0 + p, &fh, &fw);
+      const float lin = cx * fw + cy * fh + c0;
+      float4 o;
+      o.x = __expf(v.x - lse) * (lin + gz.x);
+      o.y = __expf(v.y - lse) * (lin + gz.y);
+      o.z = __expf(v.z - lse) * (lin + gz.z);
+      o.w = __expf(v.w - lse) * (lin + gz.w);
+      amx = amax4(amx, o);
+      stream_store(grad + off + (size_t)p * g.C4, o);
+    }
   }
   if (amax_out) {                                      // (the block is not a whole number of waves: reduce through LDS)
     if (amx > 0.f) atomicMax(&s_amax, __float_as_uint(amx));
     __syncthreads();
     // one atomic per block, to the sub-maximum the block index selects (common.h: recorded maxima)
-    const unsigned sub = (blockIdx.x + blockIdx.y * gridDim.x) % (unsigned)kAmaxSub;
+    const unsigned sub = (blockIdx.x + (blockIdx.y + bz * gridDim.y) * gridDim.x) % (unsigned)kAmaxSub;
     if (threadIdx.x == 0 && s_amax) atomicMax(reinterpret_cast<unsigned*>(amax_out + sub * kAmaxStride), s_amax);
   }
+}
+
+// ---- argument checks: each one is written once --------------------------------------------------------------------------
+static int check_modes(const char* who, int D, int num_hypo, int neighbor, const int64_t* z_idx, int B, int groups) {
+  XAS_REQUIRE(num_hypo >= 1 && num_hypo <= 6, "%s: num_hypo %d not in [1,6]", who, num_hypo);
+  XAS_REQUIRE(neighbor >= 0 && (neighbor > 0 || num_hypo == 1), "%s: single-hypothesis mode needs num_hypo == 1", who);
+  XAS_REQUIRE(neighbor == 0 || (z_idx != nullptr && num_hypo <= D - 2), "%s: z_idx required / too many hypotheses", who);
+  XAS_REQUIRE(groups >= 1 && B % groups == 0, "%s: B=%d does not split into %d groups", who, B, groups);
+  return 0;
+}
+
+static int check_grid(const char* who, const HeadGeom& g) {
+  XAS_REQUIRE(g.B <= 65535 && g.ntile <= 65535, "%s: B=%d K=%d exceed the launch grid", who, g.B, g.K);
+  return 0;
+}
+
+static int launch_finalize(const float* partial, const HeadGeom& g, int num_hypo, int neighbor, float* kps, int64_t* z_idx,
+                           float* depth_prob_map, int groups, float* stats, void* stream) {
+  hipLaunchKernelGGL(head_finalize_kernel, dim3(g.B * g.K), dim3(64), 0, as_stream(stream), partial, g, num_hypo,
+                     neighbor, kps, z_idx, depth_prob_map, g.B / groups, stats);
+  XAS_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace xas
@@ -257,34 +386,27 @@ __global__ void head_bwd_kernel(const float4* __restrict__ logits, const float* 
 using namespace xas;
 
 extern "C" size_t xas_head_workspace_floats(int B, int K, int D) {
-  if (!pow2_family(D)) return head_any_workspace_floats(B, K, D);
   HeadGeom g;
-  if (make_geom(B, K, D, &g)) return 0;
+  if (make_geom(B, K, D, pow2_policy(D), &g)) return 0;
   return (size_t)B * g.nchunk * K * g.rec;
 }
 
 extern "C" int xas_head_softargmax_fwd(const float* logits, int B, int K, int D, int num_hypo, int neighbor,
                                        float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                        float* partial, void* stream) {
-  if (!pow2_family(D))
-    return head_any_fwd(logits, B, K, D, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, partial, stream);
+  const bool pow2 = pow2_policy(D);
   HeadGeom g;
-  if (make_geom(B, K, D, &g)) return 1;
+  if (make_geom(B, K, D, pow2, &g)) return 1;
   XAS_REQUIRE(logits && kps && depth_prob_map && stats && partial, "head fwd: null buffer");
-  XAS_REQUIRE(num_hypo >= 1 && num_hypo <= 6, "head fwd: num_hypo %d not in [1,6]", num_hypo);
-  XAS_REQUIRE(neighbor >= 0 && (neighbor > 0 || num_hypo == 1), "head fwd: single-hypothesis mode needs num_hypo == 1");
-  XAS_REQUIRE(neighbor == 0 || (z_idx != nullptr && num_hypo <= D - 2), "head fwd: z_idx required / too many hypotheses");
+  if (check_modes("head fwd", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
   XAS_REQUIRE(((uintptr_t)logits & 15) == 0, "head fwd: logits must be 16-byte aligned");
-  XAS_REQUIRE(groups >= 1 && B % groups == 0, "head fwd: B=%d does not split into %d groups", B, groups);
-  const size_t lds = (size_t)g.R * K * g.rec * sizeof(float);
+  const size_t lds = partial_lds_bytes(g, pow2);
   XAS_REQUIRE(lds <= 64 * 1024, "head fwd: LDS %zu too large", lds);
-  hipLaunchKernelGGL(head_partial_kernel, dim3(g.nchunk, B), dim3(g.C4 * g.R), lds, as_stream(stream),
-                     reinterpret_cast<const float4*>(logits), partial, g);
+  if (check_grid("head fwd", g)) return 1;
+  hipLaunchKernelGGL(pow2 ? head_partial_kernel<true> : head_partial_kernel<false>, dim3(g.nchunk, B, g.ntile),
+                     dim3(g.C4t * g.R), lds, as_stream(stream), reinterpret_cast<const float4*>(logits), partial, g);
   XAS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_finalize_kernel, dim3(B * K), dim3(64), 0, as_stream(stream), partial, g, num_hypo,
-                     neighbor, kps, z_idx, depth_prob_map, B / groups, stats);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_finalize(partial, g, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, stream);
 }
 
 // The second pass alone, over partial records that something else produced: xas_conv_fwd_head (conv.hip) emits them from the
@@ -294,20 +416,12 @@ extern "C" int xas_head_softargmax_fwd(const float* logits, int B, int K, int D,
 extern "C" int xas_head_softargmax_from_partials(const float* partial, int B, int K, int D, int nchunk, int num_hypo, int neighbor,
                                                  float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                                  void* stream) {
-  if (!pow2_family(D))
-    return head_any_from_partials(partial, B, K, D, nchunk, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, stream);
   HeadGeom g;
-  if (make_geom(B, K, D, &g)) return 1;
+  if (make_geom(B, K, D, pow2_policy(D), &g)) return 1;
   XAS_REQUIRE(partial && kps && depth_prob_map && stats && nchunk >= 1, "head from partials: null buffer");
-  XAS_REQUIRE(num_hypo >= 1 && num_hypo <= 6, "head from partials: num_hypo %d not in [1,6]", num_hypo);
-  XAS_REQUIRE(neighbor >= 0 && (neighbor > 0 || num_hypo == 1), "head from partials: single-hypothesis mode needs num_hypo == 1");
-  XAS_REQUIRE(neighbor == 0 || (z_idx != nullptr && num_hypo <= D - 2), "head from partials: z_idx required / too many hypotheses");
-  XAS_REQUIRE(groups >= 1 && B % groups == 0, "head from partials: B=%d does not split into %d groups", B, groups);
+  if (check_modes("head from partials", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
   g.nchunk = nchunk;
-  hipLaunchKernelGGL(head_finalize_kernel, dim3(B * K), dim3(64), 0, as_stream(stream), partial, g, num_hypo,
-                     neighbor, kps, z_idx, depth_prob_map, B / groups, stats);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_finalize(partial, g, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, stream);
 }
 
 extern "C" int xas_head_softargmax_bwd(const float* logits, const float* stats, const int64_t* z_idx,
@@ -319,19 +433,20 @@ extern "C" int xas_head_softargmax_bwd(const float* logits, const float* stats, 
 extern "C" int xas_head_softargmax_bwd_amax(const float* logits, const float* stats, const int64_t* z_idx,
                                             const float* grad_kps, int B, int K, int D, int num_hypo, int neighbor,
                                             float* grad_logits, float* coef, float* amax_out, void* stream) {
-  if (!pow2_family(D))
-    return head_any_bwd(logits, stats, z_idx, grad_kps, B, K, D, num_hypo, neighbor, grad_logits, coef, amax_out, stream);
+  const bool pow2 = pow2_policy(D);
   HeadGeom g;
-  if (make_geom(B, K, D, &g)) return 1;
+  if (make_geom(B, K, D, pow2, &g)) return 1;
   XAS_REQUIRE(logits && stats && grad_kps && grad_logits && coef, "head bwd: null buffer");
   XAS_REQUIRE(num_hypo >= 1 && num_hypo <= 6, "head bwd: num_hypo %d not in [1,6]", num_hypo);
   XAS_REQUIRE(neighbor == 0 || z_idx != nullptr, "head bwd: z_idx required");
   XAS_REQUIRE((((uintptr_t)logits | (uintptr_t)grad_logits | (uintptr_t)coef) & 15) == 0, "head bwd: 16-byte alignment");
-  hipLaunchKernelGGL(head_bwd_coef_kernel, dim3(B * K), dim3(64), 0, as_stream(stream), stats, z_idx, grad_kps, g,
-                     num_hypo, neighbor, coef);
+  if (check_grid("head bwd", g)) return 1;
+  hipLaunchKernelGGL(head_bwd_coef_kernel, dim3(B * K), dim3(D <= 64 ? 64 : 128), 0, as_stream(stream), stats, z_idx,
+                     grad_kps, g, num_hypo, neighbor, coef);
   XAS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_bwd_kernel, dim3(g.nchunk, B), dim3(g.C4 * g.R), 0, as_stream(stream),
-                     reinterpret_cast<const float4*>(logits), coef, g, reinterpret_cast<float4*>(grad_logits), amax_out);
+  hipLaunchKernelGGL(pow2 ? head_bwd_kernel<true> : head_bwd_kernel<false>, dim3(g.nchunk, B, g.ntile), dim3(g.C4t * g.R), 0,
+                     as_stream(stream), reinterpret_cast<const float4*>(logits), coef, g, reinterpret_cast<float4*>(grad_logits),
+                     amax_out);
   XAS_LAUNCH_CHECK();
   return 0;
 }

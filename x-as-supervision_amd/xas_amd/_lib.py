@@ -33,7 +33,7 @@ TUNE_WGRAD_ALT_ORDER, TUNE_WGRAD_PLAIN_KLOOP = 8192, 524288
 TUNE_SLAB_SHIFT, TUNE_SLAB_MASK = 15, 3
 TUNE_SLAB_512, TUNE_SLAB_128, TUNE_SLAB_64 = 32768, 65536, 98304
 TUNE_COL_REDUCE_LEAN = 262144
-TUNE_GENERAL_KERNELS = 1 << 22       # no tap re-use conv kernels AND no streaming batch-norm kernels
+TUNE_GENERAL_KERNELS = 1 << 22       # no tap re-use conv kernels, no streaming batch-norm kernels AND the head's general policy at every D
 TUNE_NO_WIDE_TILES, TUNE_NO_STEM_WGRAD, TUNE_STEM_FWD_F32 = 1 << 23, 1 << 24, 1 << 25
 TUNE_NO_X6P, TUNE_X6P_ANY_K = 1 << 26, 1 << 27
 
