@@ -101,9 +101,10 @@ int xas_abi_version(void);
  * pick, topk, two avg_pool1d, two gathers) and keypoint_detector_integral.py:48-63.
  *
  * logits  [B][H][W][K*D] (NHWC storage of the reference's [B, K*D, H, W]); D==H==W, the heat-map is a cube.
- *          Accepted: D % 4 == 0 and 4 <= D <= 128 (input patches of side 4*D up to 512).  One kernel family (head.hip):
- *          D in {4,8,16,32,64} runs on its power-of-two policy, every other D on the general one; anything else
- *          is refused with status 1 (xas_head_workspace_floats: 0) and a message that names this range.
+ *          Accepted: D % 4 == 0 and 4 <= D <= 128 (input patches of side 4*D up to 512), for every K >= 1.  One kernel family
+ *          (head.hip): D in {4,8,16,32,64} runs on its power-of-two policy whenever that policy's block exists for K (at most
+ *          1024 threads, no more pixel slots than pixels), every other (D, K) on the general one, which tiles the joints;
+ *          any other D is refused with status 1 (xas_head_workspace_floats: 0) and a message that names this range.
  * num_hypo >= 1 with neighbor > 0 : multi-hypothesis head; num_hypo == 1 and
  * neighbor == 0 : single-hypothesis head (plain expectation along depth).
  * kps      [B][num_hypo][K][3]   normalised to [-1,1)

@@ -13,13 +13,15 @@
 // peaks (value desc, index asc), windowed expectation, write kps / indices / stats.
 //
 // One kernel family, two policies (template parameter POW2 of the partial and backward kernels):
-//   * power of two, D in {4,8,16,32,64}: pix -> (h, w) is shift/mask; the G = D/4 lanes of one (slot, joint) sit inside one
-//     wave (R is a multiple of 64 / gcd(C4, 64)) and reduce with an xor-shuffle tree; one block holds all K joints;
+//   * power of two, D in {4,8,16,32,64} where that block exists for K (pow2_policy): pix -> (h, w) is shift/mask; the
+//     G = D/4 lanes of one (slot, joint) sit inside one wave (R is a multiple of 64 / gcd(C4, 64)) and reduce with an
+//     xor-shuffle tree; one block holds all K joints;
 //   * general, every other D % 4 == 0 up to 128: one division per thread before the loop, then the thread walks (h, w) by
 //     its pixel stride (rh rows + rw columns, one carry); the G lanes reduce through LDS in lane order (G = 3, 10, 24 ... have
 //     no xor tree), wherever the group falls inside a wave; a block holds the channel quads of KT joints (all K when
 //     K*G <= 1024, else the joints are tiled over gridDim.z).
-// XAS_TUNE_GENERAL_KERNELS puts the power-of-two sides on the general policy too (coverage: pow2_policy is the one rule).
+// A power-of-two side that the first policy cannot hold runs on the general one; XAS_TUNE_GENERAL_KERNELS puts every
+// power-of-two side there (coverage).  pow2_policy is the one rule.
 #include "common.h"
 
 namespace xas {
@@ -31,9 +33,22 @@ struct HeadGeom {
   int P, nchunk;                    // pixels per block, blocks per image
 };
 
-// The dispatch rule: which policy a cube side runs on.
-static bool pow2_policy(int D) {
-  return D >= 4 && D <= 64 && (D & (D - 1)) == 0 && !(tune_flags() & XAS_TUNE_GENERAL_KERNELS);
+// Pixel slots of the power-of-two policy: its lane groups never straddle a wave, so R is a multiple of 64 / gcd(C4, 64).
+static int pow2_slots(long C4) {
+  int gcd = 1;
+  while (gcd < 64 && (C4 % (gcd * 2)) == 0) gcd *= 2;
+  return 64 / gcd;
+}
+
+// The dispatch rule: which policy a (cube side, joint count) runs on.  A power-of-two side whose power-of-two geometry does
+// not exist (fewer pixels than the slots that keep a lane group inside a wave, or a block wider than 1024 threads: K = 3 at
+// D = 4, K = 17 at D = 64) runs on the general policy, which tiles the joints.
+static bool pow2_policy(int D, int K) {
+  if (!(D >= 4 && D <= 64 && (D & (D - 1)) == 0) || (tune_flags() & XAS_TUNE_GENERAL_KERNELS)) return false;
+  if (K <= 0) return true;                        // (make_geom reports it)
+  const long C4 = (long)K * (D / 4);
+  const int R = pow2_slots(C4);
+  return R <= D * D && C4 * R <= 1024;
 }
 
 static int make_geom(int B, int K, int D, bool pow2, HeadGeom* g) {
@@ -49,11 +64,7 @@ static int make_geom(int B, int K, int D, bool pow2, HeadGeom* g) {
   g->KT = (K + g->ntile - 1) / g->ntile;
   g->C4t = g->KT * g->G;
   int R = 1;
-  if (pow2) {                                     // a lane group never straddles a wave: R is a multiple of 64 / gcd(C4, 64)
-    int gcd = 1;
-    while (gcd < 64 && (g->C4 % (gcd * 2)) == 0) gcd *= 2;
-    R = 64 / gcd;
-  }
+  if (pow2) R = pow2_slots(g->C4);
   while ((long)g->C4t * R * 2 <= 640 && R * 2 <= g->HW) R *= 2;
   XAS_REQUIRE((long)g->C4t * R <= 1024, "head: K*D=%d too wide for one workgroup", K * D);
   g->R = R; g->rh = R / g->W; g->rw = R % g->W;
@@ -387,14 +398,14 @@ using namespace xas;
 
 extern "C" size_t xas_head_workspace_floats(int B, int K, int D) {
   HeadGeom g;
-  if (make_geom(B, K, D, pow2_policy(D), &g)) return 0;
+  if (make_geom(B, K, D, pow2_policy(D, K), &g)) return 0;
   return (size_t)B * g.nchunk * K * g.rec;
 }
 
 extern "C" int xas_head_softargmax_fwd(const float* logits, int B, int K, int D, int num_hypo, int neighbor,
                                        float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                        float* partial, void* stream) {
-  const bool pow2 = pow2_policy(D);
+  const bool pow2 = pow2_policy(D, K);
   HeadGeom g;
   if (make_geom(B, K, D, pow2, &g)) return 1;
   XAS_REQUIRE(logits && kps && depth_prob_map && stats && partial, "head fwd: null buffer");
@@ -417,7 +428,7 @@ extern "C" int xas_head_softargmax_from_partials(const float* partial, int B, in
                                                  float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                                  void* stream) {
   HeadGeom g;
-  if (make_geom(B, K, D, pow2_policy(D), &g)) return 1;
+  if (make_geom(B, K, D, pow2_policy(D, K), &g)) return 1;
   XAS_REQUIRE(partial && kps && depth_prob_map && stats && nchunk >= 1, "head from partials: null buffer");
   if (check_modes("head from partials", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
   g.nchunk = nchunk;
@@ -433,7 +444,7 @@ extern "C" int xas_head_softargmax_bwd(const float* logits, const float* stats, 
 extern "C" int xas_head_softargmax_bwd_amax(const float* logits, const float* stats, const int64_t* z_idx,
                                             const float* grad_kps, int B, int K, int D, int num_hypo, int neighbor,
                                             float* grad_logits, float* coef, float* amax_out, void* stream) {
-  const bool pow2 = pow2_policy(D);
+  const bool pow2 = pow2_policy(D, K);
   HeadGeom g;
   if (make_geom(B, K, D, pow2, &g)) return 1;
   XAS_REQUIRE(logits && stats && grad_kps && grad_logits && coef, "head bwd: null buffer");
