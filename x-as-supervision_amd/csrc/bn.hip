@@ -428,216 +428,177 @@ __global__ void bn_sync_merge_kernel(const float* __restrict__ gathered, int wor
   if (running_mean) { running_mean[c] = rm; running_var[c] = rv; }
 }
 
+// ---------------------------------------------------------------- the two element-wise passes (apply, backward apply)
+// The arithmetic of an element is written ONCE per pass (bn_fwd_elem, bn_bwd_elem); a kernel template per pass wraps it in
+// one of two loop policies:
+//   streaming: the threads of a grid row are a multiple of C/4, so a thread keeps ONE channel quadruple: its per-channel
+//              quantities are read once, the loop is unrolled 4x with non-temporal 16-byte loads issued ahead plus a tail,
+//              non-temporal stores, the mode a template argument (no branches) - in the backward pass these kernels share
+//              the chip with two weight-gradient blocks per CU and get few wave slots;
+//   general  : grid-stride loop, channel quadruple from i % C4 in every trip, plain loads and stores, the mode read at run
+//              time from `act` and from which pointers are null: every combination the entry points accept.
+// bn_stream_grid (host) picks the policy.  The reductions (col_reduce_body MODE 1 / 3 / 4) and the convolution epilogues
+// (conv_shared.h) keep their own copy of the sign / xhat logic under a tuned register budget (86 / <= 64 VGPRs).
 __device__ __forceinline__ float act_fwd(float v, int act) {
   return act == 0 ? v : (act == 1 ? fmaxf(v, 0.f) : (v > 0.f ? v : 0.01f * v));
 }
 
-// grid.y = group: the rows of group g use mean / var row g ([G][C]); n4g = float4 elements per group
-__global__ void bn_apply_kernel(const float4* __restrict__ x, const float* __restrict__ mean,
-                                const float* __restrict__ var, const float* __restrict__ gamma,
-                                const float* __restrict__ beta, const float4* __restrict__ res, float eps, int act,
-                                long n4g, int C4, float4* __restrict__ y, uint8_t* __restrict__ mask_out,
-                                float* __restrict__ amax_out) {
-  float amx = 0.f;
-  const long goff = (long)blockIdx.y * n4g;
-  mean += (size_t)blockIdx.y * C4 * 4; var += (size_t)blockIdx.y * C4 * 4;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4g; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C4) * 4;
-    const float4 m = *reinterpret_cast<const float4*>(mean + c), v = *reinterpret_cast<const float4*>(var + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
-    const float4 xv = x[goff + i];
-    float4 o;
-    o.x = bn_affine(xv.x, m.x, __fmul_rn(rsqrtf(v.x + eps), g.x), b.x);
-    o.y = bn_affine(xv.y, m.y, __fmul_rn(rsqrtf(v.y + eps), g.y), b.y);
-    o.z = bn_affine(xv.z, m.z, __fmul_rn(rsqrtf(v.z + eps), g.z), b.z);
-    o.w = bn_affine(xv.w, m.w, __fmul_rn(rsqrtf(v.w + eps), g.w), b.w);
-    if (res) { const float4 r = res[goff + i]; o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w; }
-    if (mask_out)          // sign bits of the pre-activation value: what the backward needs of y (1/16 of its bytes)
-      mask_out[goff + i] = (uint8_t)((o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) | (o.w > 0.f ? 8u : 0u));
-    o.x = act_fwd(o.x, act); o.y = act_fwd(o.y, act); o.z = act_fwd(o.z, act); o.w = act_fwd(o.w, act);
-    amx = amax4(amx, o);
-    y[goff + i] = o;
-  }
-  if (amax_out) publish_amax(amax_out, amx);
+// the per-channel quantities of one channel quadruple
+struct BnChan {
+  float4 m, is, rs, g, bt;   // mean, rstd, rstd * gamma (rounded once: bn_affine's contract), gamma, beta
+  float4 a, b;               // backward: sum dz, sum dz xhat of the group
+};
+
+// of float4 element i of group blockIdx.y.  BWD: with the two sums, and beta may be null where the mode does not read it
+template <bool BWD>
+__device__ __forceinline__ BnChan bn_chan(const float* mean, const float* var, const float* gamma, const float* beta,
+                                          const float* sums, float eps, int C4, long i) {
+  const int c = (int)(i % C4) * 4;
+  BnChan ch;
+  const size_t gc = (size_t)blockIdx.y * C4 * 4 + c;
+  ch.m = *reinterpret_cast<const float4*>(mean + gc);
+  const float4 v = *reinterpret_cast<const float4*>(var + gc);
+  ch.g = *reinterpret_cast<const float4*>(gamma + c);
+  ch.bt = (!BWD || beta) ? *reinterpret_cast<const float4*>(beta + c) : make_float4(0, 0, 0, 0);   // (a value, not an lvalue: ONE load)
+  ch.a = BWD ? *reinterpret_cast<const float4*>(sums + (size_t)blockIdx.y * C4 * 8 + c) : make_float4(0, 0, 0, 0);
+  ch.b = BWD ? *reinterpret_cast<const float4*>(sums + (size_t)blockIdx.y * C4 * 8 + (size_t)C4 * 4 + c) : make_float4(0, 0, 0, 0);
+  ch.is = make_float4(rsqrtf(v.x + eps), rsqrtf(v.y + eps), rsqrtf(v.z + eps), rsqrtf(v.w + eps));
+  ch.rs = make_float4(__fmul_rn(ch.is.x, ch.g.x), __fmul_rn(ch.is.y, ch.g.y), __fmul_rn(ch.is.z, ch.g.z), __fmul_rn(ch.is.w, ch.g.w));
+  return ch;
 }
 
-// grid.y = group; sums: [G][2][C] = sum_dz | sum_dz_xhat of each group
-__global__ void bn_bwd_apply_kernel(const float4* __restrict__ x, const float4* __restrict__ y,
-                                    const float4* __restrict__ dy, const float* __restrict__ mean,
-                                    const float* __restrict__ var, const float* __restrict__ gamma,
-                                    const float* __restrict__ beta, const float* __restrict__ sums,
-                                    float eps, int act, long n4g, int C4,
-                                    float inv_count, float4* __restrict__ dx, float4* __restrict__ dres,
-                                    const uint8_t* __restrict__ mask, float* __restrict__ amax_out) {
-  float amx = 0.f;
-  const long goff = (long)blockIdx.y * n4g;
-  mean += (size_t)blockIdx.y * C4 * 4; var += (size_t)blockIdx.y * C4 * 4;
-  const float* sdz = sums + (size_t)blockIdx.y * C4 * 8;
-  const float* sdzx = sdz + (size_t)C4 * 4;
-  for (long ii = (long)blockIdx.x * blockDim.x + threadIdx.x; ii < n4g; ii += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(ii % C4) * 4;
-    const long i = goff + ii;
-    const float4 m = *reinterpret_cast<const float4*>(mean + c), v = *reinterpret_cast<const float4*>(var + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 a = *reinterpret_cast<const float4*>(sdz + c), b = *reinterpret_cast<const float4*>(sdzx + c);
-    float4 dz = dy[i];
-    float4 yv = make_float4(0, 0, 0, 0);
-    if (act && mask) {                                     // sign bits saved by the forward (layers with a residual)
-      const unsigned mb = mask[i];
-      const float neg = act == 1 ? 0.f : 0.01f;
-      dz.x *= (mb & 1u) ? 1.f : neg; dz.y *= (mb & 2u) ? 1.f : neg;
-      dz.z *= (mb & 4u) ? 1.f : neg; dz.w *= (mb & 8u) ? 1.f : neg;
-    } else if (act && y) {
-      yv = y[i];
-      const float neg = act == 1 ? 0.f : 0.01f;
-      dz.x *= yv.x > 0.f ? 1.f : neg; dz.y *= yv.y > 0.f ? 1.f : neg;
-      dz.z *= yv.z > 0.f ? 1.f : neg; dz.w *= yv.w > 0.f ? 1.f : neg;
-    } else if (act) {                                      // y not read: the mask is re-derived from x (no residual)
-      const float4 xv = x[i];
-      const float4 bt = *reinterpret_cast<const float4*>(beta + c);
-      const float neg = act == 1 ? 0.f : 0.01f;
-      dz.x *= bn_affine(xv.x, m.x, __fmul_rn(rsqrtf(v.x + eps), g.x), bt.x) > 0.f ? 1.f : neg;
-      dz.y *= bn_affine(xv.y, m.y, __fmul_rn(rsqrtf(v.y + eps), g.y), bt.y) > 0.f ? 1.f : neg;
-      dz.z *= bn_affine(xv.z, m.z, __fmul_rn(rsqrtf(v.z + eps), g.z), bt.z) > 0.f ? 1.f : neg;
-      dz.w *= bn_affine(xv.w, m.w, __fmul_rn(rsqrtf(v.w + eps), g.w), bt.w) > 0.f ? 1.f : neg;
-    }
-    if (dres) dres[i] = dz;
-    float4 xh;                                             // normalised input
-    float4 is = make_float4(rsqrtf(v.x + eps), rsqrtf(v.y + eps), rsqrtf(v.z + eps), rsqrtf(v.w + eps));
-    if (x) {
-      const float4 xv = x[i];
-      xh = make_float4((xv.x - m.x) * is.x, (xv.y - m.y) * is.y, (xv.z - m.z) * is.z, (xv.w - m.w) * is.w);
-    } else {                                               // recovered from y: z = act^-1(y), xhat = (z - beta) / gamma
-      const float4 bt = *reinterpret_cast<const float4*>(beta + c);
-      const float up = act == 1 ? 0.f : 100.f;
-      xh.x = g.x != 0.f ? ((yv.x > 0.f ? yv.x : yv.x * up) - bt.x) / g.x : 0.f;
-      xh.y = g.y != 0.f ? ((yv.y > 0.f ? yv.y : yv.y * up) - bt.y) / g.y : 0.f;
-      xh.z = g.z != 0.f ? ((yv.z > 0.f ? yv.z : yv.z * up) - bt.z) / g.z : 0.f;
-      xh.w = g.w != 0.f ? ((yv.w > 0.f ? yv.w : yv.w * up) - bt.w) / g.w : 0.f;
-    }
-    float4 o;
-    o.x = g.x * is.x * (dz.x - a.x * inv_count - xh.x * b.x * inv_count);
-    o.y = g.y * is.y * (dz.y - a.y * inv_count - xh.y * b.y * inv_count);
-    o.z = g.z * is.z * (dz.z - a.z * inv_count - xh.z * b.z * inv_count);
-    o.w = g.w * is.w * (dz.w - a.w * inv_count - xh.w * b.w * inv_count);
-    amx = fmaxf(fmaxf(amx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    dx[i] = o;
-  }
-  if (amax_out) publish_amax(amax_out, amx);
+template <bool NT> __device__ __forceinline__ void ew_store(float4* p, float4 v) { if (NT) stream_store(p, v); else *p = v; }
+
+// -> y = act((x - mean) * (rstd * gamma) + beta [+ residual]); amx: running max |y|.  has_mask: *mask = sign bits of the
+// pre-activation value (bit e = lane e > 0): what the backward needs of y, 1/16 of its bytes
+__device__ __forceinline__ float4 bn_fwd_elem(const BnChan& ch, float4 xv, float4 rv, int act, bool res, bool has_mask,
+                                              uint8_t* mask, float& amx) {
+  float4 o;
+  o.x = bn_affine(xv.x, ch.m.x, ch.rs.x, ch.bt.x); o.y = bn_affine(xv.y, ch.m.y, ch.rs.y, ch.bt.y);
+  o.z = bn_affine(xv.z, ch.m.z, ch.rs.z, ch.bt.z); o.w = bn_affine(xv.w, ch.m.w, ch.rs.w, ch.bt.w);
+  if (res) { o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w; }
+  if (has_mask) *mask = (uint8_t)((o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) | (o.w > 0.f ? 8u : 0u));
+  o.x = act_fwd(o.x, act); o.y = act_fwd(o.y, act); o.z = act_fwd(o.z, act); o.w = act_fwd(o.w, act);
+  amx = amax4(amx, o);
+  return o;
 }
 
-// ---- streaming forms of the two apply kernels.  When the number of threads in a grid row is a multiple of C/4 a thread
-// sees ONE channel quadruple for its whole life: the per-channel parameters are read once, the loop body is only the
-// activation stream, compiled per mode (no branches) and unrolled so that several 16-byte loads are in flight per lane -
-// in the backward pass these kernels share the chip with two weight-gradient blocks per CU and get few wave slots.
-template <int ACT, bool RES, bool MASKOUT>
-__global__ __launch_bounds__(256) void bn_apply_stream_kernel(const float4* __restrict__ x, const float* __restrict__ mean,
-                                                             const float* __restrict__ var, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, const float4* __restrict__ res,
-                                                             float eps, long n4g, int C4, float4* __restrict__ y,
-                                                             uint8_t* __restrict__ mask_out, float* __restrict__ amax_out) {
+// sign: where the activation sign comes from: 0 no activation, 1 y, 2 x (re-derived with bn_affine: the forward's decision
+//       bit for bit; layers without a residual), 3 mask bytes
+// xh  : normalised input from x (true) or recovered from y (false: z = act^-1(y), xhat = (z - beta) / gamma; leaky ReLU)
+// dz  : dy, then the gradient at the pre-activation value = the residual's gradient, stored to *dres if has_dres
+// -> dx; amx: running max |dx|
+template <bool NT>
+__device__ __forceinline__ float4 bn_bwd_elem(const BnChan& ch, float inv_count, float4 xv, float4 yv, float4 dz, unsigned mb,
+                                              int act, int sign, bool xh_from_x, bool has_dres, float4* dres, float& amx) {
+  const float neg = act == 1 ? 0.f : 0.01f, up = act == 1 ? 0.f : 100.f;
+  const float4 &m = ch.m, &is = ch.is, &rs = ch.rs, &g = ch.g, &bt = ch.bt, &a = ch.a, &b = ch.b;
+  if (sign == 1) {
+    dz.x *= yv.x > 0.f ? 1.f : neg; dz.y *= yv.y > 0.f ? 1.f : neg; dz.z *= yv.z > 0.f ? 1.f : neg; dz.w *= yv.w > 0.f ? 1.f : neg;
+  } else if (sign == 2) {
+    dz.x *= bn_affine(xv.x, m.x, rs.x, bt.x) > 0.f ? 1.f : neg; dz.y *= bn_affine(xv.y, m.y, rs.y, bt.y) > 0.f ? 1.f : neg;
+    dz.z *= bn_affine(xv.z, m.z, rs.z, bt.z) > 0.f ? 1.f : neg; dz.w *= bn_affine(xv.w, m.w, rs.w, bt.w) > 0.f ? 1.f : neg;
+  } else if (sign == 3) {
+    dz.x *= (mb & 1u) ? 1.f : neg; dz.y *= (mb & 2u) ? 1.f : neg; dz.z *= (mb & 4u) ? 1.f : neg; dz.w *= (mb & 8u) ? 1.f : neg;
+  }
+  if (has_dres) ew_store<NT>(dres, dz);
+  float4 xh;
+  if (xh_from_x) xh = make_float4((xv.x - m.x) * is.x, (xv.y - m.y) * is.y, (xv.z - m.z) * is.z, (xv.w - m.w) * is.w);
+  else {
+    xh.x = g.x != 0.f ? ((yv.x > 0.f ? yv.x : yv.x * up) - bt.x) / g.x : 0.f;
+    xh.y = g.y != 0.f ? ((yv.y > 0.f ? yv.y : yv.y * up) - bt.y) / g.y : 0.f;
+    xh.z = g.z != 0.f ? ((yv.z > 0.f ? yv.z : yv.z * up) - bt.z) / g.z : 0.f;
+    xh.w = g.w != 0.f ? ((yv.w > 0.f ? yv.w : yv.w * up) - bt.w) / g.w : 0.f;
+  }
+  float4 o;
+  o.x = g.x * is.x * (dz.x - a.x * inv_count - xh.x * b.x * inv_count);
+  o.y = g.y * is.y * (dz.y - a.y * inv_count - xh.y * b.y * inv_count);
+  o.z = g.z * is.z * (dz.z - a.z * inv_count - xh.z * b.z * inv_count);
+  o.w = g.w * is.w * (dz.w - a.w * inv_count - xh.w * b.w * inv_count);
+  amx = fmaxf(fmaxf(amx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+  return o;
+}
+
+// grid.y = group: the rows of group g use mean / var row g ([G][C]); n4g = float4 elements per group.
+// STREAM: mode = <ACT, RES, MASKOUT>; general: mode = (act, res != null, mask_out != null)
+template <bool STREAM, int ACT = 0, bool RES = false, bool MASKOUT = false>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float4* __restrict__ x, const float* __restrict__ mean,
+                                                      const float* __restrict__ var, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, const float4* __restrict__ res,
+                                                      float eps, int act_rt, long n4g, int C4, float4* __restrict__ y,
+                                                      uint8_t* __restrict__ mask_out, float* __restrict__ amax_out) {
+  const int act = STREAM ? ACT : act_rt;
+  const bool has_res = STREAM ? RES : res != nullptr, has_mask = STREAM ? MASKOUT : mask_out != nullptr;
   float amx = 0.f;                                     // max |y| of this thread (amax_out != null: xas_bn_apply_amax)
-  __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
+  if (STREAM) __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
   const long goff = (long)blockIdx.y * n4g;
   const long stride = (long)gridDim.x * blockDim.x;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c = (int)(i % C4) * 4;
-  const float4 m = *reinterpret_cast<const float4*>(mean + (size_t)blockIdx.y * C4 * 4 + c);
-  const float4 v = *reinterpret_cast<const float4*>(var + (size_t)blockIdx.y * C4 * 4 + c);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
-  const float4 rs = make_float4(__fmul_rn(rsqrtf(v.x + eps), g.x), __fmul_rn(rsqrtf(v.y + eps), g.y),
-                                __fmul_rn(rsqrtf(v.z + eps), g.z), __fmul_rn(rsqrtf(v.w + eps), g.w));
+  BnChan ch;
   auto one = [&](long k, float4 xv, float4 rv) {
-    float4 o;
-    o.x = bn_affine(xv.x, m.x, rs.x, b.x); o.y = bn_affine(xv.y, m.y, rs.y, b.y);
-    o.z = bn_affine(xv.z, m.z, rs.z, b.z); o.w = bn_affine(xv.w, m.w, rs.w, b.w);
-    if (RES) { o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w; }
-    if (MASKOUT)
-      mask_out[goff + k] = (uint8_t)((o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) | (o.w > 0.f ? 8u : 0u));
-    o.x = act_fwd(o.x, ACT); o.y = act_fwd(o.y, ACT); o.z = act_fwd(o.z, ACT); o.w = act_fwd(o.w, ACT);
-    amx = amax4(amx, o);
-    stream_store(y + goff + k, o);
+    ew_store<STREAM>(y + goff + k, bn_fwd_elem(ch, xv, rv, act, has_res, has_mask, mask_out + goff + k, amx));
   };
   const float4 z4 = make_float4(0, 0, 0, 0);
-  for (; i + 3 * stride < n4g; i += 4 * stride) {
-    float4 xv[4], rv[4];
+  if (STREAM) {
+    ch = bn_chan<false>(mean, var, gamma, beta, nullptr, eps, C4, i);
+    for (; i + 3 * stride < n4g; i += 4 * stride) {
+      float4 xv[4], rv[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) { xv[u] = stream_load(x + goff + i + u * stride); rv[u] = RES ? stream_load(res + goff + i + u * stride) : z4; }
+      for (int u = 0; u < 4; ++u) { xv[u] = stream_load(x + goff + i + u * stride); rv[u] = has_res ? stream_load(res + goff + i + u * stride) : z4; }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) one(i + u * stride, xv[u], rv[u]);
+      for (int u = 0; u < 4; ++u) one(i + u * stride, xv[u], rv[u]);
+    }
   }
-  for (; i < n4g; i += stride) one(i, x[goff + i], RES ? res[goff + i] : z4);
+  for (; i < n4g; i += stride) {                       // streaming: the tail; general: the whole loop
+    if (!STREAM) ch = bn_chan<false>(mean, var, gamma, beta, nullptr, eps, C4, i);
+    one(i, x[goff + i], has_res ? res[goff + i] : z4);
+  }
   if (amax_out) publish_amax(amax_out, amx);
 }
 
-// SIGN: where the activation sign comes from: 0 no activation, 1 y, 2 x (re-derived, no residual), 3 mask bytes
-// XH  : normalised input from x (true) or recovered from y (false: leaky ReLU, SIGN == 1)
-template <int ACT, int SIGN, bool XH, bool DRES>
-__global__ __launch_bounds__(256) void bn_bwd_apply_stream_kernel(
+// grid.y = group; sums: [G][2][C] = sum_dz | sum_dz_xhat of each group.
+// STREAM: mode = <ACT, SIGN, XH, DRES>; general: mode = (act, mask ? 3 : y ? 1 : 2 under an activation, x != null, dres != null)
+template <bool STREAM, int ACT = 0, int SIGN = 0, bool XH = true, bool DRES = false>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float4* __restrict__ x, const float4* __restrict__ y, const float4* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ sums, float eps, long n4g, int C4, float inv_count, float4* __restrict__ dx,
+    const float* __restrict__ sums, float eps, int act_rt, long n4g, int C4, float inv_count, float4* __restrict__ dx,
     float4* __restrict__ dres, const uint8_t* __restrict__ mask, float* __restrict__ amax_out) {
-  __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
+  const int act = STREAM ? ACT : act_rt;
+  const int sign = STREAM ? SIGN : (act_rt == 0 ? 0 : mask ? 3 : y ? 1 : 2);
+  const bool xh = STREAM ? XH : x != nullptr, has_dres = STREAM ? DRES : dres != nullptr;
+  const bool needx = xh || sign == 2, needy = sign == 1 || !xh;
+  if (STREAM) __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
   float amx = 0.f;                                     // max |dx| of this thread (amax_out != null: xas_bn_bwd_apply_amax)
   const long goff = (long)blockIdx.y * n4g;
   const long stride = (long)gridDim.x * blockDim.x;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c = (int)(i % C4) * 4;
-  const size_t gc = (size_t)blockIdx.y * C4 * 4 + c;
-  const float4 m = *reinterpret_cast<const float4*>(mean + gc), v = *reinterpret_cast<const float4*>(var + gc);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-  const float4 bt = beta ? *reinterpret_cast<const float4*>(beta + c) : make_float4(0, 0, 0, 0);
-  const float4 a = *reinterpret_cast<const float4*>(sums + (size_t)blockIdx.y * C4 * 8 + c);
-  const float4 b = *reinterpret_cast<const float4*>(sums + (size_t)blockIdx.y * C4 * 8 + (size_t)C4 * 4 + c);
-  const float4 is = make_float4(rsqrtf(v.x + eps), rsqrtf(v.y + eps), rsqrtf(v.z + eps), rsqrtf(v.w + eps));
-  const float4 rs = make_float4(__fmul_rn(is.x, g.x), __fmul_rn(is.y, g.y), __fmul_rn(is.z, g.z), __fmul_rn(is.w, g.w));
-  constexpr float neg = ACT == 1 ? 0.f : 0.01f, up = ACT == 1 ? 0.f : 100.f;
+  BnChan ch;
   auto one = [&](long k, float4 xv, float4 yv, float4 dz, unsigned mb) {
-    if (SIGN == 1) {
-      dz.x *= yv.x > 0.f ? 1.f : neg; dz.y *= yv.y > 0.f ? 1.f : neg; dz.z *= yv.z > 0.f ? 1.f : neg; dz.w *= yv.w > 0.f ? 1.f : neg;
-    } else if (SIGN == 2) {
-      dz.x *= bn_affine(xv.x, m.x, rs.x, bt.x) > 0.f ? 1.f : neg; dz.y *= bn_affine(xv.y, m.y, rs.y, bt.y) > 0.f ? 1.f : neg;
-      dz.z *= bn_affine(xv.z, m.z, rs.z, bt.z) > 0.f ? 1.f : neg; dz.w *= bn_affine(xv.w, m.w, rs.w, bt.w) > 0.f ? 1.f : neg;
-    } else if (SIGN == 3) {
-      dz.x *= (mb & 1u) ? 1.f : neg; dz.y *= (mb & 2u) ? 1.f : neg; dz.z *= (mb & 4u) ? 1.f : neg; dz.w *= (mb & 8u) ? 1.f : neg;
-    }
-    if (DRES) stream_store(dres + goff + k, dz);
-    float4 xh;
-    if (XH) xh = make_float4((xv.x - m.x) * is.x, (xv.y - m.y) * is.y, (xv.z - m.z) * is.z, (xv.w - m.w) * is.w);
-    else {
-      xh.x = g.x != 0.f ? ((yv.x > 0.f ? yv.x : yv.x * up) - bt.x) / g.x : 0.f;
-      xh.y = g.y != 0.f ? ((yv.y > 0.f ? yv.y : yv.y * up) - bt.y) / g.y : 0.f;
-      xh.z = g.z != 0.f ? ((yv.z > 0.f ? yv.z : yv.z * up) - bt.z) / g.z : 0.f;
-      xh.w = g.w != 0.f ? ((yv.w > 0.f ? yv.w : yv.w * up) - bt.w) / g.w : 0.f;
-    }
-    float4 o;
-    o.x = g.x * is.x * (dz.x - a.x * inv_count - xh.x * b.x * inv_count);
-    o.y = g.y * is.y * (dz.y - a.y * inv_count - xh.y * b.y * inv_count);
-    o.z = g.z * is.z * (dz.z - a.z * inv_count - xh.z * b.z * inv_count);
-    o.w = g.w * is.w * (dz.w - a.w * inv_count - xh.w * b.w * inv_count);
-    amx = fmaxf(fmaxf(amx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    stream_store(dx + goff + k, o);
+    ew_store<STREAM>(dx + goff + k, bn_bwd_elem<STREAM>(ch, inv_count, xv, yv, dz, mb, act, sign, xh, has_dres, dres + goff + k, amx));
   };
   const float4 z4 = make_float4(0, 0, 0, 0);
-  constexpr bool NEEDX = XH || SIGN == 2, NEEDY = SIGN == 1 || !XH;
-  for (; i + 3 * stride < n4g; i += 4 * stride) {
-    float4 xv[4], yv[4], dv[4];
-    unsigned mb[4];
+  if (STREAM) {
+    ch = bn_chan<true>(mean, var, gamma, beta, sums, eps, C4, i);
+    for (; i + 3 * stride < n4g; i += 4 * stride) {
+      float4 xv[4], yv[4], dv[4];
+      unsigned mb[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long k = goff + i + u * stride;
-      dv[u] = stream_load(dy + k);
-      xv[u] = NEEDX ? stream_load(x + k) : z4;
-      yv[u] = NEEDY ? stream_load(y + k) : z4;
-      mb[u] = SIGN == 3 ? mask[k] : 0u;
+      for (int u = 0; u < 4; ++u) {
+        const long k = goff + i + u * stride;
+        dv[u] = stream_load(dy + k);
+        xv[u] = needx ? stream_load(x + k) : z4;
+        yv[u] = needy ? stream_load(y + k) : z4;
+        mb[u] = sign == 3 ? mask[k] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(i + u * stride, xv[u], yv[u], dv[u], mb[u]);
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) one(i + u * stride, xv[u], yv[u], dv[u], mb[u]);
   }
-  for (; i < n4g; i += stride) {
+  for (; i < n4g; i += stride) {                       // streaming: the tail; general: the whole loop
+    if (!STREAM) ch = bn_chan<true>(mean, var, gamma, beta, sums, eps, C4, i);
     const long k = goff + i;
-    one(i, NEEDX ? x[k] : z4, NEEDY ? y[k] : z4, dy[k], SIGN == 3 ? mask[k] : 0u);
+    one(i, needx ? x[k] : z4, needy ? y[k] : z4, dy[k], sign == 3 ? mask[k] : 0u);
   }
   if (amax_out) publish_amax(amax_out, amx);
 }
@@ -855,6 +816,51 @@ static inline unsigned ew_grid_g(long n_per_group, int groups) {
   return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
 }
 
+// The one rule "streaming or general policy" of the two apply passes -> grid.x of the streaming launch, or 0: general policy
+// on ew_grid_g blocks.  Streaming needs the threads of a grid row to be a multiple of C/4: C/4 a power of two (it then
+// divides 256, or above 256 the row is rounded up to whole multiples of C/4 threads).  XAS_TUNE_GENERAL_KERNELS sends every
+// launch to the general policy (coverage).  Under this rule a launch is streaming in the modes of these tables, else general:
+//   forward  <ACT, RES, MASKOUT>, 9 modes: act 0 / 1 / 2 x { no residual: <act, false, false> (a mask_out WITHOUT a residual
+//            is not written by this policy), residual: <act, true, false>, residual and mask_out: <act, true, true> }
+//   backward <ACT, SIGN, XH, DRES>, 7 modes (bn_bwd_elem explains SIGN and XH):
+//            0  act 0, x, no dresidual                 <0, 0, true, false>   projection norms
+//            1  act 1, x, no y, no mask, no dresidual  <1, 2, true, false>   ReLU without residual (sign re-derived from x)
+//            2  act 2, no x, y, no dresidual           <2, 1, false, false>  leaky ReLU without x (physique net)
+//            3  act 1, x, y, no mask, dresidual        <1, 1, true, true>    residual layers, sign from y
+//            4  act 1, x, y, no mask, no dresidual     <1, 1, true, false>
+//            5  act 1, x, mask, dresidual              <1, 3, true, true>    residual layers, sign from the mask bytes
+//            6  act 1, x, mask, no dresidual           <1, 3, true, false>
+//   general only: act 0 with dresidual; leaky ReLU with x (with or without y / mask / dresidual); C/4 not a power of two.
+static unsigned bn_stream_grid(long n4g, int C4, int groups, int tune) {
+  if ((C4 & (C4 - 1)) != 0 || (tune & XAS_TUNE_GENERAL_KERNELS)) return 0;
+  unsigned gx = ew_grid_g(n4g, groups);
+  if (C4 > 256) gx = (gx + (C4 / 256) - 1) / (C4 / 256) * (C4 / 256);
+  return gx;
+}
+
+using BnFwdKernel = decltype(&bn_apply_kernel<false>);          // both policies of a pass share one signature
+using BnBwdKernel = decltype(&bn_bwd_apply_kernel<false>);
+
+static BnFwdKernel bn_fwd_stream_kernel(int act, bool res, bool mask_out) {
+#define XAS_BN_FWD(ACT) {bn_apply_kernel<true, ACT, false, false>, bn_apply_kernel<true, ACT, true, false>, bn_apply_kernel<true, ACT, true, true>}
+  static const BnFwdKernel k[3][3] = {XAS_BN_FWD(0), XAS_BN_FWD(1), XAS_BN_FWD(2)};
+#undef XAS_BN_FWD
+  return k[act][res ? (mask_out ? 2 : 1) : 0];
+}
+
+// (act, which operands are present) -> the streaming kernel of the backward's mode, or null: general
+static BnBwdKernel bn_bwd_stream_kernel(int act, bool x, bool y, bool mask, bool dres) {
+  const int sign = act == 0 ? 0 : mask ? 3 : y ? 1 : 2;
+  static const struct { int act, sign; bool xh, dres; BnBwdKernel k; } modes[7] = {
+#define XAS_BN_BWD(ACT, SIGN, XH, DR) {ACT, SIGN, XH, DR, bn_bwd_apply_kernel<true, ACT, SIGN, XH, DR>}
+      XAS_BN_BWD(0, 0, true, false), XAS_BN_BWD(1, 2, true, false), XAS_BN_BWD(2, 1, false, false), XAS_BN_BWD(1, 1, true, true),
+      XAS_BN_BWD(1, 1, true, false), XAS_BN_BWD(1, 3, true, true), XAS_BN_BWD(1, 3, true, false)};
+#undef XAS_BN_BWD
+  for (const auto& m : modes)
+    if (m.act == act && m.sign == sign && m.xh == x && m.dres == dres) return m.k;
+  return nullptr;
+}
+
 static int col_args(ColArgs* a, const ColGeom& g, long M, int C, float* workspace) {
   a->M = M; a->C = C; a->g = g; a->partial = workspace;
   a->ticket = take_tickets(g.ncb);
@@ -963,32 +969,13 @@ extern "C" int xas_bn_apply_amax(const float* x, const float* mean, const float*
   XAS_REQUIRE(x && mean && var_biased && gamma && beta && y, "bn_apply: null buffer");
   XAS_REQUIRE(M > 0 && C >= 4 && C % 4 == 0 && act >= 0 && act <= 2 && groups >= 1 && M % groups == 0,
               "bn_apply: bad shape M=%ld C=%d act=%d groups=%d", M, C, act, groups);
-  const long n4g = (M / groups) * (C / 4);
-  {
-    // streaming form: every thread keeps one channel quadruple (threads per grid row a multiple of C/4)
-    const int C4 = C / 4;
-    unsigned gx = ew_grid_g(n4g, groups);
-    const bool pow2 = (C4 & (C4 - 1)) == 0;
-    if (pow2 && C4 > 256) gx = (gx + (C4 / 256) - 1) / (C4 / 256) * (C4 / 256);
-    if (pow2 && ((long)gx * 256) % C4 == 0 && !(tune_flags() & XAS_TUNE_GENERAL_KERNELS)) {
-      const dim3 grid(gx, groups);
-      const float4* x4 = reinterpret_cast<const float4*>(x);
-      const float4* r4 = reinterpret_cast<const float4*>(residual);
-      float4* y4 = reinterpret_cast<float4*>(y);
-#define XAS_BN_FWD(ACT, RES, MK)                                                                                         \
-  hipLaunchKernelGGL((bn_apply_stream_kernel<ACT, RES, MK>), grid, dim3(256), 0, as_stream(stream), x4, mean, var_biased, \
-                     gamma, beta, r4, eps, n4g, C4, y4, mask_out, amax_out)
-      if (residual && mask_out) { if (act == 1) XAS_BN_FWD(1, true, true); else if (act == 2) XAS_BN_FWD(2, true, true); else XAS_BN_FWD(0, true, true); }
-      else if (residual) { if (act == 1) XAS_BN_FWD(1, true, false); else if (act == 2) XAS_BN_FWD(2, true, false); else XAS_BN_FWD(0, true, false); }
-      else { if (act == 1) XAS_BN_FWD(1, false, false); else if (act == 2) XAS_BN_FWD(2, false, false); else XAS_BN_FWD(0, false, false); }
-#undef XAS_BN_FWD
-      XAS_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid_g(n4g, groups), groups), dim3(256), 0, as_stream(stream),
+  const int C4 = C / 4;
+  const long n4g = (M / groups) * C4;
+  const unsigned gs = bn_stream_grid(n4g, C4, groups, tune_flags());
+  const BnFwdKernel k = gs ? bn_fwd_stream_kernel(act, residual != nullptr, mask_out != nullptr) : bn_apply_kernel<false>;
+  hipLaunchKernelGGL(k, dim3(gs ? gs : ew_grid_g(n4g, groups), groups), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const float4*>(x), mean, var_biased, gamma, beta,
-                     reinterpret_cast<const float4*>(residual), eps, act, n4g, C / 4, reinterpret_cast<float4*>(y), mask_out,
+                     reinterpret_cast<const float4*>(residual), eps, act, n4g, C4, reinterpret_cast<float4*>(y), mask_out,
                      amax_out);
   XAS_LAUNCH_CHECK();
   return 0;
@@ -1076,49 +1063,16 @@ extern "C" int xas_bn_bwd_apply_amax(const float* x, const float* y, const float
               "bn_bwd_apply: without x the layer needs an INVERTIBLE activation (leaky ReLU), y and beta: dx needs xhat "
               "of every element, also where ReLU clipped the output");
   XAS_REQUIRE(M > 0 && C >= 4 && C % 4 == 0 && count > 0 && groups >= 1 && M % groups == 0, "bn_bwd_apply: bad shape");
-  const long n4g = (M / groups) * (C / 4);
-  {
-    const int C4 = C / 4;
-    unsigned gx = ew_grid_g(n4g, groups);
-    const bool pow2 = (C4 & (C4 - 1)) == 0;
-    if (pow2 && C4 > 256) gx = (gx + (C4 / 256) - 1) / (C4 / 256) * (C4 / 256);
-    // modes of the model: ReLU without residual (sign from x), leaky ReLU without x (physique net), residual layers
-    // (sign from y or from the mask bytes), no activation (projection norms); anything else takes the generic kernel
-    int mode = -1;
-    if (act == 0 && x && !dresidual) mode = 0;
-    else if (act == 1 && x && !y && !mask && !dresidual) mode = 1;
-    else if (act == 2 && !x && y && !dresidual) mode = 2;
-    else if (act == 1 && x && y && !mask) mode = dresidual ? 3 : 4;
-    else if (act == 1 && x && mask) mode = dresidual ? 5 : 6;
-    if (mode >= 0 && pow2 && ((long)gx * 256) % C4 == 0 && !(tune_flags() & XAS_TUNE_GENERAL_KERNELS)) {
-      const dim3 grid(gx, groups);
-      const float4* x4 = reinterpret_cast<const float4*>(x);
-      const float4* y4 = reinterpret_cast<const float4*>(y);
-      const float4* d4 = reinterpret_cast<const float4*>(dy);
-      float4* o4 = reinterpret_cast<float4*>(dx);
-      float4* r4 = reinterpret_cast<float4*>(dresidual);
-      const float ic = (float)(1.0 / count);
-#define XAS_BN_BWD(ACT, SIGN, XH, DR)                                                                                      \
-  hipLaunchKernelGGL((bn_bwd_apply_stream_kernel<ACT, SIGN, XH, DR>), grid, dim3(256), 0, as_stream(stream), x4, y4, d4, mean, \
-                     var_biased, gamma, beta, sums, eps, n4g, C4, ic, o4, r4, mask, amax_out)
-      switch (mode) {
-        case 0: XAS_BN_BWD(0, 0, true, false); break;
-        case 1: XAS_BN_BWD(1, 2, true, false); break;
-        case 2: XAS_BN_BWD(2, 1, false, false); break;
-        case 3: XAS_BN_BWD(1, 1, true, true); break;
-        case 4: XAS_BN_BWD(1, 1, true, false); break;
-        case 5: XAS_BN_BWD(1, 3, true, true); break;
-        default: XAS_BN_BWD(1, 3, true, false); break;
-      }
-#undef XAS_BN_BWD
-      XAS_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid_g(n4g, groups), groups), dim3(256), 0, as_stream(stream),
+  const int C4 = C / 4;
+  const long n4g = (M / groups) * C4;
+  const unsigned gs = bn_stream_grid(n4g, C4, groups, tune_flags());
+  BnBwdKernel k = gs ? bn_bwd_stream_kernel(act, x != nullptr, y != nullptr, mask != nullptr, dresidual != nullptr) : nullptr;
+  const unsigned gx = k ? gs : ew_grid_g(n4g, groups);
+  if (!k) k = bn_bwd_apply_kernel<false>;
+  hipLaunchKernelGGL(k, dim3(gx, groups), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y),
                      reinterpret_cast<const float4*>(dy), mean, var_biased, gamma, beta, sums, eps, act, n4g,
-                     C / 4, (float)(1.0 / count), reinterpret_cast<float4*>(dx), reinterpret_cast<float4*>(dresidual), mask, amax_out);
+                     C4, (float)(1.0 / count), reinterpret_cast<float4*>(dx), reinterpret_cast<float4*>(dresidual), mask, amax_out);
   XAS_LAUNCH_CHECK();
   return 0;
 }
