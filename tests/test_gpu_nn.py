@@ -80,6 +80,67 @@ def test_conv_kernel_variants(tune, what):
         _lib.query('xas_set_tuning', 0)
 
 
+IGEMM_VARIANTS = [0, _lib.TUNE_PLAIN_KLOOP, _lib.TUNE_GLOBAL_LOAD, _lib.TUNE_GLOBAL_LOAD | _lib.TUNE_PLAIN_KLOOP]
+IGEMM_CASES = [
+    # ('conv', n, cin, h, w, cout, k, stride, pad) / ('deconv', n, cin, h, cout): 4 x 4, stride 2, pad 1
+    ('conv', 5, 32, 63, 63, 224, 3, 1, 1),   # fwd 128x128 tiles (> 256 blocks), ragged last M- and N-tile, padding taps, 9 K-steps
+                                             # (odd: peeled step); dgrad 128x32 tiles, 63 K-steps
+    ('conv', 5, 160, 63, 63, 64, 1, 1, 0),   # fwd 128x64, 5 K-steps; dgrad 128x128 with 2 K-steps (the short-loop rule)
+    ('conv', 2, 128, 17, 13, 96, 3, 2, 1),   # 64x64 tiles (accumulator pair), stride-2 fwd, four unequal dgrad phases, empty taps
+    ('conv', 2, 32, 12, 12, 32, 1, 1, 0),    # one K-step in both directions: the look-ahead loads all re-load step 0
+    ('deconv', 2, 256, 8, 256),              # two taps per phase and direction
+    ('deconv', 1, 64, 5, 32),
+]
+
+
+@pytest.mark.parametrize('case', IGEMM_CASES, ids=lambda c: '-'.join(map(str, c)))
+def test_igemm_loader_loop_variants(case):
+    """Exact-fp32 forward and data gradient with buffer loads (igemm_buf_kernel) and global loads (igemm_kernel), each
+    with the pipelined and the plain K-loop: each of the four is held to float64 of the same operands at the per-kernel
+    bar (3e-6 relative), and the four agree bit for bit: the K order and the accumulator each product
+    goes to are the same in all of them."""
+    from xas_amd import layers as L
+    g = torch.Generator().manual_seed(sum(case[1:]))
+    if case[0] == 'conv':
+        _, n, cin, h, w, cout, k, stride, pad = case
+        x = torch.randn(n, cin, h, w, generator=g)
+        wt = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
+        b = torch.randn(cout, generator=g)
+        m = L.Conv2d(cin, cout, k, stride, pad, bias=True).cuda()
+        ref = lambda xd: TF.conv2d(xd, wt.double(), b.double(), stride, pad)
+    else:
+        _, n, cin, h, cout = case
+        x = torch.randn(n, cin, h, h, generator=g)
+        wt = torch.randn(cin, cout, 4, 4, generator=g) / (cin * 4) ** 0.5
+        b = None
+        m = L.ConvTranspose2d(cin, cout, 4, 2, 1).cuda()
+        ref = lambda xd: TF.conv_transpose2d(xd, wt.double(), None, 2, 1)
+    with torch.no_grad():
+        m.weight.copy_(wt)
+        if b is not None:
+            m.bias.copy_(b)
+    xd = x.double().requires_grad_(True)
+    yd = ref(xd)
+    gy = torch.randn(yd.shape, generator=g)
+    (yd * gy.double()).sum().backward()
+    _lib.query('xas_set_precision', _lib.PREC_F32)
+    first = None
+    for tune in IGEMM_VARIANTS:
+        _lib.query('xas_set_tuning', tune)
+        xg = x.cuda().requires_grad_(True)
+        yg = m(xg)
+        (yg * gy.cuda()).sum().backward()
+        y, dx = yg.detach().cpu(), xg.grad.cpu()
+        ry, rdx = rel(y, yd), rel(dx, xd.grad)
+        print('tune %d: forward rel %.3g, data gradient rel %.3g' % (tune, ry, rdx))
+        assert y.shape == yd.shape and ry < 3e-6 and rdx < 3e-6, (tune, ry, rdx)
+        if first is None:
+            first = (y, dx)
+        else:
+            assert torch.equal(y, first[0]), 'forward differs between tuning 0 and %d' % tune
+            assert torch.equal(dx, first[1]), 'data gradient differs between tuning 0 and %d' % tune
+
+
 @pytest.mark.parametrize('h,w', [(64, 64), (50, 70), (256, 256)])
 def test_stem_conv_mfma(h, w):
     """7x7 s2 p3, 3 -> 64, no bias: the dedicated MFMA stem kernel (resnet.py:16)."""

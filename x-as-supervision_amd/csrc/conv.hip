@@ -30,46 +30,10 @@ int tune_flags() { return g_tune; }
 // Consecutive MFMAs go to DIFFERENT accumulators (k outer, tile inner): a chain of dependent
 // v_mfma_f32_32x32x2_f32 on one accumulator does not issue back to back, and a wave with a single 32x32
 // tile (64x64 block tile) keeps two partial accumulators (even / odd k) that are summed in the epilogue.
-template <int BM, int BN>
-__device__ __forceinline__ void mfma_tile(const float* __restrict__ As, const float* __restrict__ Bs,
-                                          f32x16 (&acc)[TileCfg<BM, BN>::MI][TileCfg<BM, BN>::NI],
-                                          f32x16& acc2, int wm, int wn, int lane) {
-  using C = TileCfg<BM, BN>;
-  constexpr bool SPLIT = (C::MI == 1 && C::NI == 1);
-  const int i = lane & 31, h = lane >> 5;
-  float4 a[C::MI], b[C::NI];
-#pragma unroll
-  for (int kk = 0; kk < BK / 8; ++kk) {
-#pragma unroll
-    for (int mi = 0; mi < C::MI; ++mi)
-      a[mi] = *reinterpret_cast<const float4*>(As + (wm * C::WM + mi * 32 + i) * LDK + kk * 8 + h * 4);
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-      b[ni] = *reinterpret_cast<const float4*>(Bs + (wn * C::WN + ni * 32 + i) * LDK + kk * 8 + h * 4);
-    if (SPLIT) {
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0].x, a[0].x, acc[0][0], 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0].y, a[0].y, acc2, 0, 0, 0);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0].z, a[0].z, acc[0][0], 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0].w, a[0].w, acc2, 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[ni].x, a[mi].x, acc[mi][ni], 0, 0, 0);
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[ni].y, a[mi].y, acc[mi][ni], 0, 0, 0);
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[ni].z, a[mi].z, acc[mi][ni], 0, 0, 0);
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[ni].w, a[mi].w, acc[mi][ni], 0, 0, 0);
-    }
-  }
+// Global-load kernels fetch rows that are out of range from a clamped (valid) address and zero them here, on the way to LDS.
+__device__ __forceinline__ float4 keep_if(bool ok, float4 v) {
+  v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
+  return v;
 }
 
 // ------------------------------------------------------------------------------------
@@ -119,6 +83,19 @@ __device__ __forceinline__ void mfma_slice(const float4 (&a)[TileCfg<BM, BN>::MI
   }
 }
 
+// All four K-slices of one K-step, in order (the plain K-loop and the peeled last step of the pipelined one).
+template <int BM, int BN>
+__device__ __forceinline__ void mfma_tile(const float* __restrict__ As, const float* __restrict__ Bs,
+                                          f32x16 (&acc)[TileCfg<BM, BN>::MI][TileCfg<BM, BN>::NI],
+                                          f32x16& acc2, int wm, int wn, int lane) {
+  float4 a[TileCfg<BM, BN>::MI], b[TileCfg<BM, BN>::NI];
+#pragma unroll
+  for (int kk = 0; kk < BK / 8; ++kk) {
+    frag_load<BM, BN>(As, Bs, kk, wm, wn, lane, a, b);
+    mfma_slice<BM, BN>(a, b, acc, acc2);
+  }
+}
+
 // Scheduling hint for one K-slice of the pipelined loop: NMF MFMAs with NOTH memory operations of kind MASK
 // (0x100 LDS read, 0x200 LDS write, 0x020 global read) spread evenly between them.
 template <int NMF, int NOTH, int MASK>
@@ -133,13 +110,13 @@ __device__ __forceinline__ void sched_mix() {
   if (NMF - USED > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMF - USED, 0);
 }
 
-template <int BM, int BN, int MODE, int NBUF = 2, bool PIPE = false>
+template <int BM, int BN, int MODE, bool PIPE>
 __global__ __launch_bounds__(256) void igemm_kernel(IgemmParams p) {
   using C = TileCfg<BM, BN>;
   constexpr int APASS = BM / 32, BPASS = BN / 32;
   extern __shared__ __align__(16) float lds[];
-  float* As = lds;                       // [NBUF][BM][LDK]
-  float* Bs = lds + NBUF * BM * LDK;     // [NBUF][BN][LDK]
+  float* As = lds;                       // [2][BM][LDK]
+  float* Bs = lds + 2 * BM * LDK;        // [2][BN][LDK]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / C::WAVES_N, wn = wave % C::WAVES_N;
@@ -241,19 +218,11 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmParams p) {
     float* a = As + buf * BM * LDK;
     float* b = Bs + buf * BN * LDK;
 #pragma unroll
-    for (int j = 0; j < APASS; ++j) {
-      const bool ok = (okmask >> j) & 1u;
-      float4 v = ra4[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<float4*>(a + (lrow + 32 * j) * LDK + kq * 4) = v;
-    }
+    for (int j = 0; j < APASS; ++j)
+      *reinterpret_cast<float4*>(a + (lrow + 32 * j) * LDK + kq * 4) = keep_if((okmask >> j) & 1u, ra4[j]);
 #pragma unroll
-    for (int j = 0; j < BPASS; ++j) {
-      const bool ok = (okmask >> (16 + j)) & 1u;
-      float4 v = rb4[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<float4*>(b + (lrow + 32 * j) * LDK + kq * 4) = v;
-    }
+    for (int j = 0; j < BPASS; ++j)
+      *reinterpret_cast<float4*>(b + (lrow + 32 * j) * LDK + kq * 4) = keep_if((okmask >> (16 + j)) & 1u, rb4[j]);
   };
 
 #define XAS_KSTEP(KS, BUF, RA, RB, MASK)                                                     \
@@ -629,19 +598,11 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
     float* a = As + buf * WBK * LDA;
     float* b = Bs + buf * WBK * LDB;
 #pragma unroll
-    for (int j = 0; j < APASS; ++j) {
-      const bool ok = (okmask >> j) & 1u;
-      float4 v = ra4[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<float4*>(a + (arow + AROWS * j) * LDA + aq * 4) = v;
-    }
+    for (int j = 0; j < APASS; ++j)
+      *reinterpret_cast<float4*>(a + (arow + AROWS * j) * LDA + aq * 4) = keep_if((okmask >> j) & 1u, ra4[j]);
 #pragma unroll
-    for (int j = 0; j < BPASS; ++j) {
-      const bool ok = (okmask >> (16 + j)) & 1u;
-      float4 v = rb4[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<float4*>(b + (brow + BROWS * j) * LDB + bq * 4) = v;
-    }
+    for (int j = 0; j < BPASS; ++j)
+      *reinterpret_cast<float4*>(b + (brow + BROWS * j) * LDB + bq * 4) = keep_if((okmask >> (16 + j)) & 1u, rb4[j]);
   };
 
   const int i = lane & 31, h = lane >> 5;
@@ -1511,40 +1472,21 @@ static int check_fwd_dims(const xas_conv_shape* s, const char* who) {
   return 0;
 }
 
-template <int BM, int BN, int MODE, int NBUF = 2, bool PIPE = false>
+// Launches either kernel of the exact-fp32 forward / data-gradient family (same LDS size, tile grid and block order).
+template <int BM, int BN, void (*Kernel)(IgemmParams)>
 static int launch_igemm(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
-  const size_t lds = (size_t)NBUF * (BM + BN) * LDK * sizeof(float);
-  static bool attr_set_dev[kMaxDevices] = {};          // per device: the LDS limit is a per-device function attribute
-  bool& attr_set = attr_set_dev[current_device()];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, MODE, NBUF, PIPE>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  IgemmParams q = p;
-  q.nMt = (int)cdiv(Mrows_max, BM); q.nNt = (int)cdiv(p.Cd, BN); q.mt_per_xcd = (int)cdiv(q.nMt, 8);
-  const unsigned nblk = (unsigned)(8 * q.mt_per_xcd * q.nNt);
-  dim3 grid(nblk, 1, (unsigned)phases);
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, MODE, NBUF, PIPE>), grid, dim3(256), lds, st, q);
-  XAS_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int BM, int BN, int MODE, bool PIPE, bool BNB = false>
-static int launch_igemm_buf(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
   const size_t lds = (size_t)2 * (BM + BN) * LDK * sizeof(float);
   static bool attr_set_dev[kMaxDevices] = {};          // per device: the LDS limit is a per-device function attribute
   bool& attr_set = attr_set_dev[current_device()];
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_buf_kernel<BM, BN, MODE, PIPE, BNB>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   IgemmParams q = p;
   q.nMt = (int)cdiv(Mrows_max, BM); q.nNt = (int)cdiv(p.Cd, BN); q.mt_per_xcd = (int)cdiv(q.nMt, 8);
   const unsigned nblk = (unsigned)(8 * q.mt_per_xcd * q.nNt);
   dim3 grid(nblk, 1, (unsigned)phases);
-  hipLaunchKernelGGL((igemm_buf_kernel<BM, BN, MODE, PIPE, BNB>), grid, dim3(256), lds, st, q);
+  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, st, q);
   XAS_LAUNCH_CHECK();
   return 0;
 }
@@ -1564,7 +1506,7 @@ static int launch_tile(const IgemmParams& p, int Mrows_max, int phases, hipStrea
   if constexpr (MODE == 1) {
     if (p.bnb_x) {                                    // batch-norm backward epilogue: buffer-load pipelined kernel only
       XAS_REQUIRE(fits, "conv_dgrad_bn_bwd: tensor beyond the 32-bit offset range of the buffer-load kernel");
-      return launch_igemm_buf<BM, BN, 1, true, true>(p, Mrows_max, phases, st);
+      return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, 1, true, true>>(p, Mrows_max, phases, st);
     }
   }
   // K loops of one or two steps (1x1 layers with 32 / 64 input channels): the pipelined loop's look-ahead loads have
@@ -1572,11 +1514,11 @@ static int launch_tile(const IgemmParams& p, int Mrows_max, int phases, hipStrea
   // 64 -> 256 channels at 256 x 64 x 64, r02)
   const bool short_k = p.stride == 1 && (long)p.R * p.S * p.Cs <= 2 * BK;
   if (fits && !(p.tune & XAS_TUNE_GLOBAL_LOAD)) {
-    if ((p.tune & XAS_TUNE_PLAIN_KLOOP) || short_k) return launch_igemm_buf<BM, BN, MODE, false>(p, Mrows_max, phases, st);
-    return launch_igemm_buf<BM, BN, MODE, true>(p, Mrows_max, phases, st);
+    if ((p.tune & XAS_TUNE_PLAIN_KLOOP) || short_k) return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, MODE, false>>(p, Mrows_max, phases, st);
+    return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, MODE, true>>(p, Mrows_max, phases, st);
   }
-  if (p.tune & XAS_TUNE_PLAIN_KLOOP) return launch_igemm<BM, BN, MODE, 2, false>(p, Mrows_max, phases, st);
-  return launch_igemm<BM, BN, MODE, 2, true>(p, Mrows_max, phases, st);
+  if (p.tune & XAS_TUNE_PLAIN_KLOOP) return launch_igemm<BM, BN, igemm_kernel<BM, BN, MODE, false>>(p, Mrows_max, phases, st);
+  return launch_igemm<BM, BN, igemm_kernel<BM, BN, MODE, true>>(p, Mrows_max, phases, st);
 }
 
 static int g_precision = XAS_PREC_F16X3;     // process default (xas_set_precision); a call overrides it with xas_conv_shape.mode
