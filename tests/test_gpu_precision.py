@@ -411,6 +411,37 @@ def test_conv_bf16_all_passes(n, cin, h, w, cout, k, stride, pad):
     assert rel(m.weight.grad, wref) < 2e-5 or rel(m.weight.grad, wexact) < 3e-6, (rel(m.weight.grad, wref), rel(m.weight.grad, wexact))
 
 
+# ---- the tap re-use and 64 x 256 kernels in the two non-default split modes ----------------------------------------------
+# The smallest shapes at which pick_tile / tap_tile_ok / wgrad_x6t_plan still select them (n, cin, h, w, cout, k; stride 1,
+# pad k // 2).  test_gpu_tap_kernels.py runs these kernels in the default mode only, and the other-mode sweeps above run
+# shapes at which the dispatch picks the small implicit-GEMM tiles.
+TAP_WIDE_CASES = [
+    (2, 32, 16, 16, 64, 3),        # igemm_x6t<64> forward, igemm_x6t<32> data gradient, wgrad_x6t<64> (4 patches, 2 splits)
+    (2, 32, 8, 8, 32, 3),          # 8-wide maps, one tile of two images: igemm_x6t<32> both ways, wgrad_x6t<32> (one patch)
+    (2, 64, 24, 48, 64, 3),        # three patch rows x three patch columns, two channel chunks: igemm_x6t<64>, wgrad_x6t<64>
+    (33, 32, 32, 32, 128, 3),      # 264 > 256 tiles of 128 rows: igemm_x6t<128> forward (<32> data gradient, wgrad_x6_kernel)
+    (5, 64, 64, 64, 256, 1),       # 320 > 256 tiles of 128 x 128, Cout % 256 == 0: igemm_x6_kernel<64, 256> forward
+    (5, 256, 64, 64, 64, 1),       # the same tile in the data gradient (Cin = 256)
+]
+
+
+@pytest.mark.parametrize('n,cin,h,w,cout,k', TAP_WIDE_CASES)
+def test_bf16x6_tap_and_wide_tile_kernels_vs_float64(n, cin, h, w, cout, k):
+    """The P = 3 instantiations of igemm_x6t_kernel, wgrad_x6t_kernel and igemm_x6_kernel<64, 256> (which kernel each shape
+    is for: TAP_WIDE_CASES): all three passes against a float64 convolution at the bar of every fp32-accurate conv test,
+    3e-6 relative."""
+    import test_gpu_tap_kernels as T
+    with precision_mode('bf16x6'):
+        T.test_large_problem_kernels_vs_float64(n, cin, h, w, cout, k)
+
+
+@pytest.mark.parametrize('n,cin,h,w,cout,k', TAP_WIDE_CASES)
+def test_bf16_tap_and_wide_tile_kernels(n, cin, h, w, cout, k):
+    """The P = 1 instantiations of the same kernels (TAP_WIDE_CASES): the checks of test_conv_bf16_all_passes, 2e-5 against
+    the convolution of the bf16-rounded operands and 6e-3 against the exact one."""
+    test_conv_bf16_all_passes(n, cin, h, w, cout, k, 1, k // 2)
+
+
 def test_conv_transpose_bf16():
     from xas_amd import layers as L
     g = torch.Generator().manual_seed(3)

@@ -23,7 +23,15 @@
 // rounding of the large terms of the same sum.  A launch without the maxima of its operands runs as bf16x6.  PIECES = 1 is the
 // plain bf16 variant (operands rounded once; NOT fp32 accurate; XAS_PREC_BF16), kept as the reported-separately variant.
 //
-// Kernel structure (both kernels): 256 threads = 4 waves, tile BM x BN, K-step of 32 (channels of a tap / pixels) loaded
+// Five MFMA kernels: igemm_x6_kernel (implicit GEMM, forward / data gradient), igemm_x6p_kernel (its persistent 64 x 256
+// variant for pure GEMMs), igemm_x6t_kernel (stride-1 3x3 with tap re-use), wgrad_x6_kernel and wgrad_x6t_kernel (weight
+// gradient, plain and with tap re-use).  What they have in common is written ONCE, in the section "shared pieces" below:
+// the weight-fragment stream (WeightFrags), the product loop (mfma_products), the fragment reads (read_plane_frags,
+// tr_frag), the XCD tile order (xcd_tile; pick_xcd_grid on the host), the f16x3 scales (F16Scales, F16WgradScales;
+// zero_acc / scale_acc), the patch-with-halo geometry (PatchGeom), the weight split (split_store_weight) and the
+// pieces -> P dispatch of the launchers (with_pieces).  A kernel body holds its K loop, its cursors and its staging.
+//
+// Kernel structure (igemm_x6_kernel, wgrad_x6_kernel): 256 threads = 4 waves, tile BM x BN, K-step of 32 (channels of a tap / pixels) loaded
 // two K-steps ahead into two register sets by buffer loads (hardware zero-fill for padding and ragged edges), processed as
 // two HALF-steps of 16: LDS holds two half-buffers of three bf16 planes for the operands that are split in the kernel
 // (24.6 KB for 128 activation rows; the epilogue staging, 36.9 KB, is the footprint: three blocks per CU), and during the
@@ -37,6 +45,8 @@
 //
 // Replaces the cuDNN kernels behind integral_base_modules/resnet.py:16-47, deconv_head.py:24-35,
 // physique_network.py:15-50 and torchvision's Bottleneck, like conv.hip.
+#include <type_traits>
+
 #include "conv_shared.h"
 
 namespace xas {
@@ -55,6 +65,157 @@ __device__ __forceinline__ int xswz(int row, int half) { return (half ^ ((row >>
 // (the kept partial products of a piece format, smallest first: Products<P> in conv_shared.h)
 
 // ------------------------------------------------------------------------------------
+// shared pieces of the five kernels.  All take their arrays by reference: fully unrolled, everything stays in registers.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void zero_acc(f32x16& a) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) a[e] = 0.f;
+}
+template <class T, int N>
+__device__ __forceinline__ void zero_acc(T (&a)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) zero_acc(a[n]);
+}
+// f16x3: the operands were split at power-of-two scales (2^10 w, s x); other formats: nothing to undo
+template <int P, int MI, int NI>
+__device__ __forceinline__ void scale_acc(f32x16 (&acc)[MI][NI], float desc) {
+  if constexpr (P == 2) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[mi][ni][e] *= desc;
+  }
+}
+
+// f16x3 scales (P == 2; never read otherwise) of a forward / data-gradient launch: sa = scale of the gathered operand,
+// desc = scale of the result
+template <int P>
+struct F16Scales {
+  float sa = kF16AScale, desc = kF16Descale;
+  __device__ __forceinline__ explicit F16Scales(const float* a_amax) {
+    if (P == 2 && a_amax) { float inv; sa = f16_grad_scale(a_amax, &inv); desc = inv * (1.f / kF16WScale); }
+  }
+};
+// ... of a weight-gradient launch: sd / sx = scales of dy and of x (each operand from its maximum; the launchers insist on
+// both), desc = scale of the result
+template <int P>
+struct F16WgradScales {
+  float sd = kF16AScale, sx = kF16AScale, desc = 1.f;
+  __device__ __forceinline__ explicit F16WgradScales(const WgradParams& p) {
+    if (P == 2) {
+      float id = 1.f / kF16AScale, ix = 1.f / kF16AScale;
+      if (p.a_amax) sd = f16_grad_scale(p.a_amax, &id);
+      if (p.b_amax) sx = f16_grad_scale(p.b_amax, &ix);
+      desc = id * ix;
+    }
+  }
+};
+
+// XCD-aware tile order of the igemm kernels: consecutive block ids go round the 8 XCDs; XCD (xi, xj) of the (8 / xn) x xn
+// grid owns a contiguous range of M-tiles and of N-tiles, the N-tiles of one M-tile adjacent in its queue (they share the
+// activation rows in that XCD's L2); pick_xcd_grid picks xn so that the weight slice of an XCD stays L2-resident.
+// -> (mt, nt) of this block; mt counts whatever unit mt_per_xcd counts (tiles; groups of tpb tiles in igemm_x6p_kernel)
+__device__ __forceinline__ void xcd_tile(const IgemmParams& p, int& mt, int& nt) {
+  const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
+  const int xi = xcd / p.xn, xj = xcd - xi * p.xn;
+  const int ml = qb / p.nt_per_x;
+  mt = xi * p.mt_per_xcd + ml;
+  nt = xj * p.nt_per_x + (qb - ml * p.nt_per_x);
+}
+
+// Weight-fragment stream of the igemm kernels.  The operand is [row blocks of 32][Ktot / 16][P][64 lanes][8] (see
+// split_weight_kernel): a wave loads the fragments of its NI column blocks (first one: nblk) for half-chunk hc straight into
+// MFMA operand registers, 1 KiB coalesced per instruction, all address arithmetic scalar.  Which hc comes next is the
+// kernel's business (its cursor).
+template <int P, int NI>
+struct WeightFrags {
+  __amdgpu_buffer_rsrc_t rsrc;
+  unsigned blk_bytes, voff, nblk0;                   // blk_bytes: one 32-row block over the whole K
+  __device__ __forceinline__ WeightFrags(const IgemmParams& p, int Ktot, int nblk, int lane) {
+    blk_bytes = (unsigned)(Ktot / 16) * P * 1024u;
+    const long wbytes = (long)((p.Cd + 31) / 32) * blk_bytes;
+    rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, (int)wbytes, 0x00020000);
+    voff = (unsigned)lane * 16u;
+    nblk0 = (unsigned)nblk;
+  }
+  __device__ __forceinline__ void load(uint4 (&gb)[P][NI], unsigned hc) const {
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int pc = 0; pc < P; ++pc)
+        gb[pc][ni] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
+            rsrc, (int)voff, (int)((nblk0 + ni) * blk_bytes + (hc * P + pc) * 1024u), 0));
+  }
+};
+
+// acc[mi][ni] += the kept partial products of fa[.][mi] and fb[.][ni], smallest first.  B_FIRST: fb is the MFMA's first
+// operand (the igemm kernels: weights first, so that an accumulator register holds consecutive output channels)
+template <int P, bool B_FIRST, int MI, int NI>
+__device__ __forceinline__ void mfma_products(f32x16 (&acc)[MI][NI], const uint4 (&fa)[P][MI], const uint4 (&fb)[P][NI]) {
+#pragma unroll
+  for (int t = 0; t < Products<P>::N; ++t)
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        const uint4 a = fa[Products<P>::A[t]][mi], b = fb[Products<P>::B[t]][ni];
+        acc[mi][ni] = B_FIRST ? mfma_piece<P>(b, a, acc[mi][ni]) : mfma_piece<P>(a, b, acc[mi][ni]);
+      }
+}
+
+// fragments of a wave's MI row blocks (first row: row0) out of a half-buffer of planes [P][BM][XLDH]; lane = (i = row of a
+// 32-row block, hh = k half).  Smallest pieces first: they feed the first products
+template <int BM, int P, int MI>
+__device__ __forceinline__ void read_plane_frags(uint4 (&fa)[P][MI], const unsigned short* sb, int row0, int i, int hh) {
+#pragma unroll
+  for (int pc = P - 1; pc >= 0; --pc)
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+      fa[pc][mi] = *reinterpret_cast<const uint4*>(sb + pc * (BM * XLDH) + (row0 + mi * 32 + i) * XLDH + xswz(i, hh));
+}
+
+// transposing fragment read of the weight-gradient kernels (tiles pixel-major in LDS, rows row_stride bytes apart): the
+// MFMA operand - 8 consecutive pixels of one channel per lane - is two ds_read_b64_tr_b16 (4 pixels x 16 channels per
+// 16-lane group each), pixel rows off and off + 4 rows
+typedef s16x4_t __attribute__((address_space(3))) * lds_s16x4_p;
+__device__ __forceinline__ uint4 tr_frag(const unsigned char* base, unsigned off, int row_stride) {
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(base + off));
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(base + off + 4 * row_stride));
+  return __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// Geometry of the tap re-use kernels: the 128 rows of a tile are an 8 x 16 pixel patch of one image (tw = 16) or 8 x 8
+// patches of two images (tw = 8: 8-pixel-wide maps), staged WITH A ONE-PIXEL HALO: 10 x (tw + 2) pixels per image.
+struct PatchGeom {
+  int H, W, tw, tws, tn_cnt, hw, npix_img, npix, tiles_x, per_img;
+  __device__ __forceinline__ PatchGeom(int t2d_tw, int H_, int W_) {
+    H = H_; W = W_;
+    tw = t2d_tw; tws = tw == 16 ? 4 : 3;
+    tn_cnt = 128 >> (3 + tws);                       // images per tile
+    hw = tw + 2; npix_img = 10 * hw; npix = tn_cnt * npix_img;
+    tiles_x = W / tw; per_img = tiles_x * (H >> 3);
+  }
+  // first image and top-left pixel of patch (= tile) `patch`
+  __device__ __forceinline__ void origin(int patch, int& img0, int& y0, int& x0) const {
+    img0 = (patch / per_img) * tn_cnt;
+    const int tt = patch % per_img;
+    y0 = (tt / tiles_x) * 8; x0 = (tt % tiles_x) * tw;
+  }
+  // halo pixel pix < npix -> image of the tile, position relative to the patch origin (-1 .. 8, -1 .. tw)
+  __device__ __forceinline__ void halo_pixel(int pix, int& tn, int& dy, int& dx) const {
+    tn = pix / npix_img;
+    const int pr = pix - tn * npix_img, hy = pr / hw;
+    dy = hy - 1; dx = pr - hy * hw - 1;
+  }
+  __device__ __forceinline__ bool inside(int img, int gy, int gx, int N) const {
+    return (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && img < N;
+  }
+  __device__ __forceinline__ long pixel(int img, int gy, int gx) const { return ((long)img * H + gy) * W + gx; }
+};
+
+// ------------------------------------------------------------------------------------
 // weights: fp32 packed [rows][K] -> pre-split bf16 in FRAGMENT order
 //     [rows / 32 blocks][K / 16 half-chunks][P planes][64 lanes][8 bf16],  lane = 32 * (k half) + (row in block)
 // i.e. every (row block, 16-deep k slice, plane) is the 1 KiB image of one MFMA operand register set: a wave fetches it
@@ -68,6 +229,21 @@ __device__ __forceinline__ void f16_weight_check(float4 a, float4 b) {
   const float m = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))),
                         fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
   if (!(m < 65504.f)) atomicOr(&g_f16_weight_overflow, 1u);        // (NaN weights raise it too)
+}
+// the weight split: eight weights of one row -> their P pieces, one 16-byte store per plane (planes 512 halfwords apart)
+template <int P>
+__device__ __forceinline__ void split_store_weight(float4 r0, float4 r1, unsigned short* o) {
+  if (P == 2) {                                              // fp16 pieces of 2^10 w (exact scaling)
+    r0.x *= kF16WScale; r0.y *= kF16WScale; r0.z *= kF16WScale; r0.w *= kF16WScale;
+    r1.x *= kF16WScale; r1.y *= kF16WScale; r1.z *= kF16WScale; r1.w *= kF16WScale;
+    f16_weight_check(r0, r1);
+  }
+#pragma unroll
+  for (int pc = 0; pc < P; ++pc) {
+    const uint2 q0 = pack_piece4<P>(r0), q1 = pack_piece4<P>(r1);
+    *reinterpret_cast<uint4*>(o + pc * 512) = make_uint4(q0.x, q0.y, q1.x, q1.y);
+    if (pc + 1 < P) { r0 = sub_piece4<P>(r0, q0); r1 = sub_piece4<P>(r1, q1); }
+  }
 }
 
 template <int P>
@@ -85,18 +261,7 @@ __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restri
     r0 = *reinterpret_cast<const float4*>(src + (size_t)row * K + k0);
     r1 = *reinterpret_cast<const float4*>(src + (size_t)row * K + k0 + 4);
   }
-  unsigned short* o = dst + (blk * P) * 512 + lane * 8;
-  if (P == 2) {                                              // fp16 pieces of 2^10 w (exact scaling)
-    r0.x *= kF16WScale; r0.y *= kF16WScale; r0.z *= kF16WScale; r0.w *= kF16WScale;
-    r1.x *= kF16WScale; r1.y *= kF16WScale; r1.z *= kF16WScale; r1.w *= kF16WScale;
-    f16_weight_check(r0, r1);
-  }
-#pragma unroll
-  for (int pc = 0; pc < P; ++pc) {
-    const uint2 q0 = pack_piece4<P>(r0), q1 = pack_piece4<P>(r1);
-    *reinterpret_cast<uint4*>(o + pc * 512) = make_uint4(q0.x, q0.y, q1.x, q1.y);
-    if (pc + 1 < P) { r0 = sub_piece4<P>(r0, q0); r1 = sub_piece4<P>(r1, q1); }
-  }
+  split_store_weight<P>(r0, r1, dst + (blk * P) * 512 + lane * 8);
 }
 
 // ------------------------------------------------------------------------------------
@@ -123,7 +288,6 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
   constexpr int PLANE = BM * XLDH;              // halfwords
   constexpr int HBUF = P * PLANE;               // halfwords per half-buffer
   constexpr int AP = BM / 64;                   // activation float4 per thread per half-step (4 threads x 16 B per row)
-  constexpr int NT = Products<P>::N;            // partial products
   extern __shared__ __align__(16) float lds[];
   unsigned short* S = reinterpret_cast<unsigned short*>(lds);     // [2][P][BM][XLDH]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -145,14 +309,8 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
     rstep = st; sa = 1;
   }
   const int Mrows = p.N * Hrow * Wrow;
-  // XCD-aware tile order: consecutive block ids go round the 8 XCDs; XCD (xi, xj) of the (8 / xn) x xn grid owns a
-  // contiguous range of M-tiles and of N-tiles, the N-tiles of one M-tile adjacent in its queue (they share the
-  // activation rows in that XCD's L2); launch_igemm_x6_t picks xn so that the weight slice of an XCD stays L2-resident
-  const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
-  const int xi = xcd / p.xn, xj = xcd - xi * p.xn;
-  const int ml = qb / p.nt_per_x;
-  const int mt = xi * p.mt_per_xcd + ml;
-  const int nt = xj * p.nt_per_x + (qb - ml * p.nt_per_x);
+  int mt, nt;
+  xcd_tile(p, mt, nt);
   if (mt >= p.nMt || nt >= p.nNt) return;
   const int m0 = mt * BM, n0 = nt * BN;
   if (m0 >= Mrows) return;
@@ -165,8 +323,7 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
   const int HW = Hrow * Wrow;
   const int cchunks = p.Cs / BK;
   const int nk = nr * ns * cchunks;
-  float f16_sa = kF16AScale, f16_desc = kF16Descale;   // P == 2: scale of the gathered operand, scale of the result
-  if (P == 2 && p.a_amax) { float inv; f16_sa = f16_grad_scale(p.a_amax, &inv); f16_desc = inv * (1.f / kF16WScale); }
+  const F16Scales<P> f16(p.a_amax);
 
   // activation operand: buffer base moved down so that per-lane and scalar parts are non-negative (see igemm_buf_kernel)
   const long dmin = MODE == 0 ? 0l : -((long)(nr - 1) * p.Ws + (ns - 1)) * p.Cs;
@@ -198,24 +355,12 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
       maskA[j] = msk;
     }
   }
-  // weight operand: [row blocks of 32][K/16][P][64 lanes][8]: the wave's NI column blocks, all address arithmetic scalar
-  const int Ktot = p.R * p.S * p.Cs;
-  const unsigned blk_bytes = (unsigned)(Ktot / 16) * P * 1024u;           // one 32-row block over the whole K
-  const long wbytes = (long)((p.Cd + 31) / 32) * blk_bytes;
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, (int)wbytes, 0x00020000);
-  const unsigned voffB = (unsigned)lane * 16u;
-  const unsigned nblk0 = (unsigned)(n0 / 32 + wn * (C::WN / 32));
+  const WeightFrags<P, C::NI> wfr(p, p.R * p.S * p.Cs, n0 / 32 + wn * (C::WN / 32), lane);
 
   f32x16 acc[C::MI][C::NI];
-#pragma unroll
-  for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+  zero_acc(acc);
   f32x16 acc2;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
+  zero_acc(acc2);
 
   // K-step streams, advanced with scalar ALU only; both stop at the last step (further calls re-load it: valid addresses,
   // values never consumed).  Stream A feeds the activation registers (two K-steps ahead), stream B the weight fragments.
@@ -248,20 +393,14 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
   // weight fragments of one half-step (h = 0: first 16 k of the K-step at the cursor; h = 1: second 16, then advance)
   auto load_b = [&](uint4 (&gb)[P][C::NI], int h) {
     const int wtap = (base_r + rstep * cb.jr) * p.S + (base_s + rstep * cb.js);
-    const unsigned hc = (unsigned)((wtap * p.Cs + cb.chunk * BK) / 16 + h);
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-      for (int pc = 0; pc < P; ++pc)
-        gb[pc][ni] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
-            rsrcB, (int)voffB, (int)((nblk0 + ni) * blk_bytes + (hc * P + pc) * 1024u), 0));
+    wfr.load(gb, (unsigned)((wtap * p.Cs + cb.chunk * BK) / 16 + h));
     if (h) advance(cb);
   };
   auto split_store = [&](int buf, int h, const float4 (&ra)[2 * AP]) {
     unsigned short* sb = S + buf * HBUF;
 #pragma unroll
     for (int j = 0; j < AP; ++j) {
-      const Pieces<P> pcs = split_pieces<P>(ra[h * AP + j], f16_sa);   // (P = 2: both fp16 pieces in eight instructions, conv_shared.h)
+      const Pieces<P> pcs = split_pieces<P>(ra[h * AP + j], f16.sa);   // (P = 2: both fp16 pieces in eight instructions, conv_shared.h)
 #pragma unroll
       for (int pc = 0; pc < P; ++pc)
         *reinterpret_cast<uint2*>(sb + pc * PLANE + (arow + 64 * j) * XLDH + xswz(arow, kq4 >> 1) + (kq4 & 1) * 4) = pcs.q[pc];
@@ -269,15 +408,12 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
   };
   const int i = lane & 31, hh = lane >> 5;
   auto compute = [&](int buf, const uint4 (&gb)[P][C::NI]) {
-    const unsigned short* sb = S + buf * HBUF;
     uint4 fa[P][C::MI];
+    read_plane_frags<BM>(fa, S + buf * HBUF, wm * C::WM, i, hh);
+    // mfma_products<P, true>(acc, fa, gb), written out: through the helper the compiler schedules the <64, 64, 0, 3>
+    // instantiation of THIS kernel at 89 instead of 74 VGPRs (5 instead of 6 waves per SIMD); the other four kernels call it
 #pragma unroll
-    for (int pc = P - 1; pc >= 0; --pc)              // smallest pieces first: they feed the first products
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-        fa[pc][mi] = *reinterpret_cast<const uint4*>(sb + pc * PLANE + (wm * C::WM + mi * 32 + i) * XLDH + xswz(i, hh));
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
+    for (int t = 0; t < Products<P>::N; ++t)
 #pragma unroll
       for (int mi = 0; mi < C::MI; ++mi)
 #pragma unroll
@@ -320,14 +456,7 @@ __global__ __launch_bounds__(256, (P == 2 ? (BM == 64 && BN == 256 ? XAS_X6_WAVE
       compute(1, gb_1);
     }
   }
-  if constexpr (P == 2) {                              // the operands were split as 2^10 w and 2^4 x
-#pragma unroll
-    for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[mi][ni][e] *= f16_desc;
-  }
+  scale_acc<P>(acc, f16.desc);
   igemm_epilogue<BM, BN, MODE, BNB, (BN >= 128 ? BN / 64 : 1)>(p, acc, acc2, m0, n0, wm, wn, lane, Mrows, HW, Wrow, ph, pw, lds);
 }
 
@@ -349,7 +478,7 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
   constexpr int BM = 64, BN = 256, P = 2;
   using C = TileCfg<BM, BN>;
   static_assert(C::WAVES_M == 1 && C::MI == 2 && C::NI == 2, "written for four waves side by side");
-  constexpr int PLANE = BM * XLDH, HBUF = P * PLANE, NT = Products<P>::N;
+  constexpr int PLANE = BM * XLDH, HBUF = P * PLANE;
   extern __shared__ __align__(16) float lds[];
   unsigned short* S = reinterpret_cast<unsigned short*>(lds);     // [2][P][BM][XLDH]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -357,29 +486,22 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
   const int kq4 = tid & 3, arow = tid >> 2;
   const int Hrow = MODE == 0 ? p.Hrow : p.Hd, Wrow = MODE == 0 ? p.Wrow : p.Wd;
   const int HW = Hrow * Wrow, Mrows = p.N * HW;
-  // block -> (group of tpb M-tiles, N-tile): the XCD-aware order of igemm_x6_kernel with the group as the unit
-  const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
-  const int xi = xcd / p.xn, xj = xcd - xi * p.xn;
-  const int ml = qb / p.nt_per_x;
-  const int mt0 = (xi * p.mt_per_xcd + ml) * p.tpb;
-  const int nt = xj * p.nt_per_x + (qb - ml * p.nt_per_x);
+  // block -> (group of tpb M-tiles, N-tile): the XCD-aware order with the group as the unit
+  int mg, nt;
+  xcd_tile(p, mg, nt);
+  const int mt0 = mg * p.tpb;
   if (mt0 >= p.nMt || nt >= p.nNt) return;
   const int ntl = min(p.tpb, p.nMt - mt0);
   const int n0 = nt * BN;
   const int nk = p.Cs / BK;                              // even (launcher)
-  float f16_sa = kF16AScale, f16_desc = kF16Descale;
-  if (p.a_amax) { float inv; f16_sa = f16_grad_scale(p.a_amax, &inv); f16_desc = inv * (1.f / kF16WScale); }
+  const F16Scales<P> f16(p.a_amax);
 
   const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.src), 0, (int)(p.src_elems * 4), 0x00020000);
   auto voff_of = [&](int t) -> unsigned {
     const int m = (mt0 + t) * BM + arow;
     return (t < ntl && m < Mrows) ? (unsigned)(((long)m * p.Cs + kq4 * 4) * 4) : kOOB;
   };
-  const unsigned blk_bytes = (unsigned)(p.Cs / 16) * P * 1024u;           // one 32-row block of the weights over the whole K
-  const long wbytes = (long)((p.Cd + 31) / 32) * blk_bytes;
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, (int)wbytes, 0x00020000);
-  const unsigned voffB = (unsigned)lane * 16u;
-  const unsigned nblk0 = (unsigned)(n0 / 32 + wn * (C::WN / 32));
+  const WeightFrags<P, C::NI> wfr(p, p.Cs, n0 / 32 + wn * (C::WN / 32), lane);
 
   // the two load streams: they run THROUGH the tiles of the block (activations: tile after tile; weights: the same N-tile again)
   int a_t = 0, a_c = 0, b_c = 0;
@@ -392,17 +514,11 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
     if (++a_c == nk) { a_c = 0; ++a_t; voffA = voff_of(a_t); }
   };
   auto load_b = [&](uint4 (&gb)[P][C::NI], int h) {
-    const unsigned hc = (unsigned)(b_c * (BK / 16) + h);
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-      for (int pc = 0; pc < P; ++pc)
-        gb[pc][ni] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
-            rsrcB, (int)voffB, (int)((nblk0 + ni) * blk_bytes + (hc * P + pc) * 1024u), 0));
+    wfr.load(gb, (unsigned)(b_c * (BK / 16) + h));
     if (h) { if (++b_c == nk) b_c = 0; }
   };
   auto split_store = [&](int buf, int h, const float4 (&ra)[2]) {
-    const Pieces<P> pcs = split_pieces<P>(ra[h], f16_sa);
+    const Pieces<P> pcs = split_pieces<P>(ra[h], f16.sa);
 #pragma unroll
     for (int pc = 0; pc < P; ++pc)
       *reinterpret_cast<uint2*>(S + buf * HBUF + pc * PLANE + arow * XLDH + xswz(arow, kq4 >> 1) + (kq4 & 1) * 4) = pcs.q[pc];
@@ -410,20 +526,9 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
   const int i = lane & 31, hh = lane >> 5;
   f32x16 acc[C::MI][C::NI];
   auto compute = [&](int buf, const uint4 (&gb)[P][C::NI]) {
-    const unsigned short* sb = S + buf * HBUF;
     uint4 fa[P][C::MI];
-#pragma unroll
-    for (int pc = P - 1; pc >= 0; --pc)
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-        fa[pc][mi] = *reinterpret_cast<const uint4*>(sb + pc * PLANE + (mi * 32 + i) * XLDH + xswz(i, hh));
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni)
-          acc[mi][ni] = mfma_piece<P>(gb[Products<P>::B[t]][ni], fa[Products<P>::A[t]][mi], acc[mi][ni]);
+    read_plane_frags<BM>(fa, S + buf * HBUF, 0, i, hh);
+    mfma_products<P, true>(acc, fa, gb);
   };
   uint4 gb_0[P][C::NI], gb_1[P][C::NI];
   load_a(ra_0);                                          // tile 0: K-steps 0 and 1
@@ -434,12 +539,7 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
     b_c = 0;
     load_b(gb_0, 0);
     load_b(gb_1, 1);
-#pragma unroll
-    for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+    zero_acc(acc);
     split_store(0, 0, ra_0);                             // (the staging of the previous epilogue is done: barrier below)
     for (int ks = 0; ks < nk; ks += 2) {
       __syncthreads();
@@ -460,15 +560,9 @@ __global__ __launch_bounds__(256, 3) void igemm_x6p_kernel(IgemmParams p) {
       compute(1, gb_1);
       if (ks + 2 < nk) { load_b(gb_1, 1); split_store(0, 0, ra_0); }   // else ra_0 is the next tile's first K-step: stored after the epilogue
     }
-#pragma unroll
-    for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[mi][ni][e] *= f16_desc;
+    scale_acc<P>(acc, f16.desc);
     f32x16 unused;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) unused[e] = 0.f;
+    zero_acc(unused);
     // (opaque copies: everything the epilogue derives from them would otherwise be hoisted out of the tile loop and stay in
     //  registers through the K loop - 256 registers and spills instead of ~200)
     int n0v = n0, lanev = lane, wnv = wn;
@@ -508,25 +602,18 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / C::WAVES_N, wn = wave % C::WAVES_N;
   const int H = p.Hd, W = p.Wd;                                   // stride 1, same-size: input and output maps coincide
-  const int tw = p.t2d_tw, tws = tw == 16 ? 4 : 3;
-  const int tn_cnt = 128 >> (3 + tws);                            // images per tile
-  const int hw = tw + 2, npix_img = 10 * hw, npix = tn_cnt * npix_img;
-  const int plane_b = npix * XT_PIXB;
+  const PatchGeom g(p.t2d_tw, H, W);
+  const int plane_b = g.npix * XT_PIXB;
 
-  const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;           // XCD grid: see igemm_x6_kernel
-  const int xi = xcd / p.xn, xj = xcd - xi * p.xn;
-  const int ml = qb / p.nt_per_x;
-  const int mt = xi * p.mt_per_xcd + ml;
-  const int nt = xj * p.nt_per_x + (qb - ml * p.nt_per_x);
+  int mt, nt;
+  xcd_tile(p, mt, nt);
   if (mt >= p.nMt || nt >= p.nNt) return;
   const int m0 = mt * BM, n0 = nt * BN;
   const int Mrows = p.N * H * W;
   __builtin_amdgcn_s_setprio(XAS_X6_PRIO);
-  float f16_sa = kF16AScale, f16_desc = kF16Descale;   // P == 2: scale of the gathered operand, scale of the result
-  if (P == 2 && p.a_amax) { float inv; f16_sa = f16_grad_scale(p.a_amax, &inv); f16_desc = inv * (1.f / kF16WScale); }
-  const int tiles_x = W / tw, per_img = tiles_x * (H >> 3);
-  const int img0 = (mt / per_img) * tn_cnt, tt = mt % per_img;
-  const int y0 = (tt / tiles_x) * 8, x0 = (tt % tiles_x) * tw;
+  const F16Scales<P> f16(p.a_amax);
+  int img0, y0, x0;
+  g.origin(mt, img0, y0, x0);
   const int cchunks = p.Cs / BK;
   const int ntap = p.R * p.S;
 
@@ -537,12 +624,11 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
   for (int j = 0; j < XT_NJ; ++j) {
     const int item = tid + 256 * j, pix = item >> 3, q = item & 7;
     voffA[j] = kOOB;
-    if (pix < npix) {
-      const int tn = pix / npix_img, pr = pix - tn * npix_img;
-      const int hy = pr / hw, hx = pr - hy * hw;
-      const int gy = y0 + hy - 1, gx = x0 + hx - 1, img = img0 + tn;
-      if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && img < p.N)
-        voffA[j] = (unsigned)(((((long)img * H + gy) * W + gx) * p.Cs + q * 4) * 4);
+    if (pix < g.npix) {
+      int tn, dy, dx;
+      g.halo_pixel(pix, tn, dy, dx);
+      const int gy = y0 + dy, gx = x0 + dx, img = img0 + tn;
+      if (g.inside(img, gy, gx, p.N)) voffA[j] = (unsigned)((g.pixel(img, gy, gx) * p.Cs + q * 4) * 4);
     }
   }
   float4 ra[XT_NJ];
@@ -555,8 +641,8 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
 #pragma unroll
     for (int j = 0; j < XT_NJ; ++j) {
       const int item = tid + 256 * j, pix = item >> 3, q = item & 7;
-      if (pix < npix) {
-        const Pieces<P> pcs = split_pieces<P>(ra[j], f16_sa);
+      if (pix < g.npix) {
+        const Pieces<P> pcs = split_pieces<P>(ra[j], f16.sa);
         unsigned char* d = S + pix * XT_PIXB + q * 8;
 #pragma unroll
         for (int pc = 0; pc < P; ++pc) *reinterpret_cast<uint2*>(d + pc * plane_b) = pcs.q[pc];
@@ -569,28 +655,17 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
 #pragma unroll
   for (int mi = 0; mi < C::MI; ++mi) {
     const int r = wm * C::WM + mi * 32 + i;
-    const int tn = r >> (3 + tws), ty = (r >> tws) & 7, tx = r & (tw - 1);
-    fbase[mi] = (tn * npix_img + (ty + 1) * hw + (tx + 1)) * XT_PIXB + hh * 16;
+    const int tn = r >> (3 + g.tws), ty = (r >> g.tws) & 7, tx = r & (g.tw - 1);
+    fbase[mi] = (tn * g.npix_img + (ty + 1) * g.hw + (tx + 1)) * XT_PIXB + hh * 16;
   }
-  // ---- weights (as igemm_x6_kernel)
-  const int Ktot = ntap * p.Cs;
-  const unsigned blk_bytes = (unsigned)(Ktot / 16) * P * 1024u;
-  const long wbytes = (long)((p.Cd + 31) / 32) * blk_bytes;
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, (int)wbytes, 0x00020000);
-  const unsigned voffB = (unsigned)lane * 16u;
-  const unsigned nblk0 = (unsigned)(n0 / 32 + wn * (C::WN / 32));
+  // ---- weights
+  const WeightFrags<P, C::NI> wfr(p, ntap * p.Cs, n0 / 32 + wn * (C::WN / 32), lane);
   // half-step stream of the weights: chunk outermost, taps, the two halves of a chunk innermost
   int b_chunk = 0, b_tap = 0;
   const int nhs = 2 * ntap * cchunks;
   int b_left = nhs;
   auto load_b = [&](uint4 (&gb)[P][C::NI], int h) {
-    const unsigned hc = (unsigned)((b_tap * p.Cs + b_chunk * BK) / 16 + h);
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-      for (int pc = 0; pc < P; ++pc)
-        gb[pc][ni] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
-            rsrcB, (int)voffB, (int)((nblk0 + ni) * blk_bytes + (hc * P + pc) * 1024u), 0));
+    wfr.load(gb, (unsigned)((b_tap * p.Cs + b_chunk * BK) / 16 + h));
     if (h) {                                           // next tap; past the end: stay (re-loads, never consumed)
       const bool more = b_left > 2;
       b_left -= more ? 2 : 0;
@@ -600,15 +675,9 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
     }
   };
   f32x16 acc[C::MI][C::NI];
-#pragma unroll
-  for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+  zero_acc(acc);
   f32x16 acc2;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
+  zero_acc(acc2);
   auto read_frag = [&](uint4 (&fa)[P][C::MI], int tapoff) {          // tapoff: byte offset of the tap + half inside a plane
 #pragma unroll
     for (int pc = P - 1; pc >= 0; --pc)
@@ -616,19 +685,10 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
       for (int mi = 0; mi < C::MI; ++mi)
         fa[pc][mi] = *reinterpret_cast<const uint4*>(S + pc * plane_b + fbase[mi] + tapoff);
   };
-  auto mfmas = [&](const uint4 (&fa)[P][C::MI], const uint4 (&gb)[P][C::NI]) {
-#pragma unroll
-    for (int t = 0; t < Products<P>::N; ++t)
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni)
-          acc[mi][ni] = mfma_piece<P>(gb[Products<P>::B[t]][ni], fa[Products<P>::A[t]][mi], acc[mi][ni]);
-  };
   auto tap_off = [&](int t) {                          // byte offset of tap t (= jr * S + js) inside a plane
     const int jr = t / p.S, js = t - jr * p.S;
     const int dy = MODE == 0 ? jr - p.pad : p.pad - jr, dx = MODE == 0 ? js - p.pad : p.pad - js;
-    return (dy * hw + dx) * XT_PIXB;
+    return (dy * g.hw + dx) * XT_PIXB;
   };
   uint4 gb_0[P][C::NI], gb_1[P][C::NI];
   uint4 fa_0[P][C::MI], fa_1[P][C::MI];                // fragments of the half-step in flight and of the next one
@@ -643,23 +703,16 @@ __global__ __launch_bounds__(256, XAS_X6T_WAVES) void igemm_x6t_kernel(IgemmPara
     read_frag(fa_0, off);
     for (int t = 0; t < ntap; ++t) {
       read_frag(fa_1, off + 32);                       // second half of this tap, read during the MFMAs of the first
-      mfmas(fa_0, gb_0);
+      mfma_products<P, true>(acc, fa_0, gb_0);
       load_b(gb_0, 0);
       off = tap_off(t + 1 < ntap ? t + 1 : t);
       read_frag(fa_0, off);                            // first half of the next tap (a re-read after the last one)
-      mfmas(fa_1, gb_1);
+      mfma_products<P, true>(acc, fa_1, gb_1);
       load_b(gb_1, 1);
     }
     __syncthreads();                                   // every wave has read the staging before it is overwritten
   }
-  if constexpr (P == 2) {                              // the operands were split as 2^10 w and 2^4 x
-#pragma unroll
-    for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[mi][ni][e] *= f16_desc;
-  }
+  scale_acc<P>(acc, f16.desc);
   igemm_epilogue<BM, BN, MODE, false, (BN == 128 ? 2 : 1)>(p, acc, acc2, m0, n0, wm, wn, lane, Mrows, H * W, W, 0, 0, lds);
 }
 
@@ -706,6 +759,25 @@ constexpr size_t igemm_x6_lds(int P, bool bnb) {
   return a;
 }
 
+// xn of the XCD grid (8 / xn) x xn (xcd_tile).  Model of the bytes that miss the 4 MB L2 of an XCD: the activation rows
+// (a_bytes) are fetched by the xn XCDs of a grid row; an XCD's slice of the split weights (b_bytes) is fetched once when it
+// stays resident (<= 2.5 MB), else once per round of resident M-tiles (64 blocks per XCD).  m_units: what the grid deals
+// out along M (tiles; groups of tiles for igemm_x6p_kernel).  Layer4 of the detector (8 x 8 maps, 14 MB of split 3x3
+// weights): 878 -> 260 MB of L2 misses per launch at 256 images (PMC, tools/gpu/pmc_shapes.sh)
+static int pick_xcd_grid(double a_bytes, double b_bytes, int nMt, int nNt, int m_units) {
+  double best = 0;
+  int pick = 1;
+  for (int xn = 1; xn <= 8; xn *= 2) {
+    if (nNt % xn != 0 || m_units < 8 / xn) continue;
+    const int xm = 8 / xn, ntx = nNt / xn, mtx = (int)cdiv(nMt, xm);
+    const double slice = b_bytes / xn;
+    const double rounds = slice <= 2.5e6 ? 1.0 : (double)cdiv(mtx, 64 / ntx > 0 ? 64 / ntx : 1);
+    const double cost = a_bytes * xn + slice * 8 * rounds;
+    if (xn == 1 || cost < best * 0.9) { best = cost; pick = xn; }
+  }
+  return pick;
+}
+
 template <int BM, int BN, int MODE, int P, bool BNB>
 static int launch_igemm_x6_t(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
   constexpr size_t lds = igemm_x6_lds<BM, BN>(P, BNB);
@@ -718,24 +790,8 @@ static int launch_igemm_x6_t(const IgemmParams& p, int Mrows_max, int phases, hi
   }
   IgemmParams q = p;
   q.nMt = (int)cdiv(Mrows_max, BM); q.nNt = (int)cdiv(p.Cd, BN);
-  // XCD grid (8 / xn) x xn.  Model of the bytes that miss the 4 MB L2 of an XCD: the activation rows are fetched by the
-  // xn XCDs of a grid row; an XCD's weight slice is fetched once when it stays resident (<= 2.5 MB), else once per
-  // round of resident M-tiles (64 blocks per XCD).  Layer4 of the detector (8 x 8 maps, 14 MB of split 3x3 weights):
-  // 878 -> 260 MB of L2 misses per launch at 256 images (PMC, tools/gpu/pmc_shapes.sh)
-  {
-    const double a_bytes = (double)Mrows_max * phases * p.Cs * 4.0 * (MODE == 0 ? p.stride * p.stride : 1);
-    const double b_bytes = (double)p.Cd * p.R * p.S * p.Cs * 2.0 * P;
-    double best = 0;
-    q.xn = 1;
-    for (int xn = 1; xn <= 8; xn *= 2) {
-      if (q.nNt % xn != 0 || q.nMt < 8 / xn) continue;
-      const int xm = 8 / xn, ntx = q.nNt / xn, mtx = (int)cdiv(q.nMt, xm);
-      const double slice = b_bytes / xn;
-      const double rounds = slice <= 2.5e6 ? 1.0 : (double)cdiv(mtx, 64 / ntx > 0 ? 64 / ntx : 1);
-      const double cost = a_bytes * xn + slice * 8 * rounds;
-      if (xn == 1 || cost < best * 0.9) { best = cost; q.xn = xn; }
-    }
-  }
+  q.xn = pick_xcd_grid((double)Mrows_max * phases * p.Cs * 4.0 * (MODE == 0 ? p.stride * p.stride : 1),
+                       (double)p.Cd * p.R * p.S * p.Cs * 2.0 * P, q.nMt, q.nNt, q.nMt);
   q.nt_per_x = q.nNt / q.xn;
   q.mt_per_xcd = (int)cdiv(q.nMt, 8 / q.xn);
   dim3 grid((unsigned)(8 * q.mt_per_xcd * q.nt_per_x), 1, (unsigned)phases);
@@ -783,26 +839,21 @@ static int launch_igemm_x6p(const IgemmParams& p, int Mrows_max, hipStream_t st)
   tpb = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
   q.tpb = tpb;
   const int nMg = (int)cdiv(q.nMt, tpb);
-  {                                                    // XCD grid: the model of launch_igemm_x6_t, M-groups as the unit
-    const double a_bytes = (double)Mrows_max * p.Cs * 4.0;
-    const double b_bytes = (double)p.Cd * p.Cs * 2.0 * 2;
-    double best = 0;
-    q.xn = 1;
-    for (int xn = 1; xn <= 8; xn *= 2) {
-      if (q.nNt % xn != 0 || nMg < 8 / xn) continue;
-      const int xm = 8 / xn, ntx = q.nNt / xn, mtx = (int)cdiv(q.nMt, xm);
-      const double slice = b_bytes / xn;
-      const double rounds = slice <= 2.5e6 ? 1.0 : (double)cdiv(mtx, 64 / ntx > 0 ? 64 / ntx : 1);
-      const double cost = a_bytes * xn + slice * 8 * rounds;
-      if (xn == 1 || cost < best * 0.9) { best = cost; q.xn = xn; }
-    }
-  }
+  q.xn = pick_xcd_grid((double)Mrows_max * p.Cs * 4.0, (double)p.Cd * p.Cs * 2.0 * 2, q.nMt, q.nNt, nMg);   // M-groups as the unit
   q.nt_per_x = q.nNt / q.xn;
   q.mt_per_xcd = (int)cdiv(nMg, 8 / q.xn);            // in groups
   dim3 grid((unsigned)(8 * q.mt_per_xcd * q.nt_per_x), 1, 1);
   hipLaunchKernelGGL((igemm_x6p_kernel<MODE>), grid, dim3(256), lds, st, q);
   XAS_LAUNCH_CHECK();
   return 0;
+}
+
+// pieces (3 = bf16x6, 2 = f16x3, 1 = bf16) -> the template parameter P: f(std::integral_constant<int, P>)
+template <class F>
+static int with_pieces(int pieces, F&& f) {
+  if (pieces == 2) return f(std::integral_constant<int, 2>());
+  if (pieces == 3) return f(std::integral_constant<int, 3>());
+  return f(std::integral_constant<int, 1>());
 }
 
 template <int MODE, int P>
@@ -841,18 +892,14 @@ static int launch_igemm_x6_p(const IgemmParams& p, int Mrows_max, int phases, hi
 // pieces: 3 = bf16x6, 1 = bf16, 2 = f16x3 (the gathered operand at a fixed scale when it is an activation, at a scale
 // derived from IgemmParams::a_amax when it is a gradient)
 int launch_igemm_x6(const IgemmParams& p, int mode, int Mrows_max, int phases, int pieces, hipStream_t st) {
-  if (mode == 0) {
-    if (pieces == 2) {
-      XAS_REQUIRE(p.a_amax, "conv: an f16x3 forward launch needs the maximum of its input tensor (xas_conv_shape.grad_amax)");
-      return launch_igemm_x6_p<0, 2>(p, Mrows_max, phases, st);
-    }
-    return pieces == 3 ? launch_igemm_x6_p<0, 3>(p, Mrows_max, phases, st) : launch_igemm_x6_p<0, 1>(p, Mrows_max, phases, st);
-  }
   if (pieces == 2) {
-    XAS_REQUIRE(p.a_amax && !p.bnb_x, "conv: an f16x3 data gradient needs the maximum of its gradient operand (xas_conv_shape.grad_amax)");
-    return launch_igemm_x6_p<1, 2>(p, Mrows_max, phases, st);
+    if (mode == 0) XAS_REQUIRE(p.a_amax, "conv: an f16x3 forward launch needs the maximum of its input tensor (xas_conv_shape.grad_amax)");
+    else XAS_REQUIRE(p.a_amax && !p.bnb_x, "conv: an f16x3 data gradient needs the maximum of its gradient operand (xas_conv_shape.grad_amax)");
   }
-  return pieces == 3 ? launch_igemm_x6_p<1, 3>(p, Mrows_max, phases, st) : launch_igemm_x6_p<1, 1>(p, Mrows_max, phases, st);
+  return with_pieces(pieces, [&](auto pc) {
+    constexpr int P = decltype(pc)::value;
+    return mode == 0 ? launch_igemm_x6_p<0, P>(p, Mrows_max, phases, st) : launch_igemm_x6_p<1, P>(p, Mrows_max, phases, st);
+  });
 }
 
 // ------------------------------------------------------------------------------------
@@ -900,13 +947,7 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
   const int co0 = (tile % p.nct) * BM, nn0 = (tile / p.nct) * BN;
   const int mbeg = split * p.m_per_split, mend = min(p.M, mbeg + p.m_per_split);
   const int HWo = p.Ho * p.Wo;
-  float f16_sd = kF16AScale, f16_sx = kF16AScale, f16_desc = 1.f;      // P == 2: scales of dy and of x, scale of the result
-  if (P == 2) {                                        // (each operand from its maximum; the launchers insist on both)
-    float id = 1.f / kF16AScale, ix = 1.f / kF16AScale;
-    if (p.a_amax) f16_sd = f16_grad_scale(p.a_amax, &id);
-    if (p.b_amax) f16_sx = f16_grad_scale(p.b_amax, &ix);
-    f16_desc = id * ix;
-  }
+  const F16WgradScales<P> f16(p);
 
   // ---- dy operand: per-lane offset fixed, rows of a half-step from a scalar offset, split end = buffer range
   const int aq = tid % AQ, apix = tid / AQ;
@@ -940,12 +981,7 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
   const unsigned dstB = (unsigned)(ASZ + bpix * SB + bq * 8);
 
   f32x16 acc[C::MI][C::NI];
-#pragma unroll
-  for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < C::NI; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+  zero_acc(acc);
 
   float4 ra_0[ASET], rb_0[2 * BPQ], ra_1[ASET], rb_1[2 * BPQ];
   auto load_k = [&](int mk, float4 (&ra)[ASET], float4 (&rb)[2 * BPQ]) {        // mk: first pixel of the K-step (uniform)
@@ -977,51 +1013,33 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
 #pragma unroll
     for (int j = 0; j < APH; ++j) {
       if (AHALF && ahalf != h) continue;               // (wave-uniform) this wave's dy rows belong to the other half
-      const Pieces<P> pcs = split_pieces<P>(ra[AHALF ? 0 : h * APH + j], f16_sd);
+      const Pieces<P> pcs = split_pieces<P>(ra[AHALF ? 0 : h * APH + j], f16.sd);
 #pragma unroll
       for (int pc = 0; pc < P; ++pc) *reinterpret_cast<uint2*>(sb + pc * XH * SA + AROWS * j * SA + dstA) = pcs.q[pc];
     }
 #pragma unroll
     for (int q4 = 0; q4 < BPQ; ++q4) {
-      const Pieces<P> pcs = split_pieces<P>(rb[h * BPQ + q4], f16_sx);
+      const Pieces<P> pcs = split_pieces<P>(rb[h * BPQ + q4], f16.sx);
 #pragma unroll
       for (int pc = 0; pc < P; ++pc) *reinterpret_cast<uint2*>(sb + pc * XH * SB + q4 * 128 + dstB) = pcs.q[pc];
     }
   };
-  // transposing fragment read: lane (l16 = lane & 15 -> row qd = l16 >> 2, column quad pp = l16 & 3; g1 = channel half;
-  // hh = k half) supplies the address of pixel row 8 hh + 4 t + qd, channels 16 g1 + 4 pp .. + 3 of its 32-channel block
+  // transposing fragment read (tr_frag): lane (l16 = lane & 15 -> row qd = l16 >> 2, column quad pp = l16 & 3; g1 = channel
+  // half; hh = k half) supplies the address of pixel row 8 hh + 4 t + qd, channels 16 g1 + 4 pp .. + 3 of its 32-channel block
   const int l16 = lane & 15, qd = l16 >> 2, pp = l16 & 3, g1 = (lane >> 4) & 1, hh = lane >> 5;
   const unsigned fragA = (unsigned)((8 * hh + qd) * SA + (wm * C::WM + 16 * g1 + 4 * pp) * 2);
   const unsigned fragB = (unsigned)(ASZ + (8 * hh + qd) * SB + (wn * C::WN + 16 * g1 + 4 * pp) * 2);
-  typedef s16x4_t __attribute__((address_space(3))) * lds_s16x4_p;
-  auto tr_read = [&](const unsigned char* base, unsigned off) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(base + off));
-  };
   auto compute = [&](int buf) {
     const unsigned char* sb = S + buf * HBUF;
     uint4 fa[P][C::MI], fb[P][C::NI];
 #pragma unroll
     for (int pc = P - 1; pc >= 0; --pc) {
 #pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi) {
-        const s16x4_t lo = tr_read(sb, fragA + pc * XH * SA + mi * 64);
-        const s16x4_t hi = tr_read(sb, fragA + pc * XH * SA + mi * 64 + 4 * SA);
-        fa[pc][mi] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int mi = 0; mi < C::MI; ++mi) fa[pc][mi] = tr_frag(sb, fragA + pc * XH * SA + mi * 64, SA);
 #pragma unroll
-      for (int ni = 0; ni < C::NI; ++ni) {
-        const s16x4_t lo = tr_read(sb, fragB + pc * XH * SB + ni * 64);
-        const s16x4_t hi = tr_read(sb, fragB + pc * XH * SB + ni * 64 + 4 * SB);
-        fb[pc][ni] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int ni = 0; ni < C::NI; ++ni) fb[pc][ni] = tr_frag(sb, fragB + pc * XH * SB + ni * 64, SB);
     }
-#pragma unroll
-    for (int t = 0; t < Products<P>::N; ++t)
-#pragma unroll
-      for (int mi = 0; mi < C::MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < C::NI; ++ni)
-          acc[mi][ni] = mfma_piece<P>(fa[Products<P>::A[t]][mi], fb[Products<P>::B[t]][ni], acc[mi][ni]);
+    mfma_products<P, false>(acc, fa, fb);
   };
   const int nsteps = (mend > mbeg) ? (mend - mbeg + WBK - 1) / WBK : 0;
   const int last = nsteps - 1;
@@ -1067,7 +1085,7 @@ __global__ __launch_bounds__(256, (P == 2 ? XAS_WX6_WAVES2 : 2)) void wgrad_x6_k
 #pragma unroll
       for (int ni = 0; ni < C::NI; ++ni) {
         const int nn = nn0 + wn * C::WN + ni * 32 + col_l;
-        if (nn < p.KK) slab[(size_t)co * p.KK + nn] = P == 2 ? acc[mi][ni][reg] * f16_desc : acc[mi][ni][reg];
+        if (nn < p.KK) slab[(size_t)co * p.KK + nn] = P == 2 ? acc[mi][ni][reg] * f16.desc : acc[mi][ni][reg];
       }
     }
 }
@@ -1097,27 +1115,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cb = wave % NCB, tg = wave / NCB;
   const int H = p.Ho, W = p.Wo;
-  const int tw = p.t2d_tw, tws = tw == 16 ? 4 : 3;
-  const int tn_cnt = 128 >> (3 + tws);
-  const int hw = tw + 2, npix_img = 10 * hw, npix = tn_cnt * npix_img;
-  const int xplane = npix * XPB;
+  const PatchGeom g(p.t2d_tw, H, W);
+  const int xplane = g.npix * XPB;
   unsigned char* SX = S + 2 * DYB;
   // block -> (split, Cout tile, 32-channel tile): the tiles of a split are adjacent (they share its x and dy in L2)
   const int nci = p.Cin / 32;
   const int tiles = p.nct * nci;
   const int split = blockIdx.x / tiles, tile = blockIdx.x - split * tiles;
   const int co0 = (tile / nci) * BM, c0 = (tile - (tile / nci) * nci) * 32;
-  const int tiles_x = W / tw, per_img = tiles_x * (H >> 3);
   const int np_total = p.M >> 7;
   const int pbeg = split * p.pps, pend = min(np_total, pbeg + p.pps);
   if (pbeg >= pend) return;
-  float f16_sd = kF16AScale, f16_sx = kF16AScale, f16_desc = 1.f;      // P == 2: scales of dy and of x, scale of the result
-  if (P == 2) {                                        // (each operand from its maximum; the launchers insist on both)
-    float id = 1.f / kF16AScale, ix = 1.f / kF16AScale;
-    if (p.a_amax) f16_sd = f16_grad_scale(p.a_amax, &id);
-    if (p.b_amax) f16_sx = f16_grad_scale(p.b_amax, &ix);
-    f16_desc = id * ix;
-  }
+  const F16WgradScales<P> f16(p);
 
   const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)((long)p.N * H * W * p.Cin * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dy), 0, (int)((long)p.M * p.Cout * 4), 0x00020000);
@@ -1127,20 +1136,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
   for (int j = 0; j < XT_NJ; ++j) {
     const int item = tid + 256 * j, pix = item >> 3;
     hpt[j] = -1; hpy[j] = 0; hpx[j] = 0;
-    if (pix < npix) {
-      const int tn = pix / npix_img, pr = pix - tn * npix_img;
-      hpt[j] = tn; hpy[j] = pr / hw - 1; hpx[j] = pr - (pr / hw) * hw - 1;
-    }
+    if (pix < g.npix) g.halo_pixel(pix, hpt[j], hpy[j], hpx[j]);
   }
   float4 rx[XT_NJ];
   auto load_x = [&](int patch) {                       // the halo of patch `patch` -> registers
-    const int img0 = (patch / per_img) * tn_cnt, tt = patch % per_img;
-    const int y0 = (tt / tiles_x) * 8, x0 = (tt % tiles_x) * tw;
+    int img0, y0, x0;
+    g.origin(patch, img0, y0, x0);
 #pragma unroll
     for (int j = 0; j < XT_NJ; ++j) {
       const int gy = y0 + hpy[j], gx = x0 + hpx[j], img = img0 + hpt[j];
-      const bool ok = hpt[j] >= 0 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && img < p.N;
-      const unsigned off = ok ? (unsigned)(((((long)img * H + gy) * W + gx) * p.Cin + c0 + ((tid + 256 * j) & 7) * 4) * 4) : kOOB;
+      const bool ok = hpt[j] >= 0 && g.inside(img, gy, gx, p.N);
+      const unsigned off = ok ? (unsigned)((g.pixel(img, gy, gx) * p.Cin + c0 + ((tid + 256 * j) & 7) * 4) * 4) : kOOB;
       rx[j] = buf_load16(rsrcX, off, 0u);
     }
   };
@@ -1148,8 +1154,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
 #pragma unroll
     for (int j = 0; j < XT_NJ; ++j) {
       const int item = tid + 256 * j, pix = item >> 3, q = item & 7;
-      if (pix < npix) {
-        const Pieces<P> pcs = split_pieces<P>(rx[j], f16_sx);
+      if (pix < g.npix) {
+        const Pieces<P> pcs = split_pieces<P>(rx[j], f16.sx);
         unsigned char* d = SX + pix * XPB + q * 8;
 #pragma unroll
         for (int pc = 0; pc < P; ++pc) *reinterpret_cast<uint2*>(d + pc * xplane) = pcs.q[pc];
@@ -1159,9 +1165,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
   // dy K-slice: 16 consecutive pixels (one patch row; two rows of an 8-wide map) x BM channels
   float4 rd[DJ];
   auto slice_row0 = [&](int patch, int ks) {           // global pixel index of the slice's first pixel
-    const int img0 = (patch / per_img) * tn_cnt, tt = patch % per_img;
-    const int y0 = (tt / tiles_x) * 8, x0 = (tt % tiles_x) * tw;
-    if (tw == 16) return (img0 * H + y0 + ks) * W + x0;
+    int img0, y0, x0;
+    g.origin(patch, img0, y0, x0);
+    if (g.tw == 16) return (img0 * H + y0 + ks) * W + x0;
     return ((img0 + (ks >> 2)) * H + y0 + 2 * (ks & 3)) * W + x0;
   };
   auto load_dy = [&](int patch, int ks) {
@@ -1179,53 +1185,36 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
     for (int j = 0; j < DJ; ++j) {
       const int item = tid + 256 * j, apix = item / DQ, aq = item - apix * DQ;
       if (item < XH * DQ) {
-        const Pieces<P> pcs = split_pieces<P>(rd[j], f16_sd);
+        const Pieces<P> pcs = split_pieces<P>(rd[j], f16.sd);
 #pragma unroll
         for (int pc = 0; pc < P; ++pc) *reinterpret_cast<uint2*>(sb + pc * XH * SA + apix * SA + aq * 8) = pcs.q[pc];
       }
     }
   };
-  // transposing fragment reads (see wgrad_x6_kernel): lane -> pixel row 8 hh + qd (+ 4), channels 16 g1 + 4 pp .. + 3
+  // transposing fragment reads (tr_frag; see wgrad_x6_kernel): lane -> pixel row 8 hh + qd (+ 4), channels 16 g1 + 4 pp .. + 3
   const int l16 = lane & 15, qd = l16 >> 2, pp = l16 & 3, g1 = (lane >> 4) & 1, hh = lane >> 5;
   const unsigned fragA = (unsigned)((8 * hh + qd) * SA + (cb * 32 + 16 * g1 + 4 * pp) * 2);
-  const int rs = tw == 16 ? 8 : hw;                    // pixels between the two k-halves of a slice inside the halo
+  const int rs = g.tw == 16 ? 8 : g.hw;                // pixels between the two k-halves of a slice inside the halo
   const unsigned fragX = (unsigned)((hh * rs + qd) * XPB + (16 * g1 + 4 * pp) * 2);
-  typedef s16x4_t __attribute__((address_space(3))) * lds_s16x4_p;
-  auto tr_read = [&](const unsigned char* base, unsigned off) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(base + off));
-  };
-  f32x16 acc[NTW];
-#pragma unroll
-  for (int t = 0; t < NTW; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+  f32x16 acc[NTW][1][1];                               // (one 32 x 32 block per tap: MI = NI = 1 of mfma_products)
+  zero_acc(acc);
   auto compute = [&](int buf, int ks) {
     const unsigned char* sb = S + buf * DYB;
-    uint4 fa[P];
+    uint4 fa[P][1];
 #pragma unroll
-    for (int pc = P - 1; pc >= 0; --pc) {
-      const s16x4_t lo = tr_read(sb, fragA + pc * XH * SA);
-      const s16x4_t hi = tr_read(sb, fragA + pc * XH * SA + 4 * SA);
-      fa[pc] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
+    for (int pc = P - 1; pc >= 0; --pc) fa[pc][0] = tr_frag(sb, fragA + pc * XH * SA, SA);
     // halo pixel of the slice's first pixel for tap (0, 0) offset: row ks (two rows 2 (ks & 3) of image ks >> 2 when 8-wide)
-    const int wbase = tw == 16 ? (ks + 1) * hw + 1 : (ks >> 2) * npix_img + (2 * (ks & 3) + 1) * hw + 1;
+    const int wbase = g.tw == 16 ? (ks + 1) * g.hw + 1 : (ks >> 2) * g.npix_img + (2 * (ks & 3) + 1) * g.hw + 1;
 #pragma unroll
     for (int ti = 0; ti < NTW; ++ti) {
       const int t = tg + ti * NTG;
       if (t < 9) {
         const int dy = t / 3 - 1, dx = t - (t / 3) * 3 - 1;
-        const unsigned xo = (unsigned)((wbase + dy * hw + dx) * XPB) + fragX;
-        uint4 fb[P];
+        const unsigned xo = (unsigned)((wbase + dy * g.hw + dx) * XPB) + fragX;
+        uint4 fb[P][1];
 #pragma unroll
-        for (int pc = P - 1; pc >= 0; --pc) {
-          const s16x4_t lo = tr_read(SX, xo + pc * xplane);
-          const s16x4_t hi = tr_read(SX, xo + pc * xplane + 4 * XPB);
-          fb[pc] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-#pragma unroll
-        for (int k = 0; k < Products<P>::N; ++k)
-          acc[ti] = mfma_piece<P>(fa[Products<P>::A[k]], fb[Products<P>::B[k]], acc[ti]);
+        for (int pc = P - 1; pc >= 0; --pc) fb[pc][0] = tr_frag(SX, xo + pc * xplane, XPB);
+        mfma_products<P, false>(acc[ti], fa, fb);
       }
     }
   };
@@ -1256,7 +1245,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int co = co0 + cb * 32 + (reg & 3) + 8 * (reg >> 2) + rsub;
-        if (co < p.Cout) slab[(size_t)co * p.KK + t * p.Cin + c0 + col_l] = P == 2 ? acc[ti][reg] * f16_desc : acc[ti][reg];
+        if (co < p.Cout) slab[(size_t)co * p.KK + t * p.Cin + c0 + col_l] = P == 2 ? acc[ti][0][0][reg] * f16.desc : acc[ti][0][0][reg];
       }
     }
   }
@@ -1268,7 +1257,8 @@ bool wgrad_x6t_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int st
   if (Cin % 32 != 0 || H % 8 != 0) return false;
   if (!(W % 16 == 0 || (W == 8 && N % 2 == 0))) return false;
   // measured (profiles/r03_wgrad_x6t_ab.txt): 64 and 32 output channels +15..63 %; 128 and more -5..6 % with 128- and with
-  // 64-channel blocks (nine accumulators per wave: 245 VGPRs) - those stay on wgrad_x6_kernel
+  // 64-channel blocks (nine accumulators per wave: 245 VGPRs) - those stay on wgrad_x6_kernel, and wgrad_x6t_kernel is
+  // instantiated for BM = 64 and 32 only
   if (Cout == 64) *bm = 64;
   else if (Cout == 32) *bm = 32;
   else return false;
@@ -1305,20 +1295,12 @@ static int launch_wgrad_x6t_t(const WgradParams& p, int splits, int pps, hipStre
 }
 
 int launch_wgrad_x6t(const WgradParams& p, int bm, int splits, int pps, int pieces, hipStream_t st) {
-  if (pieces == 2) {                                   // f16x3: dy at the scale of p.a_amax, x at the scale of p.b_amax
+  if (pieces == 2)                                     // f16x3: dy at the scale of p.a_amax, x at the scale of p.b_amax
     XAS_REQUIRE(p.a_amax && p.b_amax, "conv_wgrad: the f16x3 weight gradient needs the maxima of both tensor operands (xas_conv_shape.grad_amax, x_amax)");
-    if (bm == 128) return launch_wgrad_x6t_t<128, 2>(p, splits, pps, st);
-    if (bm == 64) return launch_wgrad_x6t_t<64, 2>(p, splits, pps, st);
-    return launch_wgrad_x6t_t<32, 2>(p, splits, pps, st);
-  }
-  if (pieces == 3) {
-    if (bm == 128) return launch_wgrad_x6t_t<128, 3>(p, splits, pps, st);
-    if (bm == 64) return launch_wgrad_x6t_t<64, 3>(p, splits, pps, st);
-    return launch_wgrad_x6t_t<32, 3>(p, splits, pps, st);
-  }
-  if (bm == 128) return launch_wgrad_x6t_t<128, 1>(p, splits, pps, st);
-  if (bm == 64) return launch_wgrad_x6t_t<64, 1>(p, splits, pps, st);
-  return launch_wgrad_x6t_t<32, 1>(p, splits, pps, st);
+  return with_pieces(pieces, [&](auto pc) {            // bm: 64 or 32 (wgrad_x6t_plan)
+    constexpr int P = decltype(pc)::value;
+    return bm == 64 ? launch_wgrad_x6t_t<64, P>(p, splits, pps, st) : launch_wgrad_x6t_t<32, P>(p, splits, pps, st);
+  });
 }
 
 template <int BM, int BN, int P>
@@ -1343,19 +1325,14 @@ void wgrad_x6_tile(int Cout, long KK, int* bm, int* bn) {
 }
 
 int launch_wgrad_x6(const WgradParams& p, int bm, int bn, int splits, int pieces, hipStream_t st) {
-  if (pieces == 2) {
+  if (pieces == 2)
     XAS_REQUIRE(p.a_amax && p.b_amax, "conv_wgrad: the f16x3 weight gradient needs the maxima of both tensor operands (xas_conv_shape.grad_amax, x_amax)");
-    if (bm == 32) return launch_wgrad_x6_t<32, 128, 2>(p, splits, st);
-    if (bm == 128) return bn == 128 ? launch_wgrad_x6_t<128, 128, 2>(p, splits, st) : launch_wgrad_x6_t<128, 64, 2>(p, splits, st);
-    return bn == 128 ? launch_wgrad_x6_t<64, 128, 2>(p, splits, st) : launch_wgrad_x6_t<64, 64, 2>(p, splits, st);
-  }
-  if (bm == 32) return pieces == 3 ? launch_wgrad_x6_t<32, 128, 3>(p, splits, st) : launch_wgrad_x6_t<32, 128, 1>(p, splits, st);
-  if (pieces == 3) {
-    if (bm == 128) return bn == 128 ? launch_wgrad_x6_t<128, 128, 3>(p, splits, st) : launch_wgrad_x6_t<128, 64, 3>(p, splits, st);
-    return bn == 128 ? launch_wgrad_x6_t<64, 128, 3>(p, splits, st) : launch_wgrad_x6_t<64, 64, 3>(p, splits, st);
-  }
-  if (bm == 128) return bn == 128 ? launch_wgrad_x6_t<128, 128, 1>(p, splits, st) : launch_wgrad_x6_t<128, 64, 1>(p, splits, st);
-  return bn == 128 ? launch_wgrad_x6_t<64, 128, 1>(p, splits, st) : launch_wgrad_x6_t<64, 64, 1>(p, splits, st);
+  return with_pieces(pieces, [&](auto pc) {
+    constexpr int P = decltype(pc)::value;
+    if (bm == 32) return launch_wgrad_x6_t<32, 128, P>(p, splits, st);
+    if (bm == 128) return bn == 128 ? launch_wgrad_x6_t<128, 128, P>(p, splits, st) : launch_wgrad_x6_t<128, 64, P>(p, splits, st);
+    return bn == 128 ? launch_wgrad_x6_t<64, 128, P>(p, splits, st) : launch_wgrad_x6_t<64, 64, P>(p, splits, st);
+  });
 }
 
 }  // namespace xas
@@ -1402,21 +1379,10 @@ __global__ __launch_bounds__(256) void prepare_weights_kernel(const long* __rest
   }
   float4 r0 = make_float4(v[0], v[1], v[2], v[3]), r1 = make_float4(v[4], v[5], v[6], v[7]);
   unsigned short* o = dst + (blk * P) * 512 + lane * 8;
-  if (P == 2) {                                        // two fp16 pieces of 2^10 w (split_weight_kernel<2>)
-    r0.x *= kF16WScale; r0.y *= kF16WScale; r0.z *= kF16WScale; r0.w *= kF16WScale;
-    r1.x *= kF16WScale; r1.y *= kF16WScale; r1.z *= kF16WScale; r1.w *= kF16WScale;
-    f16_weight_check(r0, r1);
-    const uint2 q0 = pack_f16x4(r0), q1 = pack_f16x4(r1);
-    *reinterpret_cast<uint4*>(o) = make_uint4(q0.x, q0.y, q1.x, q1.y);
-    r0 = sub_f16x4(r0, q0); r1 = sub_f16x4(r1, q1);
-    const uint2 t0 = pack_f16x4(r0), t1 = pack_f16x4(r1);
-    *reinterpret_cast<uint4*>(o + 512) = make_uint4(t0.x, t0.y, t1.x, t1.y);
-    return;
-  }
-  for (int pc = 0; pc < P; ++pc) {
-    const uint2 q0 = pack_bf16x4(r0), q1 = pack_bf16x4(r1);
-    *reinterpret_cast<uint4*>(o + pc * 512) = make_uint4(q0.x, q0.y, q1.x, q1.y);
-    if (pc + 1 < P) { r0 = sub_bf16x4(r0, q0); r1 = sub_bf16x4(r1, q1); }
+  switch (P) {                                         // (the split of split_weight_kernel<P>)
+    case 3: split_store_weight<3>(r0, r1, o); break;
+    case 2: split_store_weight<2>(r0, r1, o); break;
+    default: split_store_weight<1>(r0, r1, o); break;
   }
 }
 
