@@ -552,6 +552,31 @@ int xas_smpl_lbs_bwd(const float* pose, const float* betas, const float* v_templ
 int xas_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
                   float beta2, float eps, int step, void* stream);
 
+/* Guarded step: gradient norm, clipping and non-finite skip on the device, no host round trip.
+ *   xas_grad_guard         one read of the gradient arena -> its L2 norm (every sum in double, fixed order, no atomics: a
+ *                          pure function of the arena's contents) and the decision for the step, in the guard record;
+ *   xas_adam_step_guarded  xas_adam_step on g * scale, with scale, the bias corrections and the decision taken from the
+ *                          record.  A skipped step writes nothing: p, m, v keep their bits.
+ * Guard record: XAS_GUARD_FLOATS 4-byte words in device memory, zeroed by the caller before the first step, then owned by
+ * these two calls (`t` and `skipped` persist from call to call):
+ *   word 0  float norm          L2 norm of g, rounded once from double
+ *   word 1  float scale         min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); exactly 1.0f when
+ *                               clipping is off (max_norm <= 0 or infinite)
+ *   word 2  int   skip          1 when skip_nonfinite != 0 and an element of g, or the norm, is not finite
+ *   word 3  int   t             steps APPLIED so far, this one included; a skipped step leaves it alone, so the bias
+ *                               corrections continue as if that step() had never been called
+ *   word 4  int   skipped       steps skipped so far
+ *   word 5  float step_size     lr / (1 - beta1^t)         } computed in double from the device's own t
+ *   word 6  float inv_sqrt_bc2  1 / sqrt(1 - beta2^t)      }
+ *   word 7  int   nonfinite     1 when an element of g is not finite (whether or not skipping was asked for)
+ * workspace: xas_grad_guard_workspace_bytes(n) bytes, 8-byte aligned.  n % 4 == 0, g 16-byte aligned. */
+#define XAS_GUARD_FLOATS 8
+size_t xas_grad_guard_workspace_bytes(long n);
+int xas_grad_guard(const float* g, long n, float max_norm, int skip_nonfinite, float lr, float beta1, float beta2,
+                   void* guard, void* workspace, void* stream);
+int xas_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float eps,
+                          const void* guard, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Evaluation path: hypothesis selection, triangulation, pose metrics.
  * One evaluation batch stays on the device; nothing here synchronises with the host.

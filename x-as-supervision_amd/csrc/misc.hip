@@ -1,5 +1,7 @@
 // Small fused kernels: mask losses, GCN-discriminator building blocks, SMPL skinning,
-// multi-tensor Adam.  gfx950.
+// multi-tensor Adam and its gradient guard.  gfx950.
+#include <float.h>
+
 #include "common.h"
 
 namespace xas {
@@ -760,10 +762,112 @@ __global__ void adam_kernel(float4* __restrict__ p, const float4* __restrict__ g
     vv.f = b2 * vv.f + (1.f - b2) * gv.f * gv.f;                       \
     pv.f -= step_size * mv.f / (sqrtf(vv.f) * inv_sqrt_bc2 + eps);
     XAS_ADAM1(x) XAS_ADAM1(y) XAS_ADAM1(z) XAS_ADAM1(w)
-#undef XAS_ADAM1
     m[i] = mv; v[i] = vv; p[i] = pv;
   }
 }
+
+// ------------------------------------------------------------------ guarded Adam (xas_hip.h: xas_grad_guard)
+// The guard record of the header, as the kernels see it.
+struct GuardRecord {
+  float norm, scale;
+  int skip, t, skipped;
+  float step_size, inv_sqrt_bc2;
+  int nonfinite;
+};
+static_assert(sizeof(GuardRecord) == XAS_GUARD_FLOATS * sizeof(float), "guard record layout");
+
+constexpr int kGuardThreads = 256;
+
+// Sum (and OR) over the block in a fixed order: a binary tree over the thread index.  Valid in thread 0.
+__device__ __forceinline__ double guard_block_sum(double v, int& flag, double* s_sum) {
+  const int t = threadIdx.x;
+  flag = __syncthreads_or(flag);
+  s_sum[t] = v;
+  __syncthreads();
+  for (int s = kGuardThreads / 2; s > 0; s >>= 1) {
+    if (t < s) s_sum[t] += s_sum[t + s];
+    __syncthreads();
+  }
+  return s_sum[0];
+}
+
+// One pass over the gradient arena: block b -> partial[b] = sum of g^2 over its grid-stride share, accumulated in double
+// (a thread's elements in index order, then the tree above), and flags[b] = 1 if it met an element that is not finite.
+// No atomics: both are pure functions of the arena's contents and the grid.
+__global__ __launch_bounds__(kGuardThreads) void grad_sumsq_partial_kernel(const float4* __restrict__ g, long n4,
+                                                                           double* __restrict__ partial,
+                                                                           int* __restrict__ flags) {
+  __shared__ double s_sum[kGuardThreads];
+  double acc = 0.0;
+  int bad = 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float4 gv = g[i];
+#define XAS_SUMSQ1(f)                                  \
+    acc = fma((double)gv.f, (double)gv.f, acc);        \
+    bad |= !(fabsf(gv.f) <= FLT_MAX);
+    XAS_SUMSQ1(x) XAS_SUMSQ1(y) XAS_SUMSQ1(z) XAS_SUMSQ1(w)
+#undef XAS_SUMSQ1
+  }
+  const double r = guard_block_sum(acc, bad, s_sum);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = r;
+    flags[blockIdx.x] = bad;
+  }
+}
+
+// One block: the per-block sums in index order (thread t takes the t-th run of consecutive blocks, then the tree), the
+// decision, the step counter and the bias corrections of the step that follows -> the guard record.
+__global__ __launch_bounds__(kGuardThreads) void grad_guard_finalize_kernel(const double* __restrict__ partial,
+                                                                            const int* __restrict__ flags, int nblk,
+                                                                            float max_norm, int skip_nonfinite, float lr,
+                                                                            float beta1, float beta2, GuardRecord* rec) {
+  __shared__ double s_sum[kGuardThreads];
+  const int per = (nblk + kGuardThreads - 1) / kGuardThreads;
+  double acc = 0.0;
+  int bad = 0;
+  for (int k = 0, b = threadIdx.x * per; k < per && b < nblk; ++k, ++b) {
+    acc += partial[b];
+    bad |= flags[b];
+  }
+  const double sumsq = guard_block_sum(acc, bad, s_sum);
+  if (threadIdx.x != 0) return;
+  const double norm = sqrt(sumsq);
+  const float normf = (float)norm;
+  float scale = 1.0f;
+  if (max_norm > 0.f && max_norm <= FLT_MAX) {           // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
+    const double c = (double)max_norm / (norm + 1e-6);   // (a NaN norm stays a NaN scale, as it does there)
+    scale = c > 1.0 ? 1.0f : (float)c;
+  }
+  const int skip = (skip_nonfinite && (bad || !(normf <= FLT_MAX))) ? 1 : 0;
+  const int t = rec->t + (skip ? 0 : 1);
+  rec->norm = normf;
+  rec->scale = scale;
+  rec->skip = skip;
+  rec->t = t;
+  rec->skipped += skip;
+  rec->nonfinite = bad;
+  if (t >= 1) {
+    rec->step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)t)));
+    rec->inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)t)));
+  }
+}
+
+// adam_kernel on g * scale, with scale, the bias corrections and the decision read from the guard record (uniform loads).
+// A skipped step stores nothing.
+__global__ void adam_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                    float4* __restrict__ v, long n4, float b1, float b2, float eps,
+                                    const GuardRecord* __restrict__ rec) {
+  if (rec->skip != 0) return;
+  const float scale = rec->scale, step_size = rec->step_size, inv_sqrt_bc2 = rec->inv_sqrt_bc2;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    float4 gv = g[i];
+    float4 mv = m[i], vv = v[i], pv = p[i];
+    gv.x *= scale; gv.y *= scale; gv.z *= scale; gv.w *= scale;
+    XAS_ADAM1(x) XAS_ADAM1(y) XAS_ADAM1(z) XAS_ADAM1(w)
+    m[i] = mv; v[i] = vv; p[i] = pv;
+  }
+}
+#undef XAS_ADAM1
 
 static inline unsigned ew_grid(long n, int per_block = 256) {
   long b = cdiv(n, per_block);
@@ -903,6 +1007,39 @@ extern "C" int xas_adam_step(float* p, const float* g, float* m, float* v, long 
   hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream), reinterpret_cast<float4*>(p),
                      reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v),
                      n / 4, beta1, beta2, eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)));
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+// workspace of xas_grad_guard: one double and one flag word per block of the norm pass
+extern "C" size_t xas_grad_guard_workspace_bytes(long n) {
+  if (n <= 0 || n % 4 != 0) return 0;
+  return (size_t)ew_grid(n / 4, kGuardThreads) * (sizeof(double) + sizeof(int));
+}
+
+extern "C" int xas_grad_guard(const float* g, long n, float max_norm, int skip_nonfinite, float lr, float beta1,
+                              float beta2, void* guard, void* workspace, void* stream) {
+  XAS_REQUIRE(g && guard && workspace && n > 0 && n % 4 == 0, "grad_guard: bad arguments (n must be a multiple of 4)");
+  XAS_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)guard & 3) == 0 && ((uintptr_t)g & 15) == 0,
+              "grad_guard: the arena must be 16-byte, the workspace 8-byte and the guard record 4-byte aligned");
+  const unsigned nblk = ew_grid(n / 4, kGuardThreads);
+  double* partial = static_cast<double*>(workspace);
+  int* flags = reinterpret_cast<int*>(partial + nblk);
+  hipLaunchKernelGGL(grad_sumsq_partial_kernel, dim3(nblk), dim3(kGuardThreads), 0, as_stream(stream),
+                     reinterpret_cast<const float4*>(g), n / 4, partial, flags);
+  XAS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(kGuardThreads), 0, as_stream(stream), partial, flags,
+                     (int)nblk, max_norm, skip_nonfinite, lr, beta1, beta2, static_cast<GuardRecord*>(guard));
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2,
+                                     float eps, const void* guard, void* stream) {
+  XAS_REQUIRE(p && g && m && v && guard && n > 0 && n % 4 == 0, "adam guarded: bad arguments (n must be a multiple of 4)");
+  hipLaunchKernelGGL(adam_guarded_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m),
+                     reinterpret_cast<float4*>(v), n / 4, beta1, beta2, eps, static_cast<const GuardRecord*>(guard));
   XAS_LAUNCH_CHECK();
   return 0;
 }

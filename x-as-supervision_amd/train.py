@@ -116,6 +116,12 @@ class Trainer:
                     tb_vis(tb_logger, cur, self.tb_pair_ids, self.tb_parent_ids,
                            total.detach().item() if total is not None else None, loss_kp, loss_disc, output, x, self.config,
                            self.scheduler_detector)
+            if self.gpu_id == 0 and tb_logger is not None:           # guarded optimizer step (train_params.max_grad_norm /
+                skipped = self.step.skipped_steps()                   # skip_nonfinite_grads): once per epoch, one sync
+                for k, norm in self.step.last_grad_norm.items():
+                    if norm is not None:
+                        tb_logger.add_scalar('grad_guard/%s_grad_norm' % k, float(norm), epoch)
+                        tb_logger.add_scalar('grad_guard/%s_skipped_steps' % k, skipped[k], epoch)
             self.scheduler_detector.step()
             if self.scheduler_discriminator is not None:
                 self.scheduler_discriminator.step()

@@ -25,6 +25,10 @@ class ConvShape(ctypes.Structure):
 PREC_F32, PREC_BF16, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3
 PREC_NAMES = {'f32': PREC_F32, 'bf16': PREC_BF16, 'bf16x6': PREC_BF16X6, 'f16x3': PREC_F16X3}
 
+# xas_hip.h XAS_GUARD_FLOATS and the word indices of the guard record (xas_grad_guard)
+GUARD_FLOATS = 8
+GUARD_NORM, GUARD_SCALE, GUARD_SKIP, GUARD_T, GUARD_SKIPPED, GUARD_STEP_SIZE, GUARD_INV_SQRT_BC2, GUARD_NONFINITE = range(8)
+
 # xas_hip.h XAS_TUNE_*: flags of xas_set_tuning (kernel variants for coverage tests and A/B runs; 0 = shipped).  The header
 # documents each one; tests/test_abi.py keeps the two tables equal.
 TUNE_WGRAD_SPLIT_XCD = 1
@@ -123,6 +127,9 @@ SIGNATURES = {
     'xas_smpl_lbs_bwd_workspace_floats': ('ii', 'z'),
     'xas_smpl_lbs_bwd': ('ppppppppiiippppppp', 'i'),
     'xas_adam_step': ('pppplffffip', 'i'),
+    'xas_grad_guard_workspace_bytes': ('l', 'z'),
+    'xas_grad_guard': ('plfifffppp', 'i'),
+    'xas_adam_step_guarded': ('pppplfffpp', 'i'),
     'xas_eval_select': ('pppiiiifippppp', 'i'),
     'xas_projection_matrix': ('pppipp', 'i'),
     'xas_triangulate_dlt': ('ppiiipp', 'i'),

@@ -24,6 +24,12 @@ are on), so the collective overlaps the rest of backward; since the real and the
 camera-batched detector pass, the buckets complete progressively from the tail of the arena while backward walks towards
 the stem and only the LAST bucket is exposed.  `finish()` joins, launches whatever is left, waits, and divides by world size.
 
+Guarded optimizer step (optim.FusedAdam(max_grad_norm=, skip_nonfinite=)): engine.TrainStep runs it after `finish()`, exactly
+where step() is called, so every rank hands the SAME all-reduced arena to xas_grad_guard and takes the same decision (clip
+scale, skip) without another collective.  That holds only because the norm kernel is deterministic (fixed-order sums in double,
+no atomics): a norm that differed in the last bit between ranks would let the replicas drift, or one rank skip alone
+(tests/test_gpu_guarded_adam_dp.py).
+
 Works with any torch.distributed backend: `nccl` (= RCCL on ROCm) on GPUs, `gloo` in the CPU tests.
 Buffers are NOT broadcast every forward (the reference's broadcast_buffers=True re-sends 19 MB of constant SMPL
 arrays per call): SyncBatchNorm layers keep identical running statistics on every rank by construction (global

@@ -74,8 +74,10 @@ def prepare_model(config, smpl_arrays=None):
     if 'physique_mask_generator_params' in mp:
         phys = PhysiqueMaskGenerator(mp['physique_mask_generator_params']['layers'])
     net_params = list(regressor.parameters()) + (list(phys.parameters()) if phys is not None else [])
-    opt_det = FusedAdam(net_params, lr=tp['lr_kp_detector'], betas=(0.5, 0.999))
-    opt_disc = FusedAdam(disc.parameters(), lr=tp['lr_discriminator'], betas=(0.5, 0.999)) if disc is not None else None
+    # optional keys (the reference YAMLs have neither): the guarded optimizer step of optim.FusedAdam, for both optimizers
+    guard = dict(max_grad_norm=tp.get('max_grad_norm'), skip_nonfinite=bool(tp.get('skip_nonfinite_grads', False)))
+    opt_det = FusedAdam(net_params, lr=tp['lr_kp_detector'], betas=(0.5, 0.999), **guard)
+    opt_disc = FusedAdam(disc.parameters(), lr=tp['lr_discriminator'], betas=(0.5, 0.999), **guard) if disc is not None else None
     unsup_model = Counter3DModel(mp, regressor, smpl_layer, h36m, phys)
     unsup_disc = Counter3DDisc(mp, disc, smpl_layer, h36m)
     return unsup_model, unsup_disc, opt_det, opt_disc
@@ -119,6 +121,9 @@ class TrainStep:
         opt_det.grad_arena                       # materialise the gradient arenas: the kernels accumulate weight, bias and
         if opt_disc is not None:                 # norm-parameter gradients straight into them
             opt_disc.grad_arena
+        # guarded optimizers: 0-dim device tensors (views of the guard records) holding the gradient norm each optimizer's
+        # last step() saw, None without the guard.  Not part of `out`: the TensorBoard tag set is pinned.
+        self.last_grad_norm = {'det': opt_det.grad_norm, 'disc': opt_disc.grad_norm if opt_disc is not None else None}
         if dp_active():
             f = opt_det
             f.grad_arena
@@ -131,6 +136,12 @@ class TrainStep:
             dist.broadcast(opt_det.param_arena, src=0)
             if opt_disc is not None:
                 dist.broadcast(opt_disc.param_arena, src=0)
+
+    def skipped_steps(self):
+        """{'det': n, 'disc': n}: optimizer steps skipped so far because of a non-finite gradient (0 without the guard).
+        Synchronises with the device: for checkpoint / epoch time, not for the step."""
+        return {k: int(o.skipped_steps) if o is not None and o.skipped_steps is not None else 0
+                for k, o in (('det', self.opt_det), ('disc', self.opt_disc))}
 
     def _check_weight_range(self):
         """The f16x3 weight format holds |w| < 64 (2^10 w in fp16): the weight-preparation kernels and the stem kernel flag

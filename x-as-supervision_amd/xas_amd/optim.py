@@ -5,19 +5,32 @@ gradients into a second arena (`.grad` views, so autograd accumulates in place),
 `step()` is one kernel launch over the arena; `zero_grad()` is one memset.  The contiguous gradient arena
 is also what the data-parallel reducer all-reduces in large buckets (xas_amd/dp.py).
 state_dict()/load_state_dict() speak torch.optim.Adam's format so reference checkpoints resume.
+
+Guarded step (opt-in: `max_grad_norm` and / or `skip_nonfinite`): `step()` is then two enqueues, `xas_grad_guard` (one read
+of the gradient arena: its L2 norm, the clipping scale of torch.nn.utils.clip_grad_norm_, and whether a non-finite gradient
+makes this a step to skip) and `xas_adam_step_guarded` (the same update on g * scale; a skipped step stores nothing).  The
+decision and the count of APPLIED steps live in a small guard record on the device (include/xas_hip.h), so a skipped step
+costs no synchronisation and does not advance the bias correction - as if step() had not been called.
 """
+import math
+
 import torch
 
-from . import ops_nn
-from ._lib import call, ptr
+from . import _lib, ops_nn
+from ._lib import ptr
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         if len(self.param_groups) != 1:
             raise ValueError('FusedAdam updates one flat arena with one set of hyper-parameters: pass a single param group')
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError('FusedAdam: max_grad_norm must be positive (None = no clipping), got %r' % (max_grad_norm,))
+        self.max_grad_norm = None if max_grad_norm is None or math.isinf(float(max_grad_norm)) else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self._flat = None
         self._steps = 0
         self._epoch = [0]            # bumped whenever this optimizer rewrites its parameters (ops_nn._PackCache key)
@@ -46,6 +59,12 @@ class FusedAdam(torch.optim.Optimizer):
                     g.copy_(p.grad)
                 p.grad = g
         self._flat = dict(params=ps, offs=offs, n=n, p=arena, g=grads, m=torch.zeros_like(arena), v=torch.zeros_like(arena))
+        if self.guarded:
+            rec = torch.zeros(_lib.GUARD_FLOATS, device=dev, dtype=torch.float32)       # the guard record (xas_hip.h)
+            rec_i = rec.view(torch.int32)
+            rec_i[_lib.GUARD_T] = self._steps
+            ws = torch.empty((_lib.query('xas_grad_guard_workspace_bytes', n) + 7) // 8, device=dev, dtype=torch.float64)
+            self._flat.update(guard=rec, guard_i=rec_i, guard_ws=ws)
         for p in ps:
             p._xas_epoch = self._epoch
         self._epoch[0] += 1
@@ -61,6 +80,25 @@ class FusedAdam(torch.optim.Optimizer):
         if self._flat is None:
             self._build()
         return self._flat['p']
+
+    def _guard_word(self, i, as_int=False):
+        if not self.guarded:
+            return None
+        if self._flat is None:
+            self._build()
+        return self._flat['guard_i' if as_int else 'guard'][i]
+
+    @property
+    def grad_norm(self):
+        """0-dim device tensor, a view of the guard record: L2 norm of the gradient arena as the last step() saw it (before
+        clipping).  None without the guard."""
+        return self._guard_word(_lib.GUARD_NORM)
+
+    @property
+    def skipped_steps(self):
+        """0-dim device int32 tensor (view): step() calls skipped so far because of a non-finite gradient.  None without the
+        guard."""
+        return self._guard_word(_lib.GUARD_SKIPPED, as_int=True)
 
     def _check_views(self):
         f = self._flat
@@ -90,8 +128,14 @@ class FusedAdam(torch.optim.Optimizer):
         g0 = self.param_groups[0]
         self._steps += 1
         b1, b2 = g0['betas']
-        call('xas_adam_step', ptr(f['p']), ptr(f['g']), ptr(f['m']), ptr(f['v']), f['n'], float(g0['lr']), float(b1),
-             float(b2), float(g0['eps']), self._steps)
+        if not self.guarded:
+            _lib.call('xas_adam_step', ptr(f['p']), ptr(f['g']), ptr(f['m']), ptr(f['v']), f['n'], float(g0['lr']), float(b1),
+                      float(b2), float(g0['eps']), self._steps)
+        else:        # (self._steps counts the calls here; the steps APPLIED are counted on the device)
+            _lib.call('xas_grad_guard', ptr(f['g']), f['n'], float(self.max_grad_norm or 0.0), int(self.skip_nonfinite),
+                      float(g0['lr']), float(b1), float(b2), ptr(f['guard']), ptr(f['guard_ws']))
+            _lib.call('xas_adam_step_guarded', ptr(f['p']), ptr(f['g']), ptr(f['m']), ptr(f['v']), f['n'], float(b1),
+                      float(b2), float(g0['eps']), ptr(f['guard']))
         self._epoch[0] += 1          # packed weight copies of THIS optimizer's parameters are stale now
 
     def zero_grad(self, set_to_none=False):
@@ -108,9 +152,10 @@ class FusedAdam(torch.optim.Optimizer):
         if self._flat is None:
             self._build()
         f = self._flat
+        steps = int(f['guard_i'][_lib.GUARD_T]) if self.guarded else self._steps      # guarded: the steps applied
         state = {}
         for i, (p, o) in enumerate(zip(f['params'], f['offs'])):
-            state[i] = {'step': torch.tensor(float(self._steps)),
+            state[i] = {'step': torch.tensor(float(steps)),
                         'exp_avg': f['m'][o:o + p.numel()].view(p.shape).clone(),
                         'exp_avg_sq': f['v'][o:o + p.numel()].view(p.shape).clone()}
         groups = [{k: v for k, v in g.items() if k != 'params'} for g in self.param_groups]
@@ -141,3 +186,5 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError('FusedAdam keeps ONE step counter for the arena; the checkpoint has per-parameter steps %s' % sorted(steps))
         if steps:
             self._steps = steps.pop()
+            if self.guarded:
+                f['guard_i'][_lib.GUARD_T] = self._steps

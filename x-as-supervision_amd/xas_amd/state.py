@@ -10,6 +10,10 @@ def _flats(step):
     return [o._flat for o in (step.opt_det, step.opt_disc) if o is not None]
 
 
+def _keys(f):
+    return ('p', 'm', 'v', 'g') + (('guard',) if 'guard' in f else ())       # guarded FusedAdam: the applied-step count lives there
+
+
 def _buffers(step):
     return [b for m in (step.model, step.disc) for b in m.buffers()]
 
@@ -18,7 +22,7 @@ def snapshot(step):
     # (the gradient arenas too: the generator's backward leaves gradients in the DISCRIMINATOR's arena that the next
     # discriminator update consumes - train.py:160-190 never zeroes them in between, and neither does the mirror)
     torch.cuda.synchronize()
-    return ([f[k].clone() for f in _flats(step) for k in ('p', 'm', 'v', 'g')],
+    return ([f[k].clone() for f in _flats(step) for k in _keys(f)],
             [b.clone() for b in _buffers(step)],
             [o._steps for o in (step.opt_det, step.opt_disc) if o is not None], step.cur_step)
 
@@ -28,7 +32,7 @@ def restore(step, sn):
     it = iter(ts)
     with torch.no_grad():
         for f in _flats(step):
-            for k in ('p', 'm', 'v', 'g'):
+            for k in _keys(f):
                 f[k].copy_(next(it))
         for b, v in zip(_buffers(step), bs):
             b.copy_(v)
