@@ -397,6 +397,7 @@ int xas_bn_update_running(const float* mean, const float* var_biased, float* run
 /* backward, step 1: dz = dy * act'(y); sums[g][0][c] = sum_dz, sums[g][1][c] = sum_dz_xhat  ([groups][2][C]).
  * x may be NULL when the layer has an activation and no residual: xhat is then recovered from the saved output,
  * xhat = (act^-1(y) - beta) / gamma (needed only where dz != 0), one activation tensor less to read per pass.
+ * A channel with gamma == 0 has no recoverable xhat: its sum_dz_xhat is 0 (sum_dz is right, nothing is non-finite).
  * y may be NULL instead (x, gamma, beta given, no residual): the activation mask is then re-derived from x with the
  * forward's exact arithmetic and the backward never reads y.
  * dbeta_acc / dgamma_acc (both or neither, may be NULL): the parameter gradients (sums over all groups) are ALSO
