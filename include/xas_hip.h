@@ -46,7 +46,7 @@ enum {
   XAS_TUNE_SLAB_512 = 32768,                 /* ... 0 = 256 (shipped), 1 = 512, */
   XAS_TUNE_SLAB_128 = 65536,                 /* 2 = 128, */
   XAS_TUNE_SLAB_64 = 98304,                  /* 3 = 64 */
-  XAS_TUNE_COL_REDUCE_LEAN = 262144,         /* the <= 64-VGPR build of the backward column sums instead of the 86-VGPR one */
+  XAS_TUNE_COL_REDUCE_LEAN = 262144,         /* the 64-VGPR build of the backward column sums (8 waves per SIMD, 12 bytes of scratch per lane) instead of the 120-VGPR one (4 waves, none) */
   /* bf16-split kernels (XAS_PREC_F16X3 / XAS_PREC_BF16X6) */
   XAS_TUNE_GENERAL_KERNELS = 1 << 22,        /* three effects: no tap re-use kernels (stride-1 3x3 layers on the implicit-GEMM kernels:
                                               * forward, data and weight gradient), no streaming batch-norm apply / backward-apply

@@ -78,8 +78,30 @@ __device__ __forceinline__ void grad_add4(float* p, float4 v) {
 #define XAS_BN_PRIO 3
 #endif
 
+// What a launch sums per channel and what its finalize writes.  The values are the <N> of col_reduce_kernel<N> in the
+// profiles, the tests and the documents.  A mode with two sums accumulates sum(f1) and sum(f1 * w) of col_term's (f1, w);
+// dz = dy after the activation's slope, xhat = the normalised input.
+enum ColMode : int {
+  kColStats = 0,          // x: f1 = w = x - pivot (pivot = first row of the group) -> mean, biased var (, running statistics)
+  kColBwdXY = 1,          // x, dy, and y or the mask bytes under an activation: f1 = dz, w = xhat = (x - mean) * rstd -> sums
+  kColSum = 2,            // x: f1 = x, one sum -> column sums (the second sums are zeros)
+  kColBwdY = 3,           // dy, y, WITHOUT x (act != 0): f1 = dz, w = xhat = (z - beta) / gamma with z recovered from y -> sums
+  kColBwdX = 4,           // x, dy, WITHOUT y: f1 = dz with the sign re-derived from x (bn_affine), w = xhat from x -> sums
+  kColStatsPartials = 5,  // x = per-tile partial sums of a convolution epilogue, [rows][C/2 channels][sum(v-p), sum((v-p)^2)]
+                          // (C = 2 x channels, pivot per channel or null): f1 = x, one sum -> mean, var (, running statistics)
+  kColBwdPartials = 6,    // x = per-tile partial sums of a data-gradient epilogue, [rows][2][C/2 channels] (sum dz | sum dz xhat):
+                          // f1 = x, one sum -> out1 = sums [G][2][channels]; acc1 / acc2 (dbeta / dgamma) get the two halves
+};
+constexpr bool col_is_bwd(ColMode m) { return m == kColBwdXY || m == kColBwdY || m == kColBwdX; }
+constexpr bool col_two_sums(ColMode m) { return m == kColStats || col_is_bwd(m); }
+constexpr bool col_is_stats(ColMode m) { return m == kColStats || m == kColStatsPartials; }
+
 struct ColArgs {
-  const float* x; const float* y; const float* dy; const float* mean; const float* var; const float* aux;
+  const float* x; const float* y; const float* dy;       // [M][C]
+  const float* mean; const float* var;                   // [G][C]
+  const float* gamma; const float* beta;                 // [C]
+  const float* pivot;                                    // kColStatsPartials: [C/2] or null (no pivot)
+  const uint8_t* mask;                                   // kColBwdXY: != null -> activation sign bits (one byte per float4, bit e = z_e > 0) instead of y
   float eps; int act; long M; int C; ColGeom g;
   float* partial;              // [G][nslab][2][C]
   unsigned* ticket;            // [ncb]
@@ -89,8 +111,7 @@ struct ColArgs {
   float* count_out;            // != null: count_out[g * out_stride] = rows per group (SyncBatchNorm message)
   float* running_mean; float* running_var; float momentum, unbias;
   float* acc1; float* acc2;    // != null: acc1[c] += sum over groups of out1 ... (parameter gradients, in place)
-  const uint8_t* mask;         // MODE 1: != null -> activation sign bits (one byte per float4, bit e = z_e > 0) instead of y
-  long rows_real;              // MODE 5: activation rows per group behind the partial rows
+  long rows_real;              // kColStatsPartials: activation rows per group behind the partial rows
 };
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -110,104 +131,99 @@ __device__ __forceinline__ float4 load_wt(__amdgpu_buffer_rsrc_t r, unsigned byt
 // (measured with the weight gradients sharing the chip); on ONE stream the apply kernel that follows reads
 // the same x and dy again and finds part of them in the caches when the reduction did not mark them for early eviction:
 // -0.7 ms/step (in-box, interleaved, 3 rounds: 124.8 -> 124.1).
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-template <int MODE, int UNR = 4, int FL = 4>   // 0: stats of x around pivot ; 1: bn backward sums ; 2: plain column sums of x ;
-                      // 3: bn backward sums WITHOUT x: xhat = (z - beta)/gamma with z recovered from y (act != 0)
-                      // 4: bn backward sums WITHOUT y: the activation mask is re-derived from x (`y` carries gamma,
-                      //    `aux` carries beta)
-                      // 5: x = per-tile partial sums of a convolution epilogue, [rows][C/2 channels][sum(v-p), sum((v-p)^2)]
-                      //    (C = 2 x channels, `aux` = pivot per channel or null): plain column sums, finalize -> statistics
-                      // 6: x = per-tile partial sums of a data-gradient epilogue, [rows][2][C/2 channels] (sum dz | sum dz xhat):
-                      //    plain column sums -> out1 = sums [G][2][channels]; acc1 / acc2 (dbeta / dgamma) get the two halves
-__device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
-  __shared__ __align__(16) float4 red[2][256];         // 8 KB, also the double scratch of the finalize tail
-  const ColGeom& g = a.g;
-  const float* __restrict__ x = a.x; const float* __restrict__ y = a.y; const float* __restrict__ dy = a.dy;
-  const int C = a.C, act = a.act;
-  const float eps = a.eps;
-  const int tx = threadIdx.x % g.TX, ty = threadIdx.x / g.TX;
-  const int c = blockIdx.y * g.CB + tx * 4;
-  const int grp = blockIdx.z;
-  const float* mean = a.mean ? a.mean + (size_t)grp * C : nullptr;      // per-group statistics / parameters
-  const float* var = a.var ? a.var + (size_t)grp * C : nullptr;
-  const long r0 = grp * g.Mg + (long)blockIdx.x * g.rows_per_slab;
-  const long r1 = min((grp + 1) * g.Mg, r0 + g.rows_per_slab);
-  float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
-  float4 p0, p1;   // MODE 0: pivot ; MODE 1: mean, invstd
-  float4 rsg = make_float4(0, 0, 0, 0), bt = make_float4(0, 0, 0, 0);      // MODE 4: rstd * gamma, beta
-  if (MODE == 4) {
-    p0 = *reinterpret_cast<const float4*>(mean + c);
-    const float4 v = *reinterpret_cast<const float4*>(var + c);
-    p1 = make_float4(rsqrtf(v.x + eps), rsqrtf(v.y + eps), rsqrtf(v.z + eps), rsqrtf(v.w + eps));
-    const float4 gm = *reinterpret_cast<const float4*>(y + c);
-    rsg = make_float4(__fmul_rn(p1.x, gm.x), __fmul_rn(p1.y, gm.y), __fmul_rn(p1.z, gm.z), __fmul_rn(p1.w, gm.w));
-    bt = *reinterpret_cast<const float4*>(a.aux + c);
-  } else if (MODE == 0) {
-    p0 = *reinterpret_cast<const float4*>(x + (size_t)grp * g.Mg * C + c);          // pivot = first row of the group
-    p1 = p0;
-  } else if (MODE == 2 || MODE == 5 || MODE == 6) {
-    p0 = make_float4(0, 0, 0, 0); p1 = p0;
-  } else if (MODE == 3) {                                  // `aux` carries beta, `y`-side parameter pointer: see launcher
-    p0 = *reinterpret_cast<const float4*>(a.aux + c);                                 // beta
-    const float4 gm = *reinterpret_cast<const float4*>(a.x + c);                      // gamma (x unused in this mode)
-    p1 = make_float4(gm.x != 0.f ? 1.f / gm.x : 0.f, gm.y != 0.f ? 1.f / gm.y : 0.f, gm.z != 0.f ? 1.f / gm.z : 0.f,
-                     gm.w != 0.f ? 1.f / gm.w : 0.f);
+// ---- what the backward sums (col_term) and the backward apply (bn_bwd_elem) share, four lanes each --------------------
+// dz = dy times the activation's slope: 1 where the pre-activation value z was > 0, else neg (ReLU 0, leaky ReLU 0.01); the
+// sign of z comes from y (same sign), from x (re-derived with bn_affine: the forward's decision bit for bit) or from a mask
+// byte (bit e = lane e > 0)
+__device__ __forceinline__ float act_neg_slope(int act) { return act == 1 ? 0.f : 0.01f; }
+__device__ __forceinline__ float4 dz_sign_y(float4 dz, float4 yv, float neg) {
+  dz.x *= yv.x > 0.f ? 1.f : neg; dz.y *= yv.y > 0.f ? 1.f : neg; dz.z *= yv.z > 0.f ? 1.f : neg; dz.w *= yv.w > 0.f ? 1.f : neg;
+  return dz;
+}
+__device__ __forceinline__ float4 dz_sign_x(float4 dz, float4 xv, const float4& m, const float4& rs, const float4& bt, float neg) {
+  dz.x *= bn_affine(xv.x, m.x, rs.x, bt.x) > 0.f ? 1.f : neg; dz.y *= bn_affine(xv.y, m.y, rs.y, bt.y) > 0.f ? 1.f : neg;
+  dz.z *= bn_affine(xv.z, m.z, rs.z, bt.z) > 0.f ? 1.f : neg; dz.w *= bn_affine(xv.w, m.w, rs.w, bt.w) > 0.f ? 1.f : neg;
+  return dz;
+}
+__device__ __forceinline__ float4 dz_sign_mask(float4 dz, unsigned mb, float neg) {
+  dz.x *= (mb & 1u) ? 1.f : neg; dz.y *= (mb & 2u) ? 1.f : neg; dz.z *= (mb & 4u) ? 1.f : neg; dz.w *= (mb & 8u) ? 1.f : neg;
+  return dz;
+}
+// xhat = (v - m) * s: from x with (mean, rstd); the sums without x: from the recovered z with (beta, 1 / gamma)
+__device__ __forceinline__ float4 xhat4(float4 v, const float4& m, const float4& s) {
+  return make_float4((v.x - m.x) * s.x, (v.y - m.y) * s.y, (v.z - m.z) * s.z, (v.w - m.w) * s.w);
+}
+// the pre-activation value recovered from y: y where y > 0, else y / slope (leaky ReLU; ReLU clipped it: 0)
+__device__ __forceinline__ float4 act_inv4(float4 yv, int act) {
+  const float up = act == 1 ? 0.f : 100.f;
+  return make_float4(yv.x > 0.f ? yv.x : yv.x * up, yv.y > 0.f ? yv.y : yv.y * up, yv.z > 0.f ? yv.z : yv.z * up,
+                     yv.w > 0.f ? yv.w : yv.w * up);
+}
+
+// the per-channel quantities of a thread's channel quadruple; a mode fills what its term reads
+struct ColChan {
+  float4 pivot, mean, rstd, rsg, beta, inv_gamma;      // rsg = rstd * gamma (rounded once: bn_affine's contract)
+};
+
+template <ColMode MODE>
+__device__ __forceinline__ ColChan col_chan(const ColArgs& a, int grp, int c) {
+  ColChan ch{};
+  if constexpr (MODE == kColStats) ch.pivot = ld4(a.x + (size_t)grp * a.g.Mg * a.C + c);      // first row of the group
+  if constexpr (MODE == kColBwdXY || MODE == kColBwdX) {                                        // per-group statistics
+    ch.mean = ld4(a.mean + (size_t)grp * a.C + c);
+    const float4 v = ld4(a.var + (size_t)grp * a.C + c);
+    ch.rstd = make_float4(rsqrtf(v.x + a.eps), rsqrtf(v.y + a.eps), rsqrtf(v.z + a.eps), rsqrtf(v.w + a.eps));
+  }
+  if constexpr (MODE == kColBwdX) {
+    const float4 gm = ld4(a.gamma + c);
+    ch.rsg = make_float4(__fmul_rn(ch.rstd.x, gm.x), __fmul_rn(ch.rstd.y, gm.y), __fmul_rn(ch.rstd.z, gm.z), __fmul_rn(ch.rstd.w, gm.w));
+    ch.beta = ld4(a.beta + c);
+  }
+  if constexpr (MODE == kColBwdY) {
+    ch.beta = ld4(a.beta + c);
+    const float4 gm = ld4(a.gamma + c);
+    ch.inv_gamma = make_float4(gm.x != 0.f ? 1.f / gm.x : 0.f, gm.y != 0.f ? 1.f / gm.y : 0.f, gm.z != 0.f ? 1.f / gm.z : 0.f,
+                               gm.w != 0.f ? 1.f / gm.w : 0.f);
+  }
+  return ch;
+}
+
+// (f1, w) of the element at float offset i (four lanes) from the operands the mode reads: the first sum takes f1, the
+// second f1 * w
+struct ColTerm { float4 f1, w; };
+
+template <ColMode MODE>
+__device__ __forceinline__ ColTerm col_term(const ColArgs& a, const ColChan& ch, long i) {
+  const float neg = act_neg_slope(a.act);
+  if constexpr (MODE == kColBwdY) {
+    const float4 dz = ld4(a.dy + i), yv = ld4(a.y + i);
+    return {dz_sign_y(dz, yv, neg), xhat4(act_inv4(yv, a.act), ch.beta, ch.inv_gamma)};
   } else {
-    p0 = *reinterpret_cast<const float4*>(mean + c);
-    const float4 v = *reinterpret_cast<const float4*>(var + c);
-    p1 = make_float4(rsqrtf(v.x + eps), rsqrtf(v.y + eps), rsqrtf(v.z + eps), rsqrtf(v.w + eps));
-  }
-#pragma unroll UNR
-  for (long r = r0 + ty; r < r1; r += g.TY) {
-    if (MODE == 3) {
-      float4 g4 = *reinterpret_cast<const float4*>(dy + r * C + c);
-      const float4 yv = *reinterpret_cast<const float4*>(y + r * C + c);
-      const float neg = act == 1 ? 0.f : 0.01f, up = act == 1 ? 0.f : 100.f;
-      float4 z;                                            // pre-activation value
-      z.x = yv.x > 0.f ? yv.x : yv.x * up; z.y = yv.y > 0.f ? yv.y : yv.y * up;
-      z.z = yv.z > 0.f ? yv.z : yv.z * up; z.w = yv.w > 0.f ? yv.w : yv.w * up;
-      g4.x *= yv.x > 0.f ? 1.f : neg; g4.y *= yv.y > 0.f ? 1.f : neg;
-      g4.z *= yv.z > 0.f ? 1.f : neg; g4.w *= yv.w > 0.f ? 1.f : neg;
-      s1.x += g4.x; s1.y += g4.y; s1.z += g4.z; s1.w += g4.w;
-      s2.x = fmaf(g4.x, (z.x - p0.x) * p1.x, s2.x); s2.y = fmaf(g4.y, (z.y - p0.y) * p1.y, s2.y);
-      s2.z = fmaf(g4.z, (z.z - p0.z) * p1.z, s2.z); s2.w = fmaf(g4.w, (z.w - p0.w) * p1.w, s2.w);
-      continue;
-    }
-    const float4 xv = *reinterpret_cast<const float4*>(x + r * C + c);
-    if (MODE == 4) {
-      float4 g4 = *reinterpret_cast<const float4*>(dy + r * C + c);
-      const float neg = act == 1 ? 0.f : 0.01f;
-      g4.x *= bn_affine(xv.x, p0.x, rsg.x, bt.x) > 0.f ? 1.f : neg; g4.y *= bn_affine(xv.y, p0.y, rsg.y, bt.y) > 0.f ? 1.f : neg;
-      g4.z *= bn_affine(xv.z, p0.z, rsg.z, bt.z) > 0.f ? 1.f : neg; g4.w *= bn_affine(xv.w, p0.w, rsg.w, bt.w) > 0.f ? 1.f : neg;
-      s1.x += g4.x; s1.y += g4.y; s1.z += g4.z; s1.w += g4.w;
-      s2.x = fmaf(g4.x, (xv.x - p0.x) * p1.x, s2.x); s2.y = fmaf(g4.y, (xv.y - p0.y) * p1.y, s2.y);
-      s2.z = fmaf(g4.z, (xv.z - p0.z) * p1.z, s2.z); s2.w = fmaf(g4.w, (xv.w - p0.w) * p1.w, s2.w);
-      continue;
-    }
-    if (MODE == 2 || MODE == 5 || MODE == 6) {
-      s1.x += xv.x; s1.y += xv.y; s1.z += xv.z; s1.w += xv.w;
-    } else if (MODE == 0) {
-      const float a0 = xv.x - p0.x, b = xv.y - p0.y, cc = xv.z - p0.z, d = xv.w - p0.w;
-      s1.x += a0; s1.y += b; s1.z += cc; s1.w += d;
-      s2.x = fmaf(a0, a0, s2.x); s2.y = fmaf(b, b, s2.y); s2.z = fmaf(cc, cc, s2.z); s2.w = fmaf(d, d, s2.w);
+    const float4 xv = ld4(a.x + i);
+    if constexpr (MODE == kColStats) {
+      const float4 d = make_float4(xv.x - ch.pivot.x, xv.y - ch.pivot.y, xv.z - ch.pivot.z, xv.w - ch.pivot.w);
+      return {d, d};
+    } else if constexpr (MODE == kColBwdXY) {
+      float4 dz = ld4(a.dy + i);
+      if (a.act && a.mask) dz = dz_sign_mask(dz, a.mask[i >> 2], neg);
+      else if (a.act) dz = dz_sign_y(dz, ld4(a.y + i), neg);
+      return {dz, xhat4(xv, ch.mean, ch.rstd)};
+    } else if constexpr (MODE == kColBwdX) {
+      return {dz_sign_x(ld4(a.dy + i), xv, ch.mean, ch.rsg, ch.beta, neg), xhat4(xv, ch.mean, ch.rstd)};
     } else {
-      float4 g4 = *reinterpret_cast<const float4*>(dy + r * C + c);
-      if (act && a.mask) {
-        const unsigned mb = a.mask[(r * C + c) >> 2];
-        const float neg = act == 1 ? 0.f : 0.01f;
-        g4.x *= (mb & 1u) ? 1.f : neg; g4.y *= (mb & 2u) ? 1.f : neg;
-        g4.z *= (mb & 4u) ? 1.f : neg; g4.w *= (mb & 8u) ? 1.f : neg;
-      } else if (act) {
-        const float4 yv = *reinterpret_cast<const float4*>(y + r * C + c);
-        const float neg = act == 1 ? 0.f : 0.01f;
-        g4.x *= yv.x > 0.f ? 1.f : neg; g4.y *= yv.y > 0.f ? 1.f : neg;
-        g4.z *= yv.z > 0.f ? 1.f : neg; g4.w *= yv.w > 0.f ? 1.f : neg;
-      }
-      s1.x += g4.x; s1.y += g4.y; s1.z += g4.z; s1.w += g4.w;
-      s2.x = fmaf(g4.x, (xv.x - p0.x) * p1.x, s2.x); s2.y = fmaf(g4.y, (xv.y - p0.y) * p1.y, s2.y);
-      s2.z = fmaf(g4.z, (xv.z - p0.z) * p1.z, s2.z); s2.w = fmaf(g4.w, (xv.w - p0.w) * p1.w, s2.w);
+      return {xv, xv};                                        // plain column sums (w is not read)
     }
   }
+}
+
+// ---- the tail every mode shares --------------------------------------------------------------------------------------
+// Sum (s1, s2) over the row lanes of the block through `red`, publish the slab's partial sums (write-through), take a
+// ticket -> true in the block that arrives LAST at its channel block's counter; its L1 then holds no stale partials.
+__device__ __forceinline__ bool col_publish(const ColArgs& a, float4 (&red)[2][256], __amdgpu_buffer_rsrc_t prs, float4 s1,
+                                            float4 s2, int tx, int ty, int c, int grp) {
+  const ColGeom& g = a.g;
   red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
   __syncthreads();
   for (int s = g.TY >> 1; s > 0; s >>= 1) {
@@ -219,13 +235,10 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
     }
     __syncthreads();
   }
-  // ---- publish this block's partial sums (write-through), then take a ticket -------------------------------------
-  const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-      a.partial, 0, (int)((size_t)g.G * g.nslab * 2 * C * sizeof(float)), 0x00020000);
   if (ty == 0) {
-    const unsigned o = (unsigned)(((((size_t)grp * g.nslab + blockIdx.x) * 2) * C + c) * sizeof(float));
+    const unsigned o = (unsigned)(((((size_t)grp * g.nslab + blockIdx.x) * 2) * a.C + c) * sizeof(float));
     store_wt(prs, o, red[0][tx]);
-    store_wt(prs, o + (unsigned)C * 4u, red[1][tx]);
+    store_wt(prs, o + (unsigned)a.C * 4u, red[1][tx]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its stores ...
   __syncthreads();                                          // ... before one lane signals for the workgroup
@@ -242,154 +255,178 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
     s_last = last;
   }
   __syncthreads();
-  if (!s_last) return;
+  return s_last != 0;
+}
+
+// (d1, d2) = the two sums of group gi over its slabs, in double: a row lane adds every TY-th slab in slab order, then the
+// lanes are added in lane order through the 8 KB of `dred` (first sums, then second sums); complete where ty == 0
+template <int FL>
+__device__ __forceinline__ void col_slab_sums(const ColArgs& a, double* dred, __amdgpu_buffer_rsrc_t prs, int gi, int tx, int ty,
+                                              int c, double (&d1)[4], double (&d2)[4]) {
+  const ColGeom& g = a.g;
+  const int nl = g.TY;                                      // slab lanes (same thread layout as the reduction)
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d1[e] = d2[e] = 0.0;
+  const unsigned base = (unsigned)((((size_t)gi * g.nslab * 2) * a.C + c) * sizeof(float));
+  const unsigned slab_b = 2u * (unsigned)a.C * 4u, half_b = (unsigned)a.C * 4u;
+  auto add = [&](const float4& u, const float4& v) {
+    d1[0] += (double)u.x; d1[1] += (double)u.y; d1[2] += (double)u.z; d1[3] += (double)u.w;
+    d2[0] += (double)v.x; d2[1] += (double)v.y; d2[2] += (double)v.z; d2[3] += (double)v.w;
+  };
+  int s = ty;
+  for (; s + (FL - 1) * nl < g.nslab; s += FL * nl) {      // 2 * FL independent 16-byte loads in flight per lane
+    float4 u[FL], v[FL];
+#pragma unroll
+    for (int k = 0; k < FL; ++k) {
+      u[k] = load_wt(prs, base + (unsigned)(s + k * nl) * slab_b);
+      v[k] = load_wt(prs, base + (unsigned)(s + k * nl) * slab_b + half_b);
+    }
+#pragma unroll
+    for (int k = 0; k < FL; ++k) add(u[k], v[k]);
+  }
+  for (; s < g.nslab; s += nl) add(load_wt(prs, base + (unsigned)s * slab_b), load_wt(prs, base + (unsigned)s * slab_b + half_b));
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dred[(size_t)threadIdx.x * 4 + e] = half ? d2[e] : d1[e];
+    __syncthreads();
+    if (ty == 0) {
+      for (int k = 1; k < nl; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const double t = dred[(size_t)(k * g.TX + tx) * 4 + e];
+          if (half) d2[e] += t; else d1[e] += t;
+        }
+    }
+  }
+}
+
+// L = 4 or 2 consecutive floats as one 16- or 8-byte access (a thread's statistics: four channels, kColStatsPartials two)
+template <int L> __device__ __forceinline__ void ld_lanes(const float* p, float (&v)[4]) {
+  if constexpr (L == 4) { const float4 t = ld4(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+  else { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; }
+}
+template <int L> __device__ __forceinline__ void st_lanes(float* p, const float (&v)[4]) {
+  if constexpr (L == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+}
+
+// One channel's statistics from m = S1 / n and q = S2 / n of the values around `pivot` (double), then one step of the running
+// statistics.  The caller forms m and q: kColStats divides by n, kColStatsPartials multiplies by 1 / n, and their outputs
+// keep those bits.
+__device__ __forceinline__ void col_stat_lane(double m, double q, float pivot, float& mean, float& var) {
+  double v = q - m * m;
+  if (v < 0.0) v = 0.0;
+  mean = (float)((double)pivot + m); var = (float)v;
+}
+__device__ __forceinline__ void col_running_lane(float& rm, float& rv, float mean, float var, float mo, float ub) {
+  rm = (1.f - mo) * rm + mo * mean;
+  rv = (1.f - mo) * rv + mo * (var * ub);
+}
+
+// UNR: unroll of the row loop; FL: slabs a finalizing lane loads ahead
+template <ColMode MODE, int UNR, int FL>
+__device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
+  __shared__ __align__(16) float4 red[2][256];         // 8 KB, also the double scratch of the finalize tail
+  const ColGeom& g = a.g;
+  const int C = a.C;
+  const int tx = threadIdx.x % g.TX, ty = threadIdx.x / g.TX;
+  const int c = blockIdx.y * g.CB + tx * 4;
+  const int grp = blockIdx.z;
+  const long r0 = grp * g.Mg + (long)blockIdx.x * g.rows_per_slab;
+  const long r1 = min((grp + 1) * g.Mg, r0 + g.rows_per_slab);
+  const ColChan ch = col_chan<MODE>(a, grp, c);
+  const float4 z4 = make_float4(0, 0, 0, 0);
+  float4 s1 = z4, s2 = z4;
+#pragma unroll UNR
+  for (long r = r0 + ty; r < r1; r += g.TY) {
+    const ColTerm t = col_term<MODE>(a, ch, r * C + c);
+    s1.x += t.f1.x; s1.y += t.f1.y; s1.z += t.f1.z; s1.w += t.f1.w;
+    if constexpr (col_two_sums(MODE)) {
+      s2.x = fmaf(t.f1.x, t.w.x, s2.x); s2.y = fmaf(t.f1.y, t.w.y, s2.y);
+      s2.z = fmaf(t.f1.z, t.w.z, s2.z); s2.w = fmaf(t.f1.w, t.w.w, s2.w);
+    }
+  }
+  const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
+      a.partial, 0, (int)((size_t)g.G * g.nslab * 2 * C * sizeof(float)), 0x00020000);
+  if (!col_publish(a, red, prs, s1, s2, tx, ty, c, grp)) return;
 
   // ---- finalize (last arriver of this channel block): all groups, slabs summed in slab order in double ------------
-  double* dred = reinterpret_cast<double*>(&red[0][0]);     // [256][4] doubles = 8 KB
-  const int nl = g.TY;                                      // slab lanes (same thread layout as the reduction)
-  float4 accg1 = make_float4(0, 0, 0, 0), accg2 = make_float4(0, 0, 0, 0);      // sums over groups (parameter gradients)
-  float4 rm = make_float4(0, 0, 0, 0), rv = make_float4(0, 0, 0, 0);
-  if (MODE == 0 && a.running_mean && ty == 0) {
-    rm = *reinterpret_cast<const float4*>(a.running_mean + c);
-    rv = *reinterpret_cast<const float4*>(a.running_var + c);
-  }
-  const int ch = c >> 1;                                    // MODE 5: this thread's two channels are ch, ch + 1
-  if (MODE == 5 && a.running_mean && ty == 0) {
-    const float2 m2 = *reinterpret_cast<const float2*>(a.running_mean + ch);
-    const float2 v2 = *reinterpret_cast<const float2*>(a.running_var + ch);
-    rm.x = m2.x; rm.y = m2.y; rv.x = v2.x; rv.y = v2.y;
+  constexpr int L = MODE == kColStatsPartials ? 2 : 4;      // statistics of this thread: channels cs .. cs + L - 1
+  const int cs = MODE == kColStatsPartials ? c >> 1 : c;
+  const long n = MODE == kColStatsPartials ? a.rows_real : g.Mg;
+  float4 accg1 = z4, accg2 = z4;                            // sums over groups (parameter gradients)
+  float rm[4] = {0, 0, 0, 0}, rv[4] = {0, 0, 0, 0};
+  if (col_is_stats(MODE) && a.running_mean && ty == 0) {
+    ld_lanes<L>(a.running_mean + cs, rm);
+    ld_lanes<L>(a.running_var + cs, rv);
   }
   for (int gi = 0; gi < g.G; ++gi) {
-    double d1[4] = {0, 0, 0, 0}, d2[4] = {0, 0, 0, 0};
-    const unsigned base = (unsigned)((((size_t)gi * g.nslab * 2) * C + c) * sizeof(float));
-    const unsigned slab_b = 2u * (unsigned)C * 4u, half_b = (unsigned)C * 4u;
-    int s = ty;
-    for (; s + (FL - 1) * nl < g.nslab; s += FL * nl) {      // 2 * FL independent 16-byte loads in flight per lane
-      float4 u[FL], v[FL];
-#pragma unroll
-      for (int k = 0; k < FL; ++k) {
-        u[k] = load_wt(prs, base + (unsigned)(s + k * nl) * slab_b);
-        v[k] = load_wt(prs, base + (unsigned)(s + k * nl) * slab_b + half_b);
-      }
-#pragma unroll
-      for (int k = 0; k < FL; ++k) {
-        d1[0] += (double)u[k].x; d1[1] += (double)u[k].y; d1[2] += (double)u[k].z; d1[3] += (double)u[k].w;
-        d2[0] += (double)v[k].x; d2[1] += (double)v[k].y; d2[2] += (double)v[k].z; d2[3] += (double)v[k].w;
-      }
-    }
-    for (; s < g.nslab; s += nl) {
-      const float4 u = load_wt(prs, base + (unsigned)s * slab_b), v = load_wt(prs, base + (unsigned)s * slab_b + half_b);
-      d1[0] += (double)u.x; d1[1] += (double)u.y; d1[2] += (double)u.z; d1[3] += (double)u.w;
-      d2[0] += (double)v.x; d2[1] += (double)v.y; d2[2] += (double)v.z; d2[3] += (double)v.w;
-    }
-    // cross-lane sums over the slab lanes, fixed order, first sums then second sums through the same 8 KB
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dred[(size_t)threadIdx.x * 4 + e] = half ? d2[e] : d1[e];
-      __syncthreads();
-      if (ty == 0) {
-        for (int k = 1; k < nl; ++k)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const double t = dred[(size_t)(k * g.TX + tx) * 4 + e];
-            if (half) d2[e] += t; else d1[e] += t;
-          }
-      }
-    }
+    double d1[4], d2[4];
+    col_slab_sums<FL>(a, reinterpret_cast<double*>(&red[0][0]), prs, gi, tx, ty, c, d1, d2);
     if (ty != 0) continue;
-    if (MODE == 5) {
-      const float2 pv = a.aux ? *reinterpret_cast<const float2*>(a.aux + ch) : make_float2(0.f, 0.f);
-      const double inv = 1.0 / (double)a.rows_real;
-      const double m0 = d1[0] * inv, m1 = d1[2] * inv;
-      double v0 = d1[1] * inv - m0 * m0, v1 = d1[3] * inv - m1 * m1;
-      if (v0 < 0.0) v0 = 0.0;
-      if (v1 < 0.0) v1 = 0.0;
-      const float mf0 = (float)((double)pv.x + m0), mf1 = (float)((double)pv.y + m1), vf0 = (float)v0, vf1 = (float)v1;
-      *reinterpret_cast<float2*>(a.out1 + (size_t)gi * a.out_stride + ch) = make_float2(mf0, mf1);
-      *reinterpret_cast<float2*>(a.out2 + (size_t)gi * a.out_stride + ch) = make_float2(vf0, vf1);
-      if (a.running_mean) {
-        const float mo = a.momentum, ub = a.unbias;
-        rm.x = (1.f - mo) * rm.x + mo * mf0; rm.y = (1.f - mo) * rm.y + mo * mf1;
-        rv.x = (1.f - mo) * rv.x + mo * (vf0 * ub); rv.y = (1.f - mo) * rv.y + mo * (vf1 * ub);
-      }
-      if (a.count_out && blockIdx.y == 0 && tx == 0) a.count_out[(size_t)gi * a.out_stride] = (float)a.rows_real;
-      continue;
-    }
-    float* o1 = a.out1 + (size_t)gi * a.out_stride + c;
-    float* o2 = a.out2 + (size_t)gi * a.out_stride + c;
-    if (MODE == 0) {
-      const float4 pv = *reinterpret_cast<const float4*>(x + (size_t)gi * g.Mg * C + c);
-      const float piv[4] = {pv.x, pv.y, pv.z, pv.w};
-      float mf[4], vf[4];
+    if constexpr (col_is_stats(MODE)) {
+      float piv[4] = {0, 0, 0, 0}, mf[4], vf[4];
+      if constexpr (MODE == kColStats) ld_lanes<4>(a.x + (size_t)gi * g.Mg * C + c, piv);
+      else if (a.pivot) ld_lanes<2>(a.pivot + cs, piv);
+      const double inv = 1.0 / (double)n;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double m = d1[e] / (double)g.Mg;
-        double v = d2[e] / (double)g.Mg - m * m;
-        if (v < 0.0) v = 0.0;
-        mf[e] = (float)((double)piv[e] + m); vf[e] = (float)v;
+      for (int e = 0; e < L; ++e) {
+        if constexpr (MODE == kColStats) col_stat_lane(d1[e] / (double)n, d2[e] / (double)n, piv[e], mf[e], vf[e]);
+        else col_stat_lane(d1[2 * e] * inv, d1[2 * e + 1] * inv, piv[e], mf[e], vf[e]);      // columns: (S1, S2) per channel
       }
-      *reinterpret_cast<float4*>(o1) = make_float4(mf[0], mf[1], mf[2], mf[3]);
-      *reinterpret_cast<float4*>(o2) = make_float4(vf[0], vf[1], vf[2], vf[3]);
-      if (a.running_mean) {                                  // one update per group, in group order = the order of the
-        const float mo = a.momentum, ub = a.unbias;          // reference's per-camera calls
-        rm.x = (1.f - mo) * rm.x + mo * mf[0]; rm.y = (1.f - mo) * rm.y + mo * mf[1];
-        rm.z = (1.f - mo) * rm.z + mo * mf[2]; rm.w = (1.f - mo) * rm.w + mo * mf[3];
-        rv.x = (1.f - mo) * rv.x + mo * (vf[0] * ub); rv.y = (1.f - mo) * rv.y + mo * (vf[1] * ub);
-        rv.z = (1.f - mo) * rv.z + mo * (vf[2] * ub); rv.w = (1.f - mo) * rv.w + mo * (vf[3] * ub);
+      st_lanes<L>(a.out1 + (size_t)gi * a.out_stride + cs, mf);
+      st_lanes<L>(a.out2 + (size_t)gi * a.out_stride + cs, vf);
+      if (a.running_mean) {               // one update per group, in group order = the order of the reference's per-camera calls
+#pragma unroll
+        for (int e = 0; e < L; ++e) col_running_lane(rm[e], rv[e], mf[e], vf[e], a.momentum, a.unbias);
       }
     } else {
       const float4 f1 = make_float4((float)d1[0], (float)d1[1], (float)d1[2], (float)d1[3]);
       const float4 f2 = make_float4((float)d2[0], (float)d2[1], (float)d2[2], (float)d2[3]);
-      *reinterpret_cast<float4*>(o1) = f1;
-      if (MODE != 6) *reinterpret_cast<float4*>(o2) = f2;
+      *reinterpret_cast<float4*>(a.out1 + (size_t)gi * a.out_stride + c) = f1;
+      if (MODE != kColBwdPartials) *reinterpret_cast<float4*>(a.out2 + (size_t)gi * a.out_stride + c) = f2;
       accg1.x += f1.x; accg1.y += f1.y; accg1.z += f1.z; accg1.w += f1.w;
       accg2.x += f2.x; accg2.y += f2.y; accg2.z += f2.z; accg2.w += f2.w;
     }
-    if (a.count_out && blockIdx.y == 0 && tx == 0) a.count_out[(size_t)gi * a.out_stride] = (float)g.Mg;
+    if (a.count_out && blockIdx.y == 0 && tx == 0) a.count_out[(size_t)gi * a.out_stride] = (float)n;
   }
   if (ty != 0) return;
-  if (MODE == 0 && a.running_mean) {
-    *reinterpret_cast<float4*>(a.running_mean + c) = rm;
-    *reinterpret_cast<float4*>(a.running_var + c) = rv;
-  }
-  if (MODE == 5) {
+  if constexpr (col_is_stats(MODE)) {
     if (a.running_mean) {
-      *reinterpret_cast<float2*>(a.running_mean + ch) = make_float2(rm.x, rm.y);
-      *reinterpret_cast<float2*>(a.running_var + ch) = make_float2(rv.x, rv.y);
+      st_lanes<L>(a.running_mean + cs, rm);
+      st_lanes<L>(a.running_var + cs, rv);
     }
-    return;
-  }
-  if (MODE == 6) {                                           // columns [0, C/2): dbeta, [C/2, C): dgamma
-    if (a.acc1) {
+  } else if (a.acc1) {                                       // parameter gradients accumulated in place (.grad arena)
+    if constexpr (MODE == kColBwdPartials) {                 // columns [0, C/2): dbeta, [C/2, C): dgamma
       const int half = C >> 1;
-      float* ap = c < half ? a.acc1 + c : a.acc2 + (c - half);
-      grad_add4(ap, accg1);
+      grad_add4(c < half ? a.acc1 + c : a.acc2 + (c - half), accg1);
+    } else {
+      grad_add4(a.acc1 + c, accg1);
+      grad_add4(a.acc2 + c, accg2);
     }
-    return;
-  }
-  if (MODE != 0 && a.acc1) {                                 // parameter gradients accumulated in place (.grad arena)
-    grad_add4(a.acc1 + c, accg1);
-    grad_add4(a.acc2 + c, accg2);
   }
 }
 
+// (the kernels keep an int parameter: col_reduce_kernel<1> stays the name that the recorded profiles carry)
 template <int MODE>
 __global__ __launch_bounds__(256) void col_reduce_kernel(ColArgs a) {
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-  col_reduce_body<MODE, 4, 4>(a);
+  col_reduce_body<(ColMode)MODE, 4, 4>(a);
 }
 
 // Same kernel compiled for at most 64 VGPRs: shipped for the backward sums in r04, when they ran beside two weight-gradient
 // blocks per CU (which leave 112 VGPRs per SIMD lane - room for two lean waves instead of one).  On ONE stream (r05) the
-// 86-register build above is 0.7 ms/step faster (in-box, interleaved, 5 rounds: 126.95 -> 126.24) and is the shipped one;
-// XAS_TUNE_COL_REDUCE_LEAN selects this build.
+// build above is 0.7 ms/step faster (in-box, interleaved, 5 rounds: 126.95 -> 126.24) and is the shipped one;
+// XAS_TUNE_COL_REDUCE_LEAN selects this build.  What the compiler reports (gfx950, -O3): the build above takes 126 VGPRs for
+// kColStats, 120 for kColBwdXY / kColSum / kColBwdY / kColBwdX (4 waves per SIMD), 92 and 84 for the two partials modes
+// (5 waves), no scratch; this one 64 VGPRs (8 waves) and SPILLS 12 bytes of scratch per lane in each of its three modes.
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void col_reduce_lean_kernel(ColArgs a) {
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-  col_reduce_body<MODE, 2, 2>(a);
+  col_reduce_body<(ColMode)MODE, 2, 2>(a);
 }
 
 // SyncBatchNorm: merge the per-rank statistics of every group.  gathered: [world][G][msg_stride] = mean | biased var |
@@ -437,8 +474,8 @@ __global__ void bn_sync_merge_kernel(const float* __restrict__ gathered, int wor
 //              the chip with two weight-gradient blocks per CU and get few wave slots;
 //   general  : grid-stride loop, channel quadruple from i % C4 in every trip, plain loads and stores, the mode read at run
 //              time from `act` and from which pointers are null: every combination the entry points accept.
-// bn_stream_grid (host) picks the policy.  The reductions (col_reduce_body MODE 1 / 3 / 4) and the convolution epilogues
-// (conv_shared.h) keep their own copy of the sign / xhat logic under a tuned register budget (86 / <= 64 VGPRs).
+// bn_stream_grid (host) picks the policy.  The sign / xhat helpers of bn_bwd_elem are those of the backward sums (col_term,
+// above); the convolution epilogues (conv_shared.h) keep their own copy under their register budget.
 __device__ __forceinline__ float act_fwd(float v, int act) {
   return act == 0 ? v : (act == 1 ? fmaxf(v, 0.f) : (v > 0.f ? v : 0.01f * v));
 }
@@ -491,24 +528,18 @@ __device__ __forceinline__ float4 bn_fwd_elem(const BnChan& ch, float4 xv, float
 template <bool NT>
 __device__ __forceinline__ float4 bn_bwd_elem(const BnChan& ch, float inv_count, float4 xv, float4 yv, float4 dz, unsigned mb,
                                               int act, int sign, bool xh_from_x, bool has_dres, float4* dres, float& amx) {
-  const float neg = act == 1 ? 0.f : 0.01f, up = act == 1 ? 0.f : 100.f;
+  const float neg = act_neg_slope(act);
   const float4 &m = ch.m, &is = ch.is, &rs = ch.rs, &g = ch.g, &bt = ch.bt, &a = ch.a, &b = ch.b;
-  if (sign == 1) {
-    dz.x *= yv.x > 0.f ? 1.f : neg; dz.y *= yv.y > 0.f ? 1.f : neg; dz.z *= yv.z > 0.f ? 1.f : neg; dz.w *= yv.w > 0.f ? 1.f : neg;
-  } else if (sign == 2) {
-    dz.x *= bn_affine(xv.x, m.x, rs.x, bt.x) > 0.f ? 1.f : neg; dz.y *= bn_affine(xv.y, m.y, rs.y, bt.y) > 0.f ? 1.f : neg;
-    dz.z *= bn_affine(xv.z, m.z, rs.z, bt.z) > 0.f ? 1.f : neg; dz.w *= bn_affine(xv.w, m.w, rs.w, bt.w) > 0.f ? 1.f : neg;
-  } else if (sign == 3) {
-    dz.x *= (mb & 1u) ? 1.f : neg; dz.y *= (mb & 2u) ? 1.f : neg; dz.z *= (mb & 4u) ? 1.f : neg; dz.w *= (mb & 8u) ? 1.f : neg;
-  }
+  if (sign == 1) dz = dz_sign_y(dz, yv, neg);
+  else if (sign == 2) dz = dz_sign_x(dz, xv, m, rs, bt, neg);
+  else if (sign == 3) dz = dz_sign_mask(dz, mb, neg);
   if (has_dres) ew_store<NT>(dres, dz);
   float4 xh;
-  if (xh_from_x) xh = make_float4((xv.x - m.x) * is.x, (xv.y - m.y) * is.y, (xv.z - m.z) * is.z, (xv.w - m.w) * is.w);
-  else {
-    xh.x = g.x != 0.f ? ((yv.x > 0.f ? yv.x : yv.x * up) - bt.x) / g.x : 0.f;
-    xh.y = g.y != 0.f ? ((yv.y > 0.f ? yv.y : yv.y * up) - bt.y) / g.y : 0.f;
-    xh.z = g.z != 0.f ? ((yv.z > 0.f ? yv.z : yv.z * up) - bt.z) / g.z : 0.f;
-    xh.w = g.w != 0.f ? ((yv.w > 0.f ? yv.w : yv.w * up) - bt.w) / g.w : 0.f;
+  if (xh_from_x) xh = xhat4(xv, m, is);
+  else {                                               // (a division here, where the sums multiply by 1 / gamma)
+    const float4 z = act_inv4(yv, act);
+    xh.x = g.x != 0.f ? (z.x - bt.x) / g.x : 0.f; xh.y = g.y != 0.f ? (z.y - bt.y) / g.y : 0.f;
+    xh.z = g.z != 0.f ? (z.z - bt.z) / g.z : 0.f; xh.w = g.w != 0.f ? (z.w - bt.w) / g.w : 0.f;
   }
   float4 o;
   o.x = g.x * is.x * (dz.x - a.x * inv_count - xh.x * b.x * inv_count);
@@ -861,11 +892,29 @@ static BnBwdKernel bn_bwd_stream_kernel(int act, bool x, bool y, bool mask, bool
   return nullptr;
 }
 
+// (act, which operands are present) -> the mode of the backward sums: the `sign` rule of bn_bwd_stream_kernel (mask bytes,
+// else y, else re-derived from x), and without x the form that recovers xhat from y
+static ColMode bn_bwd_reduce_mode(int act, bool x, bool y, bool mask) {
+  if (!x) return kColBwdY;
+  return act != 0 && !mask && !y ? kColBwdX : kColBwdXY;
+}
+
 static int col_args(ColArgs* a, const ColGeom& g, long M, int C, float* workspace) {
   a->M = M; a->C = C; a->g = g; a->partial = workspace;
   a->ticket = take_tickets(g.ncb);
   XAS_REQUIRE(a->ticket != nullptr, "column reduce: could not allocate the ticket counters");
   XAS_REQUIRE((size_t)g.G * g.nslab * 2 * C * sizeof(float) < 0x7fffff00ul, "column reduce: partial buffer too large");
+  return 0;
+}
+
+// the one launch of the column reductions (grid: slabs x channel blocks x groups of a.g); lean: col_reduce_lean_kernel,
+// built for the backward sums only
+template <ColMode MODE>
+static int launch_col_reduce(const ColArgs& a, bool lean, void* stream) {
+  auto k = col_reduce_kernel<MODE>;
+  if constexpr (col_is_bwd(MODE)) if (lean) k = col_reduce_lean_kernel<MODE>;
+  hipLaunchKernelGGL(k, dim3(a.g.nslab, a.g.ncb, a.g.G), dim3(256), 0, as_stream(stream), a);
+  XAS_LAUNCH_CHECK();
   return 0;
 }
 
@@ -883,9 +932,7 @@ extern "C" int xas_bn_stats(const float* x, long M, int C, int groups, float* me
   a.x = x; a.out1 = mean; a.out2 = var_biased; a.out_stride = out_stride; a.count_out = count_out;
   a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum;
   a.unbias = count > 1 ? (float)((double)count / (double)(count - 1)) : 1.f;
-  hipLaunchKernelGGL(col_reduce_kernel<0>, dim3(g.nslab, g.ncb, g.G), dim3(256), 0, as_stream(stream), a);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_col_reduce<kColStats>(a, false, stream);
 }
 
 // Statistics from the per-tile partial sums a convolution epilogue left (xas_conv_fwd_bnstats): partial is
@@ -904,13 +951,11 @@ extern "C" int xas_bn_stats_from_partials(const float* partial, long rows, int C
               "bn_stats_from_partials: buffers must be 16-byte aligned, C and out_stride multiples of 4");
   ColArgs a{};
   if (col_args(&a, g, rows, 2 * C, workspace)) return 1;
-  a.x = partial; a.aux = pivot; a.out1 = mean; a.out2 = var_biased; a.out_stride = out_stride; a.count_out = count_out;
+  a.x = partial; a.pivot = pivot; a.out1 = mean; a.out2 = var_biased; a.out_stride = out_stride; a.count_out = count_out;
   a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum;
   a.rows_real = rows_per_group;
   a.unbias = rows_per_group > 1 ? (float)((double)rows_per_group / (double)(rows_per_group - 1)) : 1.f;
-  hipLaunchKernelGGL(col_reduce_kernel<5>, dim3(g.nslab, g.ncb, g.G), dim3(256), 0, as_stream(stream), a);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_col_reduce<kColStatsPartials>(a, false, stream);
 }
 
 // Batch-norm backward sums from the per-tile partial sums a data-gradient epilogue left (xas_conv_dgrad_bn_bwd):
@@ -927,9 +972,7 @@ extern "C" int xas_bn_bwd_sums_from_partials(const float* partial, long rows, in
   a.x = partial; a.out1 = sums; a.out_stride = 2 * (long)C;
   a.out2 = nullptr;                                                    // (no second sums in this mode)
   a.acc1 = dbeta_acc; a.acc2 = dgamma_acc;
-  hipLaunchKernelGGL(col_reduce_kernel<6>, dim3(g.nslab, g.ncb, g.G), dim3(256), 0, as_stream(stream), a);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_col_reduce<kColBwdPartials>(a, false, stream);
 }
 
 extern "C" int xas_bn_sync_merge(const float* gathered, int world, int groups, int C, long msg_stride, float* mean,
@@ -952,9 +995,7 @@ extern "C" int xas_col_sum(const float* x, long M, int C, float* out, float* wor
   if (col_args(&a, g, M, C, workspace)) return 1;
   a.x = x; a.out1 = out; a.out2 = workspace + (size_t)g.nslab * 2 * C;     // second sums are unused: workspace tail
   a.out_stride = C;
-  hipLaunchKernelGGL(col_reduce_kernel<2>, dim3(g.nslab, g.ncb, 1), dim3(256), 0, as_stream(stream), a);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_col_reduce<kColSum>(a, false, stream);
 }
 
 extern "C" int xas_bn_apply(const float* x, const float* mean, const float* var_biased, const float* gamma,
@@ -1002,9 +1043,7 @@ extern "C" int xas_col_sum_acc(const float* x, long M, int C, float* acc, float*
   float* scratch = workspace + (size_t)g.nslab * 2 * C;                 // C floats: plain sums, second sums and their accumulator
   a.x = x; a.out1 = scratch; a.out2 = scratch; a.out_stride = C;
   a.acc1 = acc; a.acc2 = scratch;
-  hipLaunchKernelGGL(col_reduce_kernel<2>, dim3(g.nslab, g.ncb, 1), dim3(256), 0, as_stream(stream), a);
-  XAS_LAUNCH_CHECK();
-  return 0;
+  return launch_col_reduce<kColSum>(a, false, stream);
 }
 
 extern "C" int xas_bn_bwd_reduce(const float* x, const float* y, const float* dy, const float* mean,
@@ -1018,29 +1057,18 @@ extern "C" int xas_bn_bwd_reduce(const float* x, const float* y, const float* dy
               "bn_bwd_reduce: null buffer (an activation needs y, or x with gamma and beta)");
   XAS_REQUIRE(x || (act != 0 && y && gamma && beta), "bn_bwd_reduce: without x the layer needs an activation, y, gamma, beta");
   XAS_REQUIRE((dbeta_acc == nullptr) == (dgamma_acc == nullptr), "bn_bwd_reduce: gradient accumulators come in pairs");
-  const bool lean = (tune_flags() & XAS_TUNE_COL_REDUCE_LEAN) != 0;      // shipped: the 86-VGPR build (the flag selects the <= 64-VGPR one: see col_reduce_lean_kernel)
+  const bool lean = (tune_flags() & XAS_TUNE_COL_REDUCE_LEAN) != 0;      // shipped: col_reduce_kernel (the flag selects the <= 64-VGPR build: see col_reduce_lean_kernel)
   ColArgs a{};
   if (col_args(&a, g, M, C, workspace)) return 1;
-  a.dy = dy; a.mean = mean; a.var = var_biased; a.eps = eps; a.act = act;
+  a.x = x; a.y = y; a.dy = dy; a.mask = mask; a.mean = mean; a.var = var_biased; a.gamma = gamma; a.beta = beta;
+  a.eps = eps; a.act = act;
   a.out1 = sums; a.out2 = sums + C; a.out_stride = 2 * (long)C;            // [G][2][C]
   a.acc1 = dbeta_acc; a.acc2 = dgamma_acc;
-  const dim3 grid(g.nslab, g.ncb, g.G);
-  if (mask) {                             // sign bits instead of y (layers with a residual: 1/16 of y's bytes)
-    a.x = x; a.y = nullptr; a.mask = mask;
-    hipLaunchKernelGGL(lean ? col_reduce_lean_kernel<1> : col_reduce_kernel<1>, grid, dim3(256), 0, as_stream(stream), a);
-  } else
-  if (x && act != 0 && y == nullptr) {   // y-free form: activation mask re-derived from x (layers without a residual)
-    a.x = x; a.y = gamma; a.aux = beta;
-    hipLaunchKernelGGL(lean ? col_reduce_lean_kernel<4> : col_reduce_kernel<4>, grid, dim3(256), 0, as_stream(stream), a);
-  } else if (x) {
-    a.x = x; a.y = y;
-    hipLaunchKernelGGL(lean ? col_reduce_lean_kernel<1> : col_reduce_kernel<1>, grid, dim3(256), 0, as_stream(stream), a);
-  } else {            // x-free form: xhat recovered from the saved output (one activation tensor less to read)
-    a.x = gamma; a.y = y; a.aux = beta;
-    hipLaunchKernelGGL(lean ? col_reduce_lean_kernel<3> : col_reduce_kernel<3>, grid, dim3(256), 0, as_stream(stream), a);
+  switch (bn_bwd_reduce_mode(act, x != nullptr, y != nullptr, mask != nullptr)) {
+    case kColBwdXY: return launch_col_reduce<kColBwdXY>(a, lean, stream);   // sign from the mask bytes (layers with a residual: 1/16 of y's bytes) or from y
+    case kColBwdX: return launch_col_reduce<kColBwdX>(a, lean, stream);     // layers without a residual
+    default: return launch_col_reduce<kColBwdY>(a, lean, stream);           // one activation tensor less to read
   }
-  XAS_LAUNCH_CHECK();
-  return 0;
 }
 
 extern "C" int xas_bn_bwd_apply(const float* x, const float* y, const float* dy, const float* mean,
