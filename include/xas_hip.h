@@ -578,6 +578,23 @@ int xas_grad_guard(const float* g, long n, float max_norm, int skip_nonfinite, f
 int xas_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float eps,
                           const void* guard, void* stream);
 
+/* Averaged weights: the same two steps, each also maintaining `ema`, an exponential moving average of the parameters (a
+ * shadow arena of n floats, aligned like p), in the same launch - one more arena read and one more arena write.
+ *   p, m, v   exactly what xas_adam_step / xas_adam_step_guarded compute from the same inputs, bit for bit;
+ *   ema       per element, from the NEW parameter: ema = fmaf(decay, ema, one_minus_decay * p_new) - the product rounds
+ *             once, the fused multiply-add once.  Both factors come from the host: decay in [0, 1), one_minus_decay rounded
+ *             once from 1.0 - (double)decay.  decay == 0 makes the shadow equal the parameters exactly, provided the old
+ *             shadow element is finite (0 * inf and 0 * NaN are NaN: a non-finite shadow stays non-finite at every decay).
+ *   skip      guarded form: a skipped step stores nothing, ema keeps its bits along with p, m and v.
+ * No warm-up of the decay: it would depend on the count of APPLIED steps, which the guarded form keeps on the device (guard
+ * record, word 3), and the record's layout is fixed.  The caller starts the shadow as a copy of the parameters instead, so
+ * it needs no bias correction.  Status 1 before any launch: null ema, n <= 0 or n % 4 != 0, decay outside [0, 1) or NaN,
+ * null guard. */
+int xas_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2,
+                      float eps, int step, float decay, float one_minus_decay, void* stream);
+int xas_adam_step_guarded_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2,
+                              float eps, float decay, float one_minus_decay, const void* guard, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Evaluation path: hypothesis selection, triangulation, pose metrics.
  * One evaluation batch stays on the device; nothing here synchronises with the host.

@@ -17,5 +17,6 @@ void set_error(const char* fmt, ...) {
 extern "C" const char* xas_last_error(void) { return xas::g_err; }
 extern "C" int xas_abi_version(void) { return 3; }   // 2: xas_conv_shape.mode, pre-split weights (round 3); 3: xas_conv_shape.x_amax,
                                                      // recorded maxima as slots of XAS_AMAX_SLOT_FLOATS floats (round 4)
-                                                     // (added since, nothing changed: xas_grad_guard, xas_adam_step_guarded -
-                                                     // the number stays while tests/test_abi.py pins it)
+                                                     // (added since, nothing changed: xas_grad_guard, xas_adam_step_guarded,
+                                                     // xas_adam_step_ema, xas_adam_step_guarded_ema - the number stays while
+                                                     // tests/test_abi.py pins it)

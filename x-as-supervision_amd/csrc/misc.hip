@@ -766,6 +766,24 @@ __global__ void adam_kernel(float4* __restrict__ p, const float4* __restrict__ g
   }
 }
 
+// The averaged shadow of the parameters (xas_hip.h: xas_adam_step_ema), one element: the product rounds once, the fused
+// multiply-add once.  decay == 0 gives the new parameter itself.
+#define XAS_EMA1(f) ev.f = fmaf(decay, ev.f, omd * pv.f);
+
+// adam_kernel (the same element arithmetic: XAS_ADAM1) + the shadow update while p_new is in a register: one more arena read,
+// one more arena write.
+__global__ void adam_ema_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                float4* __restrict__ v, float4* __restrict__ e, long n4, float b1, float b2, float eps,
+                                float step_size, float inv_sqrt_bc2, float decay, float omd) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float4 gv = g[i];
+    float4 mv = m[i], vv = v[i], pv = p[i], ev = e[i];
+    XAS_ADAM1(x) XAS_ADAM1(y) XAS_ADAM1(z) XAS_ADAM1(w)
+    XAS_EMA1(x) XAS_EMA1(y) XAS_EMA1(z) XAS_EMA1(w)
+    m[i] = mv; v[i] = vv; p[i] = pv; e[i] = ev;
+  }
+}
+
 // ------------------------------------------------------------------ guarded Adam (xas_hip.h: xas_grad_guard)
 // The guard record of the header, as the kernels see it.
 struct GuardRecord {
@@ -867,6 +885,23 @@ __global__ void adam_guarded_kernel(float4* __restrict__ p, const float4* __rest
     m[i] = mv; v[i] = vv; p[i] = pv;
   }
 }
+
+// adam_guarded_kernel + the shadow update of adam_ema_kernel.  A skipped step stores nothing: the shadow keeps its bits too.
+__global__ void adam_guarded_ema_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                        float4* __restrict__ v, float4* __restrict__ e, long n4, float b1, float b2,
+                                        float eps, float decay, float omd, const GuardRecord* __restrict__ rec) {
+  if (rec->skip != 0) return;
+  const float scale = rec->scale, step_size = rec->step_size, inv_sqrt_bc2 = rec->inv_sqrt_bc2;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    float4 gv = g[i];
+    float4 mv = m[i], vv = v[i], pv = p[i], ev = e[i];
+    gv.x *= scale; gv.y *= scale; gv.z *= scale; gv.w *= scale;
+    XAS_ADAM1(x) XAS_ADAM1(y) XAS_ADAM1(z) XAS_ADAM1(w)
+    XAS_EMA1(x) XAS_EMA1(y) XAS_EMA1(z) XAS_EMA1(w)
+    m[i] = mv; v[i] = vv; p[i] = pv; e[i] = ev;
+  }
+}
+#undef XAS_EMA1
 #undef XAS_ADAM1
 
 static inline unsigned ew_grid(long n, int per_block = 256) {
@@ -1043,6 +1078,39 @@ extern "C" int xas_adam_step_guarded(float* p, const float* g, float* m, float* 
   XAS_LAUNCH_CHECK();
   return 0;
 }
+
+// the two arguments every averaged step checks alike: the shadow arena and its decay
+#define XAS_REQUIRE_EMA(name)                                                                                        \
+  XAS_REQUIRE(ema, name ": the shadow arena (ema) is null");                                                         \
+  XAS_REQUIRE(decay >= 0.f && decay < 1.f, name ": decay must be in [0, 1), got %g", (double)decay)
+
+extern "C" int xas_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1,
+                                 float beta2, float eps, int step, float decay, float one_minus_decay, void* stream) {
+  XAS_REQUIRE(p && g && m && v && n > 0 && n % 4 == 0 && step >= 1, "adam ema: bad arguments (n must be a multiple of 4)");
+  XAS_REQUIRE_EMA("adam ema");
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream), reinterpret_cast<float4*>(p),
+                     reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v),
+                     reinterpret_cast<float4*>(ema), n / 4, beta1, beta2, eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)),
+                     decay, one_minus_decay);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_adam_step_guarded_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1,
+                                         float beta2, float eps, float decay, float one_minus_decay, const void* guard,
+                                         void* stream) {
+  XAS_REQUIRE(p && g && m && v && n > 0 && n % 4 == 0, "adam guarded ema: bad arguments (n must be a multiple of 4)");
+  XAS_REQUIRE(guard, "adam guarded ema: the guard record is null");
+  XAS_REQUIRE_EMA("adam guarded ema");
+  hipLaunchKernelGGL(adam_guarded_ema_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m),
+                     reinterpret_cast<float4*>(v), reinterpret_cast<float4*>(ema), n / 4, beta1, beta2, eps, decay,
+                     one_minus_decay, static_cast<const GuardRecord*>(guard));
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+#undef XAS_REQUIRE_EMA
 
 extern "C" int xas_pose_loss_fwd(const float* pred, const float* gt, int B, int Hy, int K, int kind, float w0, float w1,
                                  float w2, float* out, void* stream) {

@@ -171,12 +171,17 @@ class Eval:
 
 
 def prepare_model(config, opt):
-    """Detector from the `unsup_model` entry of a training checkpoint (eval.py:298-314)."""
+    """Detector from the `unsup_model` entry of a training checkpoint (eval.py:298-314); with --ema from `unsup_model_ema`,
+    the averaged weights a run with train_params.ema_decay saves beside it."""
     dp = config['model_params']['detector_params']
     detector = (KPDetector3DMulti_integral if dp['name'] == 'resnet_multi' else KPDetector3D_integral)(**dp)
     if opt.checkpoint is not None:
         checkpoint = torch.load(opt.checkpoint, map_location='cpu')
-        detector.load_state_dict({k.replace('regressor.', ''): v for k, v in checkpoint['unsup_model'].items()
+        key = 'unsup_model_ema' if getattr(opt, 'ema', False) else 'unsup_model'
+        if key not in checkpoint:
+            hint = ' (--ema needs a run with train_params.ema_decay set)' if key.endswith('_ema') else ''
+            raise KeyError("checkpoint %s has no '%s' entry%s" % (opt.checkpoint, key, hint))
+        detector.load_state_dict({k.replace('regressor.', ''): v for k, v in checkpoint[key].items()
                                   if 'regressor.' in k})
     return detector
 
@@ -223,6 +228,7 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--extra_tag', dict(default=' ')),
     ('--multi_hypo', dict(default='best', choices=['best', 'confident'], help='multi-hypothesis eval mode')),
     ('--synthetic', dict(default=0, type=int, help='evaluate N synthetic batches (no dataset on this machine)')),
+    ('--ema', dict(default=False, action='store_true', help="evaluate the averaged weights ('unsup_model_ema')")),
 )
 
 

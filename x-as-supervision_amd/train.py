@@ -73,6 +73,17 @@ class Trainer:
         ckpt = torch.load(checkpoint_path, map_location=f'cuda:{self.gpu_id}')
         self.unsup_model.load_state_dict(ckpt['unsup_model'], strict=False)
         self.optimizer_detector.load_state_dict(ckpt['optimizer_detector'])
+        if self.optimizer_detector.ema_arena is not None:       # averaged weights (train_params.ema_decay)
+            ema, names = ckpt.get('unsup_model_ema'), self._ema_param_names()
+            if ema is None:
+                print("Checkpoint has no 'unsup_model_ema': the averaged weights start from the loaded parameters")
+                self.optimizer_detector.load_ema([p.data for p in self.optimizer_detector.arena_params()])
+            else:                                                # all of them or none: never a mix of averaged and raw weights
+                missing = [n for n in names if n not in ema]
+                if missing:
+                    raise KeyError("checkpoint %s: 'unsup_model_ema' lacks %d of %d parameters (%s%s)" % (
+                        checkpoint_path, len(missing), len(names), ', '.join(missing[:4]), ', ...' if len(missing) > 4 else ''))
+                self.optimizer_detector.load_ema([ema[n] for n in names])
         try:
             self.unsup_disc.load_state_dict(ckpt['unsup_disc'], strict=False)
             if self.optimizer_discriminator is not None:
@@ -87,10 +98,21 @@ class Trainer:
         else:
             raise NotImplementedError
 
+    def _ema_param_names(self):
+        """Names in unsup_model.state_dict() of the detector optimizer's parameters, in the optimizer's order."""
+        by_id = {id(p): n for n, p in self.unsup_model.named_parameters()}
+        return [by_id[id(p)] for p in self.optimizer_detector.arena_params()]
+
     def _save_checkpoint(self, epoch):
         ckpt = {'unsup_model': self.unsup_model.state_dict(), 'unsup_disc': self.unsup_disc.state_dict(),
                 'epochs': epoch, 'optimizer_detector': self.optimizer_detector.state_dict(),
                 'optimizer_discriminator': self.optimizer_discriminator.state_dict()}
+        if self.optimizer_detector.ema_arena is not None:
+            # the keys of 'unsup_model': parameters from the shadow arena, buffers (the batch-norm running statistics are
+            # momentum averages already) from the live model
+            ema = dict(ckpt['unsup_model'])
+            ema.update((n, v.clone()) for n, v in zip(self._ema_param_names(), self.optimizer_detector.ema_views()))
+            ckpt['unsup_model_ema'] = ema
         torch.save(ckpt, os.path.join(self.save_dir, '{:05d}_ckpt.pth.tar'.format(epoch)))
 
     def convert_data_to_device(self, x):

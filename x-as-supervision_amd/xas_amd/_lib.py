@@ -130,6 +130,8 @@ SIGNATURES = {
     'xas_grad_guard_workspace_bytes': ('l', 'z'),
     'xas_grad_guard': ('plfifffppp', 'i'),
     'xas_adam_step_guarded': ('pppplfffpp', 'i'),
+    'xas_adam_step_ema': ('ppppplffffiffp', 'i'),
+    'xas_adam_step_guarded_ema': ('ppppplfffffpp', 'i'),
     'xas_eval_select': ('pppiiiifippppp', 'i'),
     'xas_projection_matrix': ('pppipp', 'i'),
     'xas_triangulate_dlt': ('ppiiipp', 'i'),

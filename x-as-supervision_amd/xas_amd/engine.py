@@ -76,7 +76,8 @@ def prepare_model(config, smpl_arrays=None):
     net_params = list(regressor.parameters()) + (list(phys.parameters()) if phys is not None else [])
     # optional keys (the reference YAMLs have neither): the guarded optimizer step of optim.FusedAdam, for both optimizers
     guard = dict(max_grad_norm=tp.get('max_grad_norm'), skip_nonfinite=bool(tp.get('skip_nonfinite_grads', False)))
-    opt_det = FusedAdam(net_params, lr=tp['lr_kp_detector'], betas=(0.5, 0.999), **guard)
+    # optional too: averaged weights of the detector side (the generator of the LSGAN game); the discriminator is not averaged
+    opt_det = FusedAdam(net_params, lr=tp['lr_kp_detector'], betas=(0.5, 0.999), ema_decay=tp.get('ema_decay'), **guard)
     opt_disc = FusedAdam(disc.parameters(), lr=tp['lr_discriminator'], betas=(0.5, 0.999), **guard) if disc is not None else None
     unsup_model = Counter3DModel(mp, regressor, smpl_layer, h36m, phys)
     unsup_disc = Counter3DDisc(mp, disc, smpl_layer, h36m)
@@ -134,6 +135,8 @@ class TrainStep:
                 self.red_disc = GradReducer(g._flat['g'], g._flat['params'], g._flat['offs'], 1, name='discriminator')
             sync_buffers(self.model)
             dist.broadcast(opt_det.param_arena, src=0)
+            if opt_det.ema_arena is not None:    # the averaged weights follow: built above as a copy of THIS rank's parameters,
+                dist.broadcast(opt_det.ema_arena, src=0)     # or restored from a checkpoint - rank 0's either way
             if opt_disc is not None:
                 dist.broadcast(opt_disc.param_arena, src=0)
 

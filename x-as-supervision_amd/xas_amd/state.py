@@ -11,7 +11,8 @@ def _flats(step):
 
 
 def _keys(f):
-    return ('p', 'm', 'v', 'g') + (('guard',) if 'guard' in f else ())       # guarded FusedAdam: the applied-step count lives there
+    # guarded FusedAdam: the applied-step count lives in 'guard'; with ema_decay: the shadow arena
+    return ('p', 'm', 'v', 'g') + (('guard',) if 'guard' in f else ()) + (('ema',) if 'ema' in f else ())
 
 
 def _buffers(step):
