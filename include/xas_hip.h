@@ -125,6 +125,23 @@ int xas_head_softargmax_fwd(const float* logits, int B, int K, int D, int num_hy
 int xas_head_softargmax_from_partials(const float* partial, int B, int K, int D, int nchunk, int num_hypo, int neighbor,
                                       float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* stats,
                                       void* stream);
+/* Flip test: the head of keypoint_detector_integral_multi.py:36-88 (and keypoint_detector_integral.py:21-65 when
+ * neighbor == 0) on the AVERAGE of an image's heat-map and the mirrored, left/right-swapped heat-map of its horizontal
+ * mirror.  `partial` holds the first-pass records of 2B images, image B + b being the mirror of image b; `perm` is a DEVICE
+ * int32 [K] table, perm[k] = the joint that joint k takes from the mirrored image (its left/right partner; k itself for an
+ * unpaired joint; every entry in [0, K): the caller checks it, an entry outside reads as k).  A mirror leaves a record's depth
+ * sums and H moment alone and turns its W moment into (W - 1) * sum e - sum e*w, so the merge needs only the records of
+ * (b, k) and (B + b, perm[k]), each normalised by its own softmax sum.  kps, z_idx and depth_prob_map are those of
+ * xas_head_softargmax_from_partials for B images ([B][num_hypo][K][3], [B][K][num_hypo], [groups][K][D], B % groups == 0).
+ * Forward only: no statistics for a backward are written. */
+int xas_head_softargmax_flip_from_partials(const float* partial, int B, int K, int D, int nchunk, int num_hypo, int neighbor,
+                                           const int* perm, float* kps, int64_t* z_idx, float* depth_prob_map, int groups,
+                                           void* stream);
+/* The same from the logits [2B][H][W][K*D] (keypoint_detector_integral_multi.py:36-88 on the averaged heat-map): the first
+ * pass of xas_head_softargmax_fwd over the 2B images, then the merge above.  partial: workspace of
+ * xas_head_workspace_floats(2B, K, D) floats. */
+int xas_head_softargmax_fwd_flip(const float* logits, int B, int K, int D, int num_hypo, int neighbor, const int* perm,
+                                 float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* partial, void* stream);
 
 int xas_head_softargmax_bwd(const float* logits, const float* stats, const int64_t* z_idx,
                             const float* grad_kps, int B, int K, int D, int num_hypo, int neighbor,
@@ -435,6 +452,9 @@ int xas_sigmoid_bwd(const float* y, const float* dy, long n, float* dx, void* st
 /* NCHW -> NHWC and back (input images arrive NCHW: dataloader.py:166) */
 int xas_nchw_to_nhwc(const float* x, int N, int C, int H, int W, float* y, void* stream);
 int xas_nhwc_to_nchw(const float* x, int N, int C, int H, int W, float* y, void* stream);
+/* Input of a flip-test pass (the mirrored image that the head of keypoint_detector_integral_multi.py:36-88 is averaged
+ * over): x [B][C][H][W] -> y [2B][H][W][C], y[b] = x[b] and y[B + b][h][w] = x[b][h][W - 1 - w]; x is read once. */
+int xas_nchw_to_nhwc_mirror_pair(const float* x, int B, int C, int H, int W, float* y, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * GPU input pipeline: the per-sample work of the reference's CPU loader

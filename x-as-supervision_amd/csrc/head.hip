@@ -11,6 +11,8 @@
 // Pass 1 (head_partial): per (b, pixel chunk) -> per joint {max, sum e*w, sum e*h, pz[D]}.
 // Pass 2 (head_finalize): one wave per (b,k): merge chunks, normalise, pick the depth
 // peaks (value desc, index asc), windowed expectation, write kps / indices / stats.
+// Pass 2 of the flip test (head_finalize_flip_kernel): the same, on the average of an image's heat-map and the mirrored,
+// left/right-swapped heat-map of its mirror image, formed from the two images' records.
 //
 // One kernel family, two policies (template parameter POW2 of the partial and backward kernels):
 //   * power of two, D in {4,8,16,32,64} where that block exists for K (pow2_policy): pix -> (h, w) is shift/mask; the
@@ -218,31 +220,40 @@ __global__ void head_partial_kernel(const float4* __restrict__ logits, float* __
   }
 }
 
-// One wave per (b,k); lane l keeps depth bins l and l + 64 (the second one is dead for D <= 64: it holds 0 and scores -1).
-__global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom g, int num_hypo, int neighbor,
-                                     float* __restrict__ kps, int64_t* __restrict__ z_idx,
-                                     float* __restrict__ depth_prob_map, int dmap_every, float* __restrict__ stats) {
-  const int b = blockIdx.x / g.K, k = blockIdx.x % g.K;
+// ---- second pass: one wave per (b,k); lane l keeps depth bins l and l + 64 (the second one is dead for D <= 64: it holds 0
+// and scores -1).  Two kernels share its two halves: head_finalize_kernel (one image) and head_finalize_flip_kernel (an image
+// and its mirror).
+// The chunks of one (image, joint) merged under their own running maximum: this lane's two depth-bin sums and the moments
+// along W and H, all still scaled by exp(-M).
+struct ChunkSums { float M, sd0, sd1, SX, SY; };
+
+__device__ __forceinline__ ChunkSums merge_chunks(const float* __restrict__ p0, const HeadGeom& g, int d0, int d1, bool live0, bool live1) {
+  const size_t cstride = (size_t)g.K * g.rec;
+  ChunkSums a;
+  a.M = -INFINITY;
+  for (int c = 0; c < g.nchunk; ++c) a.M = fmaxf(a.M, p0[c * cstride]);
+  a.sd0 = 0.f; a.sd1 = 0.f; a.SX = 0.f; a.SY = 0.f;
+  for (int c = 0; c < g.nchunk; ++c) {
+    const float* r = p0 + c * cstride;
+    const float sc = __expf(r[0] - a.M);
+    if (live0) a.sd0 += r[3 + d0] * sc;
+    if (live1) a.sd1 += r[3 + d1] * sc;
+    a.SX += r[1] * sc;
+    a.SY += r[2] * sc;
+  }
+  return a;
+}
+
+// Everything after the marginals: the depth-probability map, then either the plain expectation (neighbor == 0) or the peak
+// scores, the lowest-bin tie rule, the num_hypo picks and their windowed expectations, and the int64 peak bins.  pz0 / pz1:
+// this lane's bins of the depth marginal (dead bins 0); X, Y: expectations along W and H in pixels.  st: this joint's
+// statistics for the backward, or null (a forward-only caller).
+__device__ __forceinline__ void finalize_tail(const HeadGeom& g, int b, int k, float pz0, float pz1, float X, float Y, int num_hypo,
+                                              int neighbor, float* __restrict__ kps, int64_t* __restrict__ z_idx,
+                                              float* __restrict__ depth_prob_map, int dmap_every, float* __restrict__ st) {
   const int lane = threadIdx.x;
   const int d0 = lane, d1 = lane + 64;
   const bool live0 = d0 < g.D, live1 = d1 < g.D;
-  const float* p0 = partial + ((size_t)b * g.nchunk * g.K + k) * g.rec;
-  const size_t cstride = (size_t)g.K * g.rec;
-  float M = -INFINITY;
-  for (int c = 0; c < g.nchunk; ++c) M = fmaxf(M, p0[c * cstride]);
-  float sd0 = 0.f, sd1 = 0.f, SX = 0.f, SY = 0.f;
-  for (int c = 0; c < g.nchunk; ++c) {
-    const float* r = p0 + c * cstride;
-    const float sc = __expf(r[0] - M);
-    if (live0) sd0 += r[3 + d0] * sc;
-    if (live1) sd1 += r[3 + d1] * sc;
-    SX += r[1] * sc;
-    SY += r[2] * sc;
-  }
-  const float S = wave_sum(sd0 + sd1);        // dead bins hold 0
-  const float pz0 = live0 ? sd0 / S : 0.f, pz1 = live1 ? sd1 / S : 0.f;
-  const float X = SX / S, Y = SY / S;
-  float* st = stats + ((size_t)b * g.K + k) * XAS_HEAD_STATS;
   if (b % dmap_every == 0) {
     float* dm = depth_prob_map + ((size_t)(b / dmap_every) * g.K + k) * g.D;
     if (live0) dm[d0] = pz0;
@@ -250,14 +261,13 @@ __global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom
   }
   const float fD = (float)g.D;
   const float xn = X / fD * 2.f - 1.f, yn = Y / fD * 2.f - 1.f;
-  if (lane == 0) { st[0] = M + __logf(S); st[1] = X; st[2] = Y; }
 
   if (neighbor == 0) {                        // single hypothesis: plain expectation
     const float Z = wave_sum(pz0 * (float)d0 + pz1 * (float)d1);
     if (lane == 0) {
       float* o = kps + ((size_t)b * g.K + k) * 3;
       o[0] = xn; o[1] = yn; o[2] = Z / fD * 2.f - 1.f;
-      st[3] = Z;
+      if (st) st[3] = Z;
       if (z_idx) z_idx[(size_t)b * g.K + k] = 0;
     }
     return;
@@ -288,10 +298,48 @@ __global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom
       float* o = kps + (((size_t)b * num_hypo + h) * g.K + k) * 3;
       o[0] = xn; o[1] = yn; o[2] = Z / fD * 2.f - 1.f;
       z_idx[((size_t)b * g.K + k) * num_hypo + h] = idx;
-      st[3 + h] = Z;
-      st[9 + h] = sw;
+      if (st) { st[3 + h] = Z; st[9 + h] = sw; }
     }
   }
+}
+
+__global__ void head_finalize_kernel(const float* __restrict__ partial, HeadGeom g, int num_hypo, int neighbor,
+                                     float* __restrict__ kps, int64_t* __restrict__ z_idx,
+                                     float* __restrict__ depth_prob_map, int dmap_every, float* __restrict__ stats) {
+  const int b = blockIdx.x / g.K, k = blockIdx.x % g.K;
+  const int lane = threadIdx.x;
+  const int d0 = lane, d1 = lane + 64;
+  const bool live0 = d0 < g.D, live1 = d1 < g.D;
+  const ChunkSums a = merge_chunks(partial + ((size_t)b * g.nchunk * g.K + k) * g.rec, g, d0, d1, live0, live1);
+  const float S = wave_sum(a.sd0 + a.sd1);    // dead bins hold 0
+  const float pz0 = live0 ? a.sd0 / S : 0.f, pz1 = live1 ? a.sd1 / S : 0.f;
+  const float X = a.SX / S, Y = a.SY / S;
+  float* st = stats + ((size_t)b * g.K + k) * XAS_HEAD_STATS;
+  if (lane == 0) { st[0] = a.M + __logf(S); st[1] = X; st[2] = Y; }
+  finalize_tail(g, b, k, pz0, pz1, X, Y, num_hypo, neighbor, kps, z_idx, depth_prob_map, dmap_every, st);
+}
+
+// Flip test (the test-time step of integral-regression detectors; keypoint_detector_integral_multi.py:36-88 applied to the
+// average of a heat-map and the mirrored, pair-swapped heat-map of the mirrored image).  The records hold g.B = 2B images:
+// image b and, at B + b, its horizontal mirror.  A mirror acts linearly on a record - depth sums and the H moment stay, the
+// W moment becomes (W - 1) * sum e - sum e*w - so the averaged distribution's marginals come from the records of (b, k) and
+// (B + b, perm[k]), each normalised by its own softmax sum; no mirrored logits exist.  Forward only: no statistics.
+__global__ void head_finalize_flip_kernel(const float* __restrict__ partial, HeadGeom g, const int* __restrict__ perm,
+                                          int num_hypo, int neighbor, float* __restrict__ kps, int64_t* __restrict__ z_idx,
+                                          float* __restrict__ depth_prob_map, int dmap_every) {
+  const int b = blockIdx.x / g.K, k = blockIdx.x % g.K;      // b < B = g.B / 2
+  const int lane = threadIdx.x;
+  const int d0 = lane, d1 = lane + 64;
+  const bool live0 = d0 < g.D, live1 = d1 < g.D;
+  int k2 = perm[k];
+  if ((unsigned)k2 >= (unsigned)g.K) k2 = k;  // (the binding refuses such a table; no record outside the buffer is read)
+  const size_t image = (size_t)g.nchunk * g.K * g.rec;
+  const ChunkSums a = merge_chunks(partial + b * image + (size_t)k * g.rec, g, d0, d1, live0, live1);
+  const ChunkSums m = merge_chunks(partial + ((size_t)(g.B / 2) + b) * image + (size_t)k2 * g.rec, g, d0, d1, live0, live1);
+  const float S1 = wave_sum(a.sd0 + a.sd1), S2 = wave_sum(m.sd0 + m.sd1);
+  const float pz0 = live0 ? 0.5f * (a.sd0 / S1 + m.sd0 / S2) : 0.f, pz1 = live1 ? 0.5f * (a.sd1 / S1 + m.sd1 / S2) : 0.f;
+  const float X = 0.5f * (a.SX / S1 + ((float)(g.W - 1) - m.SX / S2)), Y = 0.5f * (a.SY / S1 + m.SY / S2);
+  finalize_tail(g, b, k, pz0, pz1, X, Y, num_hypo, neighbor, kps, z_idx, depth_prob_map, dmap_every, nullptr);
 }
 
 // per (b,k): {cx, cy, c0, lse, gz[D]}; thread = depth bin (64 threads for D <= 64, else 128; nothing crosses lanes here)
@@ -392,6 +440,27 @@ static int launch_finalize(const float* partial, const HeadGeom& g, int num_hypo
   return 0;
 }
 
+// Records of 2B images -> outputs of B (head_finalize_flip_kernel).  g is the geometry of the 2B-image first pass.
+static int launch_finalize_flip(const float* partial, const HeadGeom& g, const int* perm, int num_hypo, int neighbor, float* kps,
+                                int64_t* z_idx, float* depth_prob_map, int groups, void* stream) {
+  const int B = g.B / 2;
+  hipLaunchKernelGGL(head_finalize_flip_kernel, dim3(B * g.K), dim3(64), 0, as_stream(stream), partial, g, perm, num_hypo,
+                     neighbor, kps, z_idx, depth_prob_map, B / groups);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+static int launch_partial(const float* logits, float* partial, const HeadGeom& g, bool pow2, const char* who, void* stream) {
+  XAS_REQUIRE(((uintptr_t)logits & 15) == 0, "%s: logits must be 16-byte aligned", who);
+  const size_t lds = partial_lds_bytes(g, pow2);
+  XAS_REQUIRE(lds <= 64 * 1024, "%s: LDS %zu too large", who, lds);
+  if (check_grid(who, g)) return 1;
+  hipLaunchKernelGGL(pow2 ? head_partial_kernel<true> : head_partial_kernel<false>, dim3(g.nchunk, g.B, g.ntile),
+                     dim3(g.C4t * g.R), lds, as_stream(stream), reinterpret_cast<const float4*>(logits), partial, g);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace xas
 
 using namespace xas;
@@ -410,13 +479,7 @@ extern "C" int xas_head_softargmax_fwd(const float* logits, int B, int K, int D,
   if (make_geom(B, K, D, pow2, &g)) return 1;
   XAS_REQUIRE(logits && kps && depth_prob_map && stats && partial, "head fwd: null buffer");
   if (check_modes("head fwd", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
-  XAS_REQUIRE(((uintptr_t)logits & 15) == 0, "head fwd: logits must be 16-byte aligned");
-  const size_t lds = partial_lds_bytes(g, pow2);
-  XAS_REQUIRE(lds <= 64 * 1024, "head fwd: LDS %zu too large", lds);
-  if (check_grid("head fwd", g)) return 1;
-  hipLaunchKernelGGL(pow2 ? head_partial_kernel<true> : head_partial_kernel<false>, dim3(g.nchunk, B, g.ntile),
-                     dim3(g.C4t * g.R), lds, as_stream(stream), reinterpret_cast<const float4*>(logits), partial, g);
-  XAS_LAUNCH_CHECK();
+  if (launch_partial(logits, partial, g, pow2, "head fwd", stream)) return 1;
   return launch_finalize(partial, g, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, stream);
 }
 
@@ -433,6 +496,36 @@ extern "C" int xas_head_softargmax_from_partials(const float* partial, int B, in
   if (check_modes("head from partials", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
   g.nchunk = nchunk;
   return launch_finalize(partial, g, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stats, stream);
+}
+
+// Flip test, second pass alone: `partial` holds the records of 2B images (image B + b is the horizontal mirror of image b),
+// `perm` (device int32 [K]) the joint each joint takes from the mirrored image (its left/right partner, itself when unpaired).
+// Outputs are those of xas_head_softargmax_from_partials for B images of the averaged heat-map, minus the statistics.
+extern "C" int xas_head_softargmax_flip_from_partials(const float* partial, int B, int K, int D, int nchunk, int num_hypo,
+                                                      int neighbor, const int* perm, float* kps, int64_t* z_idx,
+                                                      float* depth_prob_map, int groups, void* stream) {
+  XAS_REQUIRE(B > 0 && B <= (1 << 29), "head flip from partials: need 0 < B, got B=%d (the records hold 2B images)", B);
+  HeadGeom g;
+  if (make_geom(2 * B, K, D, pow2_policy(D, K), &g)) return 1;
+  XAS_REQUIRE(partial && perm && kps && depth_prob_map && nchunk >= 1, "head flip from partials: null buffer");
+  if (check_modes("head flip from partials", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
+  g.nchunk = nchunk;
+  return launch_finalize_flip(partial, g, perm, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stream);
+}
+
+// Flip test from the logits of 2B images: the first pass of xas_head_softargmax_fwd over all of them, then the flip merge.
+// partial: xas_head_workspace_floats(2B, K, D) floats.
+extern "C" int xas_head_softargmax_fwd_flip(const float* logits, int B, int K, int D, int num_hypo, int neighbor, const int* perm,
+                                            float* kps, int64_t* z_idx, float* depth_prob_map, int groups, float* partial,
+                                            void* stream) {
+  XAS_REQUIRE(B > 0 && B <= (1 << 29), "head fwd flip: need 0 < B, got B=%d (the logits hold 2B images)", B);
+  const bool pow2 = pow2_policy(D, K);
+  HeadGeom g;
+  if (make_geom(2 * B, K, D, pow2, &g)) return 1;
+  XAS_REQUIRE(logits && perm && kps && depth_prob_map && partial, "head fwd flip: null buffer");
+  if (check_modes("head fwd flip", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
+  if (launch_partial(logits, partial, g, pow2, "head fwd flip", stream)) return 1;
+  return launch_finalize_flip(partial, g, perm, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stream);
 }
 
 extern "C" int xas_head_softargmax_bwd(const float* logits, const float* stats, const int64_t* z_idx,

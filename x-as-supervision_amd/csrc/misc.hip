@@ -904,6 +904,26 @@ __global__ void adam_guarded_ema_kernel(float4* __restrict__ p, const float4* __
 #undef XAS_EMA1
 #undef XAS_ADAM1
 
+// ------------------------------------------------------------------ mirrored pair stack (flip test)
+// x [B][C][H][W] -> y [2B][H][W][C]: y[b] = x[b] and y[B + b][h][w] = x[b][h][W - 1 - w], the batch a flip-test pass feeds
+// the detector (torch.flip + torch.cat + the layout change in one pass that reads x once).  A thread owns one pixel of x:
+// the loads of a wave are contiguous in every channel plane, its stores contiguous in both halves of y.
+__global__ void nchw_to_nhwc_mirror_pair_kernel(const float* __restrict__ x, int B, int C, int H, int W, float* __restrict__ y) {
+  const long HW = (long)H * W, pixels = (long)B * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / HW, p = i - b * HW;
+    const int w = (int)(p % W);
+    const float* src = x + b * C * HW + p;
+    float* same = y + i * C;
+    float* mirrored = y + (pixels + i + (W - 1 - 2 * w)) * C;      // pixel (B + b, h, W - 1 - w)
+    for (int c = 0; c < C; ++c) {
+      const float v = src[c * HW];
+      same[c] = v;
+      mirrored[c] = v;
+    }
+  }
+}
+
 static inline unsigned ew_grid(long n, int per_block = 256) {
   long b = cdiv(n, per_block);
   return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
@@ -1111,6 +1131,15 @@ extern "C" int xas_adam_step_guarded_ema(float* p, const float* g, float* m, flo
   return 0;
 }
 #undef XAS_REQUIRE_EMA
+
+extern "C" int xas_nchw_to_nhwc_mirror_pair(const float* x, int B, int C, int H, int W, float* y, void* stream) {
+  XAS_REQUIRE(x && y && x != y && B > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc_mirror_pair: bad arguments");
+  XAS_REQUIRE((long)2 * B * C * H * W < (1l << 40), "nchw_to_nhwc_mirror_pair: tensor too large");
+  hipLaunchKernelGGL(nchw_to_nhwc_mirror_pair_kernel, dim3(ew_grid((long)B * H * W)), dim3(256), 0, as_stream(stream), x, B, C,
+                     H, W, y);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int xas_pose_loss_fwd(const float* pred, const float* gt, int B, int Hy, int K, int kind, float w0, float w1,
                                  float w2, float* out, void* stream) {

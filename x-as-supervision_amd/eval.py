@@ -2,7 +2,7 @@
 """torchrun entry of the MI355X-native evaluation (reference: eval.py:1-408, same CLI and result file).
 
     torchrun --nproc-per-node=N eval.py --config config/HM36_Multi_SurS1.yaml --checkpoint ckpt.pth.tar
-             [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS]
+             [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -54,7 +54,7 @@ def ddp_setup():
 class Eval:
     """Same constructor and method signatures as the reference Eval (eval.py:63-107)."""
 
-    def __init__(self, config, detector, eval_data, log_dir, img_size=256.0):
+    def __init__(self, config, detector, eval_data, log_dir, img_size=256.0, flip_test=False):
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -64,6 +64,14 @@ class Eval:
         self.eval_data = eval_data
         self.log_dir = log_dir
         self.img_size = img_size
+        self.flip_test = bool(flip_test)           # --flip: every image is evaluated together with its horizontal mirror
+
+    def detect(self, img):
+        """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
+        the average of each heat-map and the mirrored, left/right-swapped heat-map of the mirrored image)."""
+        if self.flip_test:
+            return self.detector.forward_flip(img, self.config['model_params']['flip_pairs'])[0]
+        return self.detector(img)[0]
 
     def convert_data_to_device(self, x):
         for key, v in x.items():
@@ -82,7 +90,7 @@ class Eval:
         cams = ['cam_{}'.format(c) for c in self.cam_id_list]
         sel, out, trans = {}, {}, None
         for m in cams:
-            kps = kps_by_cam[m] if kps_by_cam is not None else self.detector(x[m + '_img'])[0]
+            kps = kps_by_cam[m] if kps_by_cam is not None else self.detect(x[m + '_img'])
             s = ops_eval.eval_select(kps, x[m + '_joints'], image_size=self.img_size, mode=mode)
             sel[m] = s['sel3d']
             out['err2d_' + m] = s['err2d']
@@ -229,6 +237,8 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--multi_hypo', dict(default='best', choices=['best', 'confident'], help='multi-hypothesis eval mode')),
     ('--synthetic', dict(default=0, type=int, help='evaluate N synthetic batches (no dataset on this machine)')),
     ('--ema', dict(default=False, action='store_true', help="evaluate the averaged weights ('unsup_model_ema')")),
+    ('--flip', dict(default=False, action='store_true',
+                    help='flip test: average every heat-map with the one of the mirrored image (model_params.flip_pairs)')),
 )
 
 
@@ -249,7 +259,7 @@ def main():
     log_dir = os.path.dirname(opt.checkpoint) if opt.checkpoint else opt.log_dir
     detector = prepare_model(config, opt)
     loader = prepare_data(config, world, opt.worker, opt.synthetic, torch.device('cuda', rank_local))
-    ev = Eval(config, detector, loader, log_dir)
+    ev = Eval(config, detector, loader, log_dir, flip_test=opt.flip)
     tables = init_tables(ev.cal_per_act)
     record = ev.eval(None, *tables, mode=opt.multi_hypo)
     destroy_process_group()

@@ -22,6 +22,12 @@ class KPDetector3D(nn.Module):
         kps, depth_prob_map = ops_head.softargmax_single(self.net(x), self.num_kp)
         return kps, depth_prob_map          # kps [B, 1, num_kp, 3], aligned with the multi-hypothesis layout
 
+    def forward_flip(self, x, flip_pairs):
+        """Flip test (eval() only, no autograd): see KPDetector3DMulti.forward_flip.  -> what forward returns."""
+        x2, perm = ops_head.detector_flip_input(self, x, flip_pairs, 'KPDetector3D')
+        kps, depth_prob_map, _ = ops_head.softargmax_flip(self.net(x2), self.num_kp, 1, 0, perm)
+        return kps, depth_prob_map
+
     def forward_groups(self, x, groups):
         """`groups` consecutive reference calls as one camera-batched pass (see KPDetector3DMulti.forward_groups)."""
         ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3D')

@@ -37,6 +37,17 @@ class KPDetector3DMulti(nn.Module):
         self.last_peak_indices = idx
         return kps, depth_prob_map
 
+    def forward_flip(self, x, flip_pairs):
+        """Flip test (eval() only, no autograd): x and its horizontal mirrors go through the network as ONE batch of 2B
+        images - batch norm uses running statistics, so the mirrors change nothing for the originals - and the head runs on
+        the average of each heat-map and the mirrored, left/right-swapped heat-map of its mirror, formed from the first-pass
+        records alone (ops_head.softargmax_flip).  flip_pairs: model_params.flip_pairs.  -> what forward returns."""
+        x2, perm = ops_head.detector_flip_input(self, x, flip_pairs, 'KPDetector3DMulti')
+        heatmap = self.net(x2)
+        kps, depth_prob_map, idx = ops_head.softargmax_flip(heatmap, self.num_kp, self.num_hypo, self.neighbor_size, perm)
+        self.last_peak_indices = idx
+        return kps, depth_prob_map
+
     def forward_groups(self, x, groups, prefix_groups=0):
         """The reference's `groups` consecutive calls forward(x[0:B]), forward(x[B:2B]), ... as ONE pass over the
         concatenated batch: convolutions see G*B images, every batch-norm layer keeps per-call statistics and applies

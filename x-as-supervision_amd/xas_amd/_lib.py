@@ -71,6 +71,8 @@ SIGNATURES = {
     'xas_conv_fwd_head_chunks': ('sii', 'i'),
     'xas_conv_fwd_head': ('ppppsiipp', 'i'),
     'xas_head_softargmax_from_partials': ('piiiiiipppipp', 'i'),
+    'xas_head_softargmax_flip_from_partials': ('piiiiiippppip', 'i'),
+    'xas_head_softargmax_fwd_flip': ('piiiiippppipp', 'i'),
     'xas_conv_fwd_bnstats_workspace_floats': ('si', 'z'),
     'xas_conv_fwd_bnstats': ('pppsippplppppfp', 'i'),
     'xas_conv_dgrad_bn_bwd_workspace_floats': ('si', 'z'),
@@ -106,6 +108,7 @@ SIGNATURES = {
     'xas_sigmoid_bwd': ('pplpp', 'i'),
     'xas_nchw_to_nhwc': ('piiiipp', 'i'),
     'xas_nhwc_to_nchw': ('piiiipp', 'i'),
+    'xas_nchw_to_nhwc_mirror_pair': ('piiiipp', 'i'),
     'xas_warp_affine_u8': ('ppppiiipp', 'i'),
     'xas_mask_blur_threshold': ('piipp', 'i'),
     'xas_patch_finish': ('pppppiiippp', 'i'),

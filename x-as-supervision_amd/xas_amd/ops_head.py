@@ -99,6 +99,96 @@ def softargmax_single(logits, num_kp, groups=1):
     return kps, (dmap[0] if groups == 1 else dmap)
 
 
+def flip_perm(flip_pairs, num_kp, device):
+    """Left/right pair list ([[1, 4], [2, 5], ...], model_params.flip_pairs) -> device int32 [K] table for softargmax_flip:
+    perm[a] = b and perm[b] = a for every pair, perm[k] = k for an unpaired joint.  Joints outside [0, K) and joints named
+    twice are refused here, on the host: the kernel indexes the records with this table."""
+    perm = list(range(num_kp))
+    for pair in flip_pairs:
+        a, b = (int(v) for v in pair)
+        if not (0 <= a < num_kp and 0 <= b < num_kp) or a == b:
+            raise RuntimeError('flip pair (%d, %d) does not name two of the %d joints' % (a, b, num_kp))
+        if perm[a] != a or perm[b] != b:
+            raise RuntimeError('flip pair (%d, %d): a joint has two partners' % (a, b))
+        perm[a], perm[b] = b, a
+    t = torch.tensor(perm, dtype=torch.int32, device=device)
+    t._xas_perm_k = num_kp                            # checked: softargmax_flip does not read it back
+    return t
+
+
+def softargmax_flip(heatmap_2b, num_kp, num_hypo, neighbor_size, perm, groups=1):
+    """Flip test: the head on the average of each image's heat-map and the mirrored, pair-swapped heat-map of its mirror.
+    heatmap_2b: logits [2B, K*D, D, D] of images 0..B-1 followed by their horizontal mirrors; perm: flip_perm(...), or any
+    int32 [K] tensor / sequence (checked here: every entry in [0, K)); num_hypo = 1 and neighbor_size = 0: the
+    single-hypothesis head.  -> kps [B,num_hypo,K,3], depth_prob_map [K,D] ([groups,K,D] for groups > 1), z_idx [B,K,num_hypo]
+    int64 (zeros for the single-hypothesis head).  Runs over the first-pass records of the final convolution's epilogue when
+    the logits carry them, else over the logits.  Inference only: raises when autograd is recording."""
+    from . import ops_nn
+    if torch.is_grad_enabled() and heatmap_2b.requires_grad:
+        raise RuntimeError('softargmax_flip is an inference path without a backward: call it under torch.no_grad()')
+    if ops_nn._prefix[0]:
+        raise RuntimeError('softargmax_flip does not run inside a prefix pass')
+    logits = _nhwc_storage(heatmap_2b)
+    B2, C, H, W = logits.shape
+    D = C // num_kp
+    if not (C == num_kp * D and D == H == W):
+        raise RuntimeError('soft-argmax head needs a heat-map cube D == H == W with D a multiple of 4 in [4,128] '
+                           '(got C=%d K=%d H=%d W=%d)' % (C, num_kp, H, W))
+    if B2 < 2 or B2 % 2:
+        raise RuntimeError('softargmax_flip takes the logits of B images followed by their B mirrors, got %d images' % B2)
+    B = B2 // 2
+    dev = logits.device
+    if not isinstance(perm, torch.Tensor):
+        perm = torch.as_tensor(perm)
+    if getattr(perm, '_xas_perm_k', None) != num_kp:
+        host = perm.detach().cpu().reshape(-1).tolist()
+        if len(host) != num_kp or any(int(v) != v or not 0 <= v < num_kp for v in host):
+            raise RuntimeError('softargmax_flip: perm must hold %d joint indices in [0, %d), got %s' % (num_kp, num_kp, host))
+        perm = perm.to(device=dev, dtype=torch.int32).contiguous()
+        perm._xas_perm_k = num_kp
+    if perm.device != dev or perm.dtype != torch.int32 or not perm.is_contiguous():
+        raise RuntimeError('softargmax_flip: perm must be a contiguous int32 tensor on %s' % dev)
+    kps = torch.empty(B, num_hypo, num_kp, 3, device=dev, dtype=torch.float32)
+    z_idx = torch.zeros(B, num_kp, num_hypo, device=dev, dtype=torch.int64)
+    dmap = torch.empty(groups, num_kp, D, device=dev, dtype=torch.float32)
+    pre = getattr(heatmap_2b, '_xas_head', None)     # first-pass records from the final convolution's epilogue (ops_nn._Conv2d)
+    if pre is not None and pre[2] == heatmap_2b._version and pre[0].shape[0] == B2 and pre[0].shape[2] == num_kp:
+        ops_nn.head_stats['fused'] += 1
+        call('xas_head_softargmax_flip_from_partials', ptr(pre[0]), B, num_kp, D, pre[1], num_hypo, neighbor_size, ptr(perm),
+             ptr(kps), ptr(z_idx), ptr(dmap), groups)
+    else:
+        ops_nn.head_stats['separate'] += 1
+        ws = torch.empty(query('xas_head_workspace_floats', B2, num_kp, D), device=dev, dtype=torch.float32)
+        call('xas_head_softargmax_fwd_flip', ptr(logits), B, num_kp, D, num_hypo, neighbor_size, ptr(perm), ptr(kps),
+             ptr(z_idx), ptr(dmap), groups, ptr(ws))
+    if peak_probe is not None:
+        peak_probe(z_idx.clone())
+    return kps, (dmap[0] if groups == 1 else dmap), z_idx
+
+
+FLIP_MAX_IMAGES = 384      # images of one detector pass (originals + mirrors): the logit budget of modules/model.py
+
+
+def detector_flip_input(det, x, flip_pairs, who):
+    """What both detectors' forward_flip do before the network: the checks, the cached pair table and the mirrored pair stack.
+    -> (channels_last batch [2B,C,S,S] of x and its mirrors, perm)."""
+    from . import ops_nn
+    check_patch_size(x, det.depth_dim, who)
+    if det.training:
+        raise RuntimeError('%s.forward_flip is a test-time pass: put the detector in eval() (batch norm must use its running '
+                           'statistics for the mirrored images to share the batch)' % who)
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in det.parameters())):
+        raise RuntimeError('%s.forward_flip is an inference path without a backward: call it under torch.no_grad()' % who)
+    if 2 * x.shape[0] > FLIP_MAX_IMAGES:
+        raise RuntimeError('%s.forward_flip: %d images and their mirrors exceed the %d images of one pass'
+                           % (who, x.shape[0], FLIP_MAX_IMAGES))
+    key = (tuple(tuple(int(v) for v in p) for p in flip_pairs), str(x.device))
+    if getattr(det, '_flip_key', None) != key:         # uploaded once per (pairs, device), as GCNDiscriminator_base._bone_index
+        det._flip_perm = flip_perm(flip_pairs, det.num_kp, x.device)
+        det._flip_key = key
+    return ops_nn.mirror_pair_nchw(x), det._flip_perm
+
+
 class _PatchToWorld(torch.autograd.Function):
     @staticmethod
     def forward(ctx, kps, ti, km, pv, rw, tw, image_size, rect_width, flags):

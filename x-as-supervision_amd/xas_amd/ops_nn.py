@@ -295,6 +295,18 @@ def stack_nchw(tensors):
     return y
 
 
+def mirror_pair_nchw(x):
+    """[B,C,H,W] image batch -> channels_last [2B,C,H,W]: the images followed by their horizontal mirrors, i.e.
+    torch.cat([x, x.flip(3)]) in NHWC storage, written by one kernel that reads x once (xas_nchw_to_nhwc_mirror_pair)."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise RuntimeError('mirror_pair_nchw: expected a float32 [B,C,H,W] image batch')
+    x = x.detach().contiguous()
+    n, c, h, w = x.shape
+    y = empty_cl(2 * n, c, h, w, x)
+    call('xas_nchw_to_nhwc_mirror_pair', ptr(x), n, c, h, w, ptr(y))
+    return y
+
+
 def _shape(n, hi, wi, cin, cout, r, s, stride, pad, ho, wo, mode=0):
     return ConvShape(n, hi, wi, cin, cout, r, s, stride, pad, ho, wo, mode)
 
