@@ -224,8 +224,9 @@ int xas_draw_lines_max_bwd(const float* kps, long kp_stride_b, long kp_stride_j,
  *
  * x  [N][Hi][Wi][Cin]      w  packed [Cout][R][S][Cin] (see xas_pack_weight)
  * y  [N][Ho][Wo][Cout]     Ho = (Hi + 2*pad - R)/stride + 1
- * bias (Cout) may be NULL.  Shapes outside the MFMA tiles (Cin % 32 != 0 or Cout < 16:
- * the 3-channel stem, the 1-channel mask convs) run a direct VALU kernel.
+ * bias (Cout) may be NULL.  One route function per pass (conv.hip: fwd_route, dgrad_route, wgrad_route) decides the
+ * kernel, for the launch and for every query below.  Forward: the 7x7 stem without a bias and the one-channel 3x3 layers
+ * have kernels of their own; other shapes outside the MFMA tiles (Cin % 32 != 0 or Cout < 16) run a direct VALU kernel.
  * ---------------------------------------------------------------------------------- */
 typedef struct {
   int N, Hi, Wi, Cin;

@@ -257,6 +257,50 @@ def test_conv_fwd_bnstats(n, cin, h, w, cout, k, stride, pad, G, form):
         assert float(((var.double() - var64).abs() / var64).max()) < 2e-5
 
 
+# (n, cin, h, w, cout, k, pad, groups, rows per tile of the statistics epilogue; 0: the separate statistics pass): the smallest
+# shape for every tile the split-precision forward launch can run on (pick_tile_x6), and one whose groups end inside a tile
+TILE_ROW_CASES = [('tap', 2, 32, 16, 16, 64, 3, 1, 2, 128), ('general128', 2, 32, 16, 16, 64, 1, 0, 2, 128),
+                  ('small64', 2, 32, 16, 16, 128, 1, 0, 2, 64), ('wide64x256', 6, 32, 64, 64, 256, 1, 0, 2, 64),
+                  ('fallback', 2, 32, 8, 8, 64, 1, 0, 2, 0)]
+
+
+@pytest.mark.parametrize('tag,n,cin,h,w,cout,k,pad,G,bm', TILE_ROW_CASES, ids=[c[0] for c in TILE_ROW_CASES])
+@pytest.mark.parametrize('prec', ['f16x3', 'bf16x6'])
+def test_conv_fwd_bnstats_on_every_tile(prec, tag, n, cin, h, w, cout, k, pad, G, bm):
+    """The partial sums of xas_conv_fwd_bnstats are laid out by the rows per tile of the launch: the workspace size says
+    which tile the host expects (bm), y is bit-identical to xas_conv_fwd, and mean / biased variance per group equal
+    float64 statistics of that y within the bars of test_conv_fwd_bnstats - a layout that disagreed with the launch would
+    sum the wrong rows."""
+    from conftest import precision_mode
+    from xas_amd import ops_nn as F
+    from xas_amd._lib import call, ptr, query
+    x, wt, _, ho, wo = _conv_case(n, cin, h, w, cout, k, 1, pad, seed=11 + cout + k + h)
+    x = x + 0.7
+    with precision_mode(prec):
+        cache = F._PackCache()
+        wg = wt.cuda()
+        xg = x.cuda().contiguous(memory_format=torch.channels_last)
+        shp = F.shape_with_maxima(F._shape(n, h, w, cin, cout, k, k, 1, pad, ho, wo), xg)
+        M = n * ho * wo
+        want = (M // bm * 2 * cout + query('xas_bn_workspace_floats', M // bm, 2 * cout, G)) if bm else query('xas_bn_workspace_floats', M, cout, G)
+        floats = query('xas_conv_fwd_bnstats_workspace_floats', shp, G)
+        assert floats == want, (floats, want)
+        y0 = torch.empty(n, cout, ho, wo, device='cuda').contiguous(memory_format=torch.channels_last)
+        call('xas_conv_fwd', ptr(xg), ptr(cache.get(wg, 0, shp)), None, ptr(y0), shp)
+        rows = y0.permute(0, 2, 3, 1).reshape(G, M // G, cout).double()
+        mean64, var64 = rows.mean(1), rows.var(1, unbiased=False)
+        y = torch.full_like(y0, float('nan'))
+        ws = torch.empty(floats, device='cuda')
+        mean = torch.empty(G, cout, device='cuda'); var = torch.empty(G, cout, device='cuda')
+        call('xas_conv_fwd_bnstats', ptr(xg), ptr(cache.get(wg, 0, shp)), ptr(y), shp, G, None, ptr(mean), ptr(var), cout, None, ptr(ws),
+             None, None, 0.1)
+    assert torch.equal(y, y0)
+    em = float((mean.double() - mean64).abs().max()) / float(mean64.abs().max() + var64.max().sqrt())
+    ev = float(((var.double() - var64).abs() / var64).max())
+    print('fwd_bnstats %s %s: mean %.2e, var %.2e' % (tag, prec, em, ev))
+    assert em < 2e-6 and ev < 2e-5
+
+
 # (n, cin, h, w, cout, k, stride, pad, groups): conv3 / conv2 of a bottleneck seen from their data gradient; the norm in
 # front has `cin` channels.  Last four: tile grid does not line up (odd rows), strided conv, tiny layer -> three-call fallback
 DGRAD_BN_CASES = [(8, 64, 32, 32, 256, 1, 1, 0, 1), (8, 64, 32, 32, 256, 1, 1, 0, 4), (16, 128, 16, 16, 128, 3, 1, 1, 8),

@@ -15,6 +15,8 @@
 //
 // Replaces the cuDNN conv kernels behind integral_base_modules/resnet.py:16-47,
 // deconv_head.py:24-35, physique_network.py:15-50 and torchvision's Bottleneck.
+#include <type_traits>
+
 #include "conv_shared.h"
 
 namespace xas {
@@ -1559,9 +1561,6 @@ static int dispatch_igemm(const IgemmParams& p, int prec, int Mrows_max, int pha
 
 using namespace xas;
 
-static bool wgrad_on_x6(const xas_conv_shape* s, const float* x);
-static int images_per_launch(int N, long elems_per_image_a, long elems_per_image_b);
-
 // Images per launch so that a gathered tensor stays below the 2 GiB range of the 32-bit buffer offsets (camera-batched
 // passes: the logits of 128+ images are 2.4 GB and more).  Images are independent in all three convolution passes, so
 // a larger batch is processed as several launches over image ranges (weight gradients: the later ones accumulate).
@@ -1575,6 +1574,109 @@ static int images_per_launch(int N, long elems_per_image_a, long elems_per_image
   return (int)cdiv(N, launches);                               // equal-sized ranges
 }
 
+// pass(first image, shape of the range) over ranges of `per` images
+template <class F>
+static int for_image_ranges(const xas_conv_shape* s, int per, F&& pass) {
+  for (int n0 = 0; n0 < s->N; n0 += per) {
+    xas_conv_shape part = *s;
+    part.N = s->N - n0 < per ? s->N - n0 : per;
+    if (const int rc = pass(n0, &part)) return rc;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// Routes: which kernel a pass of a shape runs on.  conv_fwd_impl / conv_dgrad_impl / conv_wgrad_impl switch on them, and
+// everything that has to know the answer without launching (xas_conv_weight_planes, xas_conv_kernel_class, the workspace
+// sizes, the tile rows of the statistics epilogues) asks the same functions - with no bias and an aligned x, which is what
+// a query assumes.
+// ------------------------------------------------------------------------------------
+// one-channel "thin" 3x3 layer: the channels of its vector side, else 0
+static int thin_channels(const xas_conv_shape* s) {
+  if (s->Cout == 1 && thin_ok(s, s->Cin)) return s->Cin;
+  if (s->Cin == 1 && thin_ok(s, s->Cout)) return s->Cout;
+  return 0;
+}
+// the detector's stem, 3 -> 64 channels 7x7 stride 2 pad 3 (its forward kernels take no bias)
+static bool is_stem(const xas_conv_shape* s) {
+  return s->Cin == 3 && s->R == 7 && s->S == 7 && s->stride == 2 && s->pad == 3 && s->Cout == ST_CO;
+}
+// MFMA tiles: whole K-steps of the gathered tensor's channels, at least 16 channels produced; else the direct kernels
+static bool mfma_ok(int c_gathered, int c_produced) { return c_gathered % BK == 0 && c_produced >= 16; }
+
+enum class FwdRoute { StemF16, StemF32, ThinVecToScalar, ThinScalarToVec, Direct, Mfma };
+static FwdRoute fwd_route(const xas_conv_shape* s, bool has_bias) {
+  // f16x3 needs max |image| (the scale of the split); without it - and under XAS_TUNE_STEM_FWD_F32 - the exact-fp32 stem kernel
+  if (is_stem(s) && !has_bias)
+    return precision_of(s) == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & XAS_TUNE_STEM_FWD_F32) ? FwdRoute::StemF16 : FwdRoute::StemF32;
+  if (thin_channels(s)) return s->Cout == 1 ? FwdRoute::ThinVecToScalar : FwdRoute::ThinScalarToVec;
+  return mfma_ok(s->Cin, s->Cout) ? FwdRoute::Mfma : FwdRoute::Direct;
+}
+
+enum class DgradRoute { ThinVecToScalar, ThinScalarToVec, Direct, Mfma };
+static DgradRoute dgrad_route(const xas_conv_shape* s) {
+  if (thin_channels(s)) return s->Cin == 1 ? DgradRoute::ThinVecToScalar : DgradRoute::ThinScalarToVec;
+  return mfma_ok(s->Cout, s->Cin) ? DgradRoute::Mfma : DgradRoute::Direct;
+}
+
+// The buffer-load weight-gradient kernels (split and exact fp32): 32-bit byte offsets (tensors below 2 GiB, incl. the pad
+// region in front of x) and at most one carry per coordinate in the per-thread pixel decode
+static bool wgrad_offsets_fit(const xas_conv_shape* s) {
+  const long xbytes = ((long)s->N * s->Hi * s->Wi + (long)s->pad * s->Wi + s->pad) * s->Cin * 4;
+  const long dybytes = (long)s->N * s->Ho * s->Wo * s->Cout * 4;
+  return xbytes < 0x7fffff00l && dybytes < 0x7fffff00l && 31 / s->Wo + 1 <= s->Ho;
+}
+
+enum class WgradKernel { Thin, Cout1, Stem, SplitTap, Split, F32Buf, F32Global };
+struct WgradRoute {
+  WgradKernel kernel;
+  int bm, bn, splits, m_per_split;     // tile (BM over Cout, BN over KK = R*S*Cin) and pixel splits; SplitTap: bm, splits, 128-pixel patches per split
+  bool vec;                            // F32Global: float4 loads of x
+};
+
+#ifndef XAS_WGRAD_XTARGET
+#define XAS_WGRAD_XTARGET 1024          // blocks per launch the pixel splits aim for.  r03 sweeps (weight gradients on a side stream, sharing the CUs): 512 best.  r05, ONE stream (the kernel has the chip to itself): 384 +3.2 ms/step, 512 +0.7, 768 +0.6, 1024 best, 1536 / 2048 +0.7, 3072 +2.2 (in-box, interleaved, 3 rounds)
+#endif
+// tile and pixel splits of the general kernels: split = wgrad_x6_kernel, else the exact-fp32 ones
+static void wgrad_plan(const xas_conv_shape* s, bool split, WgradRoute* r) {
+  const long KK = (long)s->R * s->S * s->Cin, M = (long)s->N * s->Ho * s->Wo;
+  r->bm = s->Cout >= 96 ? 128 : (s->Cout > 32 ? 64 : 32);
+  r->bn = (KK <= 64 && r->bm != 32) ? 64 : 128;
+  const long nct = cdiv(s->Cout, r->bm), tiles = nct * cdiv(KK, r->bn);
+  // ~4 blocks per CU in total, >= 8 K-steps (4 for the bf16-split kernel) per block.  These kernels run beside the main
+  // chain of the step: shorter blocks hand the CUs over sooner, but every split costs a slab of dW to write and to reduce;
+  // with the round-3 kernels the slab traffic weighs more (sweeps in the define above)
+  long sp = cdiv(split ? XAS_WGRAD_XTARGET : 1024, tiles);
+  const long maxsp = M / (split ? 128 : 256);
+  if (sp > maxsp) sp = maxsp;
+  if (sp < 1) sp = 1;
+  if (split && sp >= 8) sp -= sp % 8;              // bf16-split kernel: whole pixel splits per XCD (wgrad_x6_kernel)
+  else if (split || !(g_tune & XAS_TUNE_WGRAD_ALT_ORDER))   // XCD-grouped order: (splits x Cout tiles) groups, 8 XCDs -> keep them balanced
+    while (sp > 1 && (sp * nct) % 8 != 0 && (sp * nct) > 8) --sp;
+  const long per = cdiv(cdiv(M, sp), WBK) * WBK;
+  r->m_per_split = (int)per;
+  r->splits = (int)cdiv(M, per);
+}
+
+static WgradRoute wgrad_route(const xas_conv_shape* s, bool x_aligned) {
+  if (thin_channels(s)) return {WgradKernel::Thin};
+  if (s->Cout == 1) return {WgradKernel::Cout1};
+  if (stem_wgrad_ok(s) && !(g_tune & XAS_TUNE_NO_STEM_WGRAD)) return {WgradKernel::Stem};   // (the flag: the general kernel)
+  // buffer loads unless the offsets do not fit or XAS_TUNE_WGRAD_GLOBAL_LOAD forces the old kernel; the split kernels
+  // need them, whole float4s inside one filter tap and 16 output channels
+  WgradRoute r{};
+  r.vec = x_aligned && s->Cin % 4 == 0;
+  const bool buf = r.vec && wgrad_offsets_fit(s) && !(g_tune & XAS_TUNE_WGRAD_GLOBAL_LOAD);
+  if (buf && precision_of(s) != XAS_PREC_F32 && s->Cout % 4 == 0 && s->Cout >= 16) {
+    if (!(g_tune & XAS_TUNE_GENERAL_KERNELS) && wgrad_x6t_plan(s, &r.bm, &r.splits, &r.m_per_split)) r.kernel = WgradKernel::SplitTap;   // (the flag: no tap re-use kernels)
+    else { r.kernel = WgradKernel::Split; wgrad_plan(s, true, &r); }
+  } else {
+    r.kernel = buf && s->Cin % 32 == 0 ? WgradKernel::F32Buf : WgradKernel::F32Global;
+    wgrad_plan(s, false, &r);
+  }
+  return r;
+}
+
 extern "C" int xas_set_tuning(int flags) { g_tune = flags; return 0; }
 extern "C" int xas_set_precision(int mode) {
   XAS_REQUIRE(mode >= 0 && mode <= 3, "set_precision: 0 = exact fp32 MFMA, 1 = bf16 MFMA (not fp32 accurate), 2 = bf16x6 (fp32-accurate, no "
@@ -1583,9 +1685,6 @@ extern "C" int xas_set_precision(int mode) {
   return 0;
 }
 extern "C" int xas_get_precision(void) { return g_precision; }
-
-static int conv_fwd_impl(const float* x, const float* w_packed, const float* bias, float* y, const xas_conv_shape* s,
-                         void* stream, float* stat_partial, const float* stat_pivot, float* head_partial = nullptr);
 
 namespace xas {
 __global__ void stem_overflow_peek_kernel(unsigned* out) { if (g_f16_weight_overflow_stem) atomicOr(out, 1u); }
@@ -1605,96 +1704,94 @@ int stem_weight_overflow(int reset) {
 }
 }  // namespace xas
 
-extern "C" int xas_conv_fwd(const float* x, const float* w_packed, const float* bias, float* y,
-                            const xas_conv_shape* s, void* stream) {
-  return conv_fwd_impl(x, w_packed, bias, y, s, stream, nullptr, nullptr);
+// The forward problem of `s` as the implicit-GEMM launchers see it; the buffers are the caller's to fill in.
+static IgemmParams fwd_problem(const xas_conv_shape* s) {
+  IgemmParams p{};
+  p.N = s->N; p.a_amax = s->grad_amax;
+  p.Hs = s->Hi; p.Ws = s->Wi; p.Cs = s->Cin; p.Hd = s->Ho; p.Wd = s->Wo; p.Cd = s->Cout;
+  p.R = s->R; p.S = s->S; p.stride = s->stride; p.pad = s->pad; p.Hrow = s->Ho; p.Wrow = s->Wo; p.tune = g_tune;
+  p.div_hw.init((unsigned)(s->Ho * s->Wo)); p.div_w.init((unsigned)s->Wo);
+  p.src_elems = (long)p.N * p.Hs * p.Ws * p.Cs; p.wgt_elems = (long)p.Cd * p.R * p.S * p.Cs;
+  return p;
 }
 
 // Rows per tile when the forward pass of `s` can emit batch-norm partial sums for `groups` camera groups (MFMA path, one
-// launch, no tile straddles a group), else 0.
+// launch, no tile straddles a group), else 0.  The tile is the one the launch will run on: pick_tile_x6 / pick_tile.
 static int fwd_stats_tile_rows(const xas_conv_shape* s, int groups) {
   if (!s || groups < 1) return 0;
-  if (s->Cin % BK != 0 || s->Cout < 16 || s->Cout % 4 != 0) return 0;
-  if (s->Cin == 3 || (s->Cout == 1 && thin_ok(s, s->Cin)) || (s->Cin == 1 && thin_ok(s, s->Cout))) return 0;
+  if (fwd_route(s, false) != FwdRoute::Mfma || s->Cout % 4 != 0) return 0;
   if (images_per_launch(s->N, (long)s->Hi * s->Wi * s->Cin, 0) < s->N || s->N % groups) return 0;
   const long M = (long)s->N * s->Ho * s->Wo, Mg = M / groups;
+  const int prec = precision_of(s);
   int bm, bn;
-  pick_tile(s->Cout, M, 1, &bm, &bn);
-  // the bf16-split kernels use 64 x 256 tiles for wide layers, unless the tap re-use kernel (128-row patches) takes the shape
-  const bool x6 = precision_of(s) != XAS_PREC_F32;
-  const bool tap = x6 && bm == 128 && !(g_tune & XAS_TUNE_GENERAL_KERNELS) &&
-                   tap_tile_ok(s->R, s->S, s->stride, s->pad, s->Hi, s->Wi, s->Ho, s->Wo, s->Cin, s->N);
-  if (x6 && !tap && !(g_tune & XAS_TUNE_NO_WIDE_TILES)) pick_tile(s->Cout, M, 1, &bm, &bn, true);
+  if (prec == XAS_PREC_F32) pick_tile(s->Cout, M, 1, &bm, &bn);
+  else bm = pick_tile_x6(fwd_problem(s), 0, (int)M, 1, planes_of(prec, 0, has_amax_for(s, 0))).bm;
   if (Mg % bm) return 0;
   if ((M / bm) * 2 * (long)s->Cout * 4 >= 0x7fffff00l) return 0;
   return bm;
 }
 
+static int launch_thin(bool vec_to_scalar, const xas_conv_shape* s, const float* src, const float* w, const float* bias,
+                       float* out, int flip, hipStream_t st) {
+  const int C = thin_channels(s);
+  const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, C, s->pad, flip);
+  const dim3 grid(thin_grid((long)s->N * s->Hi * s->Wi, C));
+  if (vec_to_scalar) hipLaunchKernelGGL(thin_vec2scalar_kernel, grid, dim3(256), 0, st, src, w, bias, out, tp);
+  else hipLaunchKernelGGL(thin_scalar2vec_kernel, grid, dim3(256), 0, st, src, w, bias, out, tp);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
 static int conv_fwd_impl(const float* x, const float* w_packed, const float* bias, float* y, const xas_conv_shape* s,
-                         void* stream, float* stat_partial, const float* stat_pivot, float* head_partial) {
+                         void* stream, float* stat_partial, const float* stat_pivot, float* head_partial = nullptr) {
   if (check_shape(s, "conv_fwd") || check_fwd_dims(s, "conv_fwd")) return 1;
   XAS_REQUIRE(x && w_packed && y, "conv_fwd: null buffer");
-  {
-    const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
-    const int per = images_per_launch(s->N, xi, 0);
-    if (per < s->N) {
-      XAS_REQUIRE(!stat_partial, "conv_fwd: the statistics epilogue needs a single launch");
-      for (int n0 = 0; n0 < s->N; n0 += per) {
-        xas_conv_shape part = *s;
-        part.N = s->N - n0 < per ? s->N - n0 : per;
-        // (head partial records: [image][Ho * Wo / 64][Cout / 64][67] - the image range of this launch)
-        float* hp = head_partial ? head_partial + (size_t)n0 * (s->Ho * s->Wo / 64) * (s->Cout / 64) * 67 : nullptr;
-        const int rc = conv_fwd_impl(x + (size_t)n0 * xi, w_packed, bias, y + (size_t)n0 * yi, &part, stream, nullptr, nullptr, hp);
-        if (rc) return rc;
-      }
-      return 0;
-    }
+  const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
+  const int per = images_per_launch(s->N, xi, 0);
+  if (per < s->N) {
+    XAS_REQUIRE(!stat_partial, "conv_fwd: the statistics epilogue needs a single launch");
+    return for_image_ranges(s, per, [&](int n0, const xas_conv_shape* part) {
+      // (head partial records: [image][Ho * Wo / 64][Cout / 64][67] - the image range of this launch)
+      float* hp = head_partial ? head_partial + (size_t)n0 * (s->Ho * s->Wo / 64) * (s->Cout / 64) * 67 : nullptr;
+      return conv_fwd_impl(x + (size_t)n0 * xi, w_packed, bias, y + (size_t)n0 * yi, part, stream, nullptr, nullptr, hp);
+    });
   }
   hipStream_t st = as_stream(stream);
-  if (s->Cin == 3 && s->R == 7 && s->S == 7 && s->stride == 2 && s->pad == 3 && s->Cout == ST_CO && bias == nullptr) {
-    const int tiles = (int)(cdiv(s->Ho, ST_TH) * cdiv(s->Wo, ST_TW));
-    // f16x3 needs max |image| (the scale of the split); without it - and under XAS_TUNE_STEM_FWD_F32 - the exact-fp32 stem kernel
-    if (precision_of(s) == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & XAS_TUNE_STEM_FWD_F32))
-      hipLaunchKernelGGL(stem_fwd_f16_kernel, dim3((unsigned)cdiv(tiles, STH_TPB), s->N), dim3(256), 0, st, x, w_packed, y, s->N, s->Hi,
-                         s->Wi, s->Ho, s->Wo, s->grad_amax);
-    else
-    hipLaunchKernelGGL(stem_fwd_kernel, dim3((unsigned)cdiv(tiles, ST_TPB), s->N), dim3(256), 0, st, x, w_packed, y, s->N, s->Hi,
-                       s->Wi, s->Ho, s->Wo);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s->Cout == 1 && thin_ok(s, s->Cin)) {
-    const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, s->Cin, s->pad, 0);
-    const long M = (long)s->N * s->Hi * s->Wi;
-    hipLaunchKernelGGL(thin_vec2scalar_kernel, dim3(thin_grid(M, s->Cin)), dim3(256), 0, st, x, w_packed, bias, y, tp);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s->Cin == 1 && thin_ok(s, s->Cout)) {
-    const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, s->Cout, s->pad, 0);
-    const long M = (long)s->N * s->Hi * s->Wi;
-    hipLaunchKernelGGL(thin_scalar2vec_kernel, dim3(thin_grid(M, s->Cout)), dim3(256), 0, st, x, w_packed,
-                       bias, y, tp);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s->Cin % BK != 0 || s->Cout < 16) {
-    const long total = (long)s->N * s->Ho * s->Wo * s->Cout;
-    hipLaunchKernelGGL(direct_fwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, x, w_packed, bias, y, *s);
-    XAS_LAUNCH_CHECK();
-    return 0;
+  const FwdRoute route = fwd_route(s, bias != nullptr);
+  switch (route) {
+    case FwdRoute::StemF16:
+    case FwdRoute::StemF32: {
+      const int tiles = (int)(cdiv(s->Ho, ST_TH) * cdiv(s->Wo, ST_TW));
+      if (route == FwdRoute::StemF16)
+        hipLaunchKernelGGL(stem_fwd_f16_kernel, dim3((unsigned)cdiv(tiles, STH_TPB), s->N), dim3(256), 0, st, x, w_packed, y, s->N, s->Hi,
+                           s->Wi, s->Ho, s->Wo, s->grad_amax);
+      else
+        hipLaunchKernelGGL(stem_fwd_kernel, dim3((unsigned)cdiv(tiles, ST_TPB), s->N), dim3(256), 0, st, x, w_packed, y, s->N, s->Hi,
+                           s->Wi, s->Ho, s->Wo);
+      XAS_LAUNCH_CHECK();
+      return 0;
+    }
+    case FwdRoute::ThinVecToScalar: return launch_thin(true, s, x, w_packed, bias, y, 0, st);
+    case FwdRoute::ThinScalarToVec: return launch_thin(false, s, x, w_packed, bias, y, 0, st);
+    case FwdRoute::Direct: {
+      const long total = (long)s->N * s->Ho * s->Wo * s->Cout;
+      hipLaunchKernelGGL(direct_fwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, x, w_packed, bias, y, *s);
+      XAS_LAUNCH_CHECK();
+      return 0;
+    }
+    case FwdRoute::Mfma: break;
   }
   XAS_REQUIRE((((uintptr_t)x | (uintptr_t)w_packed) & 15) == 0, "conv_fwd: operands must be 16-byte aligned");
-  IgemmParams p{};
-  p.src = x; p.wgt = w_packed; p.bias = bias; p.out = y; p.N = s->N;
-  p.a_amax = s->grad_amax;
-  p.Hs = s->Hi; p.Ws = s->Wi; p.Cs = s->Cin; p.Hd = s->Ho; p.Wd = s->Wo; p.Cd = s->Cout;
-  p.R = s->R; p.S = s->S; p.stride = s->stride; p.pad = s->pad; p.Hrow = s->Ho; p.Wrow = s->Wo; p.tune = g_tune;
-  p.div_hw.init((unsigned)(s->Ho * s->Wo)); p.div_w.init((unsigned)s->Wo);
-  p.src_elems = (long)p.N * p.Hs * p.Ws * p.Cs; p.wgt_elems = (long)p.Cd * p.R * p.S * p.Cs;
+  IgemmParams p = fwd_problem(s);
+  p.src = x; p.wgt = w_packed; p.bias = bias; p.out = y;
   p.stat_partial = stat_partial; p.stat_pivot = stat_pivot;
   p.head_partial = head_partial;
   return dispatch_igemm<0>(p, precision_of(s), s->N * s->Ho * s->Wo, 1, st);
+}
+
+extern "C" int xas_conv_fwd(const float* x, const float* w_packed, const float* bias, float* y,
+                            const xas_conv_shape* s, void* stream) {
+  return conv_fwd_impl(x, w_packed, bias, y, s, stream, nullptr, nullptr);
 }
 
 // Final 1x1 convolution of the detector + the soft-argmax head's pass over its result (forward
@@ -1705,7 +1802,7 @@ static int conv_fwd_impl(const float* x, const float* w_packed, const float* bia
 extern "C" int xas_conv_fwd_head_chunks(const xas_conv_shape* s, int K, int D) {
   if (!s || K < 1 || D != 64) return 0;
   if (s->R != 1 || s->S != 1 || s->stride != 1 || s->pad != 0 || s->Wo != 64 || (s->Ho * s->Wo) % 64 != 0) return 0;
-  if (s->Cout != K * D || s->Cin % BK != 0 || precision_of(s) == XAS_PREC_F32) return 0;
+  if (s->Cout != K * D || fwd_route(s, false) != FwdRoute::Mfma || precision_of(s) == XAS_PREC_F32) return 0;
   return s->Ho * s->Wo / 64;
 }
 
@@ -1723,10 +1820,7 @@ extern "C" int xas_conv_weight_planes(const xas_conv_shape* s, int pass) {
   if (!s) return 0;
   const int prec = precision_of(s);
   if (prec == XAS_PREC_F32) return 0;
-  const bool thin = (s->Cout == 1 && thin_ok(s, s->Cin)) || (s->Cin == 1 && thin_ok(s, s->Cout));
-  bool mfma;
-  if (pass == 0) mfma = !thin && !(s->Cin == 3 && s->R == 7) && s->Cin % BK == 0 && s->Cout >= 16;
-  else mfma = !thin && s->Cout % BK == 0 && s->Cin >= 16;
+  const bool mfma = pass == 0 ? fwd_route(s, false) == FwdRoute::Mfma : dgrad_route(s) == DgradRoute::Mfma;
   return mfma ? planes_of(prec, pass, has_amax_for(s, pass)) : 0;
 }
 
@@ -1737,31 +1831,31 @@ extern "C" int xas_conv_kernel_class(const xas_conv_shape* s, int pass) {
   if (!s) return 0;
   const int prec = precision_of(s);
   const int split = prec == XAS_PREC_F32 ? 1 : (prec == XAS_PREC_BF16 ? 2 : (planes_of(prec, pass, has_amax_for(s, pass)) == 2 ? 4 : 3));
-  const bool thin = (s->Cout == 1 && thin_ok(s, s->Cin)) || (s->Cin == 1 && thin_ok(s, s->Cout));
-  if (thin) return 0;
   if (pass == 0) {
-    if (s->Cin == 3 && s->R == 7 && s->S == 7 && s->stride == 2 && s->pad == 3 && s->Cout == ST_CO)              // stem kernels
-      return (prec == XAS_PREC_F16X3 && s->grad_amax && !(g_tune & XAS_TUNE_STEM_FWD_F32)) ? 4 : 1;
-    return (s->Cin % BK == 0 && s->Cout >= 16) ? split : 0;
+    const FwdRoute f = fwd_route(s, false);
+    return f == FwdRoute::StemF16 ? 4 : f == FwdRoute::StemF32 ? 1 : f == FwdRoute::Mfma ? split : 0;
   }
-  if (pass == 1) return (s->Cout % BK == 0 && s->Cin >= 16) ? split : 0;
-  if (s->Cout == 1) return 0;
+  if (pass == 1) return dgrad_route(s) == DgradRoute::Mfma ? split : 0;
   xas_conv_shape part = *s;          // tensors beyond the 32-bit offset range run as several launches over image ranges
   part.N = images_per_launch(s->N, (long)s->Hi * s->Wi * s->Cin, (long)s->Ho * s->Wo * s->Cout);
-  return wgrad_on_x6(&part, nullptr) ? split : 1;
+  const WgradKernel k = wgrad_route(&part, true).kernel;
+  if (k == WgradKernel::Thin || k == WgradKernel::Cout1) return 0;
+  return (k == WgradKernel::SplitTap || k == WgradKernel::Split) ? split : 1;   // 1: the stem kernel and the general exact-fp32 kernels
 }
 
 // Convolution (no bias) + the training-mode batch-norm statistics of its result.  When the tile grid lines up with the
 // camera groups the statistics come out of the convolution's epilogue (per-tile partial sums, reduced by
 // xas_bn_stats_from_partials); otherwise the result is read once more by xas_bn_stats.  Same outputs either way (up to
 // the order of the fp32 partial sums).
+// workspace of a convolution + norm reduction over M rows of C channels: per-tile partial sums and their reduction when the
+// epilogue takes it (bm rows per tile), else (bm = 0) the separate pass over the result
+static size_t epilogue_workspace_floats(long M, int C, int groups, int bm) {
+  if (!bm) return xas_bn_workspace_floats(M, C, groups);
+  return (size_t)(M / bm) * 2 * C + xas_bn_workspace_floats(M / bm, 2 * C, groups);
+}
 extern "C" size_t xas_conv_fwd_bnstats_workspace_floats(const xas_conv_shape* s, int groups) {
   if (!s || groups < 1) return 0;
-  const long M = (long)s->N * s->Ho * s->Wo;
-  const int bm = fwd_stats_tile_rows(s, groups);
-  if (!bm) return xas_bn_workspace_floats(M, s->Cout, groups);
-  const long rows = M / bm;
-  return (size_t)rows * 2 * s->Cout + xas_bn_workspace_floats(rows, 2 * s->Cout, groups);
+  return epilogue_workspace_floats((long)s->N * s->Ho * s->Wo, s->Cout, groups, fwd_stats_tile_rows(s, groups));
 }
 
 extern "C" int xas_conv_fwd_bnstats(const float* x, const float* w_packed, float* y, const xas_conv_shape* s, int groups,
@@ -1787,69 +1881,35 @@ extern "C" int xas_conv_fwd_bnstats(const float* x, const float* w_packed, float
 
 static int conv_dgrad_impl(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s, void* stream,
                            int accumulate, const float* acc_src = nullptr, const unsigned char* acc_mask = nullptr,
-                           const IgemmParams* bnb = nullptr);
-
-extern "C" int xas_conv_dgrad(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
-                              void* stream) {
-  return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 0);
-}
-
-extern "C" int xas_conv_dgrad_acc(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
-                                  void* stream) {
-  return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 1);
-}
-
-extern "C" int xas_conv_dgrad_acc_masked(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
-                                         const float* dprev, const uint8_t* mask, void* stream) {
-  XAS_REQUIRE(dprev && mask, "conv_dgrad_acc_masked: null buffer");
-  return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 2, dprev, mask);
-}
-
-static int conv_dgrad_impl(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s, void* stream,
-                           int accumulate, const float* acc_src, const unsigned char* acc_mask, const IgemmParams* bnb) {
+                           const IgemmParams* bnb = nullptr) {
   if (check_shape(s, "conv_dgrad")) return 1;
-  XAS_REQUIRE(!accumulate || (s->Cout % BK == 0 && s->Cin >= 16 && s->Cin % 4 == 0 && !(s->Cin == 1 || s->Cout == 1)),
+  const DgradRoute route = dgrad_route(s);
+  XAS_REQUIRE(!accumulate || (route == DgradRoute::Mfma && s->Cin % 4 == 0),
               "conv_dgrad_acc: only the MFMA path accumulates (Cout %% 32 == 0, Cin %% 4 == 0, Cin >= 16)");
   XAS_REQUIRE(dy && w_packed_t && dx, "conv_dgrad: null buffer");
   // valid for the conv (Hi -> Ho) and for ConvTranspose2d forward (Ho given, Hi = (Ho-1)*stride - 2*pad + R)
   XAS_REQUIRE((s->Ho - 1) * s->stride - 2 * s->pad + s->R <= s->Hi && (s->Wo - 1) * s->stride - 2 * s->pad + s->S <= s->Wi,
               "conv_dgrad: Hi/Wi (%d,%d) too small for Ho/Wo (%d,%d)", s->Hi, s->Wi, s->Ho, s->Wo);
-  {
-    const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
-    const int per = images_per_launch(s->N, yi, 0);
-    if (per < s->N) {
-      XAS_REQUIRE(!bnb, "conv_dgrad: the batch-norm epilogue needs a single launch");
-      for (int n0 = 0; n0 < s->N; n0 += per) {
-        xas_conv_shape part = *s;
-        part.N = s->N - n0 < per ? s->N - n0 : per;
-        const int rc = conv_dgrad_impl(dy + (size_t)n0 * yi, w_packed_t, dx + (size_t)n0 * xi, &part, stream, accumulate,
-                                       acc_src ? acc_src + (size_t)n0 * xi : nullptr, acc_mask ? acc_mask + (size_t)n0 * xi / 4 : nullptr);
-        if (rc) return rc;
-      }
-      return 0;
-    }
+  const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
+  const int per = images_per_launch(s->N, yi, 0);
+  if (per < s->N) {
+    XAS_REQUIRE(!bnb, "conv_dgrad: the batch-norm epilogue needs a single launch");
+    return for_image_ranges(s, per, [&](int n0, const xas_conv_shape* part) {
+      return conv_dgrad_impl(dy + (size_t)n0 * yi, w_packed_t, dx + (size_t)n0 * xi, part, stream, accumulate,
+                             acc_src ? acc_src + (size_t)n0 * xi : nullptr, acc_mask ? acc_mask + (size_t)n0 * xi / 4 : nullptr);
+    });
   }
   hipStream_t st = as_stream(stream);
-  if (s->Cin == 1 && thin_ok(s, s->Cout)) {          // dx[m] = sum dy[src] . wt[0][tap][:]
-    const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, s->Cout, s->pad, 1);
-    const long M = (long)s->N * s->Hi * s->Wi;
-    hipLaunchKernelGGL(thin_vec2scalar_kernel, dim3(thin_grid(M, s->Cout)), dim3(256), 0, st, dy, w_packed_t, nullptr, dx, tp);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s->Cout == 1 && thin_ok(s, s->Cin)) {          // dx[m][ci] = sum dy[src] * wt[ci][tap]
-    const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, s->Cin, s->pad, 1);
-    const long M = (long)s->N * s->Hi * s->Wi;
-    hipLaunchKernelGGL(thin_scalar2vec_kernel, dim3(thin_grid(M, s->Cin)), dim3(256), 0, st, dy,
-                       w_packed_t, nullptr, dx, tp);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s->Cout % BK != 0 || s->Cin < 16) {
-    const long total = (long)s->N * s->Hi * s->Wi * s->Cin;
-    hipLaunchKernelGGL(direct_dgrad_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, dy, w_packed_t, dx, *s);
-    XAS_LAUNCH_CHECK();
-    return 0;
+  switch (route) {
+    case DgradRoute::ThinVecToScalar: return launch_thin(true, s, dy, w_packed_t, nullptr, dx, 1, st);    // dx[m] = sum dy[src] . wt[0][tap][:]
+    case DgradRoute::ThinScalarToVec: return launch_thin(false, s, dy, w_packed_t, nullptr, dx, 1, st);   // dx[m][ci] = sum dy[src] * wt[ci][tap]
+    case DgradRoute::Direct: {
+      const long total = (long)s->N * s->Hi * s->Wi * s->Cin;
+      hipLaunchKernelGGL(direct_dgrad_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, dy, w_packed_t, dx, *s);
+      XAS_LAUNCH_CHECK();
+      return 0;
+    }
+    case DgradRoute::Mfma: break;
   }
   XAS_REQUIRE((((uintptr_t)dy | (uintptr_t)w_packed_t) & 15) == 0, "conv_dgrad: operands must be 16-byte aligned");
   IgemmParams p{};
@@ -1868,11 +1928,27 @@ static int conv_dgrad_impl(const float* dy, const float* w_packed_t, float* dx, 
   return dispatch_igemm<1>(p, precision_of(s), s->N * Hp * Wp, s->stride * s->stride, st);
 }
 
+extern "C" int xas_conv_dgrad(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
+                              void* stream) {
+  return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 0);
+}
+
+extern "C" int xas_conv_dgrad_acc(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
+                                  void* stream) {
+  return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 1);
+}
+
+extern "C" int xas_conv_dgrad_acc_masked(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
+                                         const float* dprev, const uint8_t* mask, void* stream) {
+  XAS_REQUIRE(dprev && mask, "conv_dgrad_acc_masked: null buffer");
+  return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 2, dprev, mask);
+}
+
 // Rows per tile when the data gradient of `s` can carry the batch-norm backward reduction of the layer in front of the
 // convolution in its epilogue (MFMA path, stride 1, one launch, full tiles that do not straddle a camera group), else 0.
 static int dgrad_bnb_tile_rows(const xas_conv_shape* s, int groups) {
   if (!s || groups < 1 || s->stride != 1) return 0;
-  if (s->Cout % BK != 0 || s->Cin < 16 || s->Cin % 4 != 0 || s->Cin == 1 || s->Cout == 1) return 0;
+  if (dgrad_route(s) != DgradRoute::Mfma || s->Cin % 4 != 0) return 0;
   if (images_per_launch(s->N, (long)s->Ho * s->Wo * s->Cout, 0) < s->N || s->N % groups) return 0;
   const long M = (long)s->N * s->Hi * s->Wi, Mg = M / groups;
   int bm, bn;
@@ -1889,11 +1965,7 @@ static int dgrad_bnb_tile_rows(const xas_conv_shape* s, int groups) {
 // the convolution's epilogue (dz is never re-read for them); otherwise xas_conv_dgrad + xas_bn_bwd_reduce.
 extern "C" size_t xas_conv_dgrad_bn_bwd_workspace_floats(const xas_conv_shape* s, int groups) {
   if (!s || groups < 1) return 0;
-  const long M = (long)s->N * s->Hi * s->Wi;
-  const int bm = dgrad_bnb_tile_rows(s, groups);
-  if (!bm) return xas_bn_workspace_floats(M, s->Cin, groups);
-  const long rows = M / bm;
-  return (size_t)rows * 2 * s->Cin + xas_bn_workspace_floats(rows, 2 * s->Cin, groups);
+  return epilogue_workspace_floats((long)s->N * s->Hi * s->Wi, s->Cin, groups, dgrad_bnb_tile_rows(s, groups));
 }
 
 extern "C" int xas_conv_dgrad_bn_bwd(const float* dy, const float* w_packed_t, const xas_conv_shape* s, const float* xb,
@@ -1938,64 +2010,22 @@ extern "C" int xas_conv_dgrad_bn_bwd(const float* dy, const float* w_packed_t, c
 #endif
 static inline unsigned slab_threads() { return XAS_SLAB_THREADS; }
 
-// does the weight gradient of this shape run on the bf16-split kernel (conv_x6.hip)?  32-bit byte offsets (tensors below
-// 2 GiB), whole float4s inside one filter tap, at most one carry per coordinate in the per-thread pixel decode
-static bool wgrad_on_x6(const xas_conv_shape* s, const float* x) {
-  if (precision_of(s) == XAS_PREC_F32 || (g_tune & XAS_TUNE_WGRAD_GLOBAL_LOAD)) return false;
-  const long xbytes = ((long)s->N * s->Hi * s->Wi + (long)s->pad * s->Wi + s->pad) * s->Cin * 4;
-  const long dybytes = (long)s->N * s->Ho * s->Wo * s->Cout * 4;
-  return s->Cin % 4 == 0 && s->Cout % 4 == 0 && s->Cout >= 16 && (x == nullptr || ((uintptr_t)x & 15) == 0) &&
-         xbytes < 0x7fffff00l && dybytes < 0x7fffff00l && 31 / s->Wo + 1 <= s->Ho;
-}
-
-static void wgrad_plan(const xas_conv_shape* s, bool x6, int* bm, int* bn, int* splits, int* mps) {
-  const long KK = (long)s->R * s->S * s->Cin, M = (long)s->N * s->Ho * s->Wo;
-  if (x6) wgrad_x6_tile(s->Cout, KK, bm, bn);
-  else {
-    *bm = s->Cout >= 96 ? 128 : (s->Cout > 32 ? 64 : 32);
-    *bn = KK <= 64 ? 64 : 128;
-    if (*bm == 32) *bn = 128;
-  }
-  const long tiles = cdiv(s->Cout, *bm) * cdiv(KK, *bn);
-  // ~4 blocks per CU in total, >= 8 K-steps (4 for the bf16-split kernel) per block.  These kernels run beside the main
-  // chain of the step: shorter blocks hand the CUs over sooner, but every split costs a slab of dW to write and to reduce;
-  // with the round-3 kernels the slab traffic weighs more (sweeps in the define below)
-#ifndef XAS_WGRAD_XTARGET
-#define XAS_WGRAD_XTARGET 1024          // blocks per launch the pixel splits aim for.  r03 sweeps (weight gradients on a side stream, sharing the CUs): 512 best.  r05, ONE stream (the kernel has the chip to itself): 384 +3.2 ms/step, 512 +0.7, 768 +0.6, 1024 best, 1536 / 2048 +0.7, 3072 +2.2 (in-box, interleaved, 3 rounds)
-#endif
-  const int xtarget = XAS_WGRAD_XTARGET;
-  long sp = cdiv(x6 ? xtarget : 1024, tiles);
-  const long maxsp = x6 ? (M / 128 > 0 ? M / 128 : 1) : (M / 256 > 0 ? M / 256 : 1);
-  if (sp > maxsp) sp = maxsp;
-  if (sp < 1) sp = 1;
-  if (x6 && sp >= 8) sp -= sp % 8;                 // bf16-split kernel: whole pixel splits per XCD (wgrad_x6_kernel)
-  else if (x6 || !(g_tune & XAS_TUNE_WGRAD_ALT_ORDER)) {   // XCD-grouped order: (splits x Cout tiles) groups, 8 XCDs -> keep them balanced
-    const long nct = cdiv(s->Cout, *bm);
-    while (sp > 1 && (sp * nct) % 8 != 0 && (sp * nct) > 8) --sp;
-  }
-  long per = cdiv(M, sp);
-  per = cdiv(per, WBK) * WBK;
-  *mps = (int)per;
-  *splits = (int)cdiv(M, per);
-}
-
 constexpr int kCout1Chunk = 2048;
 
 extern "C" size_t xas_conv_wgrad_workspace_floats(const xas_conv_shape* s) {
   if (!s) return 0;
-  if ((s->Cout == 1 && thin_ok(s, s->Cin)) || (s->Cin == 1 && thin_ok(s, s->Cout))) {
-    const long C = s->Cout == 1 ? s->Cin : s->Cout;
-    return (size_t)(cdiv((long)s->N * s->Hi * s->Wi, kThinChunk) + 1) * C * 9;
-  }
-  if (s->Cout == 1) return (size_t)cdiv((long)s->N * s->Ho * s->Wo, kCout1Chunk) * s->R * s->S * s->Cin;
-  if (stem_wgrad_ok(s)) return (size_t)2 * kStemWgradBlocks * ST_CO * ST_K;
-  int bm, bn, sp, mps, sp2;
-  wgrad_plan(s, false, &bm, &bn, &sp, &mps);       // the largest of the kernels' slab counts: the choice between them
-  wgrad_plan(s, true, &bm, &bn, &sp2, &mps);       // also depends on the alignment of x, unknown here
-  int sp3 = 0, pps = 0;
-  if (!wgrad_x6t_plan(s->N, s->Hi, s->Wi, s->Cin, s->Cout, s->R, s->S, s->stride, s->pad, s->Ho, s->Wo, &bm, &sp3, &pps)) sp3 = 0;
-  if (sp2 > sp) sp = sp2;
-  if (sp3 > sp) sp = sp3;
+  const WgradKernel k = wgrad_route(s, true).kernel;
+  if (k == WgradKernel::Thin) return (size_t)(cdiv((long)s->N * s->Hi * s->Wi, kThinChunk) + 1) * thin_channels(s) * 9;
+  if (k == WgradKernel::Cout1) return (size_t)cdiv((long)s->N * s->Ho * s->Wo, kCout1Chunk) * s->R * s->S * s->Cin;
+  if (stem_wgrad_ok(s)) return (size_t)2 * kStemWgradBlocks * ST_CO * ST_K;   // under XAS_TUNE_NO_STEM_WGRAD too: one size serves both settings
+  // the largest of the general kernels' slab counts: the choice between them also depends on the alignment of x, unknown
+  // here (the tap re-use plan: 0 splits when it does not take the shape)
+  WgradRoute f32{}, split{}, tap{};
+  wgrad_plan(s, false, &f32);
+  wgrad_plan(s, true, &split);
+  wgrad_x6t_plan(s, &tap.bm, &tap.splits, &tap.m_per_split);
+  int sp = f32.splits > split.splits ? f32.splits : split.splits;
+  if (tap.splits > sp) sp = tap.splits;
   return (size_t)sp * s->Cout * s->R * s->S * s->Cin;
 }
 
@@ -2054,8 +2084,118 @@ static int launch_wgrad_buf(const WgradParams& p, int splits, hipStream_t st) {
   return 1;
 }
 
-static int conv_wgrad_impl(const float* x, const float* dy, float* dw_out, float* workspace, const xas_conv_shape* s,
-                           void* stream, bool oihw, bool accumulate = false);
+// (bm, bn) of wgrad_plan -> f(BM, BN) as integral constants: the one tile ladder of the two exact-fp32 launchers
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F>
+static int with_wgrad_tile(int bm, int bn, F&& f) {
+  if (bm == 32) return f(IntC<32>(), IntC<128>());
+  if (bn == 64) return bm == 128 ? f(IntC<128>(), IntC<64>()) : f(IntC<64>(), IntC<64>());
+  return bm == 128 ? f(IntC<128>(), IntC<128>()) : f(IntC<64>(), IntC<128>());
+}
+
+static int conv_wgrad_impl(const float* x, const float* dy, float* dw_packed, float* workspace, const xas_conv_shape* s,
+                           void* stream, bool oihw, bool accumulate = false) {
+  const int rflag = (oihw ? 1 : 0) | (accumulate ? 2 : 0);
+  if (check_shape(s, "conv_wgrad")) return 1;
+  XAS_REQUIRE(x && dy && dw_packed && workspace, "conv_wgrad: null buffer");
+  XAS_REQUIRE(s->Cout % 4 == 0 || s->Cout == 1, "conv_wgrad: Cout=%d must be a multiple of 4 (or 1)", s->Cout);
+  const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
+  const int per = images_per_launch(s->N, xi, yi);
+  if (per < s->N && (oihw || accumulate))              // the packed single-slab form (linear layers) is never this large
+    return for_image_ranges(s, per, [&](int n0, const xas_conv_shape* part) {      // the later ranges accumulate
+      return conv_wgrad_impl(x + (size_t)n0 * xi, dy + (size_t)n0 * yi, dw_packed, workspace, part, stream, oihw, accumulate || n0 > 0);
+    });
+  hipStream_t st = as_stream(stream);
+  const WgradRoute r = wgrad_route(s, ((uintptr_t)x & 15) == 0);
+  switch (r.kernel) {
+    case WgradKernel::Thin: {
+      // slabs [chunk][c][tap] == OIHW order for both cases ([1][Cin][3][3] resp. [Cout][1][3][3]); the packed
+      // layouts are [1][tap][c] resp. [c][tap]
+      const bool cout1 = s->Cout == 1;
+      const int C = cout1 ? s->Cin : s->Cout;
+      const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, C, s->pad, 0);
+      const long M = (long)s->N * s->Hi * s->Wi;
+      // ~4 blocks per CU at most: long chunks amortise the block-level reduction (the workspace is sized for kThinChunk)
+      int chunks = (int)cdiv(M, kThinChunk);
+      if (chunks > 1024) chunks = 1024;
+      const int per_chunk = (int)(cdiv(cdiv(M, chunks), 256) * 256);
+      chunks = (int)cdiv(M, per_chunk);
+      hipLaunchKernelGGL(thin_wgrad_kernel, dim3(chunks), dim3(256), 0, st, cout1 ? dy : x, cout1 ? x : dy, workspace, tp,
+                         cout1 ? -1 : 1, per_chunk);
+      XAS_LAUNCH_CHECK();
+      const long n = (long)C * 9;
+      if (oihw || !cout1) {
+        hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, chunks, n,
+                           accumulate ? 2 : 0, 1, 1, 1, dw_packed);
+      } else {          // packed [1][tap][c] wanted: treat the [c][tap] sums as an "OIHW" with Cout=1 and repack
+        hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, chunks, n, 0, 1, 1, 1,
+                           workspace + (size_t)chunks * n);
+        XAS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, workspace + (size_t)chunks * n,
+                           dw_packed, 1, C, 3, 3, 0, 0);
+      }
+      XAS_LAUNCH_CHECK();
+      return 0;
+    }
+    case WgradKernel::Cout1: {
+      const int KK = s->R * s->S * s->Cin;
+      const int chunks = (int)cdiv((long)s->N * s->Ho * s->Wo, kCout1Chunk);
+      hipLaunchKernelGGL(wgrad_cout1_kernel, dim3((unsigned)cdiv(KK, 64), (unsigned)chunks), dim3(64), 0, st, x, dy,
+                         workspace, *s, kCout1Chunk);
+      XAS_LAUNCH_CHECK();
+      hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(KK, 64)), dim3(slab_threads()), 0, st, workspace, chunks, (long)KK,
+                         rflag, s->Cin, s->R, s->S, dw_packed);
+      XAS_LAUNCH_CHECK();
+      return 0;
+    }
+    case WgradKernel::Stem: {
+      const int patches = s->N * (s->Ho / ST_TH) * (s->Wo / ST_TW);
+      const int ppb = (int)cdiv(patches, kStemWgradBlocks), blocks = (int)cdiv(patches, ppb);
+      hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, dy, workspace, s->N, s->Hi, s->Wi,
+                         s->Ho, s->Wo, patches, ppb);
+      XAS_LAUNCH_CHECK();
+      const long n = (long)ST_CO * ST_K;
+      hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, 2 * blocks, n,
+                         rflag, s->Cin, s->R, s->S, dw_packed);
+      XAS_LAUNCH_CHECK();
+      return 0;
+    }
+    default: break;
+  }
+  const int splits = r.splits;
+  WgradParams p{};
+  p.x = x; p.dy = dy; p.out = (splits == 1 && !oihw) ? dw_packed : workspace;
+  // which argument is the gradient tensor: dy (a conv's weight gradient) or x (XAS_GRAD_IS_X: a ConvTranspose2d's)
+  p.a_amax = (s->mode & XAS_GRAD_IS_X) ? s->x_amax : s->grad_amax;      // max |dy argument|
+  p.b_amax = (s->mode & XAS_GRAD_IS_X) ? s->grad_amax : s->x_amax;      // max |x argument|
+  p.N = s->N; p.Hi = s->Hi; p.Wi = s->Wi; p.Cin = s->Cin; p.Cout = s->Cout; p.R = s->R; p.S = s->S;
+  p.stride = s->stride; p.pad = s->pad; p.Ho = s->Ho; p.Wo = s->Wo;
+  p.KK = s->R * s->S * s->Cin; p.M = s->N * s->Ho * s->Wo; p.m_per_split = r.m_per_split;
+  p.div_hw.init((unsigned)(s->Ho * s->Wo)); p.div_w.init((unsigned)s->Wo);
+  p.div_cin.init((unsigned)s->Cin); p.div_s.init((unsigned)s->S);
+  const int pieces = planes_of(precision_of(s), 2, has_amax_for(s, 2));
+  int rc;
+  switch (r.kernel) {
+    case WgradKernel::SplitTap: rc = launch_wgrad_x6t(p, r.bm, splits, r.m_per_split, pieces, st); break;
+    case WgradKernel::Split: rc = launch_wgrad_x6(p, r.bm, r.bn, splits, pieces, st); break;
+    case WgradKernel::F32Buf:
+      rc = with_wgrad_tile(r.bm, r.bn, [&](auto bm, auto bn) { return launch_wgrad_buf<decltype(bm)::value, decltype(bn)::value>(p, splits, st); });
+      break;
+    default:                           // F32Global; it has no <*, 64, false> instantiation: 128 columns when x takes no float4 loads
+      rc = with_wgrad_tile(r.bm, r.bn, [&](auto bm, auto bn) {
+        constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+        return r.vec ? launch_wgrad<BM, BN, true>(p, splits, st) : launch_wgrad<BM, 128, false>(p, splits, st);
+      });
+  }
+  if (rc) return rc;
+  const long n = (long)s->Cout * p.KK;
+  if (oihw || splits > 1) {
+    hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, splits, n,
+                       rflag, s->Cin, s->R, s->S, dw_packed);
+    XAS_LAUNCH_CHECK();
+  }
+  return 0;
+}
 
 extern "C" int xas_conv_wgrad(const float* x, const float* dy, float* dw_packed, float* workspace,
                               const xas_conv_shape* s, void* stream) {
@@ -2070,128 +2210,6 @@ extern "C" int xas_conv_wgrad_oihw(const float* x, const float* dy, float* dw_oi
 extern "C" int xas_conv_wgrad_acc(const float* x, const float* dy, float* dw_oihw, float* workspace,
                                   const xas_conv_shape* s, void* stream) {
   return conv_wgrad_impl(x, dy, dw_oihw, workspace, s, stream, true, true);
-}
-
-static int conv_wgrad_impl(const float* x, const float* dy, float* dw_packed, float* workspace, const xas_conv_shape* s,
-                           void* stream, bool oihw, bool accumulate) {
-  const int rflag = (oihw ? 1 : 0) | (accumulate ? 2 : 0);
-  if (check_shape(s, "conv_wgrad")) return 1;
-  XAS_REQUIRE(x && dy && dw_packed && workspace, "conv_wgrad: null buffer");
-  XAS_REQUIRE(s->Cout % 4 == 0 || s->Cout == 1, "conv_wgrad: Cout=%d must be a multiple of 4 (or 1)", s->Cout);
-  {
-    const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
-    const int per = images_per_launch(s->N, xi, yi);
-    if (per < s->N && (oihw || accumulate)) {            // the packed single-slab form (linear layers) is never this large
-      for (int n0 = 0; n0 < s->N; n0 += per) {
-        xas_conv_shape part = *s;
-        part.N = s->N - n0 < per ? s->N - n0 : per;
-        const int rc = conv_wgrad_impl(x + (size_t)n0 * xi, dy + (size_t)n0 * yi, dw_packed, workspace, &part, stream, oihw,
-                                       accumulate || n0 > 0);
-        if (rc) return rc;
-      }
-      return 0;
-    }
-  }
-  hipStream_t st = as_stream(stream);
-  if ((s->Cout == 1 && thin_ok(s, s->Cin)) || (s->Cin == 1 && thin_ok(s, s->Cout))) {
-    // slabs [chunk][c][tap] == OIHW order for both cases ([1][Cin][3][3] resp. [Cout][1][3][3]); the packed
-    // layouts are [1][tap][c] resp. [c][tap]
-    const bool cout1 = s->Cout == 1;
-    const int C = cout1 ? s->Cin : s->Cout;
-    const ThinParams tp = thin_params(s->N, s->Hi, s->Wi, C, s->pad, 0);
-    const long M = (long)s->N * s->Hi * s->Wi;
-    // ~4 blocks per CU at most: long chunks amortise the block-level reduction (the workspace is sized for kThinChunk)
-    int chunks = (int)cdiv(M, kThinChunk);
-    if (chunks > 1024) chunks = 1024;
-    const int per_chunk = (int)(cdiv(cdiv(M, chunks), 256) * 256);
-    chunks = (int)cdiv(M, per_chunk);
-    hipLaunchKernelGGL(thin_wgrad_kernel, dim3(chunks), dim3(256), 0, st, cout1 ? dy : x, cout1 ? x : dy, workspace, tp,
-                       cout1 ? -1 : 1, per_chunk);
-    XAS_LAUNCH_CHECK();
-    const long n = (long)C * 9;
-    if (oihw || !cout1) {
-      hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, chunks, n,
-                         accumulate ? 2 : 0, 1, 1, 1, dw_packed);
-    } else {          // packed [1][tap][c] wanted: treat the [c][tap] sums as an "OIHW" with Cout=1 and repack
-      hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, chunks, n, 0, 1, 1, 1,
-                         workspace + (size_t)chunks * n);
-      XAS_LAUNCH_CHECK();
-      hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, workspace + (size_t)chunks * n,
-                         dw_packed, 1, C, 3, 3, 0, 0);
-    }
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s->Cout == 1) {
-    const int KK = s->R * s->S * s->Cin;
-    const int chunks = (int)cdiv((long)s->N * s->Ho * s->Wo, kCout1Chunk);
-    hipLaunchKernelGGL(wgrad_cout1_kernel, dim3((unsigned)cdiv(KK, 64), (unsigned)chunks), dim3(64), 0, st, x, dy,
-                       workspace, *s, kCout1Chunk);
-    XAS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(KK, 64)), dim3(slab_threads()), 0, st, workspace, chunks, (long)KK,
-                       rflag, s->Cin, s->R, s->S, dw_packed);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (stem_wgrad_ok(s) && !(g_tune & XAS_TUNE_NO_STEM_WGRAD)) {    // (the flag: the general kernel)
-    const int patches = s->N * (s->Ho / ST_TH) * (s->Wo / ST_TW);
-    const int ppb = (int)cdiv(patches, kStemWgradBlocks), blocks = (int)cdiv(patches, ppb);
-    hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, dy, workspace, s->N, s->Hi, s->Wi,
-                       s->Ho, s->Wo, patches, ppb);
-    XAS_LAUNCH_CHECK();
-    const long n = (long)ST_CO * ST_K;
-    hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, 2 * blocks, n,
-                       rflag, s->Cin, s->R, s->S, dw_packed);
-    XAS_LAUNCH_CHECK();
-    return 0;
-  }
-  const bool x6 = wgrad_on_x6(s, x);
-  int bm, bn, splits, mps;
-  wgrad_plan(s, x6, &bm, &bn, &splits, &mps);
-  WgradParams p{};
-  p.x = x; p.dy = dy; p.out = (splits == 1 && !oihw) ? dw_packed : workspace;
-  // which argument is the gradient tensor: dy (a conv's weight gradient) or x (XAS_GRAD_IS_X: a ConvTranspose2d's)
-  p.a_amax = (s->mode & XAS_GRAD_IS_X) ? s->x_amax : s->grad_amax;      // max |dy argument|
-  p.b_amax = (s->mode & XAS_GRAD_IS_X) ? s->grad_amax : s->x_amax;      // max |x argument|
-  p.N = s->N; p.Hi = s->Hi; p.Wi = s->Wi; p.Cin = s->Cin; p.Cout = s->Cout; p.R = s->R; p.S = s->S;
-  p.stride = s->stride; p.pad = s->pad; p.Ho = s->Ho; p.Wo = s->Wo;
-  p.KK = s->R * s->S * s->Cin; p.M = s->N * s->Ho * s->Wo; p.m_per_split = mps;
-  p.div_hw.init((unsigned)(s->Ho * s->Wo)); p.div_w.init((unsigned)s->Wo);
-  p.div_cin.init((unsigned)s->Cin); p.div_s.init((unsigned)s->S);
-  XAS_REQUIRE(s->Cout % 4 == 0, "conv_wgrad: Cout=%d not supported by the MFMA path", s->Cout);
-  const bool vec = (s->Cin % 4 == 0) && (((uintptr_t)x & 15) == 0);
-  int rc;
-  // buffer-load kernel: 32-bit byte offsets (tensors < 2 GiB) and at most one carry per coordinate in the per-thread
-  // pixel decode (31 / Wo + 1 <= Ho); XAS_TUNE_WGRAD_GLOBAL_LOAD forces the old kernel
-  const long xbytes = ((long)s->N * s->Hi * s->Wi + (long)s->pad * s->Wi + s->pad) * s->Cin * 4;
-  const long dybytes = (long)p.M * s->Cout * 4;
-  const bool buf_ok = vec && s->Cin % 32 == 0 && xbytes < 0x7fffff00l && dybytes < 0x7fffff00l && 31 / s->Wo + 1 <= s->Ho && !(g_tune & XAS_TUNE_WGRAD_GLOBAL_LOAD);
-  int tbm = 0, tsplits = 0, tpps = 0;
-  if (x6 && !(g_tune & XAS_TUNE_GENERAL_KERNELS) &&   // (the flag: no tap re-use kernels)
-      wgrad_x6t_plan(s->N, s->Hi, s->Wi, s->Cin, s->Cout, s->R, s->S, s->stride, s->pad, s->Ho, s->Wo, &tbm, &tsplits, &tpps)) {
-    splits = tsplits;
-    p.out = (splits == 1 && !oihw) ? dw_packed : workspace;
-    rc = launch_wgrad_x6t(p, tbm, tsplits, tpps, planes_of(precision_of(s), 2, has_amax_for(s, 2)), st);
-  } else
-  if (x6) rc = launch_wgrad_x6(p, bm, bn, splits, planes_of(precision_of(s), 2, has_amax_for(s, 2)), st);
-  else if (buf_ok) {
-    if (bm == 32) rc = launch_wgrad_buf<32, 128>(p, splits, st);
-    else if (bn == 64) rc = bm == 128 ? launch_wgrad_buf<128, 64>(p, splits, st) : launch_wgrad_buf<64, 64>(p, splits, st);
-    else if (bm == 128) rc = launch_wgrad_buf<128, 128>(p, splits, st);
-    else rc = launch_wgrad_buf<64, 128>(p, splits, st);
-  } else
-  if (bm == 32) rc = vec ? launch_wgrad<32, 128, true>(p, splits, st) : launch_wgrad<32, 128, false>(p, splits, st);
-  else if (bn == 64 && vec) rc = bm == 128 ? launch_wgrad<128, 64, true>(p, splits, st) : launch_wgrad<64, 64, true>(p, splits, st);
-  else if (bm == 128) rc = vec ? launch_wgrad<128, 128, true>(p, splits, st) : launch_wgrad<128, 128, false>(p, splits, st);
-  else rc = vec ? launch_wgrad<64, 128, true>(p, splits, st) : launch_wgrad<64, 128, false>(p, splits, st);
-  if (rc) return rc;
-  const long n = (long)s->Cout * p.KK;
-  if (oihw || splits > 1) {
-    hipLaunchKernelGGL(slab_reduce_kernel2, dim3((unsigned)cdiv(n, 64)), dim3(slab_threads()), 0, st, workspace, splits, n,
-                       rflag, s->Cin, s->R, s->S, dw_packed);
-    XAS_LAUNCH_CHECK();
-  }
-  return 0;
 }
 
 extern "C" int xas_pack_weight(const float* oihw, float* packed, int Cout, int Cin, int R, int S, int transposed,

@@ -556,9 +556,16 @@ static inline void pick_tile(int Cd, long Mrows_max, int phases, int* bm, int* b
 // conv_x6.hip: bf16-split kernels (pieces = 3: bf16x6, fp32 accurate; 1: plain bf16).  mode: 0 forward, 1 data gradient.
 // p.wgt points to PRE-SPLIT weights (xas_split_weight).
 int launch_igemm_x6(const IgemmParams& p, int mode, int Mrows_max, int phases, int pieces, hipStream_t st);
-void wgrad_x6_tile(int Cout, long KK, int* bm, int* bn);
+// The tile and kernel launch_igemm_x6 runs a problem on, decided in this order: the head epilogue (64 x 256), tap re-use
+// (128-row patches), the batch-norm backward epilogue (pick_tile), wide 64 x 256 tiles - on the persistent GEMM where it
+// takes the problem - and pick_tile.  xas_conv_fwd_bnstats lays its partial sums out by bm, one row per tile.
+struct X6Tile {
+  int bm, bn;
+  enum Kernel { General, Tap, Persistent } kernel;    // igemm_x6_kernel, igemm_x6t_kernel, igemm_x6p_kernel
+};
+X6Tile pick_tile_x6(const IgemmParams& p, int mode, int Mrows_max, int phases, int pieces);
 int launch_wgrad_x6(const WgradParams& p, int bm, int bn, int splits, int pieces, hipStream_t st);
-bool wgrad_x6t_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int Ho, int Wo, int* bm, int* splits, int* pps);
+bool wgrad_x6t_plan(const xas_conv_shape* s, int* bm, int* splits, int* pps);
 int launch_wgrad_x6t(const WgradParams& p, int bm, int splits, int pps, int pieces, hipStream_t st);
 
 }  // namespace xas

@@ -723,13 +723,6 @@ constexpr size_t igemm_x6t_lds(int P) {
   return a > b ? a : b;
 }
 
-// does the tap-reuse kernel take this problem?  (stride-1 3x3, same-size maps, 128-row tiles that are whole patches)
-static bool x6t_takes(const IgemmParams& p, int bm, int phases) {
-  if (p.tune & XAS_TUNE_GENERAL_KERNELS) return false;   // implicit-GEMM kernel for every shape
-  if (bm != 128 || phases != 1 || p.bnb_x) return false;
-  return tap_tile_ok(p.R, p.S, p.stride, p.pad, p.Hs, p.Ws, p.Hd, p.Wd, p.Cs, p.N);
-}
-
 // Tried and dropped:
 // * (commit "Experiment: igemm_x6d_kernel", profiles/r03_igemm_x6_dma_vs_regstaged.txt) the fp32 activation rows by
 //   LDS-DMA (buffer_load_dwordx4 ... lds into a 4-slot ring, swizzle on the source address, counted vmcnt + raw s_barrier)
@@ -856,37 +849,48 @@ static int with_pieces(int pieces, F&& f) {
   return f(std::integral_constant<int, 1>());
 }
 
+X6Tile pick_tile_x6(const IgemmParams& p, int mode, int Mrows_max, int phases, int pieces) {
+  X6Tile t{64, 256, X6Tile::General};
+  if (mode == 0 && p.head_partial) return t;           // the head epilogue lives in the 64 x 256 tile (one image row x four joints)
+  pick_tile(p.Cd, Mrows_max, phases, &t.bm, &t.bn);
+  const bool bnb = mode == 1 && pieces != 2 && p.bnb_x;        // the batch-norm backward epilogue: no wide tile
+  // the tap re-use kernel: stride-1 3x3, same-size maps, 128-row tiles that are whole patches (XAS_TUNE_GENERAL_KERNELS: never)
+  if (!(p.tune & XAS_TUNE_GENERAL_KERNELS) && t.bm == 128 && phases == 1 && !p.bnb_x &&
+      tap_tile_ok(p.R, p.S, p.stride, p.pad, p.Hs, p.Ws, p.Hd, p.Wd, p.Cs, p.N)) t.kernel = X6Tile::Tap;
+  else if (!bnb && !(p.tune & XAS_TUNE_NO_WIDE_TILES)) {
+    pick_tile(p.Cd, Mrows_max, phases, &t.bm, &t.bn, true);
+    if (pieces == 2 && t.bn == 256 && x6p_takes(p, mode, phases)) t.kernel = X6Tile::Persistent;
+  }
+  return t;
+}
+
+// (bm, bn) of pick_tile -> igemm_x6_kernel<BM, BN, MODE, P, BNB>
+template <int MODE, int P, bool BNB>
+static int launch_igemm_x6_tile(const IgemmParams& p, const X6Tile& t, int Mrows_max, int phases, hipStream_t st) {
+  if constexpr (!BNB) {
+    if (t.bn == 256) return launch_igemm_x6_t<64, 256, MODE, P, false>(p, Mrows_max, phases, st);
+  }
+  if (t.bn == 128) return launch_igemm_x6_t<128, 128, MODE, P, BNB>(p, Mrows_max, phases, st);
+  if (t.bm == 64) return launch_igemm_x6_t<64, 64, MODE, P, BNB>(p, Mrows_max, phases, st);
+  if (t.bn == 64) return launch_igemm_x6_t<128, 64, MODE, P, BNB>(p, Mrows_max, phases, st);
+  return launch_igemm_x6_t<128, 32, MODE, P, BNB>(p, Mrows_max, phases, st);
+}
+
 template <int MODE, int P>
 static int launch_igemm_x6_p(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
-  int bm, bn;
-  if constexpr (MODE == 0) {                           // the head epilogue lives in the 64 x 256 tile (one image row x four joints)
-    if (p.head_partial) return launch_igemm_x6_t<64, 256, 0, P, false>(p, Mrows_max, phases, st);
-  }
-  pick_tile(p.Cd, Mrows_max, phases, &bm, &bn);
-  if (x6t_takes(p, bm, phases)) {
-    if (bn == 128) return launch_igemm_x6t<128, MODE, P>(p, Mrows_max, st);
-    if (bn == 64) return launch_igemm_x6t<64, MODE, P>(p, Mrows_max, st);
+  const X6Tile t = pick_tile_x6(p, MODE, Mrows_max, phases, P);
+  if (t.kernel == X6Tile::Tap) {
+    if (t.bn == 128) return launch_igemm_x6t<128, MODE, P>(p, Mrows_max, st);
+    if (t.bn == 64) return launch_igemm_x6t<64, MODE, P>(p, Mrows_max, st);
     return launch_igemm_x6t<32, MODE, P>(p, Mrows_max, st);
   }
+  if constexpr (P == 2) {
+    if (t.kernel == X6Tile::Persistent) return launch_igemm_x6p<MODE>(p, Mrows_max, st);
+  }
   if constexpr (MODE == 1 && P != 2) {
-    if (p.bnb_x) {
-      if (bn == 128) return launch_igemm_x6_t<128, 128, 1, P, true>(p, Mrows_max, phases, st);
-      if (bm == 64) return launch_igemm_x6_t<64, 64, 1, P, true>(p, Mrows_max, phases, st);
-      if (bn == 64) return launch_igemm_x6_t<128, 64, 1, P, true>(p, Mrows_max, phases, st);
-      return launch_igemm_x6_t<128, 32, 1, P, true>(p, Mrows_max, phases, st);
-    }
+    if (p.bnb_x) return launch_igemm_x6_tile<1, P, true>(p, t, Mrows_max, phases, st);
   }
-  if (!(p.tune & XAS_TUNE_NO_WIDE_TILES)) {
-    pick_tile(p.Cd, Mrows_max, phases, &bm, &bn, true);
-    if constexpr (P == 2) {
-      if (bn == 256 && x6p_takes(p, MODE, phases)) return launch_igemm_x6p<MODE>(p, Mrows_max, st);
-    }
-    if (bn == 256) return launch_igemm_x6_t<64, 256, MODE, P, false>(p, Mrows_max, phases, st);
-  }
-  if (bn == 128) return launch_igemm_x6_t<128, 128, MODE, P, false>(p, Mrows_max, phases, st);
-  if (bm == 64) return launch_igemm_x6_t<64, 64, MODE, P, false>(p, Mrows_max, phases, st);
-  if (bn == 64) return launch_igemm_x6_t<128, 64, MODE, P, false>(p, Mrows_max, phases, st);
-  return launch_igemm_x6_t<128, 32, MODE, P, false>(p, Mrows_max, phases, st);
+  return launch_igemm_x6_tile<MODE, P, false>(p, t, Mrows_max, phases, st);
 }
 
 // pieces: 3 = bf16x6, 1 = bf16, 2 = f16x3 (the gathered operand at a fixed scale when it is an activation, at a scale
@@ -1252,18 +1256,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6t_kernel(WgradParams p) {
 }
 
 // plan of the tap-reuse weight gradient; false: the shape is not taken (wgrad_x6_kernel does it)
-bool wgrad_x6t_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int Ho, int Wo, int* bm, int* splits, int* pps) {
-  if (R != 3 || S != 3 || stride != 1 || pad != 1 || Ho != H || Wo != W) return false;
-  if (Cin % 32 != 0 || H % 8 != 0) return false;
-  if (!(W % 16 == 0 || (W == 8 && N % 2 == 0))) return false;
+bool wgrad_x6t_plan(const xas_conv_shape* s, int* bm, int* splits, int* pps) {
+  if (!tap_tile_ok(s->R, s->S, s->stride, s->pad, s->Hi, s->Wi, s->Ho, s->Wo, s->Cin, s->N)) return false;
   // measured (profiles/r03_wgrad_x6t_ab.txt): 64 and 32 output channels +15..63 %; 128 and more -5..6 % with 128- and with
   // 64-channel blocks (nine accumulators per wave: 245 VGPRs) - those stay on wgrad_x6_kernel, and wgrad_x6t_kernel is
   // instantiated for BM = 64 and 32 only
-  if (Cout == 64) *bm = 64;
-  else if (Cout == 32) *bm = 32;
-  else return false;
-  const long np = (long)N * H * W / 128;
-  const long tiles = (long)(Cout / *bm) * (Cin / 32);
+  if (s->Cout != 64 && s->Cout != 32) return false;
+  *bm = s->Cout;
+  const long np = (long)s->N * s->Hi * s->Wi / 128;
+  const long tiles = s->Cin / 32;                      // one Cout tile
 #ifndef XAS_WX6T_BLOCKS
 #define XAS_WX6T_BLOCKS 1536
 #endif
@@ -1317,13 +1318,7 @@ static int launch_wgrad_x6_t(const WgradParams& p, int splits, hipStream_t st) {
   return 0;
 }
 
-// tile of the bf16-split weight gradient: BM over Cout, BN over KK = R*S*Cin
-void wgrad_x6_tile(int Cout, long KK, int* bm, int* bn) {
-  *bm = Cout >= 96 ? 128 : (Cout > 32 ? 64 : 32);
-  *bn = KK <= 64 ? 64 : 128;
-  if (*bm == 32) *bn = 128;
-}
-
+// (bm, bn): wgrad_plan's tile, BM over Cout, BN over KK = R*S*Cin
 int launch_wgrad_x6(const WgradParams& p, int bm, int bn, int splits, int pieces, hipStream_t st) {
   if (pieces == 2)
     XAS_REQUIRE(p.a_amax && p.b_amax, "conv_wgrad: the f16x3 weight gradient needs the maxima of both tensor operands (xas_conv_shape.grad_amax, x_amax)");
