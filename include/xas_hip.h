@@ -645,6 +645,22 @@ int xas_projection_matrix(const float* k_mat, const float* rot_world, const floa
  * out [B][K][4] = (X/w, Y/w, Z/w, mean weight).  V >= 2. */
 int xas_triangulate_dlt(const float* points, const float* P, int B, int V, int K, float* out, void* stream);
 
+/* Outlier-robust triangulation by exhaustive consensus (eval.py --tri robust; the reference has no counterpart, its
+ * modules/util.py:198-230 is the DLT above over all views).  points [B][V][K][3] = (u, v, weight), P [B][V][3][4] as for
+ * xas_triangulate_dlt; threshold_px > 0.  A view is VALID if its weight is finite and > 0.  Every subset S of >= 2 valid
+ * views is a candidate: X_S = its DLT solution; the residual of a view is the pixel distance between its (u, v) and the
+ * projection of X_S (+inf behind the camera); I(S) = the valid views with residual < threshold_px.  The best candidate has
+ * the most inliers, then the smallest sum of squared inlier residuals, then the smallest bit mask.  The views used, F, are
+ * its inliers, or all valid views if it has fewer than two.
+ * out [B][K][4] = (X, Y, Z, mean weight over the views used): the DLT over F, the arithmetic of xas_triangulate_dlt
+ * restricted to F (bit-identical to it where F is all V views); inliers [B][K] (bit v = view v used; 0 = fallback),
+ * resid [B][K] = RMS reprojection residual in pixels of the result over the views used.  inliers / resid may be NULL.
+ * Fewer than 2 valid views: NaN in xyz and resid, inliers 0, out[3] = mean weight of the valid views (NaN if none).
+ * One wave per (b, joint), lane = subset mask: 2 <= V <= XAS_TRI_MAX_VIEWS. */
+#define XAS_TRI_MAX_VIEWS 6
+int xas_triangulate_robust(const float* points, const float* P, int B, int V, int K, float threshold_px, float* out,
+                           unsigned char* inliers, float* resid, void* stream);
+
 /* Pose metrics, replaces metrics.py:5-244 (numpy, per-sample SVD on the host).
  * pred, gt [N][K][3]; both are divided by in_div on load (eval.py:52-53 passes mm / 1000 for PCK / AUC);
  * mask [N][K] (0/1) or NULL = all visible.  Outputs (each may be NULL):

@@ -6,6 +6,8 @@
 //   eval_select     : eval.py:117-148 + eval_utils.py:7-43 (switch_points, best/confident, per_act_mse)
 //   projection      : modules/util.py:188 (P = K [R | t])
 //   triangulate_dlt : modules/util.py:198-230 (null vector of the weighted DLT system)
+//   triangulate_robust : the same DLT over the largest set of views that agree within a pixel threshold (no reference
+//                     counterpart: eval.py --tri robust)
 //   pose_metrics    : metrics.py:5-244 (MPJPE under none / scale / procrustes alignment, 3DPCK, AUC hit counts)
 //
 // Small symmetric eigenproblems (4x4) are solved with cyclic Jacobi rotations in double precision, fully unrolled
@@ -146,9 +148,60 @@ __global__ void projection_kernel(const float* __restrict__ km, const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------------
+// DLT pieces shared by triangulate_dlt and triangulate_robust.  Rows are formed in fp32 as the reference forms them
+// (util.py:215-221; u P2 - P0 with one rounding), then A^T A and its smallest eigenvector are computed in double.
+// ------------------------------------------------------------------------------------------------------
+// One view's contribution to the upper triangle of A^T A, row-major (00 01 02 03 11 12 13 22 23 33): its two rows
+// a_u = c (u P2 - P0), a_v = c (v P2 - P1) in fp32, their outer products in double.
+__device__ __forceinline__ void dlt_view_gram(float u, float w, float c, const float* __restrict__ Pm, double (&t)[10]) {
+  float au[4], av[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    // u P2 - P0 as ONE fused multiply-add, written out: that is what the compiler has always made of this line in
+    // triangulate_kernel, but left to itself it does not make it in every kernel, and the null vector of a nearly singular
+    // system moves by tens of fp32 ulps with the last bit of a row
+    au[j] = __fmul_rn(c, __builtin_fmaf(u, Pm[8 + j], -Pm[j]));
+    av[j] = __fmul_rn(c, __builtin_fmaf(w, Pm[8 + j], -Pm[4 + j]));
+  }
+  int n = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int cc = r; cc < 4; ++cc) t[n++] = (double)au[r] * (double)au[cc] + (double)av[r] * (double)av[cc];
+}
+
+// g (upper triangle) += one view.  Both kernels add their views through here in ascending view order, so the same set
+// of views gives the same matrix bit for bit.
+template <typename T>
+__device__ __forceinline__ void dlt_gram_add(double (&g)[4][4], const T& t) {
+  int n = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int cc = r; cc < 4; ++cc) g[r][cc] += t[n++];
+}
+
+// Homogeneous null vector of the accumulated system: eigenvector of the smallest eigenvalue (g's upper triangle is used).
+// NOT inlined: inlined into two kernels the compiler contracts the rotations' multiply-adds differently in each, and the
+// two then differ in the last bits.  One body that both call makes the same matrix give the same vector by construction.
+__device__ __noinline__ void dlt_null_vector(double (&g)[4][4], double (&X)[4]) {
+#pragma unroll
+  for (int r = 1; r < 4; ++r)
+#pragma unroll
+    for (int cc = 0; cc < r; ++cc) g[r][cc] = g[cc][r];
+  double vec[4][4];
+  jacobi4(g, vec);
+  int best = 0;
+  double lo = g[0][0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j)
+    if (g[j][j] < lo) { lo = g[j][j]; best = j; }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) X[r] = best == 0 ? vec[r][0] : (best == 1 ? vec[r][1] : (best == 2 ? vec[r][2] : vec[r][3]));
+}
+
+// ------------------------------------------------------------------------------------------------------
 // triangulate_dlt: thread per (b, joint).  points [B][V][K][3] = (u, v, weight), P [B][V][3][4].
-// Rows are formed in fp32 exactly as the reference forms them (util.py:215-221), then A^T A and its smallest
-// eigenvector are computed in double.
 // ------------------------------------------------------------------------------------------------------
 __global__ void triangulate_kernel(const float* __restrict__ pts, const float* __restrict__ P, int B, int V, int K,
                                    float* __restrict__ out) {
@@ -164,38 +217,128 @@ __global__ void triangulate_kernel(const float* __restrict__ pts, const float* _
   int wpos = 0;
   for (int v = 0; v < V; ++v) {
     const float* q = pts + (((size_t)b * V + v) * K + k) * 3;
-    const float* Pm = P + ((size_t)b * V + v) * 12;
-    const float u = q[0], w = q[1], c = q[2];
+    const float c = q[2];
     wsum += c;
     wpos += c > 0.f ? 1 : 0;
-    float au[4], av[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      au[j] = __fmul_rn(c, __fsub_rn(__fmul_rn(u, Pm[8 + j]), Pm[j]));
-      av[j] = __fmul_rn(c, __fsub_rn(__fmul_rn(w, Pm[8 + j]), Pm[4 + j]));
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int cc = r; cc < 4; ++cc) g[r][cc] += (double)au[r] * (double)au[cc] + (double)av[r] * (double)av[cc];
+    double t[10];
+    dlt_view_gram(q[0], q[1], c, P + ((size_t)b * V + v) * 12, t);
+    dlt_gram_add(g, t);
   }
-#pragma unroll
-  for (int r = 1; r < 4; ++r)
-#pragma unroll
-    for (int cc = 0; cc < r; ++cc) g[r][cc] = g[cc][r];
-  double vec[4][4];
-  jacobi4(g, vec);
-  int best = 0;
-  double lo = g[0][0];
-#pragma unroll
-  for (int j = 1; j < 4; ++j)
-    if (g[j][j] < lo) { lo = g[j][j]; best = j; }
   double X[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) X[r] = best == 0 ? vec[r][0] : (best == 1 ? vec[r][1] : (best == 2 ? vec[r][2] : vec[r][3]));
+  dlt_null_vector(g, X);
   float* o = out + (size_t)i * 4;
   o[0] = (float)(X[0] / X[3]); o[1] = (float)(X[1] / X[3]); o[2] = (float)(X[2] / X[3]);
   o[3] = wsum / (float)wpos;                                          // util.py:207-209 (mean weight)
+}
+
+// ------------------------------------------------------------------------------------------------------
+// triangulate_robust: exhaustive consensus over the subsets of the views, one wave per (b, joint), lane = subset mask.
+// With V <= 6 the 2^V masks fit the 64 lanes, so nothing is sampled: every subset of >= 2 valid views is solved (DLT,
+// as above), scored by how many valid views reproject within the threshold, and the best one's inlier set F is the
+// answer.  F is itself a subset of >= 2 valid views, so the lane whose mask IS F has already solved exactly the system
+// that triangulate_dlt restricted to F would solve, and has F's residuals: it writes the result.  No second solve.
+// ------------------------------------------------------------------------------------------------------
+struct TriView {
+  double gram[10];        // dlt_view_gram of the view
+  float P[12];
+  float u, v, w, pad;
+};
+
+// Squared reprojection residual (px^2) of homogeneous X in one view, in double; +inf behind the camera.
+__device__ __forceinline__ double reproj_r2(const TriView& s, const double (&X)[4]) {
+  double h[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    h[r] = (double)s.P[4 * r] * X[0] + (double)s.P[4 * r + 1] * X[1] + (double)s.P[4 * r + 2] * X[2] + (double)s.P[4 * r + 3] * X[3];
+  if (h[2] / X[3] <= 0.0) return INFINITY;
+  const double du = h[0] / h[2] - (double)s.u, dv = h[1] / h[2] - (double)s.v;
+  return du * du + dv * dv;
+}
+
+__global__ __launch_bounds__(64) void triangulate_robust_kernel(const float* __restrict__ pts, const float* __restrict__ P,
+                                                                int V, int K, float threshold_px, float* __restrict__ out,
+                                                                unsigned char* __restrict__ inliers,
+                                                                float* __restrict__ resid) {
+  __shared__ TriView sv[XAS_TRI_MAX_VIEWS];
+  const int i = blockIdx.x, b = i / K, k = i % K;
+  const int lane = threadIdx.x;
+  bool ok = false;
+  if (lane < V) {                                                     // lane v stages view v
+    const float* q = pts + (((size_t)b * V + lane) * K + k) * 3;
+    const float* Pm = P + ((size_t)b * V + lane) * 12;
+    TriView& s = sv[lane];
+    s.u = q[0]; s.v = q[1]; s.w = q[2]; s.pad = 0.f;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) s.P[j] = Pm[j];
+    double t[10];
+    dlt_view_gram(s.u, s.v, s.w, Pm, t);
+#pragma unroll
+    for (int j = 0; j < 10; ++j) s.gram[j] = t[j];
+    ok = s.w > 0.f && s.w < INFINITY;                                 // valid: finite and positive weight
+  }
+  const int valid = (int)__ballot(ok);                                // bits < V only
+  __syncthreads();
+
+  // --- candidate = this lane's mask, if it is a set of >= 2 valid views
+  const bool cand = (lane & ~valid) == 0 && __popc(lane) >= 2;
+  double X[4] = {0.0, 0.0, 0.0, 0.0}, r2[XAS_TRI_MAX_VIEWS];
+  int cnt = -1, inl = 0;
+  double cost = INFINITY;
+  if (cand) {
+    double g[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) g[r][c] = 0.0;
+#pragma unroll
+    for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v)
+      if ((lane >> v) & 1) dlt_gram_add(g, sv[v].gram);
+    dlt_null_vector(g, X);
+    cnt = 0;
+    cost = 0.0;
+#pragma unroll
+    for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
+      r2[v] = 0.0;
+      if ((valid >> v) & 1) {
+        r2[v] = reproj_r2(sv[v], X);
+        if (sqrt(r2[v]) < (double)threshold_px) { ++cnt; cost += r2[v]; inl |= 1 << v; }
+      }
+    }
+  }
+  // --- wave arg-best: more inliers, then smaller sum of squared inlier residuals, then smaller mask.  A total order
+  // (masks are distinct), so the xor butterfly leaves the same winner in every lane.
+  int bcnt = cnt, binl = inl, bid = lane;
+  double bcost = cost;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int ocnt = __shfl_xor(bcnt, o, 64), oinl = __shfl_xor(binl, o, 64), oid = __shfl_xor(bid, o, 64);
+    const double ocost = __shfl_xor(bcost, o, 64);
+    const bool take = ocnt > bcnt || (ocnt == bcnt && (ocost < bcost || (ocost == bcost && oid < bid)));
+    if (take) { bcnt = ocnt; binl = oinl; bid = oid; bcost = ocost; }
+  }
+  const int used = bcnt >= 2 ? binl : valid;                          // no consensus of two views: all valid views
+  const int nused = __popc(used);
+  float* o = out + (size_t)i * 4;
+  if (__popc(valid) < 2) {                                            // nothing to solve
+    if (lane == 0) {
+      float wsum = 0.f;
+      for (int v = 0; v < V; ++v) wsum += ((valid >> v) & 1) ? sv[v].w : 0.f;
+      o[0] = NAN; o[1] = NAN; o[2] = NAN; o[3] = wsum / (float)nused;
+      if (inliers) inliers[i] = 0;
+      if (resid) resid[i] = NAN;
+    }
+    return;
+  }
+  if (lane != used) return;                                           // the lane that solved exactly the views used
+  float wsum = 0.f;
+  double rsum = 0.0;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v)
+    if ((used >> v) & 1) { wsum += sv[v].w; rsum += r2[v]; }
+  o[0] = (float)(X[0] / X[3]); o[1] = (float)(X[1] / X[3]); o[2] = (float)(X[2] / X[3]);
+  o[3] = wsum / (float)nused;
+  if (inliers) inliers[i] = (unsigned char)(bcnt >= 2 ? binl : 0);
+  if (resid) resid[i] = (float)sqrt(rsum / (double)nused);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -330,6 +473,19 @@ extern "C" int xas_triangulate_dlt(const float* points, const float* P, int B, i
   XAS_REQUIRE(B > 0 && V >= 2 && K > 0, "triangulate_dlt: bad shape B=%d V=%d K=%d (needs >= 2 views)", B, V, K);
   hipLaunchKernelGGL(triangulate_kernel, dim3((unsigned)cdiv((long)B * K, 64)), dim3(64), 0, as_stream(stream), points, P, B,
                      V, K, out);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_triangulate_robust(const float* points, const float* P, int B, int V, int K, float threshold_px,
+                                      float* out, unsigned char* inliers, float* resid, void* stream) {
+  XAS_REQUIRE(points && P && out, "triangulate_robust: null buffer (points, P and out are required)");
+  XAS_REQUIRE(V >= 2 && V <= XAS_TRI_MAX_VIEWS, "triangulate_robust: V=%d views (needs 2 <= V <= XAS_TRI_MAX_VIEWS = %d)", V,
+              XAS_TRI_MAX_VIEWS);
+  XAS_REQUIRE(B > 0 && K > 0 && (long)B * K <= 0x7fffffffL, "triangulate_robust: bad shape B=%d K=%d (B, K > 0, B*K < 2^31)", B, K);
+  XAS_REQUIRE(threshold_px > 0.f, "triangulate_robust: threshold_px %f (needs a threshold > 0 px)", (double)threshold_px);
+  hipLaunchKernelGGL(triangulate_robust_kernel, dim3((unsigned)((long)B * K)), dim3(64), 0, as_stream(stream), points, P, V, K,
+                     threshold_px, out, inliers, resid);
   XAS_LAUNCH_CHECK();
   return 0;
 }

@@ -3,6 +3,7 @@
 
     torchrun --nproc-per-node=N eval.py --config config/HM36_Multi_SurS1.yaml --checkpoint ckpt.pth.tar
              [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
+             [--tri dlt|robust --tri_thresh PX]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -54,7 +55,10 @@ def ddp_setup():
 class Eval:
     """Same constructor and method signatures as the reference Eval (eval.py:63-107)."""
 
-    def __init__(self, config, detector, eval_data, log_dir, img_size=256.0, flip_test=False):
+    def __init__(self, config, detector, eval_data, log_dir, img_size=256.0, flip_test=False, tri='dlt',
+                 tri_thresh=ops_eval.TRI_ROBUST_PX):
+        if tri not in ('dlt', 'robust'):
+            raise ValueError('Unknown triangulation: {}'.format(tri))
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -65,6 +69,8 @@ class Eval:
         self.log_dir = log_dir
         self.img_size = img_size
         self.flip_test = bool(flip_test)           # --flip: every image is evaluated together with its horizontal mirror
+        self.tri, self.tri_thresh = tri, float(tri_thresh)   # --tri robust: DLT over the views that agree within tri_thresh px
+        self.tri_views, self.tri_batches = 0.0, 0  # robust only: mean views used per joint, summed over the batches
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -98,7 +104,14 @@ class Eval:
             trans = t if trans is None else trans + t
         out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
         gt = convert_patch_to_world(x['cam_0_joints'], x, 'cam_0', is_norm=False)          # eval.py:170
-        preds = {'tri': triangulation(sel, x, self.cam_id_list)}
+        if self.tri == 'robust':
+            tri, used = triangulation(sel, x, self.cam_id_list, robust_px=self.tri_thresh, return_inliers=True)
+            bits = (used.unsqueeze(-1).int() >> torch.arange(len(cams), device=used.device, dtype=torch.int32)) & 1
+            # a zero mask is the fallback: no two views agreed, the DLT ran over all of them
+            out['tri_inlier_views'] = torch.where(used == 0, len(cams), bits.sum(dim=-1)).float().mean()
+        else:
+            tri = triangulation(sel, x, self.cam_id_list)
+        preds = {'tri': tri}
         for m in cams:
             preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
         for name, p in preds.items():
@@ -126,6 +139,9 @@ class Eval:
                     record_table = record_table + host['err2d_' + m]
                     count_table += 1
             ambiguity_ratio = ambiguity_ratio + float(host['ambiguity'])
+            if 'tri_inlier_views' in host:
+                self.tri_views += float(host['tri_inlier_views'])
+                self.tri_batches += 1
             for table, count, names in ((record_3d_tri_table, count_3d_tri_table, ['tri']),
                                         (record_3d_table, count_3d_table, ['view_' + m for m in cams])):
                 for name in names:
@@ -168,6 +184,9 @@ class Eval:
                         lines.append('{}: {} %'.format(key, float(tbl[key] / cnt[key])))
                     else:
                         lines.append('{}: {}'.format(key, float(np.mean(tbl[key]) / cnt[key])))
+        if self.tri == 'robust':                   # after the reference's lines; --tri dlt leaves the file as it was
+            lines.append('TRI inlier views ({} px): {} of {}'.format(self.tri_thresh, self.tri_views / max(self.tri_batches, 1),
+                                                                     len(self.cam_id_list)))
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -239,6 +258,10 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--ema', dict(default=False, action='store_true', help="evaluate the averaged weights ('unsup_model_ema')")),
     ('--flip', dict(default=False, action='store_true',
                     help='flip test: average every heat-map with the one of the mirrored image (model_params.flip_pairs)')),
+    ('--tri', dict(default='dlt', choices=['dlt', 'robust'],
+                   help='triangulation: the DLT over all cameras, or over the largest set of cameras that agree within --tri_thresh')),
+    ('--tri_thresh', dict(default=ops_eval.TRI_ROBUST_PX, type=float, metavar='PX',
+                          help='--tri robust: inlier threshold in pixels of the full-resolution image')),
 )
 
 
@@ -259,7 +282,7 @@ def main():
     log_dir = os.path.dirname(opt.checkpoint) if opt.checkpoint else opt.log_dir
     detector = prepare_model(config, opt)
     loader = prepare_data(config, world, opt.worker, opt.synthetic, torch.device('cuda', rank_local))
-    ev = Eval(config, detector, loader, log_dir, flip_test=opt.flip)
+    ev = Eval(config, detector, loader, log_dir, flip_test=opt.flip, tri=opt.tri, tri_thresh=opt.tri_thresh)
     tables = init_tables(ev.cal_per_act)
     record = ev.eval(None, *tables, mode=opt.multi_hypo)
     destroy_process_group()

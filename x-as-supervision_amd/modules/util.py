@@ -58,13 +58,18 @@ def convert_patch_to_image(kps, trans, image_depth, image_height, image_width, d
                                    is_norm=is_norm)
 
 
-def batch_triangulate(keypoints_, Pall):
-    """keypoints_ [B,V,K,3] = (u, v, weight), Pall [B,V,3,4] -> [B,K,4] (util.py:198-230)."""
-    return ops_eval.triangulate_dlt(keypoints_, Pall)
+def batch_triangulate(keypoints_, Pall, robust_px=None):
+    """keypoints_ [B,V,K,3] = (u, v, weight), Pall [B,V,3,4] -> [B,K,4] (util.py:198-230).  With `robust_px` (pixels) the
+    DLT runs over the largest set of views that agree within that threshold (ops_eval.triangulate_robust)."""
+    if robust_px is None:
+        return ops_eval.triangulate_dlt(keypoints_, Pall)
+    return ops_eval.triangulate_robust(keypoints_, Pall, threshold_px=robust_px, want=())['xyzw']
 
 
-def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000):
-    """{cam_key: [B,K,3]} patch predictions of all cameras -> world joints [B,K,3] (util.py:171-196)."""
+def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000, robust_px=None, return_inliers=False):
+    """{cam_key: [B,K,3]} patch predictions of all cameras -> world joints [B,K,3] (util.py:171-196).  `robust_px`: as in
+    batch_triangulate; with `return_inliers` also the [B,K] uint8 masks of the views used (bit i = cam_id_list[i];
+    None without robust_px)."""
     pts, pm = [], []
     for cam_id in cam_id_list:
         mode = 'cam_{}'.format(cam_id)
@@ -74,7 +79,12 @@ def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000)
                                            is_norm=is_norm))
         pm.append(ops_eval.projection_matrix(params['{}_k_mat'.format(mode)], params['{}_rot_world'.format(mode)],
                                              params['{}_trans_world'.format(mode)]))
-    return batch_triangulate(torch.stack(pts, dim=1), torch.stack(pm, dim=1))[..., :3]
+    if robust_px is None:
+        tri = batch_triangulate(torch.stack(pts, dim=1), torch.stack(pm, dim=1))[..., :3]
+        return (tri, None) if return_inliers else tri
+    r = ops_eval.triangulate_robust(torch.stack(pts, dim=1), torch.stack(pm, dim=1), threshold_px=robust_px,
+                                    want=('inliers',) if return_inliers else ())
+    return (r['xyzw'][..., :3], r['inliers']) if return_inliers else r['xyzw'][..., :3]
 
 
 def smpl_to_h36m(verts, h36m_regressor):

@@ -138,6 +138,7 @@ SIGNATURES = {
     'xas_eval_select': ('pppiiiifippppp', 'i'),
     'xas_projection_matrix': ('pppipp', 'i'),
     'xas_triangulate_dlt': ('ppiiipp', 'i'),
+    'xas_triangulate_robust': ('ppiiifpppp', 'i'),
     'xas_pose_metrics': ('pppiififppppp', 'i'),
 }
 

@@ -84,6 +84,32 @@ def triangulate_dlt(points, pmat):
     return out
 
 
+# Default inlier threshold of the robust triangulation, in pixels of the full-resolution image.  Argued, not measured
+# (DESIGN.md 4): a 256-px patch covers a roughly 1000-px HM36 frame, so 20 image px are about 5 patch px, a little over one
+# cell of the D = 64 heat-map (4 patch px per cell).
+TRI_ROBUST_PX = 20.0
+TRI_MAX_VIEWS = 6        # xas_hip.h XAS_TRI_MAX_VIEWS
+
+
+def triangulate_robust(points, pmat, threshold_px=TRI_ROBUST_PX, want=('inliers', 'resid')):
+    """points [B,V,K,3] (u, v, weight), pmat [B,V,3,4] -> dict: xyzw [B,K,4] (the DLT over the largest set of views that agree
+    within threshold_px, mean weight of those views), inliers [B,K] uint8 (bit v = view v used, 0 = no two views agreed and
+    all valid views were used), resid [B,K] (RMS reprojection residual of the result over the views used, px)."""
+    points, pmat = _f32(points), _f32(pmat)
+    B, V, K, _ = points.shape
+    if pmat.shape != (B, V, 3, 4):
+        raise RuntimeError('triangulate_robust: projection matrices %s do not match points %s' % (tuple(pmat.shape), tuple(points.shape)))
+    dev = points.device
+    out = {'xyzw': torch.empty(B, K, 4, device=dev)}
+    if 'inliers' in want:
+        out['inliers'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
+    if 'resid' in want:
+        out['resid'] = torch.empty(B, K, device=dev)
+    call('xas_triangulate_robust', ptr(points), ptr(pmat), B, V, K, float(threshold_px), ptr(out['xyzw']),
+         ptr(out.get('inliers')), ptr(out.get('resid')))
+    return out
+
+
 def pose_metrics(pred, gt, mask=None, in_div=1.0, pck_align=0, pck_threshold=0.15,
                  want=('err', 'pck', 'auc_hits')):
     """pred, gt [N,K,3] -> dict: err [3,N,K] (none / scale / procrustes), aligned [2,N,K,3], pck [N,K],
