@@ -632,6 +632,7 @@ int xas_adam_step_guarded_ema(float* p, const float* g, float* m, float* v, floa
 #define XAS_EVAL_CONFIDENT 1      /* take hypothesis 0 (eval.py:144-146) instead of the best one */
 #define XAS_EVAL_SWITCH_ALL 2     /* one switch decision per sample (switch_points(switch_all=True)) */
 #define XAS_EVAL_GT_NORMALISED 4  /* joints already in the detector's output range */
+#define XAS_EVAL_NO_SWITCH 8      /* no partner test: every joint is kept as given (swapped = 0), e.g. after xas_multiview_resolve */
 int xas_eval_select(const float* kps, const float* joints, const int* perm, int B, int Hy, int K, int C,
                     float image_size, int flags, float* sel3d, float* sel2d, float* err2d,
                     unsigned char* swapped, void* stream);
@@ -660,6 +661,36 @@ int xas_triangulate_dlt(const float* points, const float* P, int B, int V, int K
 #define XAS_TRI_MAX_VIEWS 6
 int xas_triangulate_robust(const float* points, const float* P, int B, int V, int K, float threshold_px, float* out,
                            unsigned char* inliers, float* resid, void* stream);
+
+/* Left/right exchange and depth hypothesis of every view WITHOUT labels, by the agreement of the views (eval.py --resolve
+ * views).  Stands beside eval_utils.py:7-29 (switch_points: one label bit per view, joint and hypothesis) and
+ * eval.py:129-148 (best / confident selection against the label), on the DLT of modules/util.py:198-230; the reference has
+ * no counterpart.
+ * points [B][V][K][3] = (u px, v px, weight) and P [B][V][3][4] as for xas_triangulate_dlt (x and y are the same for all
+ * hypotheses); kps [B][V][Hy][K][3] the detector's patch-normalised joints; world [B][V][Hy][K][3] the same joints through
+ * xas_patch_to_world_fwd (single-view world mm); perm [K] as for xas_eval_select (perm[k] == k: unpaired; an entry that
+ * is out of range or not mirrored by its partner also counts as unpaired); gt [B][V][K][3] labels in patch pixels,
+ * normalised with image_size as xas_eval_select does, or NULL.
+ * Stage 1, per sample and pair (a < c = perm[a]): a view is VALID if both joints' weights are finite and > 0; the ANCHOR is
+ * the lowest valid view.  Candidates are the masks m over the valid views with the anchor bit clear.  Under m joint a takes
+ * points[v][c] where bit v is set, else points[v][a]; joint c takes the other one.  Each joint is solved by the weighted DLT
+ * over the valid views (the arithmetic of xas_triangulate_dlt, views in ascending order); cost(m) = the sum over the valid
+ * views of both joints' squared reprojection residuals (+inf behind a camera).  The least cost wins, then the smaller mask.
+ * An unpaired joint is the DLT over its valid views, mask 0.  Fewer than two valid views: xyz = NaN, mask 0.
+ * Stage 2, per view (valid or not) and joint k: s = perm[k] if bit v of the mask is set, else k; h* = argmin_h
+ * |world[b][v][h][s] - xyz[b][k]|^2 in double (first minimum; 0 if xyz is not finite); sel[b][v][k] = kps[b][v][h*][s].
+ * Stage 3, only with gt, per sample and solved pair: a and c are exchanged in the pair's valid views and in xyzw if and only
+ * if that strictly lowers the sum over those views and both joints of |dx| + |dy| of sel against the normalised labels
+ * (the L1 criterion of switch_points, pooled); the mask is then complemented over the valid views.
+ * Outputs: sel [B][V][K][3] (required); each of the others may be NULL: xyzw [B][K][4] = the triangulated point and the mean
+ * weight of the valid views' resolved points (bit-identical to xas_triangulate_dlt on the resolved points where all views are
+ * valid); swap [B][K] (bit v = view v's joint k was taken from perm[k]); hyp [B][V][K] = h*; named [B][K] = 1 where stage
+ * 3 exchanged (written only with gt).
+ * One wave per (b, joint k <= perm[k]), lane = mask: 2 <= V <= XAS_TRI_MAX_VIEWS, 1 <= K <= 64, 1 <= Hy <= 255 (hyp is a
+ * byte), B*K < 2^31.  One launch, no host synchronisation. */
+int xas_multiview_resolve(const float* points, const float* P, const float* kps, const float* world, const int* perm,
+                          const float* gt, int B, int V, int Hy, int K, float image_size, float* sel, float* xyzw,
+                          unsigned char* swap, unsigned char* hyp, unsigned char* named, void* stream);
 
 /* Pose metrics, replaces metrics.py:5-244 (numpy, per-sample SVD on the host).
  * pred, gt [N][K][3]; both are divided by in_div on load (eval.py:52-53 passes mm / 1000 for PCK / AUC);

@@ -8,6 +8,9 @@
 //   triangulate_dlt : modules/util.py:198-230 (null vector of the weighted DLT system)
 //   triangulate_robust : the same DLT over the largest set of views that agree within a pixel threshold (no reference
 //                     counterpart: eval.py --tri robust)
+//   multiview_resolve : the left/right exchange of every view and the depth hypothesis of every view and joint, decided by the
+//                     agreement of the views instead of the labels (stands beside eval_utils.py:7-29 and eval.py:129-148,
+//                     on the DLT of modules/util.py:198-230: eval.py --resolve views)
 //   pose_metrics    : metrics.py:5-244 (MPJPE under none / scale / procrustes alignment, 3DPCK, AUC hit counts)
 //
 // Small symmetric eigenproblems (4x4) are solved with cyclic Jacobi rotations in double precision, fully unrolled
@@ -106,7 +109,7 @@ __global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict
       e_own = wave_sum(on ? e_own : 0.f);
       e_mir = wave_sum(on ? e_mir : 0.f);
     }
-    took = e_mir < e_own;
+    took = !(flags & XAS_EVAL_NO_SWITCH) && e_mir < e_own;
     if (took) { p[0] = m[0]; p[1] = m[1]; p[2] = m[2]; }
     const float d0 = p[0] - g[0], d1 = p[1] - g[1], d2 = p[2] - g[2];
     const float e2 = __fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1));
@@ -342,6 +345,162 @@ __global__ __launch_bounds__(64) void triangulate_robust_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------------
+// multiview_resolve: which views carry a left/right pair exchanged, and which depth hypothesis each view holds, from the
+// views' agreement alone.  One wave per (b, joint a with a <= perm[a]); for a pair (a, c = perm[a]) lane = exchange mask:
+// bit v set gives joint a view v's point of joint c and joint c that of joint a.  The lowest valid view (the anchor) keeps
+// its naming, which halves the masks (m and ~m name the same two points); every other mask over the valid views solves
+// both joints by the DLT above and is scored by the sum of their squared reprojection residuals.  The winning lane holds
+// both solutions, so nothing is solved twice.  Then lane = (joint, view) picks the hypothesis whose single-view world
+// point is nearest the triangulated one, and, only if labels are given, the pair is named once for all views.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void multiview_resolve_kernel(const float* __restrict__ pts, const float* __restrict__ P,
+                                                               const float* __restrict__ kps, const float* __restrict__ world,
+                                                               const int* __restrict__ perm, const float* __restrict__ gt,
+                                                               int V, int Hy, int K, float S, float* __restrict__ sel,
+                                                               float* __restrict__ xyzw, unsigned char* __restrict__ swap,
+                                                               unsigned char* __restrict__ hyp,
+                                                               unsigned char* __restrict__ named) {
+  __shared__ TriView sv[2][XAS_TRI_MAX_VIEWS];                        // [0] joint a, [1] joint c
+  const int i = blockIdx.x, b = i / K, a = i % K;
+  int c = perm[a];
+  if (c < 0 || c >= K || perm[c] != a) c = a;                         // not a pair table here: the joint stands alone
+  if (c < a) return;                                                  // the pair belongs to the block of its lower joint
+  const bool paired = c != a;
+  const int lane = threadIdx.x;
+  const int j = lane >> 5, v = lane & 31;                             // lanes 0..V-1: joint a's views, 32..32+V-1: joint c's
+  const bool stager = v < V && (j == 0 || paired);
+  const int k = j ? c : a, kp = j ? a : c;                            // this lane's joint and its partner
+  bool ok = false;
+  if (stager) {
+    const float* q = pts + (((size_t)b * V + v) * K + k) * 3;
+    const float* Pm = P + ((size_t)b * V + v) * 12;
+    TriView& s = sv[j][v];
+    s.u = q[0]; s.v = q[1]; s.w = q[2]; s.pad = 0.f;
+#pragma unroll
+    for (int n = 0; n < 12; ++n) s.P[n] = Pm[n];
+    double t[10];
+    dlt_view_gram(s.u, s.v, s.w, Pm, t);
+#pragma unroll
+    for (int n = 0; n < 10; ++n) s.gram[n] = t[n];
+    ok = s.w > 0.f && s.w < INFINITY;
+  }
+  const unsigned long long bal = __ballot(ok);
+  const int va = (int)(bal & 63ull), vc = (int)((bal >> 32) & 63ull);
+  const int valid = paired ? (va & vc) : va;                          // a view counts for the pair if it sees both joints
+  __syncthreads();
+  const int nvalid = __popc(valid);
+  const bool solved = nvalid >= 2;
+  const int anchor = valid ? __ffs(valid) - 1 : 0;
+
+  // --- stage 1: candidate = this lane's mask, if it exchanges valid views only and leaves the anchor alone
+  const bool cand = solved && (lane & ~valid) == 0 && !((lane >> anchor) & 1) && (paired || lane == 0);
+  double Xa[4] = {0.0, 0.0, 0.0, 0.0}, Xc[4] = {0.0, 0.0, 0.0, 0.0};
+  double cost = INFINITY;
+  if (cand) {
+    cost = 0.0;
+#pragma unroll 1
+    for (int jj = 0; jj < 2; ++jj) {
+      if (jj == 1 && !paired) break;
+      double g[4][4], X[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) g[r][cc] = 0.0;
+#pragma unroll
+      for (int w = 0; w < XAS_TRI_MAX_VIEWS; ++w)
+        if ((valid >> w) & 1) dlt_gram_add(g, sv[jj ^ ((lane >> w) & 1)][w].gram);
+      dlt_null_vector(g, X);
+#pragma unroll
+      for (int w = 0; w < XAS_TRI_MAX_VIEWS; ++w)
+        if ((valid >> w) & 1) cost += reproj_r2(sv[jj ^ ((lane >> w) & 1)][w], X);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (jj == 0) Xa[r] = X[r]; else Xc[r] = X[r];
+      }
+    }
+    if (!(cost < INFINITY)) cost = INFINITY;                          // NaN too: the order below must be total
+  }
+  // --- wave arg-best: a candidate before none, then the smaller cost, then the smaller mask (a total order)
+  int bnc = cand ? 0 : 1, bid = lane;
+  double bcost = cost;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int onc = __shfl_xor(bnc, o, 64), oid = __shfl_xor(bid, o, 64);
+    const double ocost = __shfl_xor(bcost, o, 64);
+    const bool take = onc < bnc || (onc == bnc && (ocost < bcost || (ocost == bcost && oid < bid)));
+    if (take) { bnc = onc; bid = oid; bcost = ocost; }
+  }
+  const int win = solved ? bid : 0;
+  float xa[3], xc[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    xa[r] = solved ? __shfl((float)(Xa[r] / Xa[3]), win, 64) : NAN;
+    xc[r] = solved ? (paired ? __shfl((float)(Xc[r] / Xc[3]), win, 64) : xa[r]) : NAN;
+  }
+  float wa = 0.f, wc = 0.f;                                           // mean weight of the views used, ascending
+#pragma unroll
+  for (int w = 0; w < XAS_TRI_MAX_VIEWS; ++w)
+    if ((valid >> w) & 1) {
+      const int bit = (win >> w) & 1;
+      wa += sv[bit][w].w;
+      if (paired) wc += sv[1 ^ bit][w].w;
+    }
+  wa = wa / (float)nvalid;
+  wc = wc / (float)nvalid;
+
+  // --- stage 2: lane = (joint, view), every view, valid or not
+  const bool swapped = ((win >> v) & 1) != 0;
+  const int src = swapped ? kp : k;
+  int hs = 0;
+  float s3[3] = {0.f, 0.f, 0.f};
+  if (stager) {
+    const double x0 = j ? xc[0] : xa[0], x1 = j ? xc[1] : xa[1], x2 = j ? xc[2] : xa[2];
+    double best = INFINITY;
+    for (int h = 0; h < Hy; ++h) {
+      const float* wp = world + ((((size_t)b * V + v) * Hy + h) * K + src) * 3;
+      const double d0 = (double)wp[0] - x0, d1 = (double)wp[1] - x1, d2 = (double)wp[2] - x2;
+      const double d = d0 * d0 + d1 * d1 + d2 * d2;
+      if (d < best) { best = d; hs = h; }                             // first minimum; NaN or inf never wins: h = 0
+    }
+    const float* q = kps + ((((size_t)b * V + v) * Hy + hs) * K + src) * 3;
+    s3[0] = q[0]; s3[1] = q[1]; s3[2] = q[2];
+  }
+  // --- stage 3: which of the two consistent namings is "left" - the one bit only labels can give
+  bool ex = false;
+  if (gt && paired && solved) {                                       // uniform over the wave
+    float own = 0.f, oth = 0.f;
+    if (stager && ((valid >> v) & 1)) {
+      const float* gk = gt + (((size_t)b * V + v) * K + k) * 3;
+      const float* gp = gt + (((size_t)b * V + v) * K + kp) * 3;
+      own = fabsf(s3[0] - (gk[0] / (S - 1.f) * 2.f - 1.f)) + fabsf(s3[1] - (gk[1] / (S - 1.f) * 2.f - 1.f));
+      oth = fabsf(s3[0] - (gp[0] / (S - 1.f) * 2.f - 1.f)) + fabsf(s3[1] - (gp[1] / (S - 1.f) * 2.f - 1.f));
+    }
+    const double sown = wave_sum_d((double)own), soth = wave_sum_d((double)oth);
+    ex = soth < sown;
+  }
+  if (stager) {
+    const int dst = (ex && ((valid >> v) & 1)) ? kp : k;
+    const size_t o = ((size_t)b * V + v) * K + dst;
+    sel[o * 3] = s3[0]; sel[o * 3 + 1] = s3[1]; sel[o * 3 + 2] = s3[2];
+    if (hyp) hyp[o] = (unsigned char)hs;
+  }
+  if (lane == 0) {
+    const unsigned char fm = (unsigned char)(ex ? (win ^ valid) : win);
+    const size_t oa = (size_t)b * K + a, oc = (size_t)b * K + c;
+    if (xyzw) {
+      float* o = xyzw + oa * 4;
+      o[0] = ex ? xc[0] : xa[0]; o[1] = ex ? xc[1] : xa[1]; o[2] = ex ? xc[2] : xa[2]; o[3] = ex ? wc : wa;
+      if (paired) {
+        o = xyzw + oc * 4;
+        o[0] = ex ? xa[0] : xc[0]; o[1] = ex ? xa[1] : xc[1]; o[2] = ex ? xa[2] : xc[2]; o[3] = ex ? wa : wc;
+      }
+    }
+    if (swap) { swap[oa] = fm; swap[oc] = fm; }
+    if (named && gt) { named[oa] = ex ? 1 : 0; named[oc] = ex ? 1 : 0; }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // pose_metrics: one wave per sample, lane = joint.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float norm3(float a, float b, float c) {
@@ -486,6 +645,24 @@ extern "C" int xas_triangulate_robust(const float* points, const float* P, int B
   XAS_REQUIRE(threshold_px > 0.f, "triangulate_robust: threshold_px %f (needs a threshold > 0 px)", (double)threshold_px);
   hipLaunchKernelGGL(triangulate_robust_kernel, dim3((unsigned)((long)B * K)), dim3(64), 0, as_stream(stream), points, P, V, K,
                      threshold_px, out, inliers, resid);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_multiview_resolve(const float* points, const float* P, const float* kps, const float* world,
+                                     const int* perm, const float* gt, int B, int V, int Hy, int K, float image_size,
+                                     float* sel, float* xyzw, unsigned char* swap, unsigned char* hyp,
+                                     unsigned char* named, void* stream) {
+  XAS_REQUIRE(points && P && kps && world && perm && sel,
+              "multiview_resolve: null buffer (points, P, kps, world, perm and sel are required)");
+  XAS_REQUIRE(V >= 2 && V <= XAS_TRI_MAX_VIEWS, "multiview_resolve: V=%d views (needs 2 <= V <= XAS_TRI_MAX_VIEWS = %d)", V,
+              XAS_TRI_MAX_VIEWS);
+  XAS_REQUIRE(K >= 1 && K <= 64, "multiview_resolve: K=%d joints (needs 1 <= K <= 64)", K);
+  XAS_REQUIRE(Hy >= 1 && Hy <= 255, "multiview_resolve: Hy=%d hypotheses (needs 1 <= Hy <= 255)", Hy);
+  XAS_REQUIRE(B > 0 && (long)B * K <= 0x7fffffffL, "multiview_resolve: bad shape B=%d K=%d (B > 0, B*K < 2^31)", B, K);
+  XAS_REQUIRE(!gt || image_size > 1.f, "multiview_resolve: image_size %f (labels need a patch size > 1)", (double)image_size);
+  hipLaunchKernelGGL(multiview_resolve_kernel, dim3((unsigned)((long)B * K)), dim3(64), 0, as_stream(stream), points, P, kps,
+                     world, perm, gt, V, Hy, K, image_size, sel, xyzw, swap, hyp, named);
   XAS_LAUNCH_CHECK();
   return 0;
 }

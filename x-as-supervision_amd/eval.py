@@ -3,7 +3,7 @@
 
     torchrun --nproc-per-node=N eval.py --config config/HM36_Multi_SurS1.yaml --checkpoint ckpt.pth.tar
              [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
-             [--tri dlt|robust --tri_thresh PX]
+             [--tri dlt|robust --tri_thresh PX] [--resolve gt|views]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -12,6 +12,12 @@ host transfer of the per-sample numbers that the per-action tables (host diction
 accumulate.  The reference does the same work with per-hypothesis tensor chains, a batched fp32 SVD and numpy
 SVDs on the host (eval.py:111-204, metrics.py).  TensorBoard pose images (eval.py:150-156,172-202) are
 visualisation and are not rebuilt.
+
+--resolve views (opt-in; the default, gt, is the reference's evaluation unchanged) decides the left/right exchange of every
+view and the depth hypothesis of every view and joint from the agreement of the cameras in one launch
+(ops_eval.multiview_resolve) instead of from the labels; the labels then only name each left/right pair, once per sample for
+all views.  --multi_hypo is ignored in that mode.  No accuracy or time figure of that mode has been measured, neither on real
+data nor on the device.
 """
 import copy
 import os
@@ -27,7 +33,7 @@ from torch.distributed import destroy_process_group, init_process_group
 from metrics import pose_errors
 from modules.keypoint_detector_integral import KPDetector3D as KPDetector3D_integral
 from modules.keypoint_detector_integral_multi import KPDetector3DMulti as KPDetector3DMulti_integral
-from modules.util import convert_patch_to_world, triangulation
+from modules.util import convert_patch_to_world, resolve_views, triangulation
 from eval_utils import cal_per_class_error
 from xas_amd import ops_eval
 from xas_amd.synthetic import synthetic_eval_batch
@@ -56,9 +62,11 @@ class Eval:
     """Same constructor and method signatures as the reference Eval (eval.py:63-107)."""
 
     def __init__(self, config, detector, eval_data, log_dir, img_size=256.0, flip_test=False, tri='dlt',
-                 tri_thresh=ops_eval.TRI_ROBUST_PX):
+                 tri_thresh=ops_eval.TRI_ROBUST_PX, resolve='gt'):
         if tri not in ('dlt', 'robust'):
             raise ValueError('Unknown triangulation: {}'.format(tri))
+        if resolve not in ('gt', 'views'):
+            raise ValueError('Unknown resolve mode: {}'.format(resolve))
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -71,6 +79,11 @@ class Eval:
         self.flip_test = bool(flip_test)           # --flip: every image is evaluated together with its horizontal mirror
         self.tri, self.tri_thresh = tri, float(tri_thresh)   # --tri robust: DLT over the views that agree within tri_thresh px
         self.tri_views, self.tri_batches = 0.0, 0  # robust only: mean views used per joint, summed over the batches
+        self.resolve = resolve                     # --resolve views: exchange and hypothesis by the cameras' agreement
+        if resolve == 'views' and not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
+            raise ValueError("resolve='views' decides by the agreement of the cameras and needs 2 to {} of them; cam_id_list "
+                             'has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
+        self.res_exchanged, self.res_hyp0, self.res_batches = 0.0, 0.0, 0      # views only, summed over the batches
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -92,10 +105,26 @@ class Eval:
     @torch.no_grad()
     def eval_batch(self, x, mode='best', kps_by_cam=None):
         """Device part of one iteration of eval.py:111-204.  Returns ({name: tensor on the device}, layout) where
-        every tensor is per sample [B] (errors), or a scalar (ambiguity, pck, auc)."""
+        every tensor is per sample [B] (errors), or a scalar (ambiguity, pck, auc).  With resolve='views' `mode` is ignored:
+        the cameras' agreement picks the hypotheses."""
         cams = ['cam_{}'.format(c) for c in self.cam_id_list]
         sel, out, trans = {}, {}, None
-        for m in cams:
+        if self.resolve == 'views':
+            raw = {m: kps_by_cam[m] if kps_by_cam is not None else self.detect(x[m + '_img']) for m in cams}
+            sel, r = resolve_views(raw, x, self.cam_id_list, ops_eval.SWITCH_PAIRS, gt=True)
+            for m in cams:                         # the labels' part from here on: measuring, no longer choosing
+                out['err2d_' + m] = ops_eval.eval_select(sel[m].unsqueeze(1), x[m + '_joints'], image_size=self.img_size,
+                                                         mode='confident', no_switch=True, want=('err2d',))['err2d']
+            shifts = torch.arange(len(cams), device=r['swap'].device, dtype=torch.int32)
+            count = lambda mask: ((mask.unsqueeze(-1).int() >> shifts) & 1).sum(dim=-1).float()     # [B,K] bits set
+            trans = count(r['swap']).unsqueeze(-1)
+            B, K = r['swap'].shape
+            perm = ops_eval.switch_perm(K, ops_eval.SWITCH_PAIRS, shifts.device)
+            paired = (perm != torch.arange(K, device=shifts.device, dtype=torch.int32)).float()       # [K], both of a pair
+            before = torch.where(r['named'].bool(), count(r['valid']) - count(r['swap']), count(r['swap']))   # naming undone
+            out['resolve_exchanged'] = (before * paired).sum() / (paired.sum().clamp(min=1.0) * B * len(cams))
+            out['resolve_hyp0'] = (r['hyp'] == 0).float().mean()
+        for m in ([] if self.resolve == 'views' else cams):
             kps = kps_by_cam[m] if kps_by_cam is not None else self.detect(x[m + '_img'])
             s = ops_eval.eval_select(kps, x[m + '_joints'], image_size=self.img_size, mode=mode)
             sel[m] = s['sel3d']
@@ -142,6 +171,10 @@ class Eval:
             if 'tri_inlier_views' in host:
                 self.tri_views += float(host['tri_inlier_views'])
                 self.tri_batches += 1
+            if 'resolve_hyp0' in host:
+                self.res_exchanged += float(host['resolve_exchanged'])
+                self.res_hyp0 += float(host['resolve_hyp0'])
+                self.res_batches += 1
             for table, count, names in ((record_3d_tri_table, count_3d_tri_table, ['tri']),
                                         (record_3d_table, count_3d_table, ['view_' + m for m in cams])):
                 for name in names:
@@ -187,6 +220,9 @@ class Eval:
         if self.tri == 'robust':                   # after the reference's lines; --tri dlt leaves the file as it was
             lines.append('TRI inlier views ({} px): {} of {}'.format(self.tri_thresh, self.tri_views / max(self.tri_batches, 1),
                                                                      len(self.cam_id_list)))
+        if self.resolve == 'views':                # after everything else; --resolve gt leaves the file as it was
+            n = max(self.res_batches, 1)
+            lines.append('RESOLVE views: exchanged {} , hypothesis 0 kept {}'.format(self.res_exchanged / n, self.res_hyp0 / n))
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -253,7 +289,8 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--batch_size', dict(default=None, type=int)),
     ('--worker', dict(default=10, type=int)),
     ('--extra_tag', dict(default=' ')),
-    ('--multi_hypo', dict(default='best', choices=['best', 'confident'], help='multi-hypothesis eval mode')),
+    ('--multi_hypo', dict(default='best', choices=['best', 'confident'],
+                          help='multi-hypothesis eval mode (ignored with --resolve views)')),
     ('--synthetic', dict(default=0, type=int, help='evaluate N synthetic batches (no dataset on this machine)')),
     ('--ema', dict(default=False, action='store_true', help="evaluate the averaged weights ('unsup_model_ema')")),
     ('--flip', dict(default=False, action='store_true',
@@ -262,6 +299,9 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
                    help='triangulation: the DLT over all cameras, or over the largest set of cameras that agree within --tri_thresh')),
     ('--tri_thresh', dict(default=ops_eval.TRI_ROBUST_PX, type=float, metavar='PX',
                           help='--tri robust: inlier threshold in pixels of the full-resolution image')),
+    ('--resolve', dict(default='gt', choices=['gt', 'views'],
+                       help='left/right exchange and depth hypothesis of every view: by the labels as the reference does, or by '
+                            'the agreement of the cameras (labels only name each pair; --multi_hypo is ignored)')),
 )
 
 
@@ -282,7 +322,8 @@ def main():
     log_dir = os.path.dirname(opt.checkpoint) if opt.checkpoint else opt.log_dir
     detector = prepare_model(config, opt)
     loader = prepare_data(config, world, opt.worker, opt.synthetic, torch.device('cuda', rank_local))
-    ev = Eval(config, detector, loader, log_dir, flip_test=opt.flip, tri=opt.tri, tri_thresh=opt.tri_thresh)
+    ev = Eval(config, detector, loader, log_dir, flip_test=opt.flip, tri=opt.tri, tri_thresh=opt.tri_thresh,
+              resolve=opt.resolve)
     tables = init_tables(ev.cal_per_act)
     record = ev.eval(None, *tables, mode=opt.multi_hypo)
     destroy_process_group()

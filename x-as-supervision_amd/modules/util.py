@@ -3,7 +3,8 @@
 Built here: `draw_lines` (+ the fused `draw_lines_max` the model actually consumes),
 `convert_patch_to_world` (all hypotheses in one launch, closed-form 2x2 / 3x3 inverses),
 `make_coordinate_grid`, `smpl_to_h36m`, and for the evaluation path `convert_patch_to_image`,
-`triangulation` / `batch_triangulate` (device DLT, no batched SVD), and the SMPL side of the geometry:
+`triangulation` / `batch_triangulate` (device DLT, no batched SVD), `resolve_views` (left/right exchange and depth hypothesis by
+the cameras' agreement, no reference counterpart), and the SMPL side of the geometry:
 `project_smpl_to_patch_kps`, `convert_pelvis_to_world` (one world->patch launch, ops_head.world_to_patch) and `flip_3D`.
 `convert_world_to_patch` / `convert_world_to_image` / `convert_image_to_patch` stay the reference's (the device version is
 ops_head.world_to_patch).  The reference's dead code (rule_transformation, my_truncated_normal) is not rebuilt
@@ -85,6 +86,36 @@ def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000,
     r = ops_eval.triangulate_robust(torch.stack(pts, dim=1), torch.stack(pm, dim=1), threshold_px=robust_px,
                                     want=('inliers',) if return_inliers else ())
     return (r['xyzw'][..., :3], r['inliers']) if return_inliers else r['xyzw'][..., :3]
+
+
+def resolve_views(kps_by_cam, params, cam_id_list, pairs, gt=True, RECT_WIDTH=2000):
+    """{cam_key: [B,Hy,K,3]} raw detections of all cameras -> ({cam_key: [B,K,3]} resolved joints, the other outputs of
+    ops_eval.multiview_resolve).  The left/right exchange of every view and the depth hypothesis of every view and joint are
+    decided by the agreement of the cameras; with `gt` the labels (`<cam>_joints`) name each pair once for all views, and
+    nothing else is read from them.  Bit i of `swap` is cam_id_list[i].  No reference counterpart."""
+    modes = ['cam_{}'.format(c) for c in cam_id_list]
+    pts, pm, world, kps = [], [], [], []
+    for mode in modes:
+        k = kps_by_cam[mode]
+        size = params['{}_img'.format(mode)].shape[-1]
+        pts.append(ops_eval.patch_to_image(k[:, 0], params['{}_trans_image'.format(mode)], params['{}_pelvis'.format(mode)],
+                                           image_size=size, rect_width=RECT_WIDTH))
+        pm.append(ops_eval.projection_matrix(params['{}_k_mat'.format(mode)], params['{}_rot_world'.format(mode)],
+                                             params['{}_trans_world'.format(mode)]))
+        world.append(convert_patch_to_world(k, params, mode, is_norm=True, RECT_WIDTH=RECT_WIDTH))
+        kps.append(k)
+    labels = torch.stack([params[mode + '_joints'] for mode in modes], dim=1) if gt else None
+    r = ops_eval.multiview_resolve(torch.stack(pts, dim=1), torch.stack(pm, dim=1), torch.stack(kps, dim=1),
+                                   torch.stack(world, dim=1), pairs=pairs, gt=labels, image_size=size)
+    sel = r.pop('sel')
+    # the views that took part, [B,K] bit masks like `swap` (derived here, the kernel keeps it to itself): finite weight > 0
+    # for the joint and for its partner
+    w = torch.stack(pts, dim=1)[..., 2]
+    ok = torch.isfinite(w) & (w > 0)
+    ok = ok & ok[..., ops_eval.switch_perm(w.shape[-1], pairs, w.device).long()]
+    bit = (1 << torch.arange(len(modes), device=w.device, dtype=torch.int32)).view(1, -1, 1)
+    r['valid'] = (ok.int() * bit).sum(dim=1).to(torch.uint8)
+    return {mode: sel[:, i] for i, mode in enumerate(modes)}, r
 
 
 def smpl_to_h36m(verts, h36m_regressor):

@@ -139,6 +139,7 @@ SIGNATURES = {
     'xas_projection_matrix': ('pppipp', 'i'),
     'xas_triangulate_dlt': ('ppiiipp', 'i'),
     'xas_triangulate_robust': ('ppiiifpppp', 'i'),
+    'xas_multiview_resolve': ('ppppppiiiifpppppp', 'i'),
     'xas_pose_metrics': ('pppiififppppp', 'i'),
 }
 

@@ -6,7 +6,7 @@ from ._lib import call, ptr
 from .ops_head import GEO_NORM, GEO_PATCH
 
 GEO_IMAGE = 8
-EVAL_CONFIDENT, EVAL_SWITCH_ALL, EVAL_GT_NORMALISED = 1, 2, 4
+EVAL_CONFIDENT, EVAL_SWITCH_ALL, EVAL_GT_NORMALISED, EVAL_NO_SWITCH = 1, 2, 4, 8
 SWITCH_PAIRS = ((1, 4), (2, 5), (3, 6), (14, 11), (15, 12), (16, 13))     # eval_utils.py:8
 
 _perm_cache = {}
@@ -27,8 +27,9 @@ def _f32(t):
 
 
 def eval_select(kps, joints, pairs=SWITCH_PAIRS, image_size=256.0, mode='best', switch_all=False, gt_normalised=False,
-                want=('sel3d', 'sel2d', 'err2d', 'swapped')):
-    """kps [B,Hy,K,C], joints [B,K,C] -> dict of the requested outputs (eval.py:117-148 for one camera)."""
+                want=('sel3d', 'sel2d', 'err2d', 'swapped'), no_switch=False):
+    """kps [B,Hy,K,C], joints [B,K,C] -> dict of the requested outputs (eval.py:117-148 for one camera).  `no_switch`: the
+    partner test is skipped and every joint kept as given (for joints that multiview_resolve has already resolved)."""
     if mode not in ('best', 'confident'):
         raise ValueError('Unknown mode: {}'.format(mode))
     kps, joints = _f32(kps), _f32(joints)
@@ -37,7 +38,7 @@ def eval_select(kps, joints, pairs=SWITCH_PAIRS, image_size=256.0, mode='best', 
         raise RuntimeError('eval_select: joints %s do not match kps %s' % (tuple(joints.shape), tuple(kps.shape)))
     dev = kps.device
     flags = (EVAL_CONFIDENT if (mode == 'confident' or Hy == 1) else 0) | (EVAL_SWITCH_ALL if switch_all else 0) | \
-        (EVAL_GT_NORMALISED if gt_normalised else 0)
+        (EVAL_GT_NORMALISED if gt_normalised else 0) | (EVAL_NO_SWITCH if no_switch else 0)
     out = {}
     if 'sel3d' in want:
         out['sel3d'] = torch.empty(B, K, C, device=dev)
@@ -107,6 +108,41 @@ def triangulate_robust(points, pmat, threshold_px=TRI_ROBUST_PX, want=('inliers'
         out['resid'] = torch.empty(B, K, device=dev)
     call('xas_triangulate_robust', ptr(points), ptr(pmat), B, V, K, float(threshold_px), ptr(out['xyzw']),
          ptr(out.get('inliers')), ptr(out.get('resid')))
+    return out
+
+
+def multiview_resolve(points, pmat, kps, world, pairs=SWITCH_PAIRS, gt=None, image_size=256.0,
+                      want=('xyzw', 'swap', 'hyp', 'named')):
+    """Left/right exchange and depth hypothesis of every view from the agreement of the views (xas_multiview_resolve).
+    points [B,V,K,3] (u, v, weight; one per joint, the hypotheses share x and y), pmat [B,V,3,4], kps and world [B,V,Hy,K,3]
+    (patch-normalised joints and their single-view world points), gt [B,V,K,3] patch pixels or None (only names the pair).
+    -> dict: sel [B,V,K,3] always; xyzw [B,K,4], swap [B,K] uint8 (bit v = view v's joint was taken from its partner),
+    hyp [B,V,K] uint8, named [B,K] uint8 (only with gt) as requested."""
+    points, pmat, kps, world = _f32(points), _f32(pmat), _f32(kps), _f32(world)
+    B, V, K, _ = points.shape
+    if pmat.shape != (B, V, 3, 4):
+        raise RuntimeError('multiview_resolve: projection matrices %s do not match points %s' % (tuple(pmat.shape), tuple(points.shape)))
+    if kps.dim() != 5 or kps.shape[:2] != (B, V) or kps.shape[3:] != (K, 3):
+        raise RuntimeError('multiview_resolve: kps %s do not match points %s' % (tuple(kps.shape), tuple(points.shape)))
+    if world.shape != kps.shape:
+        raise RuntimeError('multiview_resolve: world %s and kps %s differ' % (tuple(world.shape), tuple(kps.shape)))
+    if gt is not None:
+        gt = _f32(gt)
+        if gt.shape != (B, V, K, 3):
+            raise RuntimeError('multiview_resolve: labels %s do not match points %s' % (tuple(gt.shape), tuple(points.shape)))
+    Hy, dev = kps.shape[2], points.device
+    out = {'sel': torch.empty(B, V, K, 3, device=dev)}
+    if 'xyzw' in want:
+        out['xyzw'] = torch.empty(B, K, 4, device=dev)
+    if 'swap' in want:
+        out['swap'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
+    if 'hyp' in want:
+        out['hyp'] = torch.empty(B, V, K, device=dev, dtype=torch.uint8)
+    if 'named' in want and gt is not None:
+        out['named'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
+    call('xas_multiview_resolve', ptr(points), ptr(pmat), ptr(kps), ptr(world), ptr(switch_perm(K, pairs, dev)), ptr(gt),
+         B, V, Hy, K, float(image_size), ptr(out['sel']), ptr(out.get('xyzw')), ptr(out.get('swap')), ptr(out.get('hyp')),
+         ptr(out.get('named')))
     return out
 
 
