@@ -152,6 +152,18 @@ int xas_head_softargmax_bwd_amax(const float* logits, const float* stats, const 
                                  const float* grad_kps, int B, int K, int D, int num_hypo, int neighbor,
                                  float* grad_logits, float* coef, float* amax_out, void* stream);
 
+/* Heat-map spread: the spatial confidence of every joint (no counterpart in the reference).  With p the soft-max over a
+ * joint's D*H*W logits and q(h, w) = sum_d p its x-y marginal,
+ *   spread [B][K][XAS_HEAD_SPREAD] = { E_q[w], E_q[h], Var_q[w], Var_q[h], Cov_q[w, h] }   in heat-map cells,
+ * w and h being the integer cell indices.  logits, the accepted (D, K) and the refusals (status 1, workspace size 0, a
+ * message that names the range) are those of xas_head_softargmax_fwd.  One streaming pass with its own online soft-max (the
+ * logits are read once), records in mean / centred-second-moment form merged pairwise in a fixed order (no atomics: two calls
+ * agree bit for bit), then one wave per (b, k).  Variances are >= 0; a NaN logit makes that joint's five numbers NaN and no
+ * other's.  workspace: xas_head_spread_workspace_floats(B, K, D) floats ([B][nchunk][K][7] records).  Forward only. */
+#define XAS_HEAD_SPREAD 5
+size_t xas_head_spread_workspace_floats(int B, int K, int D);
+int xas_head_spread(const float* logits, int B, int K, int D, float* spread /*[B][K][5]*/, float* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Patch -> world geometry, all hypotheses in one launch.
  * Replaces modules/util.py:128-152 -> :61-95 (clone/index_put chains + two batched

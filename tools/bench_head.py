@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Soft-argmax head kernels alone at the BASELINE size (B=32, K=18, D=H=W=64): achieved HBM GB/s.
+"""Soft-argmax head kernels and the heat-map spread kernel alone at the BASELINE size (B=32, K=18, D=H=W=64): achieved HBM GB/s.
 usage: bench_head.py [B] [--depth D]      D: cube side (64; e.g. 96 for 384^2 patches - the head's general policy)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,3 +34,13 @@ nbytes = B * 18 * D * D * D * 4
 print('D=%d B=%d' % (D, B))
 print('head fwd  %.1f us  %.0f GB/s (reads %d MB once)' % (tf / reps * 1e3, nbytes / (tf / reps * 1e-3) / 1e9, nbytes >> 20))
 print('head bwd  %.1f us  %.0f GB/s (read + write)' % (tb / reps * 1e3, 2 * nbytes / (tb / reps * 1e-3) / 1e9))
+lg = lg.detach()
+ops_head.heatmap_spread(lg, 18)
+ts = 0.0
+for _ in range(reps):
+    a.record()
+    ops_head.heatmap_spread(lg, 18)
+    b.record()
+    torch.cuda.synchronize()
+    ts += a.elapsed_time(b)
+print('head spread  %.1f us  %.0f GB/s (reads %d MB once)' % (ts / reps * 1e3, nbytes / (ts / reps * 1e-3) / 1e9, nbytes >> 20))

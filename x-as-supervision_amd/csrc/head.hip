@@ -13,6 +13,8 @@
 // peaks (value desc, index asc), windowed expectation, write kps / indices / stats.
 // Pass 2 of the flip test (head_finalize_flip_kernel): the same, on the average of an image's heat-map and the mirrored,
 // left/right-swapped heat-map of its mirror image, formed from the two images' records.
+// Heat-map spread (head_spread_partial_kernel, head_spread_finalize_kernel): mean and covariance of every joint's x-y marginal,
+// a pass of its own on the same geometry and policies, for the evaluation's triangulation weights.
 //
 // One kernel family, two policies (template parameter POW2 of the partial and backward kernels):
 //   * power of two, D in {4,8,16,32,64} where that block exists for K (pow2_policy): pix -> (h, w) is shift/mask; the
@@ -418,6 +420,174 @@ __global__ void head_bwd_kernel(const float4* __restrict__ logits, const float* 
   }
 }
 
+// ---- heat-map spread: mean and covariance of every joint's x-y marginal, in cells (xas_head_spread) ------------------------
+// No counterpart in the reference: the spatial spread of the soft-max heat-map as a per-view confidence.  Self-contained (its
+// own online soft-max, the logits read once) on the geometry, thread mapping and two policies of head_partial_kernel.
+//
+// A record is a weighted sample in mean / centred-second-moment form, its weights scaled by exp(-m):
+//   {m, S = sum e, uw, uh = weighted means of w, h, Mw, Mh = sum e (w - uw)^2, sum e (h - uh)^2, C = sum e (w - uw)(h - uh)}.
+// Records merge pairwise (Chan et al.): with Sa, Sb the two weights on the common scale exp(-max(ma, mb)), f = Sb / (Sa + Sb)
+// and d = ub - ua,
+//   u = ua + d f,   M = Ma + Mb + d^2 Sa f,   C = Ca + Cb + dw dh Sa f.
+// Every added term of a second moment is a square times a weight, so nothing cancels: E[w^2] - E[w]^2 loses four digits for a
+// one-cell peak at w = 127 and can go negative.  A pixel enters as the one-point record {es, w, h, 0, 0, 0}.  The merge order
+// is fixed at every level (pixels of a thread, lanes of a group, slots of a block, chunks of an image): no atomics.
+// A NaN logit never becomes a maximum (fmaxf) but makes its exponential, hence S and every moment of that joint, NaN.
+struct SpreadRec { float m, S, uw, uh, Mw, Mh, C; };
+constexpr int kSpreadRec = 7;
+
+__device__ __forceinline__ SpreadRec spread_merge(const SpreadRec& a, const SpreadRec& b) {
+  SpreadRec r;
+  r.m = fmaxf(a.m, b.m);
+  const float sa = (a.m == -INFINITY) ? 0.f : __expf(a.m - r.m), sb = (b.m == -INFINITY) ? 0.f : __expf(b.m - r.m);
+  const float Sa = a.S * sa, Sb = b.S * sb;
+  r.S = Sa + Sb;
+  const float f = (r.S == 0.f) ? 0.f : Sb / r.S;     // (NaN == 0 is false: a NaN weight goes through)
+  const float x = Sa * f, dw = b.uw - a.uw, dh = b.uh - a.uh;
+  r.uw = a.uw + dw * f;
+  r.uh = a.uh + dh * f;
+  r.Mw = a.Mw * sa + b.Mw * sb + dw * dw * x;
+  r.Mh = a.Mh * sa + b.Mh * sb + dh * dh * x;
+  r.C = a.C * sa + b.C * sb + dw * dh * x;
+  return r;
+}
+
+// One pixel of weight es (already on the record's scale) at cell (fw, fh): spread_merge with a one-point record.
+__device__ __forceinline__ void spread_add(SpreadRec& r, float es, float fw, float fh) {
+  const float Sn = r.S + es;
+  const float f = (Sn == 0.f) ? 0.f : __fdividef(es, Sn);
+  const float x = r.S * f, dw = fw - r.uw, dh = fh - r.uh;
+  r.S = Sn;
+  r.uw += dw * f;
+  r.uh += dh * f;
+  r.Mw += dw * dw * x;
+  r.Mh += dh * dh * x;
+  r.C += dw * dh * x;
+}
+
+__device__ __forceinline__ void spread_rescale(SpreadRec& r, float mn) {
+  const float sc = __expf(r.m - mn);                 // exp(-inf) = 0 before the first pixel
+  r.m = mn;
+  r.S *= sc; r.Mw *= sc; r.Mh *= sc; r.C *= sc;
+}
+
+__device__ __forceinline__ SpreadRec spread_read(const float* p) { return {p[0], p[1], p[2], p[3], p[4], p[5], p[6]}; }
+__device__ __forceinline__ void spread_write(float* p, const SpreadRec& r) {
+  p[0] = r.m; p[1] = r.S; p[2] = r.uw; p[3] = r.uh; p[4] = r.Mw; p[5] = r.Mh; p[6] = r.C;
+}
+
+// The record of the G lanes of this thread's (slot, joint), merged in lane order (valid in the group's first thread, `lead`):
+// xor tree whose lower lane is always the left operand, or through s[blockDim.x][7] one lane after the other.
+template <bool POW2>
+__device__ SpreadRec group_merge(SpreadRec r, int G, int dq, float* s, int lead) {
+  if constexpr (POW2) {
+    for (int o = 1; o < G; o <<= 1) {
+      SpreadRec t;
+      t.m = __shfl_xor(r.m, o, 64); t.S = __shfl_xor(r.S, o, 64); t.uw = __shfl_xor(r.uw, o, 64); t.uh = __shfl_xor(r.uh, o, 64);
+      t.Mw = __shfl_xor(r.Mw, o, 64); t.Mh = __shfl_xor(r.Mh, o, 64); t.C = __shfl_xor(r.C, o, 64);
+      r = (dq & o) ? spread_merge(t, r) : spread_merge(r, t);
+    }
+    return r;
+  } else {
+    spread_write(s + (size_t)threadIdx.x * kSpreadRec, r);
+    __syncthreads();
+    if ((int)threadIdx.x == lead)
+      for (int j = 1; j < G; ++j) r = spread_merge(r, spread_read(s + (size_t)(lead + j) * kSpreadRec));
+    return r;
+  }
+}
+
+static size_t spread_lds_bytes(const HeadGeom& g, bool pow2) {
+  return ((size_t)g.R * g.KT + (pow2 ? 0 : (size_t)g.C4t * g.R)) * kSpreadRec * sizeof(float);
+}
+
+// First pass: per (b, pixel chunk, joint) one record, [B][nchunk][K][7].
+template <bool POW2>
+__global__ void head_spread_partial_kernel(const float4* __restrict__ logits, float* __restrict__ partial, HeadGeom g) {
+  extern __shared__ float smem[];            // [R][KT][7] slot records; general: then [blockDim][7] lane records
+  const int KT = POW2 ? g.K : g.KT, C4t = POW2 ? g.C4 : g.C4t;
+  float* s_lane = smem + (size_t)g.R * KT * kSpreadRec;
+  const int tid = threadIdx.x;
+  const int c4t = tid % C4t, slot = tid / C4t;
+  const int kt = c4t / g.G, dq = c4t % g.G;
+  const int k0 = POW2 ? 0 : blockIdx.z * KT, k = k0 + kt;
+  const bool live = POW2 || k < g.K;         // the last joint tile may be ragged
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const int pix0 = chunk * g.P;
+  const int pend = min(g.P, g.HW - pix0);
+
+  SpreadRec r = {-INFINITY, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    const float4* base = logits + ((size_t)b * g.HW + pix0) * g.C4 + (k * g.G + dq);
+    PixelWalk<POW2> walk(g, pix0 + slot);
+    int p = slot;
+    for (; p + 3 * g.R < pend; p += 4 * g.R) {       // four loads in flight, one rescale per 16 values (as head_partial_kernel)
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = stream_load(base + (size_t)(p + u * g.R) * g.C4);
+      float mn = r.m;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) mn = fmaxf(mn, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
+      spread_rescale(r, mn);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float fh, fw;
+        walk.next(g, pix0 + p + u * g.R, &fh, &fw);
+        const float es = (__expf(v[u].x - mn) + __expf(v[u].y - mn)) + (__expf(v[u].z - mn) + __expf(v[u].w - mn));
+        spread_add(r, es, fw, fh);
+      }
+    }
+    for (; p < pend; p += g.R) {
+      const float4 v = stream_load(base + (size_t)p * g.C4);
+      float fh, fw;
+      walk.next(g, pix0 + p, &fh, &fw);
+      const float mn = fmaxf(fmaxf(r.m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+      spread_rescale(r, mn);
+      const float es = (__expf(v.x - mn) + __expf(v.y - mn)) + (__expf(v.z - mn) + __expf(v.w - mn));
+      spread_add(r, es, fw, fh);
+    }
+  }
+  r = group_merge<POW2>(r, g.G, dq, s_lane, tid - dq);
+  if (dq == 0) spread_write(smem + ((size_t)slot * KT + kt) * kSpreadRec, r);
+  __syncthreads();
+  // merge the R slots in slot order; thread t handles joint t of this tile
+  const int kn = POW2 ? g.K : min(KT, g.K - k0);
+  if (tid < kn) {
+    SpreadRec a = spread_read(smem + (size_t)tid * kSpreadRec);
+    for (int s = 1; s < g.R; ++s) a = spread_merge(a, spread_read(smem + ((size_t)s * KT + tid) * kSpreadRec));
+    spread_write(partial + (((size_t)b * g.nchunk + chunk) * g.K + k0 + tid) * kSpreadRec, a);
+  }
+}
+
+// Second pass: one wave per (b, k).  Lane c holds chunk c's record (64 at a time); every lane merges them in ascending chunk
+// order, reading lane after lane, so the wave agrees bit for bit; lane 0 normalises and writes {E w, E h, Var w, Var h, Cov}.
+__global__ void head_spread_finalize_kernel(const float* __restrict__ partial, HeadGeom g, float* __restrict__ spread) {
+  const int b = blockIdx.x / g.K, k = blockIdx.x % g.K;
+  const int lane = threadIdx.x;
+  const float* p0 = partial + ((size_t)b * g.nchunk * g.K + k) * kSpreadRec;
+  const size_t cstride = (size_t)g.K * kSpreadRec;
+  SpreadRec a = {-INFINITY, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < g.nchunk; c0 += 64) {
+    const int n = min(64, g.nchunk - c0);
+    SpreadRec mine = a;                              // (lanes past n: never read)
+    if (lane < n) mine = spread_read(p0 + (size_t)(c0 + lane) * cstride);
+    for (int j = 0; j < n; ++j) {
+      SpreadRec t;
+      t.m = __shfl(mine.m, j, 64); t.S = __shfl(mine.S, j, 64); t.uw = __shfl(mine.uw, j, 64); t.uh = __shfl(mine.uh, j, 64);
+      t.Mw = __shfl(mine.Mw, j, 64); t.Mh = __shfl(mine.Mh, j, 64); t.C = __shfl(mine.C, j, 64);
+      a = spread_merge(a, t);
+    }
+  }
+  if (lane == 0) {
+    const float vw = a.Mw / a.S, vh = a.Mh / a.S;
+    float* o = spread + ((size_t)b * g.K + k) * XAS_HEAD_SPREAD;
+    o[0] = a.uw; o[1] = a.uh;
+    o[2] = vw < 0.f ? 0.f : vw;                      // (a comparison, not fmaxf: NaN stays NaN)
+    o[3] = vh < 0.f ? 0.f : vh;
+    o[4] = a.C / a.S;
+  }
+}
+
 // ---- argument checks: each one is written once --------------------------------------------------------------------------
 static int check_modes(const char* who, int D, int num_hypo, int neighbor, const int64_t* z_idx, int B, int groups) {
   XAS_REQUIRE(num_hypo >= 1 && num_hypo <= 6, "%s: num_hypo %d not in [1,6]", who, num_hypo);
@@ -526,6 +696,32 @@ extern "C" int xas_head_softargmax_fwd_flip(const float* logits, int B, int K, i
   if (check_modes("head fwd flip", D, num_hypo, neighbor, z_idx, B, groups)) return 1;
   if (launch_partial(logits, partial, g, pow2, "head fwd flip", stream)) return 1;
   return launch_finalize_flip(partial, g, perm, num_hypo, neighbor, kps, z_idx, depth_prob_map, groups, stream);
+}
+
+extern "C" size_t xas_head_spread_workspace_floats(int B, int K, int D) {
+  HeadGeom g;
+  if (make_geom(B, K, D, pow2_policy(D, K), &g)) return 0;
+  return (size_t)B * g.nchunk * K * kSpreadRec;
+}
+
+// Mean and covariance of every joint's x-y soft-max marginal, in heat-map cells: spread [B][K][5] = {E w, E h, Var w, Var h,
+// Cov(w, h)}.  Two launches on the caller's stream; workspace: xas_head_spread_workspace_floats(B, K, D) floats.
+extern "C" int xas_head_spread(const float* logits, int B, int K, int D, float* spread, float* workspace, void* stream) {
+  const bool pow2 = pow2_policy(D, K);
+  HeadGeom g;
+  if (make_geom(B, K, D, pow2, &g)) return 1;
+  XAS_REQUIRE(logits && spread && workspace, "head spread: null buffer");
+  XAS_REQUIRE(((uintptr_t)logits & 15) == 0, "head spread: logits must be 16-byte aligned");
+  const size_t lds = spread_lds_bytes(g, pow2);
+  XAS_REQUIRE(lds <= 64 * 1024, "head spread: LDS %zu too large", lds);
+  XAS_REQUIRE((long)B * K < (1L << 31), "head spread: B=%d K=%d exceed the launch grid", B, K);
+  if (check_grid("head spread", g)) return 1;
+  hipLaunchKernelGGL(pow2 ? head_spread_partial_kernel<true> : head_spread_partial_kernel<false>, dim3(g.nchunk, g.B, g.ntile),
+                     dim3(g.C4t * g.R), lds, as_stream(stream), reinterpret_cast<const float4*>(logits), workspace, g);
+  XAS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(head_spread_finalize_kernel, dim3(B * K), dim3(64), 0, as_stream(stream), workspace, g, spread);
+  XAS_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int xas_head_softargmax_bwd(const float* logits, const float* stats, const int64_t* z_idx,

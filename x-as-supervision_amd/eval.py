@@ -3,7 +3,7 @@
 
     torchrun --nproc-per-node=N eval.py --config config/HM36_Multi_SurS1.yaml --checkpoint ckpt.pth.tar
              [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
-             [--tri dlt|robust --tri_thresh PX] [--resolve gt|views]
+             [--tri dlt|robust --tri_thresh PX] [--resolve gt|views] [--tri-weight depth|spread]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -18,6 +18,11 @@ view and the depth hypothesis of every view and joint from the agreement of the 
 (ops_eval.multiview_resolve) instead of from the labels; the labels then only name each left/right pair, once per sample for
 all views.  --multi_hypo is ignored in that mode.  No accuracy or time figure of that mode has been measured, neither on real
 data nor on the device.
+
+--tri-weight spread (opt-in; the default, depth, is the reference's weight unchanged: the joint's depth in mm) weighs every view
+of a joint in the triangulation (both --tri modes) and in --resolve views by 1 / sigma of its heat-map in full-image pixels
+(ops_head.heatmap_spread -> modules.util.spread_weight): one more streaming pass over each camera's logits.  No accuracy or
+time figure of that mode has been measured either.
 """
 import copy
 import os
@@ -33,7 +38,7 @@ from torch.distributed import destroy_process_group, init_process_group
 from metrics import pose_errors
 from modules.keypoint_detector_integral import KPDetector3D as KPDetector3D_integral
 from modules.keypoint_detector_integral_multi import KPDetector3DMulti as KPDetector3DMulti_integral
-from modules.util import convert_patch_to_world, resolve_views, triangulation
+from modules.util import convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_weighted
 from eval_utils import cal_per_class_error
 from xas_amd import ops_eval
 from xas_amd.synthetic import synthetic_eval_batch
@@ -67,6 +72,9 @@ class Eval:
             raise ValueError('Unknown triangulation: {}'.format(tri))
         if resolve not in ('gt', 'views'):
             raise ValueError('Unknown resolve mode: {}'.format(resolve))
+        tri_weight = config['model_params'].get('tri_weight', 'depth')         # --tri-weight; not a key of the shipped configs
+        if tri_weight not in ('depth', 'spread'):
+            raise ValueError('Unknown triangulation weight: {}'.format(tri_weight))
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -84,10 +92,18 @@ class Eval:
             raise ValueError("resolve='views' decides by the agreement of the cameras and needs 2 to {} of them; cam_id_list "
                              'has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
         self.res_exchanged, self.res_hyp0, self.res_batches = 0.0, 0.0, 0      # views only, summed over the batches
+        self.tri_weight = tri_weight               # --tri-weight spread: a view counts by its heat-map's 1 / sigma, not its depth
+        self.spread = None                         # spread only: heat-map spread [B,K,5] of the latest detect()
+        self.tri_sigma, self.sigma_batches = 0.0, 0    # spread only: mean sigma in pixels, summed over the batches
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
-        the average of each heat-map and the mirrored, left/right-swapped heat-map of the mirrored image)."""
+        the average of each heat-map and the mirrored, left/right-swapped heat-map of the mirrored image).  With
+        tri_weight='spread' through forward_spread, which also leaves that heat-map's spread in self.spread."""
+        if self.tri_weight == 'spread':
+            pairs = self.config['model_params']['flip_pairs'] if self.flip_test else None
+            kps, _, self.spread = self.detector.forward_spread(img, pairs)
+            return kps
         if self.flip_test:
             return self.detector.forward_flip(img, self.config['model_params']['flip_pairs'])[0]
         return self.detector(img)[0]
@@ -109,9 +125,17 @@ class Eval:
         the cameras' agreement picks the hypotheses."""
         cams = ['cam_{}'.format(c) for c in self.cam_id_list]
         sel, out, trans = {}, {}, None
+        weights = {} if self.tri_weight == 'spread' else None
+
+        def detect(m):                             # one camera's joints; spread: also its weights, which need the detector
+            kps = self.detect(x[m + '_img']) if kps_by_cam is None or weights is not None else None
+            if weights is not None:
+                weights[m] = spread_weight(self.spread, x[m + '_trans_image'])
+            return kps if kps_by_cam is None else kps_by_cam[m]
+
         if self.resolve == 'views':
-            raw = {m: kps_by_cam[m] if kps_by_cam is not None else self.detect(x[m + '_img']) for m in cams}
-            sel, r = resolve_views(raw, x, self.cam_id_list, ops_eval.SWITCH_PAIRS, gt=True)
+            raw = {m: detect(m) for m in cams}
+            sel, r = resolve_views_weighted(raw, x, self.cam_id_list, ops_eval.SWITCH_PAIRS, weights, gt=True)   # None: the depth
             for m in cams:                         # the labels' part from here on: measuring, no longer choosing
                 out['err2d_' + m] = ops_eval.eval_select(sel[m].unsqueeze(1), x[m + '_joints'], image_size=self.img_size,
                                                          mode='confident', no_switch=True, want=('err2d',))['err2d']
@@ -125,7 +149,7 @@ class Eval:
             out['resolve_exchanged'] = (before * paired).sum() / (paired.sum().clamp(min=1.0) * B * len(cams))
             out['resolve_hyp0'] = (r['hyp'] == 0).float().mean()
         for m in ([] if self.resolve == 'views' else cams):
-            kps = kps_by_cam[m] if kps_by_cam is not None else self.detect(x[m + '_img'])
+            kps = detect(m)
             s = ops_eval.eval_select(kps, x[m + '_joints'], image_size=self.img_size, mode=mode)
             sel[m] = s['sel3d']
             out['err2d_' + m] = s['err2d']
@@ -134,12 +158,14 @@ class Eval:
         out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
         gt = convert_patch_to_world(x['cam_0_joints'], x, 'cam_0', is_norm=False)          # eval.py:170
         if self.tri == 'robust':
-            tri, used = triangulation(sel, x, self.cam_id_list, robust_px=self.tri_thresh, return_inliers=True)
+            tri, used = triangulation_weighted(sel, x, self.cam_id_list, weights, robust_px=self.tri_thresh, return_inliers=True)
             bits = (used.unsqueeze(-1).int() >> torch.arange(len(cams), device=used.device, dtype=torch.int32)) & 1
             # a zero mask is the fallback: no two views agreed, the DLT ran over all of them
             out['tri_inlier_views'] = torch.where(used == 0, len(cams), bits.sum(dim=-1)).float().mean()
         else:
-            tri = triangulation(sel, x, self.cam_id_list)
+            tri = triangulation_weighted(sel, x, self.cam_id_list, weights)
+        if weights is not None:
+            out['tri_sigma'] = torch.stack([1.0 / weights[m] for m in cams]).mean()
         preds = {'tri': tri}
         for m in cams:
             preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
@@ -171,6 +197,9 @@ class Eval:
             if 'tri_inlier_views' in host:
                 self.tri_views += float(host['tri_inlier_views'])
                 self.tri_batches += 1
+            if 'tri_sigma' in host:
+                self.tri_sigma += float(host['tri_sigma'])
+                self.sigma_batches += 1
             if 'resolve_hyp0' in host:
                 self.res_exchanged += float(host['resolve_exchanged'])
                 self.res_hyp0 += float(host['resolve_hyp0'])
@@ -223,6 +252,8 @@ class Eval:
         if self.resolve == 'views':                # after everything else; --resolve gt leaves the file as it was
             n = max(self.res_batches, 1)
             lines.append('RESOLVE views: exchanged {} , hypothesis 0 kept {}'.format(self.res_exchanged / n, self.res_hyp0 / n))
+        if self.tri_weight == 'spread':            # after everything else; --tri-weight depth leaves the file as it was
+            lines.append('TRI weight spread: mean sigma {} px'.format(self.tri_sigma / max(self.sigma_batches, 1)))
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -302,6 +333,9 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--resolve', dict(default='gt', choices=['gt', 'views'],
                        help='left/right exchange and depth hypothesis of every view: by the labels as the reference does, or by '
                             'the agreement of the cameras (labels only name each pair; --multi_hypo is ignored)')),
+    ('--tri-weight', dict(default='depth', choices=['depth', 'spread'], dest='tri_weight',
+                          help="weight of every view in the triangulation and in --resolve views: the joint's depth in mm as "
+                               'the reference has it, or 1 / sigma of its heat-map in image pixels')),
 )
 
 
@@ -313,6 +347,7 @@ def main():
     with open(opt.config) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     config['model_params']['cam_id_list'] = config['dataset_params']['cam_id_list']
+    config['model_params']['tri_weight'] = opt.tri_weight
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

@@ -6,6 +6,7 @@ D*H*W, the three marginals, the depth-peak top-k and the windowed expectations r
 reduction that reads the logits once (xas_head_softargmax_fwd) instead of ~15 ATen kernels and five
 passes over a 604 MB tensor.  Ties between equal peak scores resolve to the lower depth bin.
 """
+import torch
 import torch.nn as nn
 
 from modules.integral_base_modules.network import get_default_network_config, get_pose_net
@@ -47,6 +48,23 @@ class KPDetector3DMulti(nn.Module):
         kps, depth_prob_map, idx = ops_head.softargmax_flip(heatmap, self.num_kp, self.num_hypo, self.neighbor_size, perm)
         self.last_peak_indices = idx
         return kps, depth_prob_map
+
+    @torch.no_grad()
+    def forward_spread(self, x, flip_pairs=None):
+        """forward (forward_flip when flip_pairs is given) plus the spatial spread of the heat-map the head ran on:
+        -> (kps, depth_prob_map, spread [B, K, 5] = (E w, E h, Var w, Var h, Cov) in heat-map cells, ops_head.heatmap_spread;
+        with flip_pairs the spread of the averaged heat-map, ops_head.spread_flip).  One more pass over the logits.  For
+        eval(): records no graph."""
+        if flip_pairs is None:
+            ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3DMulti')
+            heatmap = self.net(x)
+            kps, depth_prob_map, idx = ops_head.softargmax_multi(heatmap, self.num_kp, self.num_hypo, self.neighbor_size)
+        else:
+            x2, perm = ops_head.detector_flip_input(self, x, flip_pairs, 'KPDetector3DMulti')
+            heatmap = self.net(x2)
+            kps, depth_prob_map, idx = ops_head.softargmax_flip(heatmap, self.num_kp, self.num_hypo, self.neighbor_size, perm)
+        self.last_peak_indices = idx
+        return kps, depth_prob_map, ops_head.detector_spread(self, heatmap, flip_pairs)
 
     def forward_groups(self, x, groups, prefix_groups=0):
         """The reference's `groups` consecutive calls forward(x[0:B]), forward(x[B:2B]), ... as ONE pass over the

@@ -4,7 +4,8 @@ Built here: `draw_lines` (+ the fused `draw_lines_max` the model actually consum
 `convert_patch_to_world` (all hypotheses in one launch, closed-form 2x2 / 3x3 inverses),
 `make_coordinate_grid`, `smpl_to_h36m`, and for the evaluation path `convert_patch_to_image`,
 `triangulation` / `batch_triangulate` (device DLT, no batched SVD), `resolve_views` (left/right exchange and depth hypothesis by
-the cameras' agreement, no reference counterpart), and the SMPL side of the geometry:
+the cameras' agreement, no reference counterpart), `spread_weight` (heat-map spread -> per-view weight) with `triangulation_weighted` / `resolve_views_weighted` (opt-in, no
+reference counterpart), and the SMPL side of the geometry:
 `project_smpl_to_patch_kps`, `convert_pelvis_to_world` (one world->patch launch, ops_head.world_to_patch) and `flip_3D`.
 `convert_world_to_patch` / `convert_world_to_image` / `convert_image_to_patch` stay the reference's (the device version is
 ops_head.world_to_patch).  The reference's dead code (rule_transformation, my_truncated_normal) is not rebuilt
@@ -67,10 +68,39 @@ def batch_triangulate(keypoints_, Pall, robust_px=None):
     return ops_eval.triangulate_robust(keypoints_, Pall, threshold_px=robust_px, want=())['xyzw']
 
 
+def spread_weight(spread, trans_image, cell_px=4.0):
+    """Heat-map spread [B,K,5] (ops_head.heatmap_spread) of one camera -> triangulation weight [B,K] = 1 / sigma in pixels of
+    the full image, the unit of the DLT's residuals:
+        w = 1 / sqrt((Var_w + Var_h + 2/12) * (cell_px * s)^2),   s = 1 / sqrt(|det trans_image[:, :2, :2]|)
+    `s` is the image pixels per patch pixel of the sample's crop and `cell_px` the patch pixels per heat-map cell.  The 2/12 is
+    the variance of a uniform distribution over one cell on each axis - the quantisation floor of a heat-map - and keeps a
+    one-hot map finite.  No reference counterpart."""
+    a = trans_image[:, :2, :2].to(spread.dtype)
+    det = (a[:, 0, 0] * a[:, 1, 1] - a[:, 0, 1] * a[:, 1, 0]).abs()
+    var_px = (spread[..., 2] + spread[..., 3] + 2.0 / 12.0) * (cell_px * cell_px / det).unsqueeze(-1)
+    return var_px.rsqrt()
+
+
+def _stack_points(pts, weights, modes):
+    """(u, v, depth) of every camera stacked [B,V,K,3]; with `weights` ({cam_key: [B,K]}) those replace the third column."""
+    pts = torch.stack(pts, dim=1)
+    if weights is not None:
+        pts = torch.cat([pts[..., :2], torch.stack([weights[m] for m in modes], dim=1).to(pts.dtype).unsqueeze(-1)], dim=-1)
+    return pts
+
+
 def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000, robust_px=None, return_inliers=False):
     """{cam_key: [B,K,3]} patch predictions of all cameras -> world joints [B,K,3] (util.py:171-196).  `robust_px`: as in
     batch_triangulate; with `return_inliers` also the [B,K] uint8 masks of the views used (bit i = cam_id_list[i];
-    None without robust_px)."""
+    None without robust_px).  Every view weighs by the joint's depth in mm, as in the reference."""
+    return triangulation_weighted(keypoints, params, cam_id_list, None, is_norm, RECT_WIDTH, robust_px, return_inliers)
+
+
+def triangulation_weighted(keypoints, params, cam_id_list, weights, is_norm=True, RECT_WIDTH=2000, robust_px=None,
+                           return_inliers=False):
+    """triangulation with `weights`, {cam_key: [B,K]}: the weight of every view and joint (spread_weight) in place of the
+    reference's, which is the joint's depth in mm.  A weight that is not finite or not positive marks the view invalid for that
+    joint, by the kernels' rule for the third column.  None: the reference's weights, bit for bit.  No reference counterpart."""
     pts, pm = [], []
     for cam_id in cam_id_list:
         mode = 'cam_{}'.format(cam_id)
@@ -80,10 +110,11 @@ def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000,
                                            is_norm=is_norm))
         pm.append(ops_eval.projection_matrix(params['{}_k_mat'.format(mode)], params['{}_rot_world'.format(mode)],
                                              params['{}_trans_world'.format(mode)]))
+    pts = _stack_points(pts, weights, ['cam_{}'.format(c) for c in cam_id_list])
     if robust_px is None:
-        tri = batch_triangulate(torch.stack(pts, dim=1), torch.stack(pm, dim=1))[..., :3]
+        tri = batch_triangulate(pts, torch.stack(pm, dim=1))[..., :3]
         return (tri, None) if return_inliers else tri
-    r = ops_eval.triangulate_robust(torch.stack(pts, dim=1), torch.stack(pm, dim=1), threshold_px=robust_px,
+    r = ops_eval.triangulate_robust(pts, torch.stack(pm, dim=1), threshold_px=robust_px,
                                     want=('inliers',) if return_inliers else ())
     return (r['xyzw'][..., :3], r['inliers']) if return_inliers else r['xyzw'][..., :3]
 
@@ -93,6 +124,12 @@ def resolve_views(kps_by_cam, params, cam_id_list, pairs, gt=True, RECT_WIDTH=20
     ops_eval.multiview_resolve).  The left/right exchange of every view and the depth hypothesis of every view and joint are
     decided by the agreement of the cameras; with `gt` the labels (`<cam>_joints`) name each pair once for all views, and
     nothing else is read from them.  Bit i of `swap` is cam_id_list[i].  No reference counterpart."""
+    return resolve_views_weighted(kps_by_cam, params, cam_id_list, pairs, None, gt, RECT_WIDTH)
+
+
+def resolve_views_weighted(kps_by_cam, params, cam_id_list, pairs, weights, gt=True, RECT_WIDTH=2000):
+    """resolve_views with `weights`, {cam_key: [B,K]}, in place of the depth in mm as every view's weight, as in
+    triangulation_weighted (not finite or not positive: the view is invalid for that joint).  None: the depth, bit for bit."""
     modes = ['cam_{}'.format(c) for c in cam_id_list]
     pts, pm, world, kps = [], [], [], []
     for mode in modes:
@@ -105,12 +142,13 @@ def resolve_views(kps_by_cam, params, cam_id_list, pairs, gt=True, RECT_WIDTH=20
         world.append(convert_patch_to_world(k, params, mode, is_norm=True, RECT_WIDTH=RECT_WIDTH))
         kps.append(k)
     labels = torch.stack([params[mode + '_joints'] for mode in modes], dim=1) if gt else None
-    r = ops_eval.multiview_resolve(torch.stack(pts, dim=1), torch.stack(pm, dim=1), torch.stack(kps, dim=1),
+    pts = _stack_points(pts, weights, modes)
+    r = ops_eval.multiview_resolve(pts, torch.stack(pm, dim=1), torch.stack(kps, dim=1),
                                    torch.stack(world, dim=1), pairs=pairs, gt=labels, image_size=size)
     sel = r.pop('sel')
     # the views that took part, [B,K] bit masks like `swap` (derived here, the kernel keeps it to itself): finite weight > 0
     # for the joint and for its partner
-    w = torch.stack(pts, dim=1)[..., 2]
+    w = pts[..., 2]
     ok = torch.isfinite(w) & (w > 0)
     ok = ok & ok[..., ops_eval.switch_perm(w.shape[-1], pairs, w.device).long()]
     bit = (1 << torch.arange(len(modes), device=w.device, dtype=torch.int32)).view(1, -1, 1)

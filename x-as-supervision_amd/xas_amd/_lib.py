@@ -73,6 +73,8 @@ SIGNATURES = {
     'xas_head_softargmax_from_partials': ('piiiiiipppipp', 'i'),
     'xas_head_softargmax_flip_from_partials': ('piiiiiippppip', 'i'),
     'xas_head_softargmax_fwd_flip': ('piiiiippppipp', 'i'),
+    'xas_head_spread_workspace_floats': ('iii', 'z'),
+    'xas_head_spread': ('piiippp', 'i'),
     'xas_conv_fwd_bnstats_workspace_floats': ('si', 'z'),
     'xas_conv_fwd_bnstats': ('pppsippplppppfp', 'i'),
     'xas_conv_dgrad_bn_bwd_workspace_floats': ('si', 'z'),

@@ -189,6 +189,53 @@ def detector_flip_input(det, x, flip_pairs, who):
     return ops_nn.mirror_pair_nchw(x), det._flip_perm
 
 
+HEAD_SPREAD = 5            # xas_hip.h XAS_HEAD_SPREAD: (E w, E h, Var w, Var h, Cov(w, h)) in heat-map cells
+
+
+def heatmap_spread(logits, num_kp):
+    """Mean and covariance of every joint's x-y soft-max marginal: logits [B, K*D, D, D] -> [B, K, 5] =
+    (E w, E h, Var w, Var h, Cov(w, h)) in heat-map cells (xas_head_spread: one streaming pass, fixed reduction order).
+    The spatial confidence of a view; no reference counterpart and no backward: the result records no graph."""
+    logits = _nhwc_storage(logits.detach())
+    B, C, H, W = logits.shape
+    D = C // num_kp
+    if not (C == num_kp * D and D == H == W):
+        raise RuntimeError('soft-argmax head needs a heat-map cube D == H == W with D a multiple of 4 in [4,128] '
+                           '(got C=%d K=%d H=%d W=%d)' % (C, num_kp, H, W))
+    dev = logits.device
+    spread = torch.empty(B, num_kp, HEAD_SPREAD, device=dev, dtype=torch.float32)
+    ws = torch.empty(query('xas_head_spread_workspace_floats', B, num_kp, D), device=dev, dtype=torch.float32)
+    call('xas_head_spread', ptr(logits), B, num_kp, D, ptr(spread), ptr(ws))
+    return spread
+
+
+def spread_flip(spread_2b, perm, W):
+    """Spread of the flip test's averaged heat-map from the spreads [2B, K, 5] of the B images and their B mirrors
+    (heatmap_spread of the batch softargmax_flip takes): the mirror turns E w into W - 1 - E w and Cov into -Cov and joint k
+    takes joint perm[k]; the half-half mixture of two distributions has mean (ua + ub) / 2, variance
+    (Va + Vb) / 2 + (ua - ub)^2 / 4 and covariance (Ca + Cb) / 2 + (uwa - uwb)(uha - uhb) / 4.  -> [B, K, 5]."""
+    if spread_2b.dim() != 3 or spread_2b.shape[0] % 2 or spread_2b.shape[-1] != HEAD_SPREAD:
+        raise RuntimeError('spread_flip takes the spreads [2B, K, 5] of B images followed by their B mirrors, got %s'
+                           % (tuple(spread_2b.shape),))
+    B = spread_2b.shape[0] // 2
+    if not isinstance(perm, torch.Tensor):
+        perm = torch.as_tensor(perm)
+    a, m = spread_2b[:B], spread_2b[B:][:, perm.to(spread_2b.device).long()]
+    uw_m = (W - 1) - m[..., 0]
+    dw, dh = a[..., 0] - uw_m, a[..., 1] - m[..., 1]
+    return torch.stack([0.5 * (a[..., 0] + uw_m), 0.5 * (a[..., 1] + m[..., 1]),
+                        0.5 * (a[..., 2] + m[..., 2]) + 0.25 * dw * dw,
+                        0.5 * (a[..., 3] + m[..., 3]) + 0.25 * dh * dh,
+                        0.5 * (a[..., 4] - m[..., 4]) + 0.25 * dw * dh], dim=-1)
+
+
+def detector_spread(det, heatmap, flip_pairs):
+    """What both detectors' forward_spread do after the head: the spread of the heat-map the head ran on (with flip_pairs
+    the 2B-image batch of forward_flip and its averaged heat-map)."""
+    s = heatmap_spread(heatmap, det.num_kp)
+    return s if flip_pairs is None else spread_flip(s, det._flip_perm, det.depth_dim)
+
+
 class _PatchToWorld(torch.autograd.Function):
     @staticmethod
     def forward(ctx, kps, ti, km, pv, rw, tw, image_size, rect_width, flags):
