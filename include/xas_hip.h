@@ -339,6 +339,29 @@ int xas_conv_dgrad_acc(const float* dy, const float* w_packed_t, float* dx, cons
  * xas_conv_dgrad_acc; dx is written, not read. */
 int xas_conv_dgrad_acc_masked(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
                               const float* dprev, const uint8_t* mask, void* stream);
+/* What a launch of xas_conv_fwd (pass 0; has_bias != 0: a bias comes with the call) or of xas_conv_dgrad* (pass 1) on this
+ * shape would run - under the shape's precision, the operand maximum it carries and the current tuning flags - written to
+ * out[XAS_PLAN_INTS].  Host only: never touches the device; reads the functions the launches read (16-byte aligned
+ * operands assumed).  Fields that do not apply are 0.  Non-zero status: null / invalid arguments, or a shape the launch
+ * refuses for its dimensions (Ho / Wo inconsistent in a forward, Hi / Wi too small in a data gradient, tensors beyond 32-bit
+ * row indices or beyond the offset range of the split kernels).  For tests (tests/test_gpu_igemm.py) and measurement. */
+enum {
+  XAS_PLAN_ROUTE = 0,        /* XAS_ROUTE_* */
+  XAS_PLAN_KERNEL = 1,       /* XAS_KERNEL_* (MFMA route) */
+  XAS_PLAN_BM = 2,           /* tile: rows (pixels) ... */
+  XAS_PLAN_BN = 3,           /* ... and columns (produced channels) */
+  XAS_PLAN_PIPELINED = 4,    /* exact-fp32 kernels: 1 pipelined K-loop, 0 plain */
+  XAS_PLAN_PHASES = 5,       /* stride phases (grid z): 1 forward, stride^2 data gradient */
+  XAS_PLAN_PIECES = 6,       /* operand planes of the split kernels: 3 bf16x6, 2 f16x3, 1 bf16; 0 exact fp32 */
+  XAS_PLAN_PATCH_WIDTH = 7,  /* igemm_x6t_kernel: 16 (8 x 16 patches of one image) or 8 (8 x 8 of two images) */
+  XAS_PLAN_TPB = 8,          /* igemm_x6p_kernel: consecutive M-tiles per block */
+  XAS_PLAN_IMAGES = 9,       /* images per launch (< N: the call runs as several launches over image ranges) */
+  XAS_PLAN_INTS = 10
+};
+enum { XAS_ROUTE_STEM_F16 = 1, XAS_ROUTE_STEM_F32 = 2, XAS_ROUTE_THIN_VEC_TO_SCALAR = 3, XAS_ROUTE_THIN_SCALAR_TO_VEC = 4,
+       XAS_ROUTE_DIRECT = 5, XAS_ROUTE_MFMA = 6 };
+enum { XAS_KERNEL_IGEMM_BUF = 1, XAS_KERNEL_IGEMM = 2, XAS_KERNEL_IGEMM_X6 = 3, XAS_KERNEL_IGEMM_X6T = 4, XAS_KERNEL_IGEMM_X6P = 5 };
+int xas_conv_igemm_plan(const xas_conv_shape* s, int pass, int has_bias, int* out);
 /* dw_packed [Cout][R][S][Cin] (+)= sum_n,ho,wo dy * x ; workspace for split-K partials. */
 size_t xas_conv_wgrad_workspace_floats(const xas_conv_shape* s);
 int xas_conv_wgrad(const float* x, const float* dy, float* dw_packed, float* workspace,

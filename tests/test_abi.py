@@ -85,6 +85,61 @@ def test_tuning_flags_match_the_header():
     assert header == mirror
 
 
+def test_plan_tables_match_the_header():
+    """The field, route and kernel names of _lib's xas_conv_igemm_plan wrapper are the header's enums, in the header's order."""
+    from xas_amd import _lib
+    src = open(os.path.join(ROOT, 'include', 'xas_hip.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+
+    def enum(prefix):
+        return {n.lower(): int(v) for n, v in re.findall(r'\bXAS_%s_(\w+)\s*=\s*(\d+)' % prefix, src)}
+    fields = enum('PLAN')
+    assert fields.pop('ints') == len(_lib.PLAN_FIELDS)
+    assert fields == {n: i for i, n in enumerate(_lib.PLAN_FIELDS)}
+    assert enum('ROUTE') == {n: i for i, n in enumerate(_lib.PLAN_ROUTES) if n}
+    assert enum('KERNEL') == {n: i for i, n in enumerate(_lib.PLAN_KERNELS) if n}
+
+
+def test_igemm_plan_answers_without_a_gpu():
+    """xas_conv_igemm_plan never touches the device: one shape per route, the refusals, and the fields that do not apply."""
+    import ctypes
+    from xas_amd import _lib
+    lib = _lib.load()
+    f = _lib.fn('xas_conv_igemm_plan')
+    out = (ctypes.c_int * len(_lib.PLAN_FIELDS))()
+    outp = ctypes.cast(out, ctypes.c_void_p)
+    good = _lib.ConvShape(2, 8, 8, 32, 32, 3, 3, 1, 1, 8, 8, 1 + _lib.PREC_F32)
+    assert f(None, 0, 0, outp) == 1 and 'null shape' in lib.xas_last_error().decode()
+    assert f(ctypes.byref(good), 0, 0, None) == 1 and f(ctypes.byref(good), 2, 0, outp) == 1
+    assert 'conv_igemm_plan' in lib.xas_last_error().decode()
+    bad = _lib.ConvShape(2, 8, 8, 0, 32, 3, 3, 1, 1, 8, 8)
+    assert f(ctypes.byref(bad), 0, 0, outp) == 1
+    assert f(ctypes.byref(_lib.ConvShape(2, 8, 8, 32, 32, 3, 3, 1, 1, 7, 8)), 0, 0, outp) == 1 and 'inconsistent' in lib.xas_last_error().decode()
+    assert f(ctypes.byref(_lib.ConvShape(2, 7, 8, 32, 32, 3, 3, 1, 1, 8, 8)), 1, 0, outp) == 1 and 'too small' in lib.xas_last_error().decode()
+    prec = _lib.query('xas_get_precision')
+    try:
+        _lib.query('xas_set_tuning', 0)
+        p = _lib.conv_igemm_plan(good, 0)
+        assert p == dict(route='mfma', kernel='igemm_buf', bm=128, bn=32, pipelined=1, phases=1, pieces=0, patch_width=0, tpb=0, images=2)
+        p = _lib.conv_igemm_plan(_lib.ConvShape(2, 8, 8, 32, 32, 3, 3, 1, 1, 8, 8, 1 + _lib.PREC_BF16X6), 1)
+        assert (p['kernel'], p['bn'], p['pieces'], p['patch_width'], p['pipelined']) == ('igemm_x6t', 32, 3, 8, 0)
+        stem = _lib.ConvShape(1, 16, 32, 3, 64, 7, 7, 2, 3, 8, 16, 1 + _lib.PREC_F32)
+        assert _lib.conv_igemm_plan(stem, 0)['route'] == 'stem_f32' and _lib.conv_igemm_plan(stem, 0, True)['route'] == 'direct'
+        assert _lib.conv_igemm_plan(stem, 1) == dict(route='direct', kernel=None, bm=0, bn=0, pipelined=0, phases=0, pieces=0,
+                                                     patch_width=0, tpb=0, images=1)
+        thin = _lib.ConvShape(1, 3, 5, 4, 1, 3, 3, 1, 1, 3, 5)
+        assert _lib.conv_igemm_plan(thin, 0)['route'] == 'thin_vec_to_scalar' and _lib.conv_igemm_plan(thin, 1)['route'] == 'thin_scalar_to_vec'
+        # stride 2: four phases in the data gradient, one in the forward; the tuning flags are read at the time of the query
+        s2 = _lib.ConvShape(2, 17, 13, 128, 128, 3, 3, 2, 1, 9, 7, 1 + _lib.PREC_F32)
+        assert _lib.conv_igemm_plan(s2, 1)['phases'] == 4 and _lib.conv_igemm_plan(s2, 0)['phases'] == 1
+        _lib.query('xas_set_tuning', _lib.TUNE_GLOBAL_LOAD | _lib.TUNE_PLAIN_KLOOP)
+        p = _lib.conv_igemm_plan(s2, 1)
+        assert (p['kernel'], p['pipelined']) == ('igemm', 0)
+    finally:
+        _lib.query('xas_set_tuning', 0)                 # (the library has no getter: 0 is what every test starts from and leaves)
+    assert _lib.query('xas_get_precision') == prec
+
+
 def test_no_cpu_fallback():
     import torch
     from xas_amd import ops_head

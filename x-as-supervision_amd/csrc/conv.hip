@@ -1474,6 +1474,13 @@ static int check_fwd_dims(const xas_conv_shape* s, const char* who) {
   return 0;
 }
 
+// valid for the conv (Hi -> Ho) and for ConvTranspose2d forward (Ho given, Hi = (Ho-1)*stride - 2*pad + R)
+static int check_dgrad_dims(const xas_conv_shape* s, const char* who) {
+  XAS_REQUIRE((s->Ho - 1) * s->stride - 2 * s->pad + s->R <= s->Hi && (s->Wo - 1) * s->stride - 2 * s->pad + s->S <= s->Wi,
+              "%s: Hi/Wi (%d,%d) too small for Ho/Wo (%d,%d)", who, s->Hi, s->Wi, s->Ho, s->Wo);
+  return 0;
+}
+
 // Launches either kernel of the exact-fp32 forward / data-gradient family (same LDS size, tile grid and block order).
 template <int BM, int BN, void (*Kernel)(IgemmParams)>
 static int launch_igemm(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
@@ -1500,26 +1507,33 @@ static bool igemm_fits(const IgemmParams& p) {
   return (bias + p.src_elems) * 4 < 0x7fffff00l && p.wgt_elems * 6 < 0x7fffff00l && p.R * p.S <= 32;
 }
 
-// Exact-fp32 MFMA path: buffer-load kernel unless its offset scheme cannot address the tensor or a coverage test asks for
-// the global-load kernel (XAS_TUNE_GLOBAL_LOAD); XAS_TUNE_PLAIN_KLOOP: plain K-loop instead of the pipelined one.
+// Exact-fp32 MFMA path, operand loader and K loop of a problem (launch_tile and xas_conv_igemm_plan): buffer-load kernel
+// unless its offset scheme cannot address the tensor or a coverage test asks for the global-load kernel
+// (XAS_TUNE_GLOBAL_LOAD); XAS_TUNE_PLAIN_KLOOP: plain K-loop instead of the pipelined one.
+struct F32Loop { bool buf, pipe; };
+static F32Loop f32_loop(const IgemmParams& p) {
+  // K loops of one or two steps (1x1 layers with 32 / 64 input channels): the pipelined loop's look-ahead loads have
+  // nothing to look ahead to (they re-load the last step) - the plain loop is 18 % faster there (0.608 -> 0.497 ms for
+  // 64 -> 256 channels at 256 x 64 x 64, r02).  Buffer-load kernel only.
+  const bool short_k = p.stride == 1 && (long)p.R * p.S * p.Cs <= 2 * BK;
+  const bool buf = igemm_fits(p) && !(p.tune & XAS_TUNE_GLOBAL_LOAD);
+  return {buf, !((p.tune & XAS_TUNE_PLAIN_KLOOP) || (buf && short_k))};
+}
+
 template <int BM, int BN, int MODE>
 static int launch_tile(const IgemmParams& p, int Mrows_max, int phases, hipStream_t st) {
-  const bool fits = igemm_fits(p);
   if constexpr (MODE == 1) {
     if (p.bnb_x) {                                    // batch-norm backward epilogue: buffer-load pipelined kernel only
-      XAS_REQUIRE(fits, "conv_dgrad_bn_bwd: tensor beyond the 32-bit offset range of the buffer-load kernel");
+      XAS_REQUIRE(igemm_fits(p), "conv_dgrad_bn_bwd: tensor beyond the 32-bit offset range of the buffer-load kernel");
       return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, 1, true, true>>(p, Mrows_max, phases, st);
     }
   }
-  // K loops of one or two steps (1x1 layers with 32 / 64 input channels): the pipelined loop's look-ahead loads have
-  // nothing to look ahead to (they re-load the last step) - the plain loop is 18 % faster there (0.608 -> 0.497 ms for
-  // 64 -> 256 channels at 256 x 64 x 64, r02)
-  const bool short_k = p.stride == 1 && (long)p.R * p.S * p.Cs <= 2 * BK;
-  if (fits && !(p.tune & XAS_TUNE_GLOBAL_LOAD)) {
-    if ((p.tune & XAS_TUNE_PLAIN_KLOOP) || short_k) return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, MODE, false>>(p, Mrows_max, phases, st);
+  const F32Loop l = f32_loop(p);
+  if (l.buf) {
+    if (!l.pipe) return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, MODE, false>>(p, Mrows_max, phases, st);
     return launch_igemm<BM, BN, igemm_buf_kernel<BM, BN, MODE, true>>(p, Mrows_max, phases, st);
   }
-  if (p.tune & XAS_TUNE_PLAIN_KLOOP) return launch_igemm<BM, BN, igemm_kernel<BM, BN, MODE, false>>(p, Mrows_max, phases, st);
+  if (!l.pipe) return launch_igemm<BM, BN, igemm_kernel<BM, BN, MODE, false>>(p, Mrows_max, phases, st);
   return launch_igemm<BM, BN, igemm_kernel<BM, BN, MODE, true>>(p, Mrows_max, phases, st);
 }
 
@@ -1543,11 +1557,22 @@ static inline bool has_amax_for(const xas_conv_shape* s, int pass) {
 
 // prec: XAS_PREC_*.  The bf16-split kernels (conv_x6.hip) take PRE-SPLIT weights (xas_split_weight); the exact-fp32 kernels
 // take fp32 packed weights: xas_conv_weight_planes tells the caller which of the two a (shape, pass) wants.
+// operand pieces of a split-arithmetic launch of problem p (mode: 0 forward, 1 data gradient)
+static inline int igemm_pieces(const IgemmParams& p, int prec, int mode) {
+  return planes_of(prec, mode, p.a_amax != nullptr && !p.bnb_x);
+}
+
+// the split kernels have no global-load fallback: a problem beyond their offset scheme is refused
+static int check_split_fits(const IgemmParams& p) {
+  XAS_REQUIRE(igemm_fits(p), "conv: tensor beyond the 32-bit offset range of the bf16-split kernels (use XAS_PREC_F32)");
+  return 0;
+}
+
 template <int MODE>
 static int dispatch_igemm(const IgemmParams& p, int prec, int Mrows_max, int phases, hipStream_t st) {
   if (prec != XAS_PREC_F32) {
-    XAS_REQUIRE(igemm_fits(p), "conv: tensor beyond the 32-bit offset range of the bf16-split kernels (use XAS_PREC_F32)");
-    return launch_igemm_x6(p, MODE, Mrows_max, phases, planes_of(prec, MODE, p.a_amax != nullptr && !p.bnb_x), st);
+    if (check_split_fits(p)) return 1;
+    return launch_igemm_x6(p, MODE, Mrows_max, phases, igemm_pieces(p, prec, MODE), st);
   }
   int bm, bn;
   pick_tile(p.Cd, Mrows_max, phases, &bm, &bn);
@@ -1573,6 +1598,9 @@ static int images_per_launch(int N, long elems_per_image_a, long elems_per_image
   const long launches = cdiv(N, n);
   return (int)cdiv(N, launches);                               // equal-sized ranges
 }
+// ... of a forward (the gathered tensor is x) and of a data gradient (dy)
+static int fwd_images_per_launch(const xas_conv_shape* s) { return images_per_launch(s->N, (long)s->Hi * s->Wi * s->Cin, 0); }
+static int dgrad_images_per_launch(const xas_conv_shape* s) { return images_per_launch(s->N, (long)s->Ho * s->Wo * s->Cout, 0); }
 
 // pass(first image, shape of the range) over ranges of `per` images
 template <class F>
@@ -1714,13 +1742,29 @@ static IgemmParams fwd_problem(const xas_conv_shape* s) {
   p.src_elems = (long)p.N * p.Hs * p.Ws * p.Cs; p.wgt_elems = (long)p.Cd * p.R * p.S * p.Cs;
   return p;
 }
+// ... and the data-gradient problem (the gathered tensor is dy, the rows are the pixels of dx, one stride phase at a time)
+static IgemmParams dgrad_problem(const xas_conv_shape* s) {
+  IgemmParams p{};
+  p.N = s->N; p.a_amax = s->grad_amax;
+  p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.Hd = s->Hi; p.Wd = s->Wi; p.Cd = s->Cin;
+  p.R = s->R; p.S = s->S; p.stride = s->stride; p.pad = s->pad; p.tune = g_tune;
+  p.src_elems = (long)p.N * p.Hs * p.Ws * p.Cs; p.wgt_elems = (long)p.Cd * p.R * p.S * p.Cs;
+  return p;
+}
+// The row grid of a pass: rows of the largest stride phase (the tile grid covers it) and the number of phases
+struct IgemmGrid { int Mrows_max, phases; };
+static IgemmGrid fwd_grid(const xas_conv_shape* s) { return {s->N * s->Ho * s->Wo, 1}; }
+static IgemmGrid dgrad_grid(const xas_conv_shape* s) {
+  const int Hp = (s->Hi + s->stride - 1) / s->stride, Wp = (s->Wi + s->stride - 1) / s->stride;
+  return {s->N * Hp * Wp, s->stride * s->stride};
+}
 
 // Rows per tile when the forward pass of `s` can emit batch-norm partial sums for `groups` camera groups (MFMA path, one
 // launch, no tile straddles a group), else 0.  The tile is the one the launch will run on: pick_tile_x6 / pick_tile.
 static int fwd_stats_tile_rows(const xas_conv_shape* s, int groups) {
   if (!s || groups < 1) return 0;
   if (fwd_route(s, false) != FwdRoute::Mfma || s->Cout % 4 != 0) return 0;
-  if (images_per_launch(s->N, (long)s->Hi * s->Wi * s->Cin, 0) < s->N || s->N % groups) return 0;
+  if (fwd_images_per_launch(s) < s->N || s->N % groups) return 0;
   const long M = (long)s->N * s->Ho * s->Wo, Mg = M / groups;
   const int prec = precision_of(s);
   int bm, bn;
@@ -1747,7 +1791,7 @@ static int conv_fwd_impl(const float* x, const float* w_packed, const float* bia
   if (check_shape(s, "conv_fwd") || check_fwd_dims(s, "conv_fwd")) return 1;
   XAS_REQUIRE(x && w_packed && y, "conv_fwd: null buffer");
   const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
-  const int per = images_per_launch(s->N, xi, 0);
+  const int per = fwd_images_per_launch(s);
   if (per < s->N) {
     XAS_REQUIRE(!stat_partial, "conv_fwd: the statistics epilogue needs a single launch");
     return for_image_ranges(s, per, [&](int n0, const xas_conv_shape* part) {
@@ -1786,7 +1830,8 @@ static int conv_fwd_impl(const float* x, const float* w_packed, const float* bia
   p.src = x; p.wgt = w_packed; p.bias = bias; p.out = y;
   p.stat_partial = stat_partial; p.stat_pivot = stat_pivot;
   p.head_partial = head_partial;
-  return dispatch_igemm<0>(p, precision_of(s), s->N * s->Ho * s->Wo, 1, st);
+  const IgemmGrid g = fwd_grid(s);
+  return dispatch_igemm<0>(p, precision_of(s), g.Mrows_max, g.phases, st);
 }
 
 extern "C" int xas_conv_fwd(const float* x, const float* w_packed, const float* bias, float* y,
@@ -1887,11 +1932,9 @@ static int conv_dgrad_impl(const float* dy, const float* w_packed_t, float* dx, 
   XAS_REQUIRE(!accumulate || (route == DgradRoute::Mfma && s->Cin % 4 == 0),
               "conv_dgrad_acc: only the MFMA path accumulates (Cout %% 32 == 0, Cin %% 4 == 0, Cin >= 16)");
   XAS_REQUIRE(dy && w_packed_t && dx, "conv_dgrad: null buffer");
-  // valid for the conv (Hi -> Ho) and for ConvTranspose2d forward (Ho given, Hi = (Ho-1)*stride - 2*pad + R)
-  XAS_REQUIRE((s->Ho - 1) * s->stride - 2 * s->pad + s->R <= s->Hi && (s->Wo - 1) * s->stride - 2 * s->pad + s->S <= s->Wi,
-              "conv_dgrad: Hi/Wi (%d,%d) too small for Ho/Wo (%d,%d)", s->Hi, s->Wi, s->Ho, s->Wo);
+  if (check_dgrad_dims(s, "conv_dgrad")) return 1;
   const long xi = (long)s->Hi * s->Wi * s->Cin, yi = (long)s->Ho * s->Wo * s->Cout;
-  const int per = images_per_launch(s->N, yi, 0);
+  const int per = dgrad_images_per_launch(s);
   if (per < s->N) {
     XAS_REQUIRE(!bnb, "conv_dgrad: the batch-norm epilogue needs a single launch");
     return for_image_ranges(s, per, [&](int n0, const xas_conv_shape* part) {
@@ -1912,20 +1955,16 @@ static int conv_dgrad_impl(const float* dy, const float* w_packed_t, float* dx, 
     case DgradRoute::Mfma: break;
   }
   XAS_REQUIRE((((uintptr_t)dy | (uintptr_t)w_packed_t) & 15) == 0, "conv_dgrad: operands must be 16-byte aligned");
-  IgemmParams p{};
-  p.src = dy; p.wgt = w_packed_t; p.bias = nullptr; p.out = dx; p.N = s->N;
-  p.a_amax = s->grad_amax;
-  p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.Hd = s->Hi; p.Wd = s->Wi; p.Cd = s->Cin;
-  p.R = s->R; p.S = s->S; p.stride = s->stride; p.pad = s->pad; p.tune = g_tune;
+  IgemmParams p = dgrad_problem(s);
+  p.src = dy; p.wgt = w_packed_t; p.bias = nullptr; p.out = dx;
   p.accumulate = accumulate; p.acc_src = acc_src; p.acc_mask = acc_mask;
-  const int Hp = (s->Hi + s->stride - 1) / s->stride, Wp = (s->Wi + s->stride - 1) / s->stride;
-  p.src_elems = (long)p.N * p.Hs * p.Ws * p.Cs; p.wgt_elems = (long)p.Cd * p.R * p.S * p.Cs;
   if (bnb) {
     p.bnb_x = bnb->bnb_x; p.bnb_mean = bnb->bnb_mean; p.bnb_var = bnb->bnb_var; p.bnb_gamma = bnb->bnb_gamma;
     p.bnb_beta = bnb->bnb_beta; p.bnb_eps = bnb->bnb_eps; p.bnb_rows_per_group = bnb->bnb_rows_per_group;
     p.bnb_partial = bnb->bnb_partial;
   }
-  return dispatch_igemm<1>(p, precision_of(s), s->N * Hp * Wp, s->stride * s->stride, st);
+  const IgemmGrid g = dgrad_grid(s);
+  return dispatch_igemm<1>(p, precision_of(s), g.Mrows_max, g.phases, st);
 }
 
 extern "C" int xas_conv_dgrad(const float* dy, const float* w_packed_t, float* dx, const xas_conv_shape* s,
@@ -1944,12 +1983,66 @@ extern "C" int xas_conv_dgrad_acc_masked(const float* dy, const float* w_packed_
   return conv_dgrad_impl(dy, w_packed_t, dx, s, stream, 2, dprev, mask);
 }
 
+// What a launch of xas_conv_fwd (pass 0; has_bias: a bias comes with the call) / xas_conv_dgrad* (pass 1) on this shape would
+// run, from the functions the launch itself reads: check_shape, check_fwd_dims / check_dgrad_dims, fwd_route / dgrad_route,
+// fwd_ / dgrad_images_per_launch, fwd_problem / dgrad_problem and their grids, pick_tile + f32_loop (exact fp32),
+// check_split_fits + igemm_pieces + pick_tile_x6 + tap_patch_width + x6p_tiles_per_block (split arithmetic).  Host only: never
+// touches the device.  Non-zero: a null or unknown argument, or one of the checks named above refuses the shape.  What the
+// query cannot see - null or misaligned buffers, xas_conv_dgrad_acc off the MFMA route - is the launch's to refuse.
+extern "C" int xas_conv_igemm_plan(const xas_conv_shape* s, int pass, int has_bias, int* out) {
+  XAS_REQUIRE(out != nullptr && (pass == 0 || pass == 1), "conv_igemm_plan: null result or pass not 0 (forward) / 1 (data gradient)");
+  if (check_shape(s, "conv_igemm_plan")) return 1;
+  if (pass == 0 ? check_fwd_dims(s, "conv_igemm_plan") : check_dgrad_dims(s, "conv_igemm_plan")) return 1;
+  for (int i = 0; i < XAS_PLAN_INTS; ++i) out[i] = 0;
+  xas_conv_shape part = *s;          // tensors beyond the 32-bit offset range run as several launches over image ranges
+  part.N = pass == 0 ? fwd_images_per_launch(s) : dgrad_images_per_launch(s);
+  out[XAS_PLAN_IMAGES] = part.N;
+  if (pass == 0) {
+    switch (fwd_route(&part, has_bias != 0)) {
+      case FwdRoute::StemF16: out[XAS_PLAN_ROUTE] = XAS_ROUTE_STEM_F16; return 0;
+      case FwdRoute::StemF32: out[XAS_PLAN_ROUTE] = XAS_ROUTE_STEM_F32; return 0;
+      case FwdRoute::ThinVecToScalar: out[XAS_PLAN_ROUTE] = XAS_ROUTE_THIN_VEC_TO_SCALAR; return 0;
+      case FwdRoute::ThinScalarToVec: out[XAS_PLAN_ROUTE] = XAS_ROUTE_THIN_SCALAR_TO_VEC; return 0;
+      case FwdRoute::Direct: out[XAS_PLAN_ROUTE] = XAS_ROUTE_DIRECT; return 0;
+      case FwdRoute::Mfma: break;
+    }
+  } else {
+    switch (dgrad_route(&part)) {
+      case DgradRoute::ThinVecToScalar: out[XAS_PLAN_ROUTE] = XAS_ROUTE_THIN_VEC_TO_SCALAR; return 0;
+      case DgradRoute::ThinScalarToVec: out[XAS_PLAN_ROUTE] = XAS_ROUTE_THIN_SCALAR_TO_VEC; return 0;
+      case DgradRoute::Direct: out[XAS_PLAN_ROUTE] = XAS_ROUTE_DIRECT; return 0;
+      case DgradRoute::Mfma: break;
+    }
+  }
+  out[XAS_PLAN_ROUTE] = XAS_ROUTE_MFMA;
+  const IgemmParams p = pass == 0 ? fwd_problem(&part) : dgrad_problem(&part);
+  const IgemmGrid g = pass == 0 ? fwd_grid(&part) : dgrad_grid(&part);
+  const int prec = precision_of(&part);
+  out[XAS_PLAN_PHASES] = g.phases;
+  if (prec == XAS_PREC_F32) {
+    const F32Loop l = f32_loop(p);
+    out[XAS_PLAN_KERNEL] = l.buf ? XAS_KERNEL_IGEMM_BUF : XAS_KERNEL_IGEMM;
+    out[XAS_PLAN_PIPELINED] = l.pipe ? 1 : 0;
+    pick_tile(p.Cd, g.Mrows_max, g.phases, &out[XAS_PLAN_BM], &out[XAS_PLAN_BN]);
+    return 0;
+  }
+  if (check_split_fits(p)) return 1;
+  const int pieces = igemm_pieces(p, prec, pass);
+  const X6Tile t = pick_tile_x6(p, pass, g.Mrows_max, g.phases, pieces);
+  out[XAS_PLAN_PIECES] = pieces;
+  out[XAS_PLAN_BM] = t.bm; out[XAS_PLAN_BN] = t.bn;
+  out[XAS_PLAN_KERNEL] = t.kernel == X6Tile::Tap ? XAS_KERNEL_IGEMM_X6T : t.kernel == X6Tile::Persistent ? XAS_KERNEL_IGEMM_X6P : XAS_KERNEL_IGEMM_X6;
+  if (t.kernel == X6Tile::Tap) out[XAS_PLAN_PATCH_WIDTH] = tap_patch_width(p.Wd);
+  if (t.kernel == X6Tile::Persistent) out[XAS_PLAN_TPB] = x6p_tiles_per_block(p, g.Mrows_max);
+  return 0;
+}
+
 // Rows per tile when the data gradient of `s` can carry the batch-norm backward reduction of the layer in front of the
 // convolution in its epilogue (MFMA path, stride 1, one launch, full tiles that do not straddle a camera group), else 0.
 static int dgrad_bnb_tile_rows(const xas_conv_shape* s, int groups) {
   if (!s || groups < 1 || s->stride != 1) return 0;
   if (dgrad_route(s) != DgradRoute::Mfma || s->Cin % 4 != 0) return 0;
-  if (images_per_launch(s->N, (long)s->Ho * s->Wo * s->Cout, 0) < s->N || s->N % groups) return 0;
+  if (dgrad_images_per_launch(s) < s->N || s->N % groups) return 0;
   const long M = (long)s->N * s->Hi * s->Wi, Mg = M / groups;
   int bm, bn;
   pick_tile(s->Cin, M, 1, &bm, &bn);

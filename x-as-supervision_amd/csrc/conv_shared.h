@@ -538,6 +538,8 @@ static inline bool tap_tile_ok(int R, int S, int stride, int pad, int Hs, int Ws
   if (R != 3 || S != 3 || stride != 1 || pad != 1 || Hd != Hs || Wd != Ws || Cs % 32 != 0 || Hd % 8 != 0) return false;
   return Wd % 16 == 0 || (Wd == 8 && N % 2 == 0);
 }
+// ... and the width of those patches: 8 x 16 of one image, or 8 x 8 of two images (IgemmParams::t2d_tw)
+static inline int tap_patch_width(int Wd) { return Wd % 16 == 0 ? 16 : 8; }
 
 #ifndef XAS_TILE128_MIN_BLOCKS
 #define XAS_TILE128_MIN_BLOCKS 256     // fewer 128 x 128 tiles than this: 64 x 64 tiles (r03 sweep, in-box: 512 -> 256 -1.4 ms/step, 128 / 192 the same, 1024 +2.6)
@@ -564,6 +566,8 @@ struct X6Tile {
   enum Kernel { General, Tap, Persistent } kernel;    // igemm_x6_kernel, igemm_x6t_kernel, igemm_x6p_kernel
 };
 X6Tile pick_tile_x6(const IgemmParams& p, int mode, int Mrows_max, int phases, int pieces);
+// consecutive 64-row M-tiles a block of igemm_x6p_kernel walks (IgemmParams::tpb) on a problem of Mrows_max rows
+int x6p_tiles_per_block(const IgemmParams& p, int Mrows_max);
 int launch_wgrad_x6(const WgradParams& p, int bm, int bn, int splits, int pieces, hipStream_t st);
 bool wgrad_x6t_plan(const xas_conv_shape* s, int* bm, int* splits, int* pps);
 int launch_wgrad_x6t(const WgradParams& p, int bm, int splits, int pps, int pieces, hipStream_t st);

@@ -797,7 +797,7 @@ template <int BN, int MODE, int P>
 static int launch_igemm_x6t(const IgemmParams& p, int Mrows_max, hipStream_t st) {
   constexpr size_t lds = igemm_x6t_lds<BN>(P);
   IgemmParams q = p;
-  q.t2d_tw = p.Wd % 16 == 0 ? 16 : 8;
+  q.t2d_tw = tap_patch_width(p.Wd);
   q.nMt = Mrows_max / 128; q.nNt = (int)cdiv(p.Cd, BN);
   q.xn = 1; q.nt_per_x = q.nNt; q.mt_per_xcd = (int)cdiv(q.nMt, 8);
   dim3 grid((unsigned)(8 * q.mt_per_xcd * q.nt_per_x), 1, 1);
@@ -821,15 +821,19 @@ static bool x6p_takes(const IgemmParams& p, int mode, int phases) {
          !p.t2d_tw && !p.bnb_x && p.a_amax != nullptr && (p.Cd & 3) == 0;
 }
 
+// tiles per block: long enough for the stream to matter, short enough for >= 4 rounds of the ~768 resident blocks
+int x6p_tiles_per_block(const IgemmParams& p, int Mrows_max) {
+  const long tiles = cdiv(Mrows_max, 64) * cdiv(p.Cd, 256);
+  const int tpb = (int)(tiles / (768 * 4));
+  return tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
+}
+
 template <int MODE>
 static int launch_igemm_x6p(const IgemmParams& p, int Mrows_max, hipStream_t st) {
   constexpr size_t lds = igemm_x6_lds<64, 256>(2, false);
   IgemmParams q = p;
   q.nMt = (int)cdiv(Mrows_max, 64); q.nNt = (int)cdiv(p.Cd, 256);
-  // tiles per block: long enough for the stream to matter, short enough for >= 4 rounds of the ~768 resident blocks
-  const long tiles = (long)q.nMt * q.nNt;
-  int tpb = (int)(tiles / (768 * 4));
-  tpb = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
+  const int tpb = x6p_tiles_per_block(p, Mrows_max);
   q.tpb = tpb;
   const int nMg = (int)cdiv(q.nMt, tpb);
   q.xn = pick_xcd_grid((double)Mrows_max * p.Cs * 4.0, (double)p.Cd * p.Cs * 2.0 * 2, q.nMt, q.nNt, nMg);   // M-groups as the unit

@@ -41,6 +41,23 @@ TUNE_GENERAL_KERNELS = 1 << 22       # no tap re-use conv kernels, no streaming 
 TUNE_NO_WIDE_TILES, TUNE_NO_STEM_WGRAD, TUNE_STEM_FWD_F32 = 1 << 23, 1 << 24, 1 << 25
 TUNE_NO_X6P, TUNE_X6P_ANY_K = 1 << 26, 1 << 27
 
+# xas_hip.h XAS_PLAN_*: the fields of xas_conv_igemm_plan's result, in order, and the values of its route and kernel fields
+# (XAS_ROUTE_*, XAS_KERNEL_*; 0 = does not apply).  tests/test_abi.py keeps them equal to the header.
+PLAN_FIELDS = ('route', 'kernel', 'bm', 'bn', 'pipelined', 'phases', 'pieces', 'patch_width', 'tpb', 'images')
+PLAN_ROUTES = (None, 'stem_f16', 'stem_f32', 'thin_vec_to_scalar', 'thin_scalar_to_vec', 'direct', 'mfma')
+PLAN_KERNELS = (None, 'igemm_buf', 'igemm', 'igemm_x6', 'igemm_x6t', 'igemm_x6p')
+
+
+def conv_igemm_plan(shp, pass_, has_bias=False):
+    """xas_conv_igemm_plan as a dict (route and kernel by name).  Host only."""
+    out = (ctypes.c_int * len(PLAN_FIELDS))()
+    rc = fn('xas_conv_igemm_plan')(shp, pass_, int(has_bias), ctypes.cast(out, ctypes.c_void_p))
+    if rc != 0:
+        raise RuntimeError('xas_conv_igemm_plan failed (%d): %s' % (rc, load().xas_last_error().decode()))
+    plan = dict(zip(PLAN_FIELDS, out))
+    plan['route'], plan['kernel'] = PLAN_ROUTES[plan['route']], PLAN_KERNELS[plan['kernel']]
+    return plan
+
 
 # name -> (argument codes, return code).  's' = pointer to ConvShape.  Last 'p' is the stream
 # for every launch function.
@@ -82,6 +99,7 @@ SIGNATURES = {
     'xas_conv_dgrad': ('pppsp', 'i'),
     'xas_conv_dgrad_acc': ('pppsp', 'i'),
     'xas_conv_dgrad_acc_masked': ('pppsppp', 'i'),
+    'xas_conv_igemm_plan': ('siip', 'i'),
     'xas_conv_wgrad_workspace_floats': ('s', 'z'),
     'xas_conv_wgrad': ('ppppsp', 'i'),
     'xas_conv_wgrad_oihw': ('ppppsp', 'i'),
