@@ -473,6 +473,31 @@ int xas_bn_bwd_apply_amax(const float* x, const float* y, const float* dy, const
                           const float* var_biased, const float* gamma, const float* beta, const float* sums,
                           float eps, int act, long M, int C, int groups, double count, float* dx,
                           float* dresidual, const uint8_t* mask, float* amax_out, void* stream);
+/* Dual forms: the output of a bottleneck WITH a projection, out = relu(bn3(x) + bn_d(xd)) (torchvision Bottleneck with
+ * `downsample`, resnet.py:2), as one pass per step over both norms.  x / xd [M][C]: the raw results of conv3 and of the
+ * projection convolution; every argument with the suffix _d belongs to the projection norm, the others to bn3; both norms
+ * share M, C and groups.  Neither the normalised skip bn_d(xd) nor its gradient is ever written; the values are
+ * those of xas_bn_apply_amax (act 0) -> xas_bn_apply_amax (act 1, residual, mask_out) forward and of xas_bn_bwd_reduce /
+ * xas_bn_bwd_apply_amax run for bn3 (mask, dresidual) and then for the projection norm on that dresidual, bit for bit
+ * (the backward apply: where C / 4 is a power of two, the streaming kernels; elsewhere to rounding).
+ * forward: y, the sign bytes mask_out (required) and max |y| (amax_out may be NULL). */
+int xas_bn_apply_dual_amax(const float* x, const float* mean, const float* var_biased, const float* gamma,
+                           const float* beta, float eps, const float* xd, const float* mean_d,
+                           const float* var_biased_d, const float* gamma_d, const float* beta_d, float eps_d,
+                           long M, int C, int groups, float* y, uint8_t* mask_out, float* amax_out, void* stream);
+/* backward, step 1: dz = dy * relu'(mask); sums [groups][2][C] = sum dz | sum dz * xhat(x), sums_d the same with xhat(xd).
+ * workspace: 2 * xas_bn_workspace_floats(M, C, groups) floats.  The accumulator pairs as xas_bn_bwd_reduce, one per norm. */
+int xas_bn_bwd_reduce_dual(const float* x, const float* xd, const float* dy, const uint8_t* mask, const float* mean,
+                           const float* var_biased, float eps, const float* mean_d, const float* var_biased_d,
+                           float eps_d, long M, int C, int groups, float* sums, float* sums_d, float* workspace,
+                           float* dbeta_acc, float* dgamma_acc, float* dbeta_d_acc, float* dgamma_d_acc, void* stream);
+/* step 2: dx = gradient wrt x, dxd = gradient wrt xd, both from the one dz; max |dx| -> amax_out, max |dxd| -> amax_d_out
+ * (each may be NULL).  count / count_d: rows per group of each norm (x world size where THAT norm is a SyncBatchNorm). */
+int xas_bn_bwd_apply_dual_amax(const float* x, const float* xd, const float* dy, const uint8_t* mask,
+                               const float* mean, const float* var_biased, const float* gamma, const float* sums,
+                               float eps, const float* mean_d, const float* var_biased_d, const float* gamma_d,
+                               const float* sums_d, float eps_d, long M, int C, int groups, double count,
+                               double count_d, float* dx, float* dxd, float* amax_out, float* amax_d_out, void* stream);
 
 /* 3x3 stride-2 pad-1 max pool (resnet.py:20), NHWC. idx: int8 argmax tap 0..8 for backward */
 int xas_maxpool3x3s2_fwd(const float* x, int N, int H, int W, int C, float* y, int8_t* idx, void* stream);

@@ -91,8 +91,10 @@ enum ColMode : int {
                           // (C = 2 x channels, pivot per channel or null): f1 = x, one sum -> mean, var (, running statistics)
   kColBwdPartials = 6,    // x = per-tile partial sums of a data-gradient epilogue, [rows][2][C/2 channels] (sum dz | sum dz xhat):
                           // f1 = x, one sum -> out1 = sums [G][2][channels]; acc1 / acc2 (dbeta / dgamma) get the two halves
+  kColBwdDual = 7,        // x, x2, dy, mask bytes: block output relu(bn3(x) + bn_d(x2)), two norms under ONE dz: f1 = dz, w = xhat of x,
+                          // w2 = xhat of x2 -> sum dz | sum dz w (first norm) and sum dz | sum dz w2 (second norm, ColSecond)
 };
-constexpr bool col_is_bwd(ColMode m) { return m == kColBwdXY || m == kColBwdY || m == kColBwdX; }
+constexpr bool col_is_bwd(ColMode m) { return m == kColBwdXY || m == kColBwdY || m == kColBwdX || m == kColBwdDual; }
 constexpr bool col_two_sums(ColMode m) { return m == kColStats || col_is_bwd(m); }
 constexpr bool col_is_stats(ColMode m) { return m == kColStats || m == kColStatsPartials; }
 
@@ -112,6 +114,11 @@ struct ColArgs {
   float* running_mean; float* running_var; float momentum, unbias;
   float* acc1; float* acc2;    // != null: acc1[c] += sum over groups of out1 ... (parameter gradients, in place)
   long rows_real;              // kColStatsPartials: activation rows per group behind the partial rows
+  // kColBwdDual: the second norm's input and statistics, and where ITS publish / finalize go (same geometry, own tickets)
+  struct ColSecond {
+    const float* x; const float* mean; const float* var; float eps;
+    float* partial; unsigned* ticket; float* out1; float* out2; float* acc1; float* acc2;
+  } second;
 };
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -165,13 +172,14 @@ __device__ __forceinline__ float4 act_inv4(float4 yv, int act) {
 // the per-channel quantities of a thread's channel quadruple; a mode fills what its term reads
 struct ColChan {
   float4 pivot, mean, rstd, rsg, beta, inv_gamma;      // rsg = rstd * gamma (rounded once: bn_affine's contract)
+  float4 mean2, rstd2;                                 // kColBwdDual: of the second norm
 };
 
 template <ColMode MODE>
 __device__ __forceinline__ ColChan col_chan(const ColArgs& a, int grp, int c) {
   ColChan ch{};
   if constexpr (MODE == kColStats) ch.pivot = ld4(a.x + (size_t)grp * a.g.Mg * a.C + c);      // first row of the group
-  if constexpr (MODE == kColBwdXY || MODE == kColBwdX) {                                        // per-group statistics
+  if constexpr (MODE == kColBwdXY || MODE == kColBwdX || MODE == kColBwdDual) {                 // per-group statistics
     ch.mean = ld4(a.mean + (size_t)grp * a.C + c);
     const float4 v = ld4(a.var + (size_t)grp * a.C + c);
     ch.rstd = make_float4(rsqrtf(v.x + a.eps), rsqrtf(v.y + a.eps), rsqrtf(v.z + a.eps), rsqrtf(v.w + a.eps));
@@ -180,6 +188,12 @@ __device__ __forceinline__ ColChan col_chan(const ColArgs& a, int grp, int c) {
     const float4 gm = ld4(a.gamma + c);
     ch.rsg = make_float4(__fmul_rn(ch.rstd.x, gm.x), __fmul_rn(ch.rstd.y, gm.y), __fmul_rn(ch.rstd.z, gm.z), __fmul_rn(ch.rstd.w, gm.w));
     ch.beta = ld4(a.beta + c);
+  }
+  if constexpr (MODE == kColBwdDual) {
+    ch.mean2 = ld4(a.second.mean + (size_t)grp * a.C + c);
+    const float4 v = ld4(a.second.var + (size_t)grp * a.C + c);
+    const float e2 = a.second.eps;
+    ch.rstd2 = make_float4(rsqrtf(v.x + e2), rsqrtf(v.y + e2), rsqrtf(v.z + e2), rsqrtf(v.w + e2));
   }
   if constexpr (MODE == kColBwdY) {
     ch.beta = ld4(a.beta + c);
@@ -191,8 +205,8 @@ __device__ __forceinline__ ColChan col_chan(const ColArgs& a, int grp, int c) {
 }
 
 // (f1, w) of the element at float offset i (four lanes) from the operands the mode reads: the first sum takes f1, the
-// second f1 * w
-struct ColTerm { float4 f1, w; };
+// second f1 * w (kColBwdDual: and the second norm's second sum f1 * w2; its first sum IS the first norm's)
+struct ColTerm { float4 f1, w, w2; };
 
 template <ColMode MODE>
 __device__ __forceinline__ ColTerm col_term(const ColArgs& a, const ColChan& ch, long i) {
@@ -205,11 +219,12 @@ __device__ __forceinline__ ColTerm col_term(const ColArgs& a, const ColChan& ch,
     if constexpr (MODE == kColStats) {
       const float4 d = make_float4(xv.x - ch.pivot.x, xv.y - ch.pivot.y, xv.z - ch.pivot.z, xv.w - ch.pivot.w);
       return {d, d};
-    } else if constexpr (MODE == kColBwdXY) {
+    } else if constexpr (MODE == kColBwdXY || MODE == kColBwdDual) {
       float4 dz = ld4(a.dy + i);
       if (a.act && a.mask) dz = dz_sign_mask(dz, a.mask[i >> 2], neg);
       else if (a.act) dz = dz_sign_y(dz, ld4(a.y + i), neg);
-      return {dz, xhat4(xv, ch.mean, ch.rstd)};
+      if constexpr (MODE == kColBwdDual) return {dz, xhat4(xv, ch.mean, ch.rstd), xhat4(ld4(a.second.x + i), ch.mean2, ch.rstd2)};
+      else return {dz, xhat4(xv, ch.mean, ch.rstd)};
     } else if constexpr (MODE == kColBwdX) {
       return {dz_sign_x(ld4(a.dy + i), xv, ch.mean, ch.rsg, ch.beta, neg), xhat4(xv, ch.mean, ch.rstd)};
     } else {
@@ -409,11 +424,67 @@ __device__ __forceinline__ void col_reduce_body(const ColArgs& a) {
   }
 }
 
+// kColBwdDual: the row loop with a third accumulator, then publish + finalize once per norm, the second time with the second
+// norm's partials, tickets, outputs and accumulators.  Each norm's sums take the path a reduction of its own takes (slab
+// geometry, lane order, double finalize): the same bits.  A body of its own, so that the code of the other modes - and with it
+// the last bits of every statistic they have ever written - stays what it is.
+template <int UNR, int FL>
+__device__ __forceinline__ void col_reduce_dual_body(const ColArgs& a0) {
+  __shared__ __align__(16) float4 red[2][256];
+  const ColGeom& g = a0.g;
+  const int C = a0.C;
+  const int tx = threadIdx.x % g.TX, ty = threadIdx.x / g.TX;
+  const int c = blockIdx.y * g.CB + tx * 4;
+  const int grp = blockIdx.z;
+  const long r0 = grp * g.Mg + (long)blockIdx.x * g.rows_per_slab;
+  const long r1 = min((grp + 1) * g.Mg, r0 + g.rows_per_slab);
+  const ColChan ch = col_chan<kColBwdDual>(a0, grp, c);
+  const float4 z4 = make_float4(0, 0, 0, 0);
+  float4 s1 = z4, s2 = z4, s3 = z4;
+#pragma unroll UNR
+  for (long r = r0 + ty; r < r1; r += g.TY) {
+    const ColTerm t = col_term<kColBwdDual>(a0, ch, r * C + c);
+    s1.x += t.f1.x; s1.y += t.f1.y; s1.z += t.f1.z; s1.w += t.f1.w;
+    s2.x = fmaf(t.f1.x, t.w.x, s2.x); s2.y = fmaf(t.f1.y, t.w.y, s2.y);
+    s2.z = fmaf(t.f1.z, t.w.z, s2.z); s2.w = fmaf(t.f1.w, t.w.w, s2.w);
+    s3.x = fmaf(t.f1.x, t.w2.x, s3.x); s3.y = fmaf(t.f1.y, t.w2.y, s3.y);
+    s3.z = fmaf(t.f1.z, t.w2.z, s3.z); s3.w = fmaf(t.f1.w, t.w2.w, s3.w);
+  }
+  for (int norm = 0; norm < 2; ++norm) {
+    ColArgs a = a0;
+    if (norm) {
+      a.partial = a0.second.partial; a.ticket = a0.second.ticket;
+      a.out1 = a0.second.out1; a.out2 = a0.second.out2; a.acc1 = a0.second.acc1; a.acc2 = a0.second.acc2;
+      __syncthreads();                                    // (the first norm's finalize is done with `red`)
+    }
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
+        a.partial, 0, (int)((size_t)g.G * g.nslab * 2 * C * sizeof(float)), 0x00020000);
+    if (!col_publish(a, red, prs, s1, norm ? s3 : s2, tx, ty, c, grp)) continue;
+    float4 accg1 = z4, accg2 = z4;                        // sums over groups (parameter gradients)
+    for (int gi = 0; gi < g.G; ++gi) {
+      double d1[4], d2[4];
+      col_slab_sums<FL>(a, reinterpret_cast<double*>(&red[0][0]), prs, gi, tx, ty, c, d1, d2);
+      if (ty != 0) continue;
+      const float4 f1 = make_float4((float)d1[0], (float)d1[1], (float)d1[2], (float)d1[3]);
+      const float4 f2 = make_float4((float)d2[0], (float)d2[1], (float)d2[2], (float)d2[3]);
+      *reinterpret_cast<float4*>(a.out1 + (size_t)gi * a.out_stride + c) = f1;
+      *reinterpret_cast<float4*>(a.out2 + (size_t)gi * a.out_stride + c) = f2;
+      accg1.x += f1.x; accg1.y += f1.y; accg1.z += f1.z; accg1.w += f1.w;
+      accg2.x += f2.x; accg2.y += f2.y; accg2.z += f2.z; accg2.w += f2.w;
+    }
+    if (ty == 0 && a.acc1) {                              // parameter gradients accumulated in place (.grad arena)
+      grad_add4(a.acc1 + c, accg1);
+      grad_add4(a.acc2 + c, accg2);
+    }
+  }
+}
+
 // (the kernels keep an int parameter: col_reduce_kernel<1> stays the name that the recorded profiles carry)
 template <int MODE>
 __global__ __launch_bounds__(256) void col_reduce_kernel(ColArgs a) {
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-  col_reduce_body<(ColMode)MODE, 4, 4>(a);
+  if constexpr (MODE == kColBwdDual) col_reduce_dual_body<4, 4>(a);
+  else col_reduce_body<(ColMode)MODE, 4, 4>(a);
 }
 
 // Same kernel compiled for at most 64 VGPRs: shipped for the backward sums in r04, when they ran beside two weight-gradient
@@ -426,7 +497,8 @@ template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void col_reduce_lean_kernel(ColArgs a) {
   __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
-  col_reduce_body<(ColMode)MODE, 2, 2>(a);
+  if constexpr (MODE == kColBwdDual) col_reduce_dual_body<2, 2>(a);
+  else col_reduce_body<(ColMode)MODE, 2, 2>(a);
 }
 
 // SyncBatchNorm: merge the per-rank statistics of every group.  gathered: [world][G][msg_stride] = mean | biased var |
@@ -632,6 +704,96 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     one(i, needx ? x[k] : z4, needy ? y[k] : z4, dy[k], sign == 3 ? mask[k] : 0u);
   }
   if (amax_out) publish_amax(amax_out, amx);
+}
+
+// ---- dual forms: the output of a block with a projection, out = relu(bn3(x) + bn_d(xd)), both norms [M][C] with the same
+// groups.  The normalised skip bn_d(xd) and the residual gradient dz exist in registers only; an element goes through
+// bn_fwd_elem / bn_bwd_elem once per norm, so the values are those of the single-norm kernels run one after the other.
+struct BnNorm {
+  const float* mean; const float* var; const float* gamma; const float* beta;      // beta: forward only
+  const float* sums;                                                                // backward only: [G][2][C]
+  float eps;
+};
+
+template <bool BWD>
+__device__ __forceinline__ BnChan bn_chan(const BnNorm& n, int C4, long i) {
+  return bn_chan<BWD>(n.mean, n.var, n.gamma, n.beta, n.sums, n.eps, C4, i);
+}
+
+// STREAM / general as bn_apply_kernel (the one mode: ReLU, sign bytes written)
+template <bool STREAM>
+__global__ __launch_bounds__(256) void bn_apply_dual_kernel(const float4* __restrict__ x, const float4* __restrict__ xd, BnNorm n3,
+                                                           BnNorm nd, long n4g, int C4, float4* __restrict__ y,
+                                                           uint8_t* __restrict__ mask_out, float* __restrict__ amax_out) {
+  float amx = 0.f;                                     // max |y| of this thread
+  if (STREAM) __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
+  const long goff = (long)blockIdx.y * n4g;
+  const long stride = (long)gridDim.x * blockDim.x;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  BnChan ch, chd;
+  const float4 z4 = make_float4(0, 0, 0, 0);
+  auto one = [&](long k, float4 xv, float4 dv) {
+    float skip_amx = 0.f;                              // (the skip's maximum has no reader)
+    const float4 skip = bn_fwd_elem(chd, dv, z4, 0, false, false, nullptr, skip_amx);
+    ew_store<STREAM>(y + goff + k, bn_fwd_elem(ch, xv, skip, 1, true, true, mask_out + goff + k, amx));
+  };
+  if (STREAM) {
+    ch = bn_chan<false>(n3, C4, i); chd = bn_chan<false>(nd, C4, i);
+    for (; i + 3 * stride < n4g; i += 4 * stride) {
+      float4 xv[4], dv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { xv[u] = stream_load(x + goff + i + u * stride); dv[u] = stream_load(xd + goff + i + u * stride); }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(i + u * stride, xv[u], dv[u]);
+    }
+  }
+  for (; i < n4g; i += stride) {                       // streaming: the tail; general: the whole loop
+    if (!STREAM) { ch = bn_chan<false>(n3, C4, i); chd = bn_chan<false>(nd, C4, i); }
+    one(i, x[goff + i], xd[goff + i]);
+  }
+  if (amax_out) publish_amax(amax_out, amx);
+}
+
+// -> dx (bn3's input gradient, sign from the mask bytes) and dxd (the projection norm's, no activation) from ONE dz
+template <bool STREAM>
+__global__ __launch_bounds__(256) void bn_bwd_apply_dual_kernel(
+    const float4* __restrict__ x, const float4* __restrict__ xd, const float4* __restrict__ dy, const uint8_t* __restrict__ mask,
+    BnNorm n3, BnNorm nd, long n4g, int C4, float inv_count, float inv_count_d, float4* __restrict__ dx, float4* __restrict__ dxd,
+    float* __restrict__ amax_out, float* __restrict__ amax_d_out) {
+  if (STREAM) __builtin_amdgcn_s_setprio(XAS_BN_PRIO);
+  float amx = 0.f, amxd = 0.f;                         // max |dx|, max |dxd| of this thread
+  const long goff = (long)blockIdx.y * n4g;
+  const long stride = (long)gridDim.x * blockDim.x;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  BnChan ch, chd;
+  const float4 z4 = make_float4(0, 0, 0, 0);
+  auto one = [&](long k, float4 xv, float4 dv, float4 dz, unsigned mb) {
+    ew_store<STREAM>(dx + goff + k, bn_bwd_elem<STREAM>(ch, inv_count, xv, z4, dz, mb, 1, 3, true, false, nullptr, amx));
+    const float4 dres = dz_sign_mask(dz, mb, act_neg_slope(1));          // what bn3's apply would have stored for the skip
+    ew_store<STREAM>(dxd + goff + k, bn_bwd_elem<STREAM>(chd, inv_count_d, dv, z4, dres, 0u, 0, 0, true, false, nullptr, amxd));
+  };
+  if (STREAM) {
+    ch = bn_chan<true>(n3, C4, i); chd = bn_chan<true>(nd, C4, i);
+    for (; i + 3 * stride < n4g; i += 4 * stride) {
+      float4 xv[4], dv[4], gv[4];
+      unsigned mb[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long k = goff + i + u * stride;
+        gv[u] = stream_load(dy + k); xv[u] = stream_load(x + k); dv[u] = stream_load(xd + k); mb[u] = mask[k];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(i + u * stride, xv[u], dv[u], gv[u], mb[u]);
+    }
+  }
+  for (; i < n4g; i += stride) {                       // streaming: the tail; general: the whole loop
+    if (!STREAM) { ch = bn_chan<true>(n3, C4, i); chd = bn_chan<true>(nd, C4, i); }
+    const long k = goff + i;
+    one(i, x[k], xd[k], dy[k], mask[k]);
+  }
+  if (amax_out) publish_amax(amax_out, amx);
+  __syncthreads();                                     // (publish_amax's LDS words are read by thread 0 after its barrier)
+  if (amax_d_out) publish_amax(amax_d_out, amxd);
 }
 
 // one update per group, in group order (mean / var: [G][C])
@@ -1101,6 +1263,79 @@ extern "C" int xas_bn_bwd_apply_amax(const float* x, const float* y, const float
                      reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y),
                      reinterpret_cast<const float4*>(dy), mean, var_biased, gamma, beta, sums, eps, act, n4g,
                      C4, (float)(1.0 / count), reinterpret_cast<float4*>(dx), reinterpret_cast<float4*>(dresidual), mask, amax_out);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- dual forms (xas_hip.h): bn3 and the projection norm of a block output in one pass each ---------------------------
+static int bn_dual_shape(const char* who, long M, int C, int groups) {
+  XAS_REQUIRE(M > 0 && C >= 4 && C % 4 == 0 && groups >= 1 && M % groups == 0, "%s: bad shape M=%ld C=%d groups=%d", who, M, C, groups);
+  return 0;
+}
+
+extern "C" int xas_bn_apply_dual_amax(const float* x, const float* mean, const float* var_biased, const float* gamma,
+                                      const float* beta, float eps, const float* xd, const float* mean_d,
+                                      const float* var_biased_d, const float* gamma_d, const float* beta_d, float eps_d,
+                                      long M, int C, int groups, float* y, uint8_t* mask_out, float* amax_out, void* stream) {
+  XAS_REQUIRE(x && mean && var_biased && gamma && beta && xd && mean_d && var_biased_d && gamma_d && beta_d && y && mask_out,
+              "bn_apply_dual: null buffer");
+  if (bn_dual_shape("bn_apply_dual", M, C, groups)) return 1;
+  const int C4 = C / 4;
+  const long n4g = (M / groups) * C4;
+  const unsigned gs = bn_stream_grid(n4g, C4, groups, tune_flags());
+  const BnNorm n3{mean, var_biased, gamma, beta, nullptr, eps}, nd{mean_d, var_biased_d, gamma_d, beta_d, nullptr, eps_d};
+  hipLaunchKernelGGL(gs ? bn_apply_dual_kernel<true> : bn_apply_dual_kernel<false>, dim3(gs ? gs : ew_grid_g(n4g, groups), groups),
+                     dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(xd), n3,
+                     nd, n4g, C4, reinterpret_cast<float4*>(y), mask_out, amax_out);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_bn_bwd_reduce_dual(const float* x, const float* xd, const float* dy, const uint8_t* mask, const float* mean,
+                                      const float* var_biased, float eps, const float* mean_d, const float* var_biased_d,
+                                      float eps_d, long M, int C, int groups, float* sums, float* sums_d, float* workspace,
+                                      float* dbeta_acc, float* dgamma_acc, float* dbeta_d_acc, float* dgamma_d_acc,
+                                      void* stream) {
+  ColGeom g;
+  if (col_geom(M, C, groups, &g)) return 1;
+  XAS_REQUIRE(x && xd && dy && mask && mean && var_biased && mean_d && var_biased_d && sums && sums_d && workspace,
+              "bn_bwd_reduce_dual: null buffer");
+  XAS_REQUIRE((dbeta_acc == nullptr) == (dgamma_acc == nullptr) && (dbeta_d_acc == nullptr) == (dgamma_d_acc == nullptr),
+              "bn_bwd_reduce_dual: gradient accumulators come in pairs");
+  const bool lean = (tune_flags() & XAS_TUNE_COL_REDUCE_LEAN) != 0;
+  const size_t per_norm = (size_t)g.G * g.nslab * 2 * C + C;               // xas_bn_workspace_floats(M, C, groups)
+  ColArgs a{};
+  a.M = M; a.C = C; a.g = g; a.partial = workspace;
+  a.ticket = take_tickets(2 * g.ncb);                                      // ncb words per norm
+  XAS_REQUIRE(a.ticket != nullptr, "column reduce: could not allocate the ticket counters");
+  XAS_REQUIRE((size_t)g.G * g.nslab * 2 * C * sizeof(float) < 0x7fffff00ul, "column reduce: partial buffer too large");
+  a.x = x; a.dy = dy; a.mask = mask; a.mean = mean; a.var = var_biased; a.eps = eps; a.act = 1;
+  a.out1 = sums; a.out2 = sums + C; a.out_stride = 2 * (long)C;            // [G][2][C]
+  a.acc1 = dbeta_acc; a.acc2 = dgamma_acc;
+  a.second = {xd, mean_d, var_biased_d, eps_d, workspace + per_norm, a.ticket + g.ncb, sums_d, sums_d + C, dbeta_d_acc, dgamma_d_acc};
+  return launch_col_reduce<kColBwdDual>(a, lean, stream);
+}
+
+extern "C" int xas_bn_bwd_apply_dual_amax(const float* x, const float* xd, const float* dy, const uint8_t* mask,
+                                          const float* mean, const float* var_biased, const float* gamma, const float* sums,
+                                          float eps, const float* mean_d, const float* var_biased_d, const float* gamma_d,
+                                          const float* sums_d, float eps_d, long M, int C, int groups, double count,
+                                          double count_d, float* dx, float* dxd, float* amax_out, float* amax_d_out,
+                                          void* stream) {
+  XAS_REQUIRE(x && xd && dy && mask && mean && var_biased && gamma && sums && mean_d && var_biased_d && gamma_d && sums_d && dx && dxd,
+              "bn_bwd_apply_dual: null buffer");
+  if (bn_dual_shape("bn_bwd_apply_dual", M, C, groups)) return 1;
+  XAS_REQUIRE(count > 0 && count_d > 0, "bn_bwd_apply_dual: bad count");
+  const int C4 = C / 4;
+  const long n4g = (M / groups) * C4;
+  const unsigned gs = bn_stream_grid(n4g, C4, groups, tune_flags());
+  const BnNorm n3{mean, var_biased, gamma, nullptr, sums, eps}, nd{mean_d, var_biased_d, gamma_d, nullptr, sums_d, eps_d};
+  hipLaunchKernelGGL(gs ? bn_bwd_apply_dual_kernel<true> : bn_bwd_apply_dual_kernel<false>,
+                     dim3(gs ? gs : ew_grid_g(n4g, groups), groups), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(xd), reinterpret_cast<const float4*>(dy),
+                     mask, n3, nd, n4g, C4, (float)(1.0 / count), (float)(1.0 / count_d), reinterpret_cast<float4*>(dx),
+                     reinterpret_cast<float4*>(dxd),
+                     amax_out, amax_d_out);
   XAS_LAUNCH_CHECK();
   return 0;
 }

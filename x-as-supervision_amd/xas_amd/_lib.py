@@ -120,6 +120,9 @@ SIGNATURES = {
     'xas_bn_bwd_reduce': ('pppppppfiliipppppp', 'i'),
     'xas_bn_bwd_apply': ('ppppppppfiliidpppp', 'i'),
     'xas_bn_bwd_apply_amax': ('ppppppppfiliidppppp', 'i'),
+    'xas_bn_apply_dual_amax': ('pppppf' 'pppppf' 'lii' 'pppp', 'i'),
+    'xas_bn_bwd_reduce_dual': ('ppppppf' 'ppf' 'lii' 'ppp' 'pppp' 'p', 'i'),
+    'xas_bn_bwd_apply_dual_amax': ('pppp' 'ppppf' 'ppppf' 'liidd' 'pppp' 'p', 'i'),
     'xas_maxpool3x3s2_fwd': ('piiiippp', 'i'),
     'xas_maxpool3x3s2_bwd': ('ppiiiipp', 'i'),
     'xas_upsample2x_fwd': ('piiiipp', 'i'),

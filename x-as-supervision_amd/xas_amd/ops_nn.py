@@ -621,15 +621,15 @@ def _conv_forward(x, weight, stride, pad, cache):
 FUSE_CONV_STATS = os.environ.get('XAS_CONV_STATS', '1') == '1'
 
 
-def _conv_bn_forward(x, conv, bn, residual, group):
+def _conv_bn_forward(x, conv, bn, residual, group, stats_only=False, proj=None):
     """conv (no bias) -> batch norm (+ residual, activation): -> (out, saved, cfg, shp).  In training mode the batch
     statistics come out of the convolution's epilogue (xas_conv_fwd_bnstats): the conv result is not read a second time
-    for them."""
+    for them.  stats_only / proj: the dual form of a block output (_bn_forward)."""
     weight = conv.weight
     if not (FUSE_CONV_STATS and bn.training):
         y, shp = _conv_forward(x, weight, conv.stride, conv.padding, conv._cache)
         out, sv, cf = _bn_forward(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, residual, bn.training,
-                                  bn.momentum, bn.eps, bn.act, group)
+                                  bn.momentum, bn.eps, bn.act, group, stats_only=stats_only, proj=proj)
         return out, sv, cf, shp
     n, ci, hi, wi = x.shape
     co, ci2, r, s = weight.shape
@@ -655,7 +655,7 @@ def _conv_bn_forward(x, conv, bn, residual, group):
              ptr(ws), rm_p, rv_p, float(momentum))
 
     out, sv, cf = _bn_forward(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, residual, True, bn.momentum,
-                              bn.eps, bn.act, group, stats_fn=stats)
+                              bn.eps, bn.act, group, stats_fn=stats, stats_only=stats_only, proj=proj)
     return out, sv, cf, shp
 
 
@@ -663,6 +663,19 @@ def _conv_bn_forward(x, conv, bn, residual, group):
 # The two reductions it removes (col_reduce_lean_kernel<4>, 7.6 ms/step) run BESIDE the weight gradients of the side
 # stream and are mostly hidden; the extra epilogue work lands in the data-gradient kernels, which are the critical path.
 FUSE_DGRAD_BN = os.environ.get('XAS_DGRAD_BN', '0') == '1'
+
+# Blocks with a projection: the projection norm is applied inside bn3's passes (xas_bn_*_dual): neither the normalised skip
+# nor the skip gradient is written or read.  '0': the separate passes (A/B measurements, tests).
+FUSE_DS = os.environ.get('XAS_DS_FUSE', '1') == '1'
+
+
+def _ds_fusable(ds, bn3):
+    """A conv + norm projection whose norm can ride in bn3's passes: both in training mode, bn3 with ReLU and the sign
+    mask, and no two different process groups for their sums."""
+    return (FUSE_DS and ds is not None and len(ds) == 2 and hasattr(ds[0], '_cache') and hasattr(ds[1], 'sync_group')
+            and ds[1].training and bn3.training and ds[1].act == ACT_NONE and bn3.act == ACT_RELU
+            and os.environ.get('XAS_BN_MASK', '1') == '1'
+            and (ds[1].sync_group() is None or bn3.sync_group() is None or ds[1].sync_group() is bn3.sync_group()))
 
 
 def _bn_bwd_fusable(cfg):
@@ -739,19 +752,26 @@ class _Bottleneck(torch.autograd.Function):
         for bn in bns + ([ds[1]] if ds is not None else []):
             bn.count_batch()
         saved, cfgs, shps = [], [], []
-        skip = x
+        skip, proj = x, None
         if ds is not None:
-            skip, sv, cf, shp_d = _conv_bn_forward(x, ds[0], ds[1], None, ds[1].sync_group())
+            dual = x.is_cuda and _ds_fusable(ds, bns[2])
+            skip, sv, cf, shp_d = _conv_bn_forward(x, ds[0], ds[1], None, ds[1].sync_group(), stats_only=dual)
+            if dual:           # skip: the raw projection result, sv: its statistics over all groups of the pass
+                proj, skip = (skip, sv, ds[1].weight, ds[1].bias, ds[1].eps), None
             saved.append(sv); cfgs.append(cf); shps.append(shp_d)
         a = x
         acts = [x]
         for i in range(3):
-            a, sv, cf, shp = _conv_bn_forward(a, convs[i], bns[i], skip if i == 2 else None, bns[i].sync_group())
+            a, sv, cf, shp = _conv_bn_forward(a, convs[i], bns[i], skip if i == 2 else None, bns[i].sync_group(),
+                                              proj=proj if i == 2 else None)
+            if i == 2 and proj is not None:
+                saved[0] = sv[4:]                             # (raw projection result twice, its statistic rows)
+                sv = sv[:4]
             saved.append(sv); cfgs.append(cf); shps.append(shp)
             acts.append(a)
         flat = [t for sv in saved for t in sv]
         ctx.save_for_backward(x, acts[1], acts[2], *flat)
-        ctx.blk, ctx.cfgs, ctx.shps, ctx.has_ds = blk, cfgs, shps, ds is not None
+        ctx.blk, ctx.cfgs, ctx.shps, ctx.has_ds, ctx.dual = blk, cfgs, shps, ds is not None, proj is not None
         if _uses['on']:
             for p, need in zip(params, ctx.needs_input_grad[2:]):
                 if need:
@@ -788,7 +808,19 @@ class _Bottleneck(torch.autograd.Function):
         # data gradient from dout and the sign bytes bn3's forward saved - it is never written to memory
         fuse_skip = (not ctx.has_ds and need_dx and cfgs[o + 2][11] and _can_accumulate(shps[o]))
         dout = to_cl(dout)
-        g, dskip = bn_b(o + 2, bns[2], dout, want_dres=not fuse_skip)          # dskip: gradient of the skip branch
+        if ctx.dual:
+            # bn3 and the projection norm from the one dz: gd = gradient of the raw projection result, no skip gradient tensor
+            both = [bns[2], blk.downsample[1]]
+            g, gd, dgb = _bn_backward_dual(saved[o + 2], cfgs[o + 2], saved[0], cfgs[0], both, dout,
+                                           [id(b.weight) in need and id(b.bias) in need for b in both])
+            for b, (dg, db) in zip(both, dgb):
+                if dg is not None:
+                    if id(b.weight) in need:
+                        pgrads[id(b.weight)] = dg
+                    if id(b.bias) in need:
+                        pgrads[id(b.bias)] = db
+        else:
+            g, dskip = bn_b(o + 2, bns[2], dout, want_dres=not fuse_skip)      # dskip: gradient of the skip branch
         for i in (2, 1):
             bn, cf = bns[i - 1], cfgs[o + i - 1]
             want_bn = id(bn.weight) in need and id(bn.bias) in need
@@ -816,7 +848,8 @@ class _Bottleneck(torch.autograd.Function):
             return (dx, None) + tuple(pgrads.get(id(p)) for p in ctx.blk._fused_params)
         if ctx.has_ds:
             ds = blk.downsample
-            gd, _ = bn_b(0, ds[1], dskip)
+            if not ctx.dual:
+                gd, _ = bn_b(0, ds[1], dskip)
             dx, dw = _conv_backward(x, ds[0].weight, gd, shps[0], ds[0]._cache, need_dx, id(ds[0].weight) in need)
             if dw is not None:
                 pgrads[id(ds[0].weight)] = dw
@@ -1010,10 +1043,15 @@ def _sync_stats(mean, var, count, group):
     return gm.float().contiguous(), gv.float().contiguous()
 
 
-def _bn_forward(x, gamma, beta, running_mean, running_var, residual, training, momentum, eps, act, group, stats_fn=None):
+def _bn_forward(x, gamma, beta, running_mean, running_var, residual, training, momentum, eps, act, group, stats_fn=None,
+                stats_only=False, proj=None):
     """-> (y, saved tensors (x|y, y|x, mean, var), cfg) - the body of _BatchNorm.forward, also used by _Bottleneck.
     The batch is `current_groups()` independent sub-batches (cameras): statistics are [G, C].  Prefix pass: the kernels run
-    over the whole buffer (all groups); what is returned and saved are the tail views / the graph groups' statistic rows."""
+    over the whole buffer (all groups); what is returned and saved are the tail views / the graph groups' statistic rows.
+    The dual form of a block output relu(bn3(x) + bn_d(xd)) (training mode, ReLU, sign mask) takes two calls:
+    stats_only (the projection norm): the statistics and their bookkeeping as ever, no apply -> (x, (mean, var) of ALL
+    groups of the pass, cfg); then proj = (xd, that pair, gamma_d, beta_d, eps_d) (bn3): one apply for both norms
+    (xas_bn_apply_dual_amax), saved = bn3's four tensors + (xd, xd, mean_d, var_d) of the graph groups."""
     x_tail = to_cl(x)
     x = _full(x_tail)
     if x is not x_tail and not training:
@@ -1080,15 +1118,25 @@ def _bn_forward(x, gamma, beta, running_mean, running_var, residual, training, m
     else:
         mean = running_mean.reshape(1, c).expand(G, c).contiguous() if G > 1 else running_mean
         var = running_var.reshape(1, c).expand(G, c).contiguous() if G > 1 else running_var
+    if stats_only:
+        k, s = (_prefix[1], _prefix[0]) if x is not x_tail else (0, 0)
+        return x_tail, (mean, var), (M - s * h * w, c, float(eps), act, count, group, True, False, False, False, G - k, False)
     res = _full(to_cl(residual)) if residual is not None else None
     y = torch.empty_like(x)
     # layers with a residual (block outputs): the backward needs only the SIGN of the pre-activation value, saved as one
     # byte per float4 (1/16 of y's bytes) - neither backward pass reads y
-    masked = training and residual is not None and act != ACT_NONE and os.environ.get('XAS_BN_MASK', '1') == '1'
+    masked = proj is not None or (training and residual is not None and act != ACT_NONE
+                                  and os.environ.get('XAS_BN_MASK', '1') == '1')
     mask = torch.empty(M * c // 4, device=dev, dtype=torch.uint8) if masked else None
     slot = grad_amax_slot(dev) if x.is_cuda else None
-    call('xas_bn_apply_amax', ptr(x), ptr(mean), ptr(var), ptr(gamma), ptr(beta), ptr(res), float(eps), act, M, c, G, ptr(y), ptr(mask),
-         ptr(slot))
+    if proj is not None:
+        xd_tail, (mean_d, var_d), gamma_d, beta_d, eps_d = proj
+        xd = _full(to_cl(xd_tail))
+        call('xas_bn_apply_dual_amax', ptr(x), ptr(mean), ptr(var), ptr(gamma), ptr(beta), float(eps), ptr(xd), ptr(mean_d),
+             ptr(var_d), ptr(gamma_d), ptr(beta_d), float(eps_d), M, c, G, ptr(y), ptr(mask), ptr(slot))
+    else:
+        call('xas_bn_apply_amax', ptr(x), ptr(mean), ptr(var), ptr(gamma), ptr(beta), ptr(res), float(eps), act, M, c, G, ptr(y),
+             ptr(mask), ptr(slot))
     if slot is not None:
         tag_grad_amax(y, slot)                   # max |y|: the next conv scales its fp16 pieces with it
     # Backward traffic: which of x / y the backward passes need
@@ -1108,9 +1156,59 @@ def _bn_forward(x, gamma, beta, running_mean, running_var, residual, training, m
         M, G = M - _prefix[0] * h * w, G - k
         mean, var = mean[k:], var[k:]
         x = x_tail
+        if proj is not None:
+            mean_d, var_d = mean_d[k:], var_d[k:]
     saved = (y if xfree else x, mask if masked else (x if yfree else y), mean, var)
-    cfg = (M, c, float(eps), act, count, group, training, residual is not None, xfree, yfree, G, masked)
+    if proj is not None:
+        saved += (xd_tail, xd_tail, mean_d, var_d)
+    cfg = (M, c, float(eps), act, count, group, training, residual is not None or proj is not None, xfree, yfree, G, masked)
     return y, saved, cfg
+
+
+def _bn_backward_dual(saved, cfg, saved_d, cfg_d, bns, dy, want):
+    """Backward of a block output relu(bn3(x) + bn_d(xd)): -> (dx, dxd, [(dgamma, dbeta) of bn3, of bn_d]) with the pairs
+    as _bn_backward returns them.  One reduction and one apply for both norms; the skip gradient is not written.  Sync
+    groups: ONE all-reduce per block - over the sums of both norms, or over the half of the one norm that is synchronised
+    (the detector's blocks: a rank-local bn3 beside a SyncBatchNorm projection norm)."""
+    x, mask, mean, var = saved
+    xd, _, mean_d, var_d = saved_d
+    M, c, eps, act, count, group, training, has_res, xfree, yfree, G, masked = cfg
+    eps_d, count_d, group_d = cfg_d[2], cfg_d[4], cfg_d[5]
+    dy = to_cl(dy)
+    dev = x.device
+    sums = torch.empty(2, G, 2, c, device=dev, dtype=torch.float32)      # [norm][g][0] = sum dz, [norm][g][1] = sum dz * xhat
+    ws = torch.empty(2 * query('xas_bn_workspace_floats', M, c, G), device=dev, dtype=torch.float32)
+    acc = []
+    for bn, w in zip(bns, want):
+        gg, gb = bn.weight.grad, bn.bias.grad
+        direct = (w and gg is not None and gb is not None and gg.is_contiguous() and gb.is_contiguous()
+                  and gg.dtype == torch.float32 and gb.dtype == torch.float32)
+        acc.append((gb, gg) if direct else None)
+    call('xas_bn_bwd_reduce_dual', ptr(x), ptr(xd), ptr(dy), ptr(mask), ptr(mean), ptr(var), eps, ptr(mean_d), ptr(var_d),
+         eps_d, M, c, G, ptr(sums[0]), ptr(sums[1]), ptr(ws), *[ptr(t) for a in acc for t in (a or (None, None))])
+    grads = []
+    for i, bn in enumerate(bns):
+        if acc[i] is not None:
+            grad_ready(bn.weight)
+            grad_ready(bn.bias)
+            grads.append((None, None))
+        else:
+            grads.append((sums[i, :, 1].sum(0), sums[i, :, 0].sum(0)))   # local sums (before the exchange)
+    if group is not None or group_d is not None:
+        from . import dp as _dp
+        if group is not None and group_d is not None and group is not group_d:
+            raise RuntimeError('dual batch norm: the two norms exchange their sums in different process groups')
+        part = sums if (group is not None and group_d is not None) else sums[0 if group is not None else 1]
+        _dp.timed_collective(lambda: dist.all_reduce(part, group=group or group_d), part.numel() * 4)     # one message per block
+    dx, dxd = torch.empty_like(x), torch.empty_like(xd)
+    slot, slot_d = grad_amax_slot(dev), grad_amax_slot(dev)
+    call('xas_bn_bwd_apply_dual_amax', ptr(x), ptr(xd), ptr(dy), ptr(mask), ptr(mean), ptr(var), ptr(bns[0].weight), ptr(sums[0]),
+         eps, ptr(mean_d), ptr(var_d), ptr(bns[1].weight), ptr(sums[1]), eps_d, M, c, G, float(count), float(count_d), ptr(dx), ptr(dxd),
+         ptr(slot), ptr(slot_d))
+    if slot is not None:
+        tag_grad_amax(dx, slot)
+        tag_grad_amax(dxd, slot_d)
+    return dx, dxd, grads
 
 
 def _bn_backward(saved, cfg, gamma, beta, dy, want_param_grads, want_dres=True):

@@ -11,7 +11,8 @@ CONV_ENTRIES = ('xas_conv_fwd', 'xas_conv_fwd_head', 'xas_conv_fwd_bnstats', 'xa
 
 
 # batch-norm entry points (HBM bound): the `flops` field of their records carries the algorithmic HBM BYTES of the call
-BN_ENTRIES = ('xas_bn_stats', 'xas_bn_apply', 'xas_bn_apply_amax', 'xas_bn_bwd_reduce', 'xas_bn_bwd_apply', 'xas_bn_bwd_apply_amax')
+BN_ENTRIES = ('xas_bn_stats', 'xas_bn_apply', 'xas_bn_apply_amax', 'xas_bn_bwd_reduce', 'xas_bn_bwd_apply', 'xas_bn_bwd_apply_amax',
+              'xas_bn_apply_dual_amax', 'xas_bn_bwd_reduce_dual', 'xas_bn_bwd_apply_dual_amax')
 
 
 def bn_bytes(name, a):
@@ -25,6 +26,16 @@ def bn_bytes(name, a):
     if name == 'xas_bn_bwd_reduce':                 # (x, y, dy, mean, var, gamma, beta, eps, act, M, C, groups, sums, ws, db, dg, mask)
         t = 4.0 * a[9] * a[10]
         return t * (1 + (1 if a[0] else 0) + (1 if a[1] else 0)) + (t / 16 if a[16] else 0.0)
+    # dual forms (M, C at 12, 13 / 10, 11 / 14, 15): x and xd read, the block output or both gradients written, sign bytes
+    if name == 'xas_bn_apply_dual_amax':            # (x, mean, var, gamma, beta, eps, xd, ..., eps_d, M, C, groups, y, mask_out, amax)
+        t = 4.0 * a[12] * a[13]
+        return t * 3 + t / 16
+    if name == 'xas_bn_bwd_reduce_dual':            # (x, xd, dy, mask, mean, var, eps, mean_d, var_d, eps_d, M, C, groups, ...)
+        t = 4.0 * a[10] * a[11]
+        return t * 3 + t / 16
+    if name == 'xas_bn_bwd_apply_dual_amax':        # (x, xd, dy, mask, 4 + eps, 4 + eps_d, M, C, groups, count, count_d, dx, dxd, amax, amax_d)
+        t = 4.0 * a[14] * a[15]
+        return t * 5 + t / 16
     # xas_bn_bwd_apply(_amax): (x, y, dy, mean, var, gamma, beta, sums, eps, act, M, C, groups, count, dx, dres, mask[, amax])
     t = 4.0 * a[10] * a[11]
     return t * (2 + (1 if a[0] else 0) + (1 if a[1] else 0) + (1 if a[15] else 0)) + (t / 16 if a[16] else 0.0)
