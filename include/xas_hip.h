@@ -578,6 +578,9 @@ int xas_mask_loss_bwd(const float* m, const float* gt, const float* weight, long
  * kind 2: w0 * kp_sym on (x,y).  out: 2+Hy floats = {min, argmin, v_0..v_{Hy-1}}.  grad_aux (kind 1 with the
  * 2-D term, else NULL): gradient w.r.t. the patch joints.
  * xas_lsgan_*: logits [B][Hy] -> out[0] = mean_b min_h (x - target)^2, idx[b] = argmin.
+ * Both minima are NaN-faithful like torch.min: the first NaN among the candidates wins (value NaN, gradient NaN
+ * there), else the first minimum.  On an exact tie the whole gradient goes to the first minimum (the reference's
+ * full-reduction torch.min over the stacked hypothesis values would split it evenly among the tied ones).
  * ---------------------------------------------------------------------------------- */
 int xas_pose_loss_fwd(const float* pred, const float* gt, int B, int Hy, int K, int kind, float w0, float w1,
                       float w2, float* out, void* stream);

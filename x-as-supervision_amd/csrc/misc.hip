@@ -69,7 +69,11 @@ __global__ void mask_loss_bwd_kernel(const float* __restrict__ m, const float* _
 // pose_loss: kind 0 = supervision  : v_h = mean_{b,k,c} (pred[b,h,k,c] - gt[b,k,c])^2
 //            kind 1 = symmetry 3-D : v_h = w0 * bone_sym(p_h) + w1 * kp_sym(p_h)      (p in mm, scaled 1e-3)
 //            kind 2 = kp_sym 2-D   : v_h = w0 * mean((mid - anchor)^2) over (x, y) only (no 1e-3 scale)
-// out[0] = min_h v_h, out[1] = argmin (as float), out[2..2+Hy) = v_h.   First minimum wins (torch.min).
+// out[0] = min_h v_h, out[1] = argmin (as float), out[2..2+Hy) = v_h.
+// Choice of the hypothesis: the first NaN if any v_h is NaN (so out[0] is NaN, as torch.min gives), else the first
+// minimum, and the backward sends the whole gradient there.  The reference takes torch.min over the stacked values, a
+// full reduction whose backward SPLITS the gradient evenly among exactly tied minima (min(dim=...) would give it to one
+// index); on an exact tie between hypotheses this kernel therefore differs from the reference: all of it to the first.
 constexpr int kPoseThreads = 256;
 __constant__ int kLimbFar[8] = {16, 15, 13, 12, 3, 2, 6, 5};
 __constant__ int kLimbNear[8] = {15, 14, 12, 11, 2, 1, 5, 4};
@@ -140,7 +144,8 @@ __global__ void pose_loss_fwd_kernel(const float* __restrict__ pred, const float
   }
   if (threadIdx.x == 0) {
     int best = 0;
-    for (int h = 1; h < Hy; ++h) if (vh[h] < vh[best]) best = h;
+    for (int h = 1; h < Hy; ++h)
+      if (vh[best] == vh[best] && (vh[h] < vh[best] || vh[h] != vh[h])) best = h;      // a NaN wins and stays
     out[0] = vh[best]; out[1] = (float)best;
     for (int h = 0; h < Hy; ++h) out[2 + h] = vh[h];
   }
@@ -226,7 +231,7 @@ __global__ void lsgan_fwd_kernel(const float* __restrict__ logits, int B, int Hy
     float best = INFINITY; int bi = 0;
     for (int h = 0; h < Hy; ++h) {
       const float d = logits[b * Hy + h] - target, e = d * d;
-      if (e < best) { best = e; bi = h; }
+      if (e < best || (e != e && best == best)) { best = e; bi = h; }      // a NaN wins and stays, as min(dim=1) gives
     }
     idx[b] = bi;
     acc += best;
@@ -265,16 +270,28 @@ __global__ void graph_aggregate_kernel(const float* __restrict__ x, const float*
 // groups of `rows` rows each (x is [G*rows, C]); statistics stay per group.
 constexpr int kGlnThreads = 256;
 
+// how many of a group's n elements block i of nblk visits in its grid-stride loop (>= 1: nblk <= ceil(n / 2048))
+__device__ __forceinline__ long gln_block_count(long n, int nblk, int i) {
+  const long period = (long)nblk * kGlnThreads, r = n % period - (long)i * kGlnThreads;
+  return n / period * kGlnThreads + (r < 0 ? 0 : (r > kGlnThreads ? kGlnThreads : r));
+}
+
+// Per block: a = sum (x - pivot) with pivot = the group's first element, then b = sum ((x - pivot) - a / count)^2, the
+// squares about the block's OWN mean.  A sum of squares about a point d standard deviations off the mean carries terms
+// (d sigma)^2 next to the variance and loses (1 + d^2) of its precision when they are subtracted again; about the block
+// mean there is nothing to subtract.  gln_stats_kernel recomputes a / count with the same float division.
 __global__ void gln_partial_kernel(const float* __restrict__ x, long n, float* __restrict__ partial) {
   __shared__ float sm[20];
   const float* xg = x + (size_t)blockIdx.y * n;
   const float pivot = xg[0];
   float a = 0.f, b = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float d = xg[i] - pivot;
-    a += d; b = fmaf(d, d, b);
-  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) a += xg[i] - pivot;
   a = block_sum(a, sm);
+  const float mu = a / (float)gln_block_count(n, gridDim.x, blockIdx.x);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float d = (xg[i] - pivot) - mu;
+    b = fmaf(d, d, b);
+  }
   b = block_sum(b, sm);
   if (threadIdx.x == 0) {
     float* o = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
@@ -286,10 +303,17 @@ __global__ void gln_stats_kernel(const float* __restrict__ partial, int nblk, co
                                  int G, float* __restrict__ stats) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= G) return;
+  const float* pg = partial + (size_t)g * nblk * 2;
   double a = 0.0, b = 0.0;
-  for (int i = 0; i < nblk; ++i) { a += partial[((size_t)g * nblk + i) * 2]; b += partial[((size_t)g * nblk + i) * 2 + 1]; }
+  for (int i = 0; i < nblk; ++i) a += pg[i * 2];
   const double m = a / (double)n;
-  double v = b / (double)n - m * m;
+  // sum (d - m)^2 over block i = b_i + 2 (mu_i - m) sum (d - mu_i) + count_i (mu_i - m)^2, with sum (d - mu_i) = a_i - count_i mu_i
+  for (int i = 0; i < nblk; ++i) {
+    const long cnt = gln_block_count(n, nblk, i);
+    const double mu = (double)(pg[i * 2] / (float)cnt), off = mu - m;
+    b += (double)pg[i * 2 + 1] + 2.0 * off * ((double)pg[i * 2] - (double)cnt * mu) + (double)cnt * off * off;
+  }
+  double v = b / (double)n;
   if (v < 0.0) v = 0.0;
   stats[g * 2] = (float)((double)x[(size_t)g * n] + m);
   stats[g * 2 + 1] = (float)sqrt(v);
@@ -1154,7 +1178,9 @@ extern "C" int xas_pose_loss_fwd(const float* pred, const float* gt, int B, int 
 extern "C" int xas_pose_loss_bwd(const float* pred, const float* gt, int B, int Hy, int K, int kind, float w0, float w1,
                                  float w2, const float* out, const float* grad_scalar, float* grad_pred, float* grad_aux,
                                  void* stream) {
-  XAS_REQUIRE(pred && out && grad_scalar && grad_pred && B > 0 && Hy >= 1 && Hy <= 6, "pose_loss bwd: bad arguments");
+  XAS_REQUIRE(pred && out && grad_scalar && grad_pred && B > 0 && Hy >= 1 && Hy <= 6 && K >= 1,
+              "pose_loss bwd: bad arguments");
+  XAS_REQUIRE(kind >= 0 && kind <= 2 && (kind != 0 || gt) && (kind == 0 || K >= 17), "pose_loss bwd: bad kind / skeleton");
   hipLaunchKernelGGL(pose_loss_bwd_kernel, dim3(1), dim3(kPoseThreads), 0, as_stream(stream), pred, gt, B, Hy, K, kind, w0,
                      w1, w2, out, grad_scalar, grad_pred, grad_aux);
   XAS_LAUNCH_CHECK();
