@@ -755,6 +755,37 @@ int xas_multiview_resolve(const float* points, const float* P, const float* kps,
                           const float* gt, int B, int V, int Hy, int K, float image_size, float* sel, float* xyzw,
                           unsigned char* swap, unsigned char* hyp, unsigned char* named, void* stream);
 
+/* Reprojection-error refinement of a triangulated point (eval.py --tri-refine lm; the reference has no counterpart: its
+ * modules/util.py:198-230 stops at the DLT, which minimises the algebraic error |c (u P2 - P0) X|, not pixels).
+ * points [B][V][K][3] = (u px, v px, weight) and P [B][V][3][4] as for xas_triangulate_dlt; init [B][K][4] = what
+ * xas_triangulate_dlt or xas_triangulate_robust wrote; views [B][K] = the inliers of xas_triangulate_robust, or NULL.
+ * A view is VALID if its weight is finite and > 0.  The views used, F, are the valid views whose bit is set in
+ * views[b][k]; all valid views where views is NULL or the byte is 0 (the robust kernel's fallback code).  Bits of views
+ * that are not valid, or >= V, are ignored.
+ * For X in R^3 and a view v: h = P_v (X, 1), formed in double from the fp32 entries; X lies BEHIND v if h2 <= 0 (the rule of
+ * xas_triangulate_robust; a NaN h2, from a P that is not finite, is not behind: the cost is then NaN, no trial is accepted and
+ * the joint ends with status 1, out = init and NaN resid);
+ * r_v = (h0 / h2 - u_v, h1 / h2 - v_v); s_v = the weight with XAS_REFINE_WEIGHTED, else 1; e_v = s_v |r_v|;
+ * C(X) = sum over F of rho(e_v), rho(e) = e^2 if e <= huber or not huber > 0 (0, negative, NaN: plain least squares), else
+ * 2 huber e - huber^2.  huber is in the unit of e: pixels unweighted, sigmas with weights 1 / sigma_px.
+ * Levenberg-Marquardt on (X, Y, Z) from init, all arithmetic in double.  At X: psi_v = min(1, huber / e_v) (1 without
+ * huber), J_v = d r_v / dX, H = sum psi_v s_v^2 J_v^T J_v, g = sum psi_v s_v^2 J_v^T r_v; a TRIAL is X + d with
+ * (H + lambda diag(H)) d = -g, lambda = 1e-3 at the start.  A trial is ACCEPTED if C strictly decreases and it lies behind
+ * no view used: X moves, lambda *= 0.1; otherwise lambda *= 10.  The loop stops when an accepted step is shorter than
+ * 1e-5 (mm), after max_iter trials (1 <= max_iter <= 64), or when lambda > 1e12.  So C(out) <= C(init), always.
+ * PASSED THROUGH: fewer than two views used, x, y or z of init not finite, or init behind a view used.
+ * out [B][K][4] (required, must not overlap init) = (X, Y, Z) rounded to fp32 and init's fourth entry; passed through:
+ * init bit for bit (NaN stays NaN).  Each of the others may be NULL:
+ *   resid [B][K][2]  RMS of |r_v| over F (px, unweighted: the resid of xas_triangulate_robust) at init and at the result
+ *   cov [B][K][6]    upper triangle (00 01 02 11 12 22) of the inverse of H at the result: the covariance of the point in
+ *                    mm^2 where the weights are 1 / sigma_px; not finite where H is singular
+ *   status [B][K]    0 = stopped on the step rule, 1 = ran out of trials or lambda, 2 = passed through (resid, cov = NaN)
+ * One thread per (b, joint): 2 <= V <= XAS_TRI_MAX_VIEWS, B > 0, K >= 1, B*K < 2^31.  One launch, no host synchronisation. */
+#define XAS_REFINE_WEIGHTED 1   /* residual of view v is scaled by its weight (points[..][2]); else by 1 */
+int xas_triangulate_refine(const float* points, const float* P, const float* init, const unsigned char* views, int B, int V,
+                           int K, int flags, float huber, int max_iter, float* out, float* resid, float* cov,
+                           unsigned char* status, void* stream);
+
 /* Pose metrics, replaces metrics.py:5-244 (numpy, per-sample SVD on the host).
  * pred, gt [N][K][3]; both are divided by in_div on load (eval.py:52-53 passes mm / 1000 for PCK / AUC);
  * mask [N][K] (0/1) or NULL = all visible.  Outputs (each may be NULL):

@@ -11,6 +11,8 @@
 //   multiview_resolve : the left/right exchange of every view and the depth hypothesis of every view and joint, decided by the
 //                     agreement of the views instead of the labels (stands beside eval_utils.py:7-29 and eval.py:129-148,
 //                     on the DLT of modules/util.py:198-230: eval.py --resolve views)
+//   triangulate_refine : Levenberg-Marquardt on the weighted reprojection error in pixels, from the DLT or robust point (no
+//                     reference counterpart: eval.py --tri-refine lm)
 //   pose_metrics    : metrics.py:5-244 (MPJPE under none / scale / procrustes alignment, 3DPCK, AUC hit counts)
 //
 // Small symmetric eigenproblems (4x4) are solved with cyclic Jacobi rotations in double precision, fully unrolled
@@ -247,13 +249,19 @@ struct TriView {
   float u, v, w, pad;
 };
 
+// h = P X of homogeneous X in one view, in double from the fp32 entries; false if X lies behind the camera (or on its
+// principal plane).  The one projection, and the one meaning of "behind", of everything that reprojects in this file.
+__device__ __forceinline__ bool project_view(const float* __restrict__ Pm, const double (&X)[4], double (&h)[3]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    h[r] = (double)Pm[4 * r] * X[0] + (double)Pm[4 * r + 1] * X[1] + (double)Pm[4 * r + 2] * X[2] + (double)Pm[4 * r + 3] * X[3];
+  return !(h[2] / X[3] <= 0.0);
+}
+
 // Squared reprojection residual (px^2) of homogeneous X in one view, in double; +inf behind the camera.
 __device__ __forceinline__ double reproj_r2(const TriView& s, const double (&X)[4]) {
   double h[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    h[r] = (double)s.P[4 * r] * X[0] + (double)s.P[4 * r + 1] * X[1] + (double)s.P[4 * r + 2] * X[2] + (double)s.P[4 * r + 3] * X[3];
-  if (h[2] / X[3] <= 0.0) return INFINITY;
+  if (!project_view(s.P, X, h)) return INFINITY;
   const double du = h[0] / h[2] - (double)s.u, dv = h[1] / h[2] - (double)s.v;
   return du * du + dv * dv;
 }
@@ -501,6 +509,150 @@ __global__ __launch_bounds__(64) void multiview_resolve_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------------
+// triangulate_refine: Levenberg-Marquardt on the weighted reprojection error from the DLT / robust result, thread per
+// (b, joint) as triangulate_kernel.  A few hundred joints of 3x3 algebra in double: latency-bound, no throughput to win.
+// A thread keeps its V points (u, v, scale) in registers and re-reads the sample's projection matrices at every
+// linearisation: at most 72 floats that all threads of a sample share, so they stay in the caches, where holding them
+// would cost every thread 72 more registers.  Every loop over the views is unrolled to XAS_TRI_MAX_VIEWS and predicated by
+// the mask of the views used, so no array is indexed at run time and no view >= V is ever read.
+// ------------------------------------------------------------------------------------------------------
+// Inverse of the symmetric 3x3 a (upper triangle 00 01 02 11 12 22) by its adjugate.  A singular a gives inf / NaN.
+__device__ __forceinline__ void sym3_inverse(const double (&a)[6], double (&inv)[6]) {
+  const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
+  const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
+  inv[0] = c00 / det; inv[1] = c01 / det; inv[2] = c02 / det;
+  inv[3] = (a[0] * a[5] - a[2] * a[2]) / det;
+  inv[4] = (a[1] * a[2] - a[0] * a[4]) / det;
+  inv[5] = (a[0] * a[3] - a[1] * a[1]) / det;
+}
+
+// The problem at one point X: cost C, sum of the squared unweighted pixel residuals r2, Gauss-Newton Hessian H (upper
+// triangle) and gradient g with the IRLS weights of X itself.  false if X lies behind a view used.
+struct RefineFit {
+  double C, r2, H[6], g[3];
+};
+
+__device__ __forceinline__ bool refine_linearise(const float* __restrict__ Pb, int used, const float (&pu)[XAS_TRI_MAX_VIEWS],
+                                                 const float (&pv)[XAS_TRI_MAX_VIEWS], const float (&ps)[XAS_TRI_MAX_VIEWS],
+                                                 double huber, const double (&X)[3], RefineFit& f) {
+  f.C = 0.0; f.r2 = 0.0;
+#pragma unroll
+  for (int n = 0; n < 6; ++n) f.H[n] = 0.0;
+#pragma unroll
+  for (int n = 0; n < 3; ++n) f.g[n] = 0.0;
+  const double Xh[4] = {X[0], X[1], X[2], 1.0};
+  bool front = true;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
+    if (!((used >> v) & 1)) continue;
+    const float* Pm = Pb + v * 12;
+    double h[3];
+    front = project_view(Pm, Xh, h) && front;
+    const double pu_ = h[0] / h[2], pv_ = h[1] / h[2];
+    const double ru = pu_ - (double)pu[v], rv = pv_ - (double)pv[v];
+    const double s = (double)ps[v], rr = ru * ru + rv * rv, e = s * sqrt(rr);
+    const bool tail = huber > 0.0 && e > huber;
+    f.r2 += rr;
+    f.C += tail ? 2.0 * huber * e - huber * huber : e * e;
+    const double wt = (tail ? huber / e : 1.0) * s * s;
+    double ju[3], jv[3];                                              // d(u, v) / dX
+#pragma unroll
+    for (int n = 0; n < 3; ++n) {
+      ju[n] = ((double)Pm[n] - pu_ * (double)Pm[8 + n]) / h[2];
+      jv[n] = ((double)Pm[4 + n] - pv_ * (double)Pm[8 + n]) / h[2];
+      f.g[n] += wt * (ju[n] * ru + jv[n] * rv);
+    }
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = r; c < 3; ++c) f.H[n++] += wt * (ju[r] * ju[c] + jv[r] * jv[c]);
+  }
+  return front;
+}
+
+__global__ __launch_bounds__(64) void triangulate_refine_kernel(const float* __restrict__ pts, const float* __restrict__ P,
+                                                                const float* __restrict__ init,
+                                                                const unsigned char* __restrict__ views, int B, int V, int K,
+                                                                int flags, float huber_, int max_iter, float* __restrict__ out,
+                                                                float* __restrict__ resid, float* __restrict__ cov,
+                                                                unsigned char* __restrict__ status) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * K) return;
+  const int b = i / K, k = i % K;
+  const float* Pb = P + (size_t)b * V * 12;
+  float pu[XAS_TRI_MAX_VIEWS], pv[XAS_TRI_MAX_VIEWS], ps[XAS_TRI_MAX_VIEWS];
+  int valid = 0;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
+    pu[v] = 0.f; pv[v] = 0.f; ps[v] = 0.f;
+    if (v < V) {
+      const float* q = pts + (((size_t)b * V + v) * K + k) * 3;
+      pu[v] = q[0]; pv[v] = q[1];
+      ps[v] = (flags & XAS_REFINE_WEIGHTED) ? q[2] : 1.f;
+      valid |= (q[2] > 0.f && q[2] < INFINITY) ? 1 << v : 0;          // the rule of triangulate_robust_kernel
+    }
+  }
+  const int sel = views ? views[i] : 0;
+  const int used = sel ? (valid & sel) : valid;                       // a zero byte is the robust kernel's fallback: all valid views
+  const int nused = __popc(used);
+  const double huber = (double)huber_;
+
+  const float* in = init + (size_t)i * 4;
+  const float x0 = in[0], x1 = in[1], x2 = in[2];
+  double X[3] = {(double)x0, (double)x1, (double)x2};
+  RefineFit fit;
+  const bool finite = fabs(X[0]) < INFINITY && fabs(X[1]) < INFINITY && fabs(X[2]) < INFINITY;
+  const bool solve = nused >= 2 && finite && refine_linearise(Pb, used, pu, pv, ps, huber, X, fit);
+  float* o = out + (size_t)i * 4;
+  o[3] = in[3];
+  if (!solve) {                                                       // passed through: init bit for bit, NaN stays NaN
+    o[0] = x0; o[1] = x1; o[2] = x2;
+    if (resid) { resid[(size_t)i * 2] = NAN; resid[(size_t)i * 2 + 1] = NAN; }
+    if (cov)
+      for (int n = 0; n < 6; ++n) cov[(size_t)i * 6 + n] = NAN;
+    if (status) status[i] = 2;
+    return;
+  }
+  const double r2_init = fit.r2;
+  double lambda = 1e-3;
+  int st = 1;
+  for (int it = 0; it < max_iter; ++it) {
+    const double a[6] = {fit.H[0] * (1.0 + lambda), fit.H[1], fit.H[2], fit.H[3] * (1.0 + lambda), fit.H[4],
+                         fit.H[5] * (1.0 + lambda)};                  // H + lambda diag(H)
+    double inv[6];
+    sym3_inverse(a, inv);
+    const double d[3] = {-(inv[0] * fit.g[0] + inv[1] * fit.g[1] + inv[2] * fit.g[2]),
+                         -(inv[1] * fit.g[0] + inv[3] * fit.g[1] + inv[4] * fit.g[2]),
+                         -(inv[2] * fit.g[0] + inv[4] * fit.g[1] + inv[5] * fit.g[2])};
+    const double Xt[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
+    RefineFit trial;
+    const bool front = refine_linearise(Pb, used, pu, pv, ps, huber, Xt, trial);
+    if (front && trial.C < fit.C) {                                   // NaN never passes
+      X[0] = Xt[0]; X[1] = Xt[1]; X[2] = Xt[2];
+      fit = trial;
+      lambda *= 0.1;
+      if (sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) < 1e-5) { st = 0; break; }
+    } else {
+      lambda *= 10.0;
+      if (lambda > 1e12) break;
+    }
+  }
+  o[0] = (float)X[0]; o[1] = (float)X[1]; o[2] = (float)X[2];
+  if (resid) {
+    resid[(size_t)i * 2] = (float)sqrt(r2_init / (double)nused);
+    resid[(size_t)i * 2 + 1] = (float)sqrt(fit.r2 / (double)nused);
+  }
+  if (cov) {
+    double c[6];
+    sym3_inverse(fit.H, c);
+#pragma unroll
+    for (int n = 0; n < 6; ++n) cov[(size_t)i * 6 + n] = (float)c[n];
+  }
+  if (status) status[i] = (unsigned char)st;
+}
+
+// ------------------------------------------------------------------------------------------------------
 // pose_metrics: one wave per sample, lane = joint.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float norm3(float a, float b, float c) {
@@ -663,6 +815,22 @@ extern "C" int xas_multiview_resolve(const float* points, const float* P, const 
   XAS_REQUIRE(!gt || image_size > 1.f, "multiview_resolve: image_size %f (labels need a patch size > 1)", (double)image_size);
   hipLaunchKernelGGL(multiview_resolve_kernel, dim3((unsigned)((long)B * K)), dim3(64), 0, as_stream(stream), points, P, kps,
                      world, perm, gt, V, Hy, K, image_size, sel, xyzw, swap, hyp, named);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_triangulate_refine(const float* points, const float* P, const float* init, const unsigned char* views,
+                                      int B, int V, int K, int flags, float huber, int max_iter, float* out, float* resid,
+                                      float* cov, unsigned char* status, void* stream) {
+  XAS_REQUIRE(points && P && init && out, "triangulate_refine: null buffer (points, P, init and out are required)");
+  XAS_REQUIRE(V >= 2 && V <= XAS_TRI_MAX_VIEWS, "triangulate_refine: V=%d views (needs 2 <= V <= XAS_TRI_MAX_VIEWS = %d)", V,
+              XAS_TRI_MAX_VIEWS);
+  XAS_REQUIRE(B > 0 && K >= 1 && (long)B * K <= 0x7fffffffL, "triangulate_refine: bad shape B=%d K=%d (B > 0, K >= 1, B*K < 2^31)", B, K);
+  XAS_REQUIRE(max_iter >= 1 && max_iter <= 64, "triangulate_refine: max_iter=%d trials (needs 1 <= max_iter <= 64)", max_iter);
+  XAS_REQUIRE((flags & ~XAS_REFINE_WEIGHTED) == 0, "triangulate_refine: unknown flag bits 0x%x (XAS_REFINE_WEIGHTED = %d is the only flag)",
+              flags & ~XAS_REFINE_WEIGHTED, XAS_REFINE_WEIGHTED);
+  hipLaunchKernelGGL(triangulate_refine_kernel, dim3((unsigned)cdiv((long)B * K, 64)), dim3(64), 0, as_stream(stream), points, P,
+                     init, views, B, V, K, flags, huber, max_iter, out, resid, cov, status);
   XAS_LAUNCH_CHECK();
   return 0;
 }

@@ -4,6 +4,7 @@
     torchrun --nproc-per-node=N eval.py --config config/HM36_Multi_SurS1.yaml --checkpoint ckpt.pth.tar
              [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
              [--tri dlt|robust --tri_thresh PX] [--resolve gt|views] [--tri-weight depth|spread]
+             [--tri-refine none|lm --tri-huber PX]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -23,6 +24,11 @@ data nor on the device.
 of a joint in the triangulation (both --tri modes) and in --resolve views by 1 / sigma of its heat-map in full-image pixels
 (ops_head.heatmap_spread -> modules.util.spread_weight): one more streaming pass over each camera's logits.  No accuracy or
 time figure of that mode has been measured either.
+
+--tri-refine lm (opt-in; the default, none, runs exactly the calls above) moves every triangulated joint from the DLT's point,
+which minimises an algebraic error, to the minimum of the reprojection error in pixels over the cameras the triangulation used
+(ops_eval.triangulate_refine: Levenberg-Marquardt in one launch; --tri-huber PX makes the loss Huber's).  With --tri-weight
+spread every residual counts in sigmas of its heat-map.  No accuracy figure has been measured: its effect on MPJPE is unknown.
 """
 import copy
 import os
@@ -38,7 +44,8 @@ from torch.distributed import destroy_process_group, init_process_group
 from metrics import pose_errors
 from modules.keypoint_detector_integral import KPDetector3D as KPDetector3D_integral
 from modules.keypoint_detector_integral_multi import KPDetector3DMulti as KPDetector3DMulti_integral
-from modules.util import convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_weighted
+from modules.util import (convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_refined,
+                          triangulation_weighted)
 from eval_utils import cal_per_class_error
 from xas_amd import ops_eval
 from xas_amd.synthetic import synthetic_eval_batch
@@ -75,6 +82,12 @@ class Eval:
         tri_weight = config['model_params'].get('tri_weight', 'depth')         # --tri-weight; not a key of the shipped configs
         if tri_weight not in ('depth', 'spread'):
             raise ValueError('Unknown triangulation weight: {}'.format(tri_weight))
+        tri_refine = config['model_params'].get('tri_refine', 'none')          # --tri-refine / --tri-huber; not keys of the shipped configs either
+        if tri_refine not in ('none', 'lm'):
+            raise ValueError('Unknown triangulation refinement: {}'.format(tri_refine))
+        if tri_refine == 'lm' and len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
+            raise ValueError("tri_refine='lm' refines over at most {} cameras; cam_id_list has {}".format(
+                ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -95,6 +108,9 @@ class Eval:
         self.tri_weight = tri_weight               # --tri-weight spread: a view counts by its heat-map's 1 / sigma, not its depth
         self.spread = None                         # spread only: heat-map spread [B,K,5] of the latest detect()
         self.tri_sigma, self.sigma_batches = 0.0, 0    # spread only: mean sigma in pixels, summed over the batches
+        self.tri_refine = tri_refine               # --tri-refine lm: the triangulated point minimises the reprojection error in pixels
+        self.tri_huber = float(config['model_params'].get('tri_huber', 0.0))   # lm only: Huber's delta, 0 = plain least squares
+        self.refine_px, self.refine_gain, self.refine_batches = 0.0, 0.0, 0    # lm only, summed over the batches
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -157,13 +173,20 @@ class Eval:
             trans = t if trans is None else trans + t
         out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
         gt = convert_patch_to_world(x['cam_0_joints'], x, 'cam_0', is_norm=False)          # eval.py:170
-        if self.tri == 'robust':
+        if self.tri_refine == 'lm':                # the same solver, then the pixel error minimised over the views it used
+            tri, r = triangulation_refined(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, want=('resid',),
+                                           robust_px=self.tri_thresh if self.tri == 'robust' else None)
+            used = r.get('inliers')
+            out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a joint passed through has no residual (NaN)
+            out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
+        elif self.tri == 'robust':
             tri, used = triangulation_weighted(sel, x, self.cam_id_list, weights, robust_px=self.tri_thresh, return_inliers=True)
+        else:
+            tri = triangulation_weighted(sel, x, self.cam_id_list, weights)
+        if self.tri == 'robust':
             bits = (used.unsqueeze(-1).int() >> torch.arange(len(cams), device=used.device, dtype=torch.int32)) & 1
             # a zero mask is the fallback: no two views agreed, the DLT ran over all of them
             out['tri_inlier_views'] = torch.where(used == 0, len(cams), bits.sum(dim=-1)).float().mean()
-        else:
-            tri = triangulation_weighted(sel, x, self.cam_id_list, weights)
         if weights is not None:
             out['tri_sigma'] = torch.stack([1.0 / weights[m] for m in cams]).mean()
         preds = {'tri': tri}
@@ -200,6 +223,10 @@ class Eval:
             if 'tri_sigma' in host:
                 self.tri_sigma += float(host['tri_sigma'])
                 self.sigma_batches += 1
+            if 'tri_refine_px' in host:
+                self.refine_px += float(host['tri_refine_px'])
+                self.refine_gain += float(host['tri_refine_gain_px'])
+                self.refine_batches += 1
             if 'resolve_hyp0' in host:
                 self.res_exchanged += float(host['resolve_exchanged'])
                 self.res_hyp0 += float(host['resolve_hyp0'])
@@ -254,6 +281,10 @@ class Eval:
             lines.append('RESOLVE views: exchanged {} , hypothesis 0 kept {}'.format(self.res_exchanged / n, self.res_hyp0 / n))
         if self.tri_weight == 'spread':            # after everything else; --tri-weight depth leaves the file as it was
             lines.append('TRI weight spread: mean sigma {} px'.format(self.tri_sigma / max(self.sigma_batches, 1)))
+        if self.tri_refine == 'lm':                # after everything else; --tri-refine none leaves the file as it was
+            n = max(self.refine_batches, 1)
+            lines.append('TRI refine lm (huber {}): reprojection RMS {} px, gained {} px'.format(
+                self.tri_huber, self.refine_px / n, self.refine_gain / n))
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -336,6 +367,12 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--tri-weight', dict(default='depth', choices=['depth', 'spread'], dest='tri_weight',
                           help="weight of every view in the triangulation and in --resolve views: the joint's depth in mm as "
                                'the reference has it, or 1 / sigma of its heat-map in image pixels')),
+    ('--tri-refine', dict(default='none', choices=['none', 'lm'], dest='tri_refine',
+                          help='after the triangulation: nothing, or Levenberg-Marquardt on the reprojection error in pixels '
+                               'over the cameras the triangulation used (scaled by the weights with --tri-weight spread)')),
+    ('--tri-huber', dict(default=0.0, type=float, metavar='PX', dest='tri_huber',
+                         help="--tri-refine lm: Huber's delta in the unit of the residual (pixels; sigmas with --tri-weight "
+                              'spread); 0 = plain least squares')),
 )
 
 
@@ -348,6 +385,7 @@ def main():
         config = yaml.load(f, Loader=yaml.FullLoader)
     config['model_params']['cam_id_list'] = config['dataset_params']['cam_id_list']
     config['model_params']['tri_weight'] = opt.tri_weight
+    config['model_params']['tri_refine'], config['model_params']['tri_huber'] = opt.tri_refine, opt.tri_huber
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

@@ -101,6 +101,16 @@ def triangulation_weighted(keypoints, params, cam_id_list, weights, is_norm=True
     """triangulation with `weights`, {cam_key: [B,K]}: the weight of every view and joint (spread_weight) in place of the
     reference's, which is the joint's depth in mm.  A weight that is not finite or not positive marks the view invalid for that
     joint, by the kernels' rule for the third column.  None: the reference's weights, bit for bit.  No reference counterpart."""
+    pts, pm = _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+    if robust_px is None:
+        tri = batch_triangulate(pts, pm)[..., :3]
+        return (tri, None) if return_inliers else tri
+    r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',) if return_inliers else ())
+    return (r['xyzw'][..., :3], r['inliers']) if return_inliers else r['xyzw'][..., :3]
+
+
+def _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH):
+    """What every triangulation starts from: points [B,V,K,3] = (u px, v px, weight) and projection matrices [B,V,3,4]."""
     pts, pm = [], []
     for cam_id in cam_id_list:
         mode = 'cam_{}'.format(cam_id)
@@ -110,13 +120,27 @@ def triangulation_weighted(keypoints, params, cam_id_list, weights, is_norm=True
                                            is_norm=is_norm))
         pm.append(ops_eval.projection_matrix(params['{}_k_mat'.format(mode)], params['{}_rot_world'.format(mode)],
                                              params['{}_trans_world'.format(mode)]))
-    pts = _stack_points(pts, weights, ['cam_{}'.format(c) for c in cam_id_list])
+    return _stack_points(pts, weights, ['cam_{}'.format(c) for c in cam_id_list]), torch.stack(pm, dim=1)
+
+
+def triangulation_refined(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000, robust_px=None,
+                          huber_px=0.0, want=()):
+    """triangulation_weighted, then Levenberg-Marquardt on the reprojection error in pixels from its point, over the views it
+    used (ops_eval.triangulate_refine).  With `weights` every view's residual is scaled by its weight, so with spread_weight
+    (1 / sigma in pixels) the cost is the detections' negative log-likelihood and `cov` the joint's covariance in mm^2; without,
+    the residuals count in plain pixels (the depth in mm is no scale of a pixel error).  `huber_px` > 0: Huber's loss.
+    -> (world joints [B,K,3], dict of ops_eval.triangulate_refine: xyzw and the outputs in `want`, + `inliers` with
+    robust_px).  No reference counterpart."""
+    pts, pm = _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
     if robust_px is None:
-        tri = batch_triangulate(pts, torch.stack(pm, dim=1))[..., :3]
-        return (tri, None) if return_inliers else tri
-    r = ops_eval.triangulate_robust(pts, torch.stack(pm, dim=1), threshold_px=robust_px,
-                                    want=('inliers',) if return_inliers else ())
-    return (r['xyzw'][..., :3], r['inliers']) if return_inliers else r['xyzw'][..., :3]
+        init, used = batch_triangulate(pts, pm), None
+    else:
+        r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',))
+        init, used = r['xyzw'], r['inliers']
+    out = ops_eval.triangulate_refine(pts, pm, init, views=used, weighted=weights is not None, huber_px=huber_px, want=want)
+    if used is not None:
+        out['inliers'] = used
+    return out['xyzw'][..., :3], out
 
 
 def resolve_views(kps_by_cam, params, cam_id_list, pairs, gt=True, RECT_WIDTH=2000):

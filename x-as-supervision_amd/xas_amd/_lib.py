@@ -163,6 +163,7 @@ SIGNATURES = {
     'xas_triangulate_dlt': ('ppiiipp', 'i'),
     'xas_triangulate_robust': ('ppiiifpppp', 'i'),
     'xas_multiview_resolve': ('ppppppiiiifpppppp', 'i'),
+    'xas_triangulate_refine': ('ppppiiiifippppp', 'i'),
     'xas_pose_metrics': ('pppiififppppp', 'i'),
 }
 

@@ -111,6 +111,41 @@ def triangulate_robust(points, pmat, threshold_px=TRI_ROBUST_PX, want=('inliers'
     return out
 
 
+REFINE_WEIGHTED = 1      # xas_hip.h XAS_REFINE_WEIGHTED
+
+
+def triangulate_refine(points, pmat, init, views=None, weighted=False, huber_px=0.0, max_iter=20, want=('resid',)):
+    """Levenberg-Marquardt on the reprojection error from a triangulated point (xas_triangulate_refine).  points [B,V,K,3]
+    (u, v, weight), pmat [B,V,3,4], init [B,K,4] (triangulate_dlt, or xyzw of triangulate_robust), views [B,K] uint8 (inliers of
+    triangulate_robust) or None = all valid views.  `weighted`: every view's residual is scaled by its weight (1 / sigma in
+    pixels makes the cost a likelihood and cov mm^2); `huber_px` > 0: Huber's loss, in the unit of the scaled residual.
+    -> dict: xyzw [B,K,4] always; resid [B,K,2] (RMS pixel residual over the views used, before and after), cov [B,K,6] (upper
+    triangle of the inverse Gauss-Newton Hessian), status [B,K] uint8 (0 converged, 1 out of trials, 2 passed through) as
+    requested."""
+    points, pmat, init = _f32(points), _f32(pmat), _f32(init)
+    B, V, K, _ = points.shape
+    if pmat.shape != (B, V, 3, 4):
+        raise RuntimeError('triangulate_refine: projection matrices %s do not match points %s' % (tuple(pmat.shape), tuple(points.shape)))
+    if init.shape != (B, K, 4):
+        raise RuntimeError('triangulate_refine: start points %s do not match points %s' % (tuple(init.shape), tuple(points.shape)))
+    if views is not None:
+        if views.shape != (B, K) or views.dtype != torch.uint8:
+            raise RuntimeError('triangulate_refine: views %s %s are not the [B,K] uint8 masks of points %s' % (
+                tuple(views.shape), views.dtype, tuple(points.shape)))
+        views = views.contiguous()
+    dev = points.device
+    out = {'xyzw': torch.empty(B, K, 4, device=dev)}
+    if 'resid' in want:
+        out['resid'] = torch.empty(B, K, 2, device=dev)
+    if 'cov' in want:
+        out['cov'] = torch.empty(B, K, 6, device=dev)
+    if 'status' in want:
+        out['status'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
+    call('xas_triangulate_refine', ptr(points), ptr(pmat), ptr(init), ptr(views), B, V, K, REFINE_WEIGHTED if weighted else 0,
+         float(huber_px), int(max_iter), ptr(out['xyzw']), ptr(out.get('resid')), ptr(out.get('cov')), ptr(out.get('status')))
+    return out
+
+
 def multiview_resolve(points, pmat, kps, world, pairs=SWITCH_PAIRS, gt=None, image_size=256.0,
                       want=('xyzw', 'swap', 'hyp', 'named')):
     """Left/right exchange and depth hypothesis of every view from the agreement of the views (xas_multiview_resolve).
