@@ -786,6 +786,63 @@ int xas_triangulate_refine(const float* points, const float* P, const float* ini
                            int K, int flags, float huber, int max_iter, float* out, float* resid, float* cov,
                            unsigned char* status, void* stream);
 
+/* Smallest (lambda_1 - lambda_0) / lambda_3 at which xas_multiview_consistency_bwd differentiates through X (below). */
+#define XAS_MV_MIN_GAP 1e-10
+/* Multi-view consistency loss of the training step (train.py --mv-2d / --mv-3d; the reference has no counterpart: its step
+ * treats the cameras of a sample as independent images).  The joint that the views triangulate to is a label-free 3-D target
+ * of every view and its reprojection a label-free 2-D target: the algebraic-triangulation loss of Iskakov et al. 2019 and
+ * the triangulated pseudo-label of Kocabas et al. 2019, differentiable through the DLT's null vector.
+ * Inputs, contiguous fp32: kps_xy [B][V][K][2] = hypothesis 0's normalised patch x, y of every camera (the hypotheses share
+ * x and y); trans_image [B][V][2][3] the crop affines; world [B][V][Hy][K][3] every hypothesis's single-view world point in
+ * mm (xas_patch_to_world_fwd); P [B][V][3][4]; weight [B][V][K] or NULL = every view counts 1.  image_size S > 1.
+ * A view is VALID for a joint if its weight is finite and > 0 (the rule of xas_triangulate_robust); x or y that is not
+ * finite does not invalidate a view, it makes X not finite.  F = the valid views, n = |F|.  Per (b, k):
+ *   1. (u_v, v_v) = A_v^-1 ((x + 1) / 2 (S - 1) - t0, (y + 1) / 2 (S - 1) - t1), A_v | t the crop affine: the patch stage
+ *      of xas_patch_to_world_fwd in fp32, rounding for rounding (bit for bit what it writes under XAS_GEO_IMAGE): det =
+ *      fl(a00 a11) - fl(a01 a10); the four entries of A^-1 each one division; p = fl(fl((x + 1) / 2) (S - 1)); d = p - t;
+ *      u = fma(i00, du, fl(i01 dv)), v = fma(i11, dv, fl(i10 du)).  Everything after this is in double from the fp32 numbers.
+ *   2. X = the DLT over F, the arithmetic of xas_triangulate_dlt restricted to F: rows c_v (u P2 - P0), c_v (v P2 - P1)
+ *      formed in fp32, Gram matrix and null vector in double, views in ascending order.
+ *   3. r_v = (h0 / h2 - u_v, h1 / h2 - v_v), h = P_v (X, 1), in pixels; e_v = |r_v|.
+ *   4. reproj[b][k] = (1 / n) sum over F of rho(e_v); rho(e) = e^2 if e <= huber_px or huber_px = 0, else
+ *      2 huber_px e - huber_px^2 (the rho of xas_triangulate_refine).
+ *   5. h*_v = argmin_h |world[b][v][h][k] - X|^2 (first minimum; NaN never wins), for every view, valid or not: the rule of
+ *      xas_multiview_resolve.  0 for a joint passed through.
+ *   6. depth[b][k] = (1 / n) sum over F of |world[b][v][h*_v][k] - X|^2 in mm^2.
+ * PASSED THROUGH (status 2; reproj = depth = 0 exactly, every gradient of the joint exactly 0, xyz = NaN): n < 2, X not
+ * finite, or X behind a view of F (h2 <= 0 there: the rule of xas_triangulate_robust).  Otherwise status 0.
+ * Outputs of the forward: reproj [B][K], depth [B][K], xyz [B][K][3] = X rounded to fp32, hsel [B][V][K] int32 = h*_v,
+ * status [B][K] bytes; all required.
+ * The backward takes the same inputs and g_reproj [B][K], g_depth [B][K], recomputes the Gram matrix and ALL its eigenpairs,
+ * and writes EVERY entry of grad_kps_xy [B][V][K][2] and grad_world [B][V][Hy][K][3] (zeros for views not in F, hypotheses
+ * not selected and joints passed through): nothing needs a memset, and no atomics, so the result is a pure function of the
+ * inputs.  h*_v is a constant of the differentiation.  With a = g_reproj / n, d = g_depth / n, psi_v = 1 or huber_px / e_v
+ * in rho's linear part:
+ *   d / d world[b][v][h*_v][k] = 2 d (world - X);       direct d / d (u_v, v_v) = -2 a psi_v r_v.
+ * With XAS_MV_DETACH_TARGET that is all: X is a constant, the 2-D term pulls each (u_v, v_v) towards the reprojection and
+ * the 3-D term each selected world point towards X.  Without it the gradient also flows through X into every view of F:
+ *   g_X = sum over F of (2 a psi_v J_v^T r_v - 2 d (world - X)), J_v = d (h0 / h2, h1 / h2) / dX;
+ *   x = the unit eigenvector of the smallest eigenvalue lambda_0 of the Gram matrix G, X = x[:3] / x[3], (lambda_j, v_j) the
+ *   other three:  g_x = (g_X / x3, -(g_X . x[:3]) / x3^2);
+ *   g_G = sum over j != 0 of (v_j . g_x) / (lambda_0 - lambda_j) sym(v_j x^T), sym(M) = (M + M^T) / 2;
+ *   d / du_v = 2 c_v^2 a_u^T g_G P2_v with a_u = u_v P2_v - P0_v, d / dv_v likewise with a_v = v_v P2_v - P1_v.
+ * The terms through X grow like 1 / (lambda_1 - lambda_0).  Where lambda_1 - lambda_0 <= XAS_MV_MIN_GAP * lambda_3 (views that
+ * coincide, rays that are parallel: x is any vector of a plane and has no derivative) they are left out and the joint gets the
+ * gradient of XAS_MV_DETACH_TARGET; above that gap they are finite but may be large, and it is the caller's gradient clipping
+ * that bounds them.
+ * Then (u, v) -> (x, y): the transposed inverse affine and (S - 1) / 2.  Gradients go to kps_xy and world only.
+ * One thread per (b, joint), loops over the views unrolled to XAS_TRI_MAX_VIEWS and predicated: 2 <= V <= XAS_TRI_MAX_VIEWS,
+ * 1 <= Hy <= 8, B >= 1, K >= 1, B*K < 2^31, huber_px >= 0 and finite.  One launch each, no host synchronisation. */
+#define XAS_MV_DETACH_TARGET 1  /* X is a constant of the backward pass (a pseudo-label), not a function of the views */
+int xas_multiview_consistency_fwd(const float* kps_xy, const float* trans_image, const float* world, const float* P,
+                                  const float* weight, int B, int V, int Hy, int K, float image_size, float huber_px,
+                                  int flags, float* reproj, float* depth, float* xyz, int* hsel, unsigned char* status,
+                                  void* stream);
+int xas_multiview_consistency_bwd(const float* kps_xy, const float* trans_image, const float* world, const float* P,
+                                  const float* weight, const float* g_reproj, const float* g_depth, int B, int V, int Hy,
+                                  int K, float image_size, float huber_px, int flags, float* grad_kps_xy,
+                                  float* grad_world, void* stream);
+
 /* Pose metrics, replaces metrics.py:5-244 (numpy, per-sample SVD on the host).
  * pred, gt [N][K][3]; both are divided by in_div on load (eval.py:52-53 passes mm / 1000 for PCK / AUC);
  * mask [N][K] (0/1) or NULL = all visible.  Outputs (each may be NULL):

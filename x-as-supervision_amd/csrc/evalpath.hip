@@ -653,6 +653,254 @@ __global__ __launch_bounds__(64) void triangulate_refine_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------------
+// multiview_consistency: the training step's multi-view term and its backward pass through the DLT's null vector, thread per
+// (b, joint) as triangulate_kernel.  [B,V,K]-sized data and a 4x4 eigenproblem per joint in double: latency-bound.  Every loop
+// over the views is unrolled to XAS_TRI_MAX_VIEWS and predicated by the view count or the mask of the valid views, so no
+// array is indexed at run time and no view >= V is ever read.  A thread writes only its own joint's outputs: no atomics.
+// ------------------------------------------------------------------------------------------------------
+// What both passes know about one joint after the solve.
+struct MvJoint {
+  double u[XAS_TRI_MAX_VIEWS], v[XAS_TRI_MAX_VIEWS];                  // image pixels of every view < V
+  double i00[XAS_TRI_MAX_VIEWS], i01[XAS_TRI_MAX_VIEWS], i10[XAS_TRI_MAX_VIEWS], i11[XAS_TRI_MAX_VIEWS];   // inverse crop affines
+  float c[XAS_TRI_MAX_VIEWS];                                         // the views' weights (1 without)
+  double G[10];                                                       // Gram matrix over the valid views, upper triangle
+  double x[4];                                                        // its null vector
+  double X[4];                                                        // (x[:3] / x[3], 1)
+  int valid, n;
+};
+
+// The patch stage of patch_to_world_fwd_kernel (geometry.hip) in fp32, rounding for rounding what the compiler makes of it there:
+// every product and difference rounded on its own, but for one fused multiply-add per coordinate, u = fma(i00, du, i01 dv) and
+// v = fma(i11, dv, i10 du).  Contraction is switched off here because __fmul_rn and its kin do not stop it (left to itself
+// the compiler fuses (x + 1) / 2 (S - 1) - t0 in this kernel and not in that one), and a point moves by 1e-4 mm with the last
+// bit of u.  So the DLT starts from the very numbers triangulate_kernel gets from xas_patch_to_world_fwd with XAS_GEO_IMAGE.
+__device__ __forceinline__ void mv_patch_stage(const float* __restrict__ A, const float* __restrict__ q, float S, float& u, float& v,
+                                               float& i00, float& i01, float& i10, float& i11) {
+#pragma clang fp contract(off)
+  const float a00 = A[0], a01 = A[1], a10 = A[3], a11 = A[4];
+  const float m0 = a00 * a11, m1 = a01 * a10;
+  const float det = m0 - m1;
+  i00 = a11 / det; i01 = -a01 / det; i10 = -a10 / det; i11 = a00 / det;
+  const float h0 = (q[0] + 1.f) / 2.f, h1 = (q[1] + 1.f) / 2.f;
+  const float p0 = h0 * (S - 1.f), p1 = h1 * (S - 1.f);
+  const float du = p0 - A[2], dv = p1 - A[5];
+  const float t0 = i01 * dv, t1 = i10 * du;
+  u = __builtin_fmaf(i00, du, t0);
+  v = __builtin_fmaf(i11, dv, t1);
+}
+
+// Patch stage, validity, Gram matrix and null vector of joint (b, k).  false: passed through.
+__device__ __forceinline__ bool mv_solve(const float* __restrict__ kps_xy, const float* __restrict__ ti,
+                                         const float* __restrict__ P, const float* __restrict__ weight, int b, int k, int V,
+                                         int K, float S, MvJoint& j) {
+  double g[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) g[r][cc] = 0.0;
+  j.valid = 0;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
+    j.u[v] = 0.0; j.v[v] = 0.0; j.c[v] = 0.f;
+    j.i00[v] = 0.0; j.i01[v] = 0.0; j.i10[v] = 0.0; j.i11[v] = 0.0;
+    if (v < V) {
+      const size_t bv = (size_t)b * V + v;
+      float uf, vf, i00, i01, i10, i11;
+      mv_patch_stage(ti + bv * 6, kps_xy + (bv * K + k) * 2, S, uf, vf, i00, i01, i10, i11);
+      j.u[v] = (double)uf; j.v[v] = (double)vf;
+      j.i00[v] = (double)i00; j.i01[v] = (double)i01; j.i10[v] = (double)i10; j.i11[v] = (double)i11;
+      j.c[v] = weight ? weight[bv * K + k] : 1.f;
+      if (j.c[v] > 0.f && j.c[v] < INFINITY) {                        // the rule of triangulate_robust_kernel
+        j.valid |= 1 << v;
+        double t[10];
+        dlt_view_gram(uf, vf, j.c[v], P + bv * 12, t);
+        dlt_gram_add(g, t);
+      }
+    }
+  }
+  j.n = __popc(j.valid);
+  int m = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int cc = r; cc < 4; ++cc) j.G[m++] = g[r][cc];
+  if (j.n < 2) return false;
+  double x[4];                                                        // not j.x: what the call takes by reference lives in scratch
+  dlt_null_vector(g, x);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) j.x[r] = x[r];
+  j.X[0] = j.x[0] / j.x[3]; j.X[1] = j.x[1] / j.x[3]; j.X[2] = j.x[2] / j.x[3]; j.X[3] = 1.0;
+  if (!(fabs(j.X[0]) < INFINITY && fabs(j.X[1]) < INFINITY && fabs(j.X[2]) < INFINITY)) return false;
+  bool front = true;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v)
+    if ((j.valid >> v) & 1) {
+      double h[3];
+      front = project_view(P + ((size_t)b * V + v) * 12, j.X, h) && front;
+    }
+  return front;
+}
+
+// argmin_h |world[b][v][h][k] - X|^2 of one view: first minimum, NaN or inf never wins (the rule of multiview_resolve_kernel).
+__device__ __forceinline__ int mv_nearest(const float* __restrict__ world, size_t bv, int Hy, int K, int k, const double (&X)[4],
+                                          double (&d)[3]) {
+  int hs = 0;
+  double best = INFINITY;
+  for (int h = 0; h < Hy; ++h) {
+    const float* wp = world + ((bv * Hy + h) * K + k) * 3;
+    const double d0 = (double)wp[0] - X[0], d1 = (double)wp[1] - X[1], d2 = (double)wp[2] - X[2];
+    const double dd = d0 * d0 + d1 * d1 + d2 * d2;
+    if (dd < best) { best = dd; hs = h; }
+  }
+  const float* wp = world + ((bv * Hy + hs) * K + k) * 3;
+  d[0] = (double)wp[0] - X[0]; d[1] = (double)wp[1] - X[1]; d[2] = (double)wp[2] - X[2];
+  return hs;
+}
+
+__global__ __launch_bounds__(64) void multiview_consistency_fwd_kernel(
+    const float* __restrict__ kps_xy, const float* __restrict__ ti, const float* __restrict__ world, const float* __restrict__ P,
+    const float* __restrict__ weight, int B, int V, int Hy, int K, float S, float huber_, float* __restrict__ reproj,
+    float* __restrict__ depth, float* __restrict__ xyz, int* __restrict__ hsel, unsigned char* __restrict__ status) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * K) return;
+  const int b = i / K, k = i % K;
+  MvJoint j;
+  const bool solved = mv_solve(kps_xy, ti, P, weight, b, k, V, K, S, j);
+  const double huber = (double)huber_;
+  double rsum = 0.0, dsum = 0.0;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
+    if (v >= V) continue;
+    const size_t bv = (size_t)b * V + v;
+    int hs = 0;
+    if (solved) {
+      double d[3];
+      hs = mv_nearest(world, bv, Hy, K, k, j.X, d);
+      if ((j.valid >> v) & 1) {
+        dsum += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        double h[3];
+        project_view(P + bv * 12, j.X, h);
+        const double ru = h[0] / h[2] - j.u[v], rv = h[1] / h[2] - j.v[v];
+        const double e = sqrt(ru * ru + rv * rv);
+        rsum += (huber > 0.0 && e > huber) ? 2.0 * huber * e - huber * huber : ru * ru + rv * rv;
+      }
+    }
+    hsel[bv * K + k] = hs;
+  }
+  reproj[i] = solved ? (float)(rsum / (double)j.n) : 0.f;
+  depth[i] = solved ? (float)(dsum / (double)j.n) : 0.f;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) xyz[(size_t)i * 3 + r] = solved ? (float)j.X[r] : NAN;
+  status[i] = solved ? 0 : 2;
+}
+
+__global__ __launch_bounds__(64) void multiview_consistency_bwd_kernel(
+    const float* __restrict__ kps_xy, const float* __restrict__ ti, const float* __restrict__ world, const float* __restrict__ P,
+    const float* __restrict__ weight, const float* __restrict__ g_reproj, const float* __restrict__ g_depth, int B, int V, int Hy,
+    int K, float S, float huber_, int flags, float* __restrict__ grad_kps_xy, float* __restrict__ grad_world) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * K) return;
+  const int b = i / K, k = i % K;
+  MvJoint j;
+  const bool solved = mv_solve(kps_xy, ti, P, weight, b, k, V, K, S, j);
+  const double huber = (double)huber_;
+  const double a = solved ? (double)g_reproj[i] / (double)j.n : 0.0, dw = solved ? (double)g_depth[i] / (double)j.n : 0.0;
+  double gu[XAS_TRI_MAX_VIEWS], gv[XAS_TRI_MAX_VIEWS];                // d / d (u_v, v_v)
+  double gX[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
+    gu[v] = 0.0; gv[v] = 0.0;
+    if (v >= V) continue;
+    const size_t bv = (size_t)b * V + v;
+    const bool on = solved && ((j.valid >> v) & 1);
+    int hs = 0;
+    double d[3] = {0.0, 0.0, 0.0};
+    if (on) {
+      hs = mv_nearest(world, bv, Hy, K, k, j.X, d);
+      const float* Pm = P + bv * 12;
+      double h[3];
+      project_view(Pm, j.X, h);
+      const double pu = h[0] / h[2], pv = h[1] / h[2];
+      const double ru = pu - j.u[v], rv = pv - j.v[v];
+      const double e = sqrt(ru * ru + rv * rv);
+      const double wt = 2.0 * a * ((huber > 0.0 && e > huber) ? huber / e : 1.0);
+      gu[v] = -wt * ru; gv[v] = -wt * rv;
+#pragma unroll
+      for (int n = 0; n < 3; ++n) {
+        const double ju = ((double)Pm[n] - pu * (double)Pm[8 + n]) / h[2], jv = ((double)Pm[4 + n] - pv * (double)Pm[8 + n]) / h[2];
+        gX[n] += wt * (ju * ru + jv * rv) - 2.0 * dw * d[n];
+      }
+    }
+    for (int h = 0; h < Hy; ++h) {                                    // every hypothesis of every view < V is written
+      float* o = grad_world + ((bv * Hy + h) * K + k) * 3;
+      const bool sel = on && h == hs;
+#pragma unroll
+      for (int n = 0; n < 3; ++n) o[n] = sel ? (float)(2.0 * dw * d[n]) : 0.f;
+    }
+  }
+  if (solved && !(flags & XAS_MV_DETACH_TARGET)) {
+    // through X: all four eigenpairs of G.  x itself stays dlt_null_vector's, the one the forward pass solved with
+    double g[4][4], vec[4][4];
+    int m = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int cc = r; cc < 4; ++cc) { g[r][cc] = j.G[m]; g[cc][r] = j.G[m]; ++m; }
+    jacobi4(g, vec);
+    int best = 0;
+    double lo = g[0][0];
+#pragma unroll
+    for (int n = 1; n < 4; ++n)
+      if (g[n][n] < lo) { lo = g[n][n]; best = n; }
+    double next = INFINITY, hi = lo;
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      if (n != best && g[n][n] < next) next = g[n][n];
+      if (g[n][n] > hi) hi = g[n][n];
+    }
+    // lambda_1 - lambda_0 below what the eigenvectors of a double G resolve (views that coincide, rays that are parallel): x is
+    // any vector of a plane there and has no derivative, so the term is left out and the joint gets its detached gradient
+    const bool gap = next - lo > XAS_MV_MIN_GAP * hi;
+    const double x3 = j.x[3];
+    const double gx[4] = {gX[0] / x3, gX[1] / x3, gX[2] / x3, -(gX[0] * j.x[0] + gX[1] * j.x[1] + gX[2] * j.x[2]) / (x3 * x3)};
+    double mv[4] = {0.0, 0.0, 0.0, 0.0};                              // sum_j (v_j . g_x) / (lambda_0 - lambda_j) v_j:  g_G = sym(mv x^T)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      if (n == best || !gap) continue;
+      const double cf = (vec[0][n] * gx[0] + vec[1][n] * gx[1] + vec[2][n] * gx[2] + vec[3][n] * gx[3]) / (lo - g[n][n]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mv[r] += cf * vec[r][n];
+    }
+#pragma unroll
+    for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v)
+      if ((j.valid >> v) & 1) {
+        const float* Pm = P + ((size_t)b * V + v) * 12;
+        double mp2 = 0.0, xp2 = 0.0, aum = 0.0, aux = 0.0, avm = 0.0, avx = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double p2 = (double)Pm[8 + r];
+          const double au = j.u[v] * p2 - (double)Pm[r], av = j.v[v] * p2 - (double)Pm[4 + r];
+          mp2 += mv[r] * p2; xp2 += j.x[r] * p2;
+          aum += au * mv[r]; aux += au * j.x[r];
+          avm += av * mv[r]; avx += av * j.x[r];
+        }
+        const double c2 = (double)j.c[v] * (double)j.c[v];            // 2 c^2 a^T sym(mv x^T) P2
+        gu[v] += c2 * (aum * xp2 + aux * mp2);
+        gv[v] += c2 * (avm * xp2 + avx * mp2);
+      }
+  }
+  const double half = ((double)S - 1.0) / 2.0;
+#pragma unroll
+  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v)
+    if (v < V) {
+      float* o = grad_kps_xy + (((size_t)b * V + v) * K + k) * 2;
+      const bool on = solved && ((j.valid >> v) & 1);                 // exact zeros elsewhere, whatever the affine holds
+      o[0] = on ? (float)((j.i00[v] * gu[v] + j.i10[v] * gv[v]) * half) : 0.f;
+      o[1] = on ? (float)((j.i01[v] * gu[v] + j.i11[v] * gv[v]) * half) : 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // pose_metrics: one wave per sample, lane = joint.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float norm3(float a, float b, float c) {
@@ -831,6 +1079,46 @@ extern "C" int xas_triangulate_refine(const float* points, const float* P, const
               flags & ~XAS_REFINE_WEIGHTED, XAS_REFINE_WEIGHTED);
   hipLaunchKernelGGL(triangulate_refine_kernel, dim3((unsigned)cdiv((long)B * K, 64)), dim3(64), 0, as_stream(stream), points, P,
                      init, views, B, V, K, flags, huber, max_iter, out, resid, cov, status);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+// The argument checks that the two passes of the multi-view term share.
+static int mv_check(const char* who, int B, int V, int Hy, int K, float image_size, float huber_px, int flags) {
+  XAS_REQUIRE(V >= 2 && V <= XAS_TRI_MAX_VIEWS, "%s: V=%d views (needs 2 <= V <= XAS_TRI_MAX_VIEWS = %d)", who, V, XAS_TRI_MAX_VIEWS);
+  XAS_REQUIRE(Hy >= 1 && Hy <= 8, "%s: Hy=%d hypotheses (needs 1 <= Hy <= 8)", who, Hy);
+  XAS_REQUIRE(B >= 1 && K >= 1 && (long)B * K <= 0x7fffffffL, "%s: bad shape B=%d K=%d (B >= 1, K >= 1, B*K < 2^31)", who, B, K);
+  XAS_REQUIRE(image_size > 1.f, "%s: image_size %f (needs a patch size > 1)", who, (double)image_size);
+  XAS_REQUIRE(huber_px >= 0.f && huber_px < INFINITY, "%s: huber_px %f (needs a finite huber_px >= 0; 0 = squared loss)", who,
+              (double)huber_px);
+  XAS_REQUIRE((flags & ~XAS_MV_DETACH_TARGET) == 0, "%s: unknown flag bits 0x%x (XAS_MV_DETACH_TARGET = %d is the only flag)", who,
+              flags & ~XAS_MV_DETACH_TARGET, XAS_MV_DETACH_TARGET);
+  return 0;
+}
+
+extern "C" int xas_multiview_consistency_fwd(const float* kps_xy, const float* trans_image, const float* world, const float* P,
+                                             const float* weight, int B, int V, int Hy, int K, float image_size, float huber_px,
+                                             int flags, float* reproj, float* depth, float* xyz, int* hsel,
+                                             unsigned char* status, void* stream) {
+  XAS_REQUIRE(kps_xy && trans_image && world && P && reproj && depth && xyz && hsel && status,
+              "multiview_consistency_fwd: null buffer (everything but weight is required)");
+  if (mv_check("multiview_consistency_fwd", B, V, Hy, K, image_size, huber_px, flags)) return 1;
+  hipLaunchKernelGGL(multiview_consistency_fwd_kernel, dim3((unsigned)cdiv((long)B * K, 64)), dim3(64), 0, as_stream(stream),
+                     kps_xy, trans_image, world, P, weight, B, V, Hy, K, image_size, huber_px, reproj, depth, xyz, hsel, status);
+  XAS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int xas_multiview_consistency_bwd(const float* kps_xy, const float* trans_image, const float* world, const float* P,
+                                             const float* weight, const float* g_reproj, const float* g_depth, int B, int V,
+                                             int Hy, int K, float image_size, float huber_px, int flags, float* grad_kps_xy,
+                                             float* grad_world, void* stream) {
+  XAS_REQUIRE(kps_xy && trans_image && world && P && g_reproj && g_depth && grad_kps_xy && grad_world,
+              "multiview_consistency_bwd: null buffer (everything but weight is required)");
+  if (mv_check("multiview_consistency_bwd", B, V, Hy, K, image_size, huber_px, flags)) return 1;
+  hipLaunchKernelGGL(multiview_consistency_bwd_kernel, dim3((unsigned)cdiv((long)B * K, 64)), dim3(64), 0, as_stream(stream),
+                     kps_xy, trans_image, world, P, weight, g_reproj, g_depth, B, V, Hy, K, image_size, huber_px, flags,
+                     grad_kps_xy, grad_world);
   XAS_LAUNCH_CHECK();
   return 0;
 }

@@ -13,8 +13,8 @@ import torch
 
 from modules.base_losses.loss_func import (compute_disc_loss, compute_mask_reconstruction_loss,
                                            compute_supervision_min, compute_symmetry_min)
-from modules.util import convert_patch_to_world, draw_lines_max, random_rotation_3D
-from xas_amd import ops_nn, streams
+from modules.util import convert_patch_to_world, draw_lines_max, multiview_consistency_loss, random_rotation_3D
+from xas_amd import ops_eval, ops_nn, streams
 
 
 def cal_links(parent_ids, line_select_ids=None, use_root=False, extension=True):
@@ -93,6 +93,9 @@ class Counter3DModel(torch.nn.Module):
         self.parent_ids, self.child_ids = cal_links(cfg['parent_ids'], line_select_ids=cfg.get('line_select_ids'),
                                                     use_root=False, extension=True)
         self.loss_config = cfg['loss_config']
+        if 'multiview_loss' in self.loss_config and not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
+            raise ValueError('multiview_loss triangulates over 2 to {} cameras; cam_id_list has {}'.format(
+                ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
         self.use_learned_width = cfg.get('use_learned_width', False)
         self.smpl_layer = smpl_layer
         self.h36m_regressor = h36m_regressor
@@ -281,6 +284,15 @@ class Counter3DModel(torch.nn.Module):
                 key = 'cam_{}'.format(cam)
                 total = total + compute_symmetry_min(world[key], w['bone'], w['kp'], kps[key], w.get('kp_2d'))
             losses['symmetry'] = total
+
+        if 'multiview_loss' in lc:                 # not a key of the shipped configs (train.py --mv-2d / --mv-3d); current stream
+            if 'mono' in cams:
+                raise ValueError('multiview_loss needs the cameras of a rig; this batch is a mono batch')
+            mv = lc['multiview_loss']
+            losses['multiview'], tri = multiview_consistency_loss(
+                kps, world, x, cams, mv['weight_2d'], mv['weight_3d'], huber_px=mv.get('huber_px', 0.0),
+                detach_target=mv.get('detach_target', False))
+            out['pose_3d_tri'] = tri[0:1]
 
         if 'smpl_gen_loss' in lc:
             if gen_val is None and wait_for is not None:

@@ -180,6 +180,29 @@ def resolve_views_weighted(kps_by_cam, params, cam_id_list, pairs, weights, gt=T
     return {mode: sel[:, i] for i, mode in enumerate(modes)}, r
 
 
+def multiview_consistency_loss(kps_by_cam, world_by_cam, params, cam_id_list, weight_2d, weight_3d, huber_px=0.0,
+                               detach_target=False, weights=None):
+    """Multi-view consistency term of the training step (ops_eval.multiview_consistency, called once).  {cam_key: [B,Hy,K,3]}
+    raw detections of all cameras and their single-view world points (convert_patch_to_world, with its graph); `weights`
+    {cam_key: [B,K]} as in triangulation_weighted, None: every view counts 1.
+    -> ((weight_2d * sum of the reprojection terms in px^2 + weight_3d * sum of the depth terms in mm^2) / max(joints that were
+    solved, 1) as a device scalar, the triangulated joints [B,K,3] without a graph (NaN where a joint was passed through)).
+    Nothing here synchronises with the host.  No reference counterpart."""
+    modes = ['cam_{}'.format(c) for c in cam_id_list]
+    size = params['{}_img'.format(modes[0])].shape[-1]
+    stack = lambda fmt: torch.stack([params[fmt.format(mode)] for mode in modes], dim=1)
+    B, V = params['{}_k_mat'.format(modes[0])].shape[0], len(modes)
+    pm = ops_eval.projection_matrix(stack('{}_k_mat').flatten(0, 1), stack('{}_rot_world').flatten(0, 1),
+                                    stack('{}_trans_world').flatten(0, 1)).view(B, V, 3, 4)
+    reproj, depth, xyz, status = ops_eval.multiview_consistency(
+        torch.stack([kps_by_cam[mode][:, 0, :, :2] for mode in modes], dim=1), stack('{}_trans_image'),
+        torch.stack([world_by_cam[mode] for mode in modes], dim=1), pm,
+        weight=None if weights is None else torch.stack([weights[mode] for mode in modes], dim=1), image_size=size,
+        huber_px=huber_px, detach_target=detach_target)
+    solved = (status == 0).sum().clamp(min=1)
+    return (weight_2d * reproj.sum() + weight_3d * depth.sum()) / solved, xyz.detach()
+
+
 def smpl_to_h36m(verts, h36m_regressor):
     """17 regressed joints, L/R arms swapped, thorax appended, root centred (util.py:331-341)."""
     j = torch.einsum('bki,lk->bli', verts, h36m_regressor)

@@ -3,6 +3,7 @@
 
     torchrun --nproc-per-node=N train.py --config config/HM36_Multi_SurS1.yaml [--checkpoint ... --finetune]
              [--batch_size B --epoch E --worker W --seed S --extra_tag T --log_dir D] [--synthetic STEPS]
+             [--mv-2d W --mv-3d W --mv-huber PX --mv-detach]
 
 Differences from the reference, all outside the hot step: the two DistributedDataParallel wrappers are
 replaced by xas_amd.engine.TrainStep (flat gradient arenas + bucketed RCCL all-reduce on a side stream);
@@ -206,7 +207,25 @@ CLI = (  # same flags as the reference entry (train.py:305-315) + --synthetic
     ('--finetune', dict(default=False, action='store_true', help='finetune the model')),
     ('--seed', dict(default=-1, type=int)),
     ('--synthetic', dict(default=0, type=int, help='train on N synthetic batches per epoch')),
+    # (no reference counterpart) the multi-view consistency term, model_params.loss_config.multiview_loss; given neither weight,
+    # nothing is inserted and the step runs the launches it ran before
+    ('--mv-2d', dict(default=None, type=float, metavar='W', dest='mv_2d',
+                     help='weight of the multi-view reprojection term (px^2 per joint) against the triangulated joint')),
+    ('--mv-3d', dict(default=None, type=float, metavar='W', dest='mv_3d',
+                     help="weight of the multi-view depth term (mm^2 per joint): every view's nearest hypothesis against the "
+                          'triangulated joint')),
+    ('--mv-huber', dict(default=0.0, type=float, metavar='PX', dest='mv_huber',
+                        help="Huber's delta of the reprojection term in pixels, 0 = squared loss")),
+    ('--mv-detach', dict(default=False, action='store_true', dest='mv_detach',
+                         help='the triangulated joint is a constant target (a pseudo-label), not a function of the views')),
 )
+
+
+def multiview_entry(opt):
+    """loss_config's `multiview_loss` entry of --mv-2d / --mv-3d / --mv-huber / --mv-detach, or None if neither weight is given."""
+    if opt.mv_2d is None and opt.mv_3d is None:
+        return None
+    return dict(weight_2d=opt.mv_2d or 0.0, weight_3d=opt.mv_3d or 0.0, huber_px=opt.mv_huber, detach_target=opt.mv_detach)
 
 
 def main():
@@ -217,6 +236,8 @@ def main():
     with open(opt.config) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     config['model_params']['cam_id_list'] = config['dataset_params']['cam_id_list']
+    if multiview_entry(opt) is not None:
+        config['model_params']['loss_config']['multiview_loss'] = multiview_entry(opt)
     for key, val in (('batch_size', opt.batch_size), ('num_epochs', opt.epoch)):
         if val:
             config['train_params'][key] = val

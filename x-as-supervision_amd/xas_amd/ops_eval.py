@@ -1,5 +1,6 @@
 """Evaluation-path ops over the C ABI: hypothesis selection, triangulation, pose metrics (no autograd: eval runs
-under torch.no_grad, eval.py:393).  Everything returns device tensors; nothing here synchronises with the host."""
+under torch.no_grad, eval.py:393), and the one op of the same geometry that training differentiates, multiview_consistency.
+Everything returns device tensors; nothing here synchronises with the host."""
 import torch
 
 from ._lib import call, ptr
@@ -179,6 +180,69 @@ def multiview_resolve(points, pmat, kps, world, pairs=SWITCH_PAIRS, gt=None, ima
          B, V, Hy, K, float(image_size), ptr(out['sel']), ptr(out.get('xyzw')), ptr(out.get('swap')), ptr(out.get('hyp')),
          ptr(out.get('named')))
     return out
+
+
+MV_DETACH_TARGET = 1     # xas_hip.h XAS_MV_DETACH_TARGET
+
+
+class _MultiviewConsistency(torch.autograd.Function):
+    """xas_multiview_consistency_fwd / _bwd: the one part of this module that training differentiates."""
+
+    @staticmethod
+    def forward(ctx, kps_xy, world, trans_image, pmat, weight, image_size, huber_px, flags):
+        B, V, Hy, K = world.shape[:4]
+        dev = kps_xy.device
+        reproj, depth = torch.empty(B, K, device=dev), torch.empty(B, K, device=dev)
+        xyz = torch.empty(B, K, 3, device=dev)
+        hsel = torch.empty(B, V, K, device=dev, dtype=torch.int32)
+        status = torch.empty(B, K, device=dev, dtype=torch.uint8)
+        call('xas_multiview_consistency_fwd', ptr(kps_xy), ptr(trans_image), ptr(world), ptr(pmat), ptr(weight), B, V, Hy, K,
+             image_size, huber_px, flags, ptr(reproj), ptr(depth), ptr(xyz), ptr(hsel), ptr(status))
+        ctx.save_for_backward(kps_xy, world, trans_image, pmat, weight)
+        ctx.scalars = (image_size, huber_px, flags)
+        ctx.mark_non_differentiable(xyz, hsel, status)
+        return reproj, depth, xyz, hsel, status
+
+    @staticmethod
+    def backward(ctx, g_reproj, g_depth, *_):
+        kps_xy, world, trans_image, pmat, weight = ctx.saved_tensors
+        B, V, Hy, K = world.shape[:4]
+        zero = lambda g: torch.zeros(B, K, device=kps_xy.device) if g is None else g.contiguous().float()
+        g_reproj, g_depth = zero(g_reproj), zero(g_depth)
+        grad_xy, grad_world = torch.empty_like(kps_xy), torch.empty_like(world)      # the kernel writes every entry
+        call('xas_multiview_consistency_bwd', ptr(kps_xy), ptr(trans_image), ptr(world), ptr(pmat), ptr(weight), ptr(g_reproj),
+             ptr(g_depth), B, V, Hy, K, *ctx.scalars, ptr(grad_xy), ptr(grad_world))
+        return grad_xy, grad_world, None, None, None, None, None, None
+
+
+def multiview_consistency(kps_xy, trans_image, world, pmat, weight=None, image_size=256.0, huber_px=0.0, detach_target=False):
+    """Multi-view consistency of the training step (xas_multiview_consistency_fwd / _bwd, two launches).  kps_xy [B,V,K,2]
+    hypothesis 0's normalised patch x, y of every camera, trans_image [B,V,2,3], world [B,V,Hy,K,3] every hypothesis's single-view
+    world point in mm, pmat [B,V,3,4], weight [B,V,K] or None = every view counts 1 (not finite or not positive: the view is
+    invalid for that joint).  X = the DLT over the valid views.
+    -> (reproj [B,K]: mean over the valid views of the squared (huber_px > 0: Huber's) pixel distance between X's reprojection
+    and the view's point; depth [B,K]: mean squared distance in mm^2 between X and the view's nearest hypothesis; xyz [B,K,3] = X;
+    status [B,K] uint8, 0 or 2 = passed through: fewer than two valid views, X not finite or behind a valid view - both terms and
+    every gradient exactly 0, xyz NaN).  Gradients go to kps_xy and world only; with `detach_target` X is a constant of the
+    backward pass."""
+    kps_xy, world = kps_xy.contiguous().float(), world.contiguous().float()
+    trans_image, pmat = _f32(trans_image), _f32(pmat)
+    if kps_xy.dim() != 4 or kps_xy.shape[-1] != 2:
+        raise RuntimeError('multiview_consistency: kps_xy %s is not [B,V,K,2]' % (tuple(kps_xy.shape),))
+    B, V, K, _ = kps_xy.shape
+    if world.dim() != 5 or world.shape[:2] != (B, V) or world.shape[3:] != (K, 3):
+        raise RuntimeError('multiview_consistency: world %s does not match kps_xy %s' % (tuple(world.shape), tuple(kps_xy.shape)))
+    if trans_image.shape != (B, V, 2, 3):
+        raise RuntimeError('multiview_consistency: crop affines %s do not match kps_xy %s' % (tuple(trans_image.shape), tuple(kps_xy.shape)))
+    if pmat.shape != (B, V, 3, 4):
+        raise RuntimeError('multiview_consistency: projection matrices %s do not match kps_xy %s' % (tuple(pmat.shape), tuple(kps_xy.shape)))
+    if weight is not None:
+        weight = _f32(weight)
+        if weight.shape != (B, V, K):
+            raise RuntimeError('multiview_consistency: weights %s do not match kps_xy %s' % (tuple(weight.shape), tuple(kps_xy.shape)))
+    reproj, depth, xyz, _, status = _MultiviewConsistency.apply(kps_xy, world, trans_image, pmat, weight, float(image_size),
+                                                                float(huber_px), MV_DETACH_TARGET if detach_target else 0)
+    return reproj, depth, xyz, status
 
 
 def pose_metrics(pred, gt, mask=None, in_div=1.0, pck_align=0, pck_threshold=0.15,
