@@ -786,6 +786,46 @@ int xas_triangulate_refine(const float* points, const float* P, const float* ini
                            int K, int flags, float huber, int max_iter, float* out, float* resid, float* cov,
                            unsigned char* status, void* stream);
 
+/* Skeleton-level refinement: xas_triangulate_refine with the joints of a sample coupled by left/right limb symmetry (eval.py
+ * --tri-skeleton; the reference has no counterpart).  One least-squares problem per sample instead of one per joint.
+ * points [B][V][K][3], P [B][V][3][4], init [B][K][4] and views [B][K] (or NULL) are exactly as for xas_triangulate_refine,
+ * with its rules for VALID views, the views used F_k, BEHIND, XAS_REFINE_WEIGHTED (the only flag) and huber.
+ * limbs [L][4] int32, a HOST array read before the launch: (far_a, near_a, far_b, near_b); limb a runs from joint far_a to
+ * joint near_a and limb b is its mirror.  An index outside [0, K) is an error, not skipped.  NULL is allowed with L = 0.
+ * sym_w >= 0 and finite, in px^2 per mm^2 (sigma^2 per mm^2 with XAS_REFINE_WEIGHTED).
+ * A joint is FREE if xas_triangulate_refine would not pass it through: at least two views used, x, y and z of init finite, and
+ * init behind none of the views used.  Otherwise it is FIXED: it leaves as init, bit for bit (NaN stays NaN), and takes part in
+ * nothing.  A limb pair is ACTIVE if all four of its joints are free.
+ * The cost over the free joints of one sample, in double from the fp32 inputs:
+ *   C(X) = sum over free k and v in F_k of rho(s_vk |r_vk|)            (term for term the cost of xas_triangulate_refine)
+ *        + sym_w * sum over active limb pairs of e^2,   e = |X_far_a - X_near_a| - |X_far_b - X_near_b|  (mm)
+ * Levenberg-Marquardt on all free coordinates of the sample at once, in double.  H = the 3x3 blocks of
+ * xas_triangulate_refine on the diagonal (with its psi) + sym_w * sum of J^T J over the active pairs, g = its g per joint +
+ * sym_w * sum of J^T e, where J = d e / dX is +a / |a| at far_a, -a / |a| at near_a, -b / |b| at far_b, +b / |b| at near_b
+ * (summed where a joint stands in several places).  If limb a or limb b of a pair is shorter than 1e-9 mm, the pair
+ * contributes its residual but a zero row J: nothing is divided by the length.
+ * A TRIAL is X + d with (H + lambda diag(H)) d = -g, solved by Cholesky; lambda = 1e-3 at the start.  A trial is ACCEPTED if
+ * C strictly decreases and no free joint lies behind a view it uses: X moves, lambda *= 0.1; otherwise, and at a pivot that
+ * is not positive, lambda *= 10.  The loop stops when the largest |coordinate change| of an accepted step is under 1e-5 (mm),
+ * after max_iter trials (1 <= max_iter <= 64), or when lambda > 1e12.  So C(out) <= C(init), always.
+ * out [B][K][4] (required, must not overlap init) = the point rounded to fp32 and init's fourth entry.  Each of the others may
+ * be NULL:
+ *   resid [B][K][2]  as in xas_triangulate_refine: RMS of |r_v| over F_k (px, unweighted) at init and at the result; NaN
+ *                    for a fixed joint
+ *   sym [B][L][2]    e in mm at init and at the result; NaN where the pair is not active
+ *   cost [B][2]      C at init and at the result (0 for a sample with no free joint)
+ *   status [B][K]    0 = the sample stopped on the step rule, 1 = it ran out of trials or lambda, 2 = the joint is fixed
+ * There is no covariance output: the inverse of the coupled matrix is not formed.
+ * One wave per sample; H and its Cholesky factor packed in LDS, 61 KB static per block: 2 <= V <= XAS_TRI_MAX_VIEWS,
+ * 3 <= K <= XAS_SKEL_MAX_JOINTS, 0 <= L <= XAS_SKEL_MAX_LIMBS, B > 0, B*K < 2^31.  One launch, no host synchronisation, no
+ * atomics: the result is a pure function of the inputs, bit for bit from run to run. */
+#define XAS_SKEL_MAX_JOINTS 24
+#define XAS_SKEL_MAX_LIMBS 16
+int xas_triangulate_skeleton(const float* points, const float* P, const float* init, const unsigned char* views,
+                             const int* limbs, int B, int V, int K, int L, int flags, float huber, float sym_w,
+                             int max_iter, float* out, float* resid, float* sym, float* cost,
+                             unsigned char* status, void* stream);
+
 /* Smallest (lambda_1 - lambda_0) / lambda_3 at which xas_multiview_consistency_bwd differentiates through X (below). */
 #define XAS_MV_MIN_GAP 1e-10
 /* Multi-view consistency loss of the training step (train.py --mv-2d / --mv-3d; the reference has no counterpart: its step

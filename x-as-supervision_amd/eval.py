@@ -4,7 +4,7 @@
     torchrun --nproc-per-node=N eval.py --config config/HM36_Multi_SurS1.yaml --checkpoint ckpt.pth.tar
              [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
              [--tri dlt|robust --tri_thresh PX] [--resolve gt|views] [--tri-weight depth|spread]
-             [--tri-refine none|lm --tri-huber PX]
+             [--tri-refine none|lm --tri-huber PX] [--tri-skeleton --tri-sym W]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -29,6 +29,14 @@ time figure of that mode has been measured either.
 which minimises an algebraic error, to the minimum of the reprojection error in pixels over the cameras the triangulation used
 (ops_eval.triangulate_refine: Levenberg-Marquardt in one launch; --tri-huber PX makes the loss Huber's).  With --tri-weight
 spread every residual counts in sigmas of its heat-map.  No accuracy figure has been measured: its effect on MPJPE is unknown.
+
+--tri-skeleton (opt-in; model_params.tri_refine = 'skeleton'; it takes the place of --tri-refine, whose two choices stay as
+they were) refines the joints of a sample TOGETHER instead: the same reprojection error over the same
+cameras, plus --tri-sym W (px^2 per mm^2, default 0.1) times the squared difference in length of every left/right limb pair,
+upper and lower arm and leg (ops_eval.triangulate_skeleton: one wave per sample, one launch).  A limb seen well on one side
+then says how long its mirror is, where a wrist or elbow is ill determined along the rays.  A joint that lm would pass through
+stays where it was and switches its limb pairs off.  Unknown: its effect on MPJPE, and the right --tri-sym; the default only
+puts a 1 mm mismatch on the scale of a 1 px residual at roughly 0.3 px per mm.
 """
 import copy
 import os
@@ -45,7 +53,7 @@ from metrics import pose_errors
 from modules.keypoint_detector_integral import KPDetector3D as KPDetector3D_integral
 from modules.keypoint_detector_integral_multi import KPDetector3DMulti as KPDetector3DMulti_integral
 from modules.util import (convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_refined,
-                          triangulation_weighted)
+                          triangulation_skeleton, triangulation_weighted)
 from eval_utils import cal_per_class_error
 from xas_amd import ops_eval
 from xas_amd.synthetic import synthetic_eval_batch
@@ -83,11 +91,19 @@ class Eval:
         if tri_weight not in ('depth', 'spread'):
             raise ValueError('Unknown triangulation weight: {}'.format(tri_weight))
         tri_refine = config['model_params'].get('tri_refine', 'none')          # --tri-refine / --tri-huber; not keys of the shipped configs either
-        if tri_refine not in ('none', 'lm'):
+        if tri_refine not in ('none', 'lm', 'skeleton'):
             raise ValueError('Unknown triangulation refinement: {}'.format(tri_refine))
         if tri_refine == 'lm' and len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
             raise ValueError("tri_refine='lm' refines over at most {} cameras; cam_id_list has {}".format(
                 ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
+        if tri_refine == 'skeleton':
+            if len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
+                raise ValueError("tri_refine='skeleton' refines over at most {} cameras; cam_id_list has {}".format(
+                    ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
+            num_kp = getattr(detector, 'num_kp', config['model_params'].get('detector_params', {}).get('num_kp'))
+            if num_kp is not None and num_kp > ops_eval.SKEL_MAX_JOINTS:
+                raise ValueError("tri_refine='skeleton' couples at most {} joints; the detector has {}".format(
+                    ops_eval.SKEL_MAX_JOINTS, num_kp))
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -110,7 +126,9 @@ class Eval:
         self.tri_sigma, self.sigma_batches = 0.0, 0    # spread only: mean sigma in pixels, summed over the batches
         self.tri_refine = tri_refine               # --tri-refine lm: the triangulated point minimises the reprojection error in pixels
         self.tri_huber = float(config['model_params'].get('tri_huber', 0.0))   # lm only: Huber's delta, 0 = plain least squares
-        self.refine_px, self.refine_gain, self.refine_batches = 0.0, 0.0, 0    # lm only, summed over the batches
+        self.refine_px, self.refine_gain, self.refine_batches = 0.0, 0.0, 0    # lm and skeleton, summed over the batches
+        self.tri_sym = float(config['model_params'].get('tri_sym', ops_eval.TRI_SYM_W))    # skeleton only: --tri-sym, px^2 per mm^2
+        self.sym_mm = np.zeros(2)                  # skeleton only: mean |limb a| - |limb b| in mm before and after, summed
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -179,6 +197,13 @@ class Eval:
             used = r.get('inliers')
             out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a joint passed through has no residual (NaN)
             out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
+        elif self.tri_refine == 'skeleton':        # the same start and views, the joints of a sample refined together
+            tri, r = triangulation_skeleton(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, sym_w=self.tri_sym,
+                                            want=('resid', 'sym'), robust_px=self.tri_thresh if self.tri == 'robust' else None)
+            used = r.get('inliers')
+            out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a fixed joint has no residual (NaN)
+            out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
+            out['tri_sym_mm'] = r['sym'].abs().reshape(-1, 2).nanmean(dim=0)   # [2]: before, after; a pair switched off is NaN
         elif self.tri == 'robust':
             tri, used = triangulation_weighted(sel, x, self.cam_id_list, weights, robust_px=self.tri_thresh, return_inliers=True)
         else:
@@ -227,6 +252,8 @@ class Eval:
                 self.refine_px += float(host['tri_refine_px'])
                 self.refine_gain += float(host['tri_refine_gain_px'])
                 self.refine_batches += 1
+            if 'tri_sym_mm' in host:
+                self.sym_mm += host['tri_sym_mm']
             if 'resolve_hyp0' in host:
                 self.res_exchanged += float(host['resolve_exchanged'])
                 self.res_hyp0 += float(host['resolve_hyp0'])
@@ -285,6 +312,10 @@ class Eval:
             n = max(self.refine_batches, 1)
             lines.append('TRI refine lm (huber {}): reprojection RMS {} px, gained {} px'.format(
                 self.tri_huber, self.refine_px / n, self.refine_gain / n))
+        if self.tri_refine == 'skeleton':          # after everything else; none and lm leave the file as it was
+            n = max(self.refine_batches, 1)
+            lines.append('TRI refine skeleton (huber {}, sym {}): reprojection RMS {} px, gained {} px, limb asymmetry {} -> {} mm'.format(
+                self.tri_huber, self.tri_sym, self.refine_px / n, self.refine_gain / n, self.sym_mm[0] / n, self.sym_mm[1] / n))
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -373,6 +404,12 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
     ('--tri-huber', dict(default=0.0, type=float, metavar='PX', dest='tri_huber',
                          help="--tri-refine lm: Huber's delta in the unit of the residual (pixels; sigmas with --tri-weight "
                               'spread); 0 = plain least squares')),
+    ('--tri-skeleton', dict(default=False, action='store_true', dest='tri_skeleton',
+                            help='after the triangulation, in place of --tri-refine: the same Levenberg-Marquardt over all joints '
+                                 'of a sample together, with left/right limb symmetry (--tri-huber applies; weight: --tri-sym)')),
+    ('--tri-sym', dict(default=ops_eval.TRI_SYM_W, type=float, metavar='W', dest='tri_sym',
+                       help='--tri-skeleton: weight of the squared length difference of a left/right limb pair, in px^2 '
+                            'per mm^2 (sigma^2 per mm^2 with --tri-weight spread)')),
 )
 
 
@@ -385,7 +422,9 @@ def main():
         config = yaml.load(f, Loader=yaml.FullLoader)
     config['model_params']['cam_id_list'] = config['dataset_params']['cam_id_list']
     config['model_params']['tri_weight'] = opt.tri_weight
-    config['model_params']['tri_refine'], config['model_params']['tri_huber'] = opt.tri_refine, opt.tri_huber
+    config['model_params']['tri_refine'] = 'skeleton' if opt.tri_skeleton else opt.tri_refine
+    config['model_params']['tri_huber'] = opt.tri_huber
+    config['model_params']['tri_sym'] = opt.tri_sym
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

@@ -143,6 +143,26 @@ def triangulation_refined(keypoints, params, cam_id_list, weights=None, is_norm=
     return out['xyzw'][..., :3], out
 
 
+def triangulation_skeleton(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000, robust_px=None,
+                           huber_px=0.0, sym_w=ops_eval.TRI_SYM_W, limbs=ops_eval.SYM_LIMBS, want=()):
+    """triangulation_refined with the joints of every sample refined together under left/right limb symmetry
+    (ops_eval.triangulate_skeleton): the same inputs, the same start (the DLT, or the robust point and its inlier masks with
+    robust_px), the same weights; `sym_w` px^2 per mm^2 on the squared difference of each limb pair's lengths.
+    -> (world joints [B,K,3], dict of ops_eval.triangulate_skeleton: xyzw and the outputs in `want`, + `inliers` with
+    robust_px).  No reference counterpart."""
+    pts, pm = _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+    if robust_px is None:
+        init, used = batch_triangulate(pts, pm), None
+    else:
+        r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',))
+        init, used = r['xyzw'], r['inliers']
+    out = ops_eval.triangulate_skeleton(pts, pm, init, views=used, limbs=limbs, weighted=weights is not None, huber_px=huber_px,
+                                        sym_w=sym_w, want=want)
+    if used is not None:
+        out['inliers'] = used
+    return out['xyzw'][..., :3], out
+
+
 def resolve_views(kps_by_cam, params, cam_id_list, pairs, gt=True, RECT_WIDTH=2000):
     """{cam_key: [B,Hy,K,3]} raw detections of all cameras -> ({cam_key: [B,K,3]} resolved joints, the other outputs of
     ops_eval.multiview_resolve).  The left/right exchange of every view and the depth hypothesis of every view and joint are

@@ -1,6 +1,8 @@
 """Evaluation-path ops over the C ABI: hypothesis selection, triangulation, pose metrics (no autograd: eval runs
 under torch.no_grad, eval.py:393), and the one op of the same geometry that training differentiates, multiview_consistency.
 Everything returns device tensors; nothing here synchronises with the host."""
+import ctypes
+
 import torch
 
 from ._lib import call, ptr
@@ -144,6 +146,55 @@ def triangulate_refine(points, pmat, init, views=None, weighted=False, huber_px=
         out['status'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
     call('xas_triangulate_refine', ptr(points), ptr(pmat), ptr(init), ptr(views), B, V, K, REFINE_WEIGHTED if weighted else 0,
          float(huber_px), int(max_iter), ptr(out['xyzw']), ptr(out.get('resid')), ptr(out.get('cov')), ptr(out.get('status')))
+    return out
+
+
+# Left/right limb pairs (far_a, near_a, far_b, near_b) of the 18-joint skeleton: the limbs of the training loss's symmetry term
+# (modules/base_losses/loss_func.py: _LIMB_FAR / _LIMB_NEAR, upper and lower arm and leg), each paired with its mirror.
+SYM_LIMBS = ((16, 15, 13, 12), (15, 14, 12, 11), (3, 2, 6, 5), (2, 1, 5, 4))
+SKEL_MAX_JOINTS, SKEL_MAX_LIMBS = 24, 16      # xas_hip.h XAS_SKEL_MAX_JOINTS, XAS_SKEL_MAX_LIMBS
+TRI_SYM_W = 0.1          # default --tri-sym, px^2 per mm^2: at ~0.3 px per mm a 1 mm limb mismatch weighs about like a 1 px residual
+
+
+def triangulate_skeleton(points, pmat, init, views=None, limbs=SYM_LIMBS, weighted=False, huber_px=0.0, sym_w=TRI_SYM_W, max_iter=20,
+                         want=('resid',)):
+    """triangulate_refine with the joints of a sample coupled by left/right limb symmetry (xas_triangulate_skeleton): one
+    Levenberg-Marquardt problem per sample on  sum of rho(reprojection residuals) + sym_w * sum over the limb pairs of
+    (|limb a| - |limb b|)^2.  points, pmat, init, views, weighted, huber_px as for triangulate_refine; limbs = rows
+    (far_a, near_a, far_b, near_b) of joint indices; sym_w in px^2 per mm^2.  A joint that triangulate_refine would pass through
+    is fixed (init bit for bit) and switches off every limb pair it belongs to.
+    -> dict: xyzw [B,K,4] always; resid [B,K,2] (RMS pixel residual before and after; NaN for a fixed joint), sym [B,L,2]
+    (|limb a| - |limb b| in mm before and after; NaN where the pair is off), cost [B,2], status [B,K] uint8 (0 the sample
+    converged, 1 out of trials, 2 fixed joint) as requested."""
+    points, pmat, init = _f32(points), _f32(pmat), _f32(init)
+    B, V, K, _ = points.shape
+    if pmat.shape != (B, V, 3, 4):
+        raise RuntimeError('triangulate_skeleton: projection matrices %s do not match points %s' % (tuple(pmat.shape), tuple(points.shape)))
+    if init.shape != (B, K, 4):
+        raise RuntimeError('triangulate_skeleton: start points %s do not match points %s' % (tuple(init.shape), tuple(points.shape)))
+    if views is not None:
+        if views.shape != (B, K) or views.dtype != torch.uint8:
+            raise RuntimeError('triangulate_skeleton: views %s %s are not the [B,K] uint8 masks of points %s' % (
+                tuple(views.shape), views.dtype, tuple(points.shape)))
+        views = views.contiguous()
+    limbs = [tuple(int(j) for j in row) for row in limbs]
+    if any(len(row) != 4 for row in limbs):
+        raise RuntimeError('triangulate_skeleton: every limb pair is (far_a, near_a, far_b, near_b); got %s' % (limbs,))
+    L = len(limbs)
+    table = (ctypes.c_int * max(4 * L, 1))(*[j for row in limbs for j in row])      # read by the host before the launch
+    dev = points.device
+    out = {'xyzw': torch.empty(B, K, 4, device=dev)}
+    if 'resid' in want:
+        out['resid'] = torch.empty(B, K, 2, device=dev)
+    if 'sym' in want:
+        out['sym'] = torch.empty(B, L, 2, device=dev)
+    if 'cost' in want:
+        out['cost'] = torch.empty(B, 2, device=dev)
+    if 'status' in want:
+        out['status'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
+    call('xas_triangulate_skeleton', ptr(points), ptr(pmat), ptr(init), ptr(views), table if L else None, B, V, K, L,
+         REFINE_WEIGHTED if weighted else 0, float(huber_px), float(sym_w), int(max_iter), ptr(out['xyzw']), ptr(out.get('resid')),
+         ptr(out.get('sym')), ptr(out.get('cost')), ptr(out.get('status')))
     return out
 
 
