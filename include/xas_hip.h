@@ -826,6 +826,44 @@ int xas_triangulate_skeleton(const float* points, const float* P, const float* i
                              int max_iter, float* out, float* resid, float* sym, float* cost,
                              unsigned char* status, void* stream);
 
+/* Volumetric fusion of the views' heat-map cubes (eval.py --tri-volume; the reference has no counterpart).  Every other
+ * triangulation here starts from ONE point per view, the soft-argmax of that view's heat-map; this one multiplies the views'
+ * whole distributions over a voxel grid round the triangulated point (a product of experts) and takes the soft-argmax of the
+ * product in world space, so a view whose heat-map has two modes contributes both and the other views choose.
+ * logits: a HOST array of V device pointers, read before the launch; logits[v] is view v's [B][H][W][K*D] fp32 logits, the
+ * head's NHWC layout (L[b,k,d,h,w] = logits[v][((b H + h) W + w) K D + k D + d]), D == H == W.
+ * chan [V][B][K] int32 on the device, or NULL = k: the heat-map channel that view v reads for joint k (it carries a left/right
+ * exchange of a view or of a joint).  trans_image [V][B][2][3], k_mat [V][B][3][3], pelvis [V][B][3], rot_world [V][B][3][3],
+ * trans_world [V][B][3]: the arrays of xas_world_to_patch_fwd with a leading [V].  init [B][K][3] world mm.  views [B][K] or
+ * NULL = every bit set: bit v = view v is selected (a zero byte selects NO view here).  weight [V][B][K] or NULL = 1.
+ * View v TAKES PART in joint (b, k) if its bit is set, its weight is finite and > 0 and its channel lies in [0, K).
+ * Grid: level l = 0 .. levels - 1 is an axis-aligned world cube of side side_l = side_mm 2^-l with G^3 voxels, centres
+ * c_l + ((i + 0.5) / G - 0.5) side_l per axis, i = 0 .. G - 1; c_0 = init, c_(l+1) = the result of level l (in double).
+ * World -> cube of view v, with S = image_size (the inverse of the head's normalisation followed by xas_patch_to_world_fwd):
+ *   Pc = R X + T;  u = fx Xc / Zc + cx, v = fy Yc / Zc + cy;  (u', v') = A (u, v) + t;
+ *   w = u' W / (S - 1), h = v' H / (S - 1), d = ((Zc - pelvis_z) S / rect_width / (S - 1) + 1) D / 2.
+ * sample_v(X): each of (w, h, d) is clamped to [0, D - 1]; o = the L1 distance in cells that the clamp removed; the sample
+ * is the trilinear interpolation of the logits at the clamped point (base cell min(floor(c), D - 2) per axis) minus
+ * out_penalty * o: continuous across the cube's border, and no softmax normaliser is needed because a constant per view
+ * changes nothing below.  Zc <= 0: o = 3 D and the point is (0, 0, 0).
+ * score(X) = beta * sum over the views taking part, in ascending order, of weight_v sample_v(X).  The result of a level is
+ * sum over its voxels of softmax(score) X; cov is the covariance of that distribution at the last level.
+ * Logits are read as fp32; projections, interpolation, exp and every sum run in double; xyz and cov are rounded once.
+ * xyz [B][K][3] (required); cov [B][K][6] mm^2 (xx xy xz yy yz zz) and status [B][K] may be NULL.  status:
+ *   0 fused;  1 passed through (xyz = init bit for bit, cov = NaN): fewer than two views take part, or init is not finite;
+ *   2 fused, but the voxel of the largest score at the last level (the first in x-fastest order among equals) lies on a face
+ *     of the grid: the mode may lie outside;
+ *   3 one of the eight logits read for a sample, at any level, was not finite: passed through as for 1, that joint only.
+ * One workgroup per (b, joint), voxels strided over its threads, per-thread online-softmax records merged by wave shuffles
+ * and then through LDS in a fixed order; the level loop runs inside the kernel: one launch, no host synchronisation, no
+ * atomics, the result is a pure function of the inputs bit for bit.  D % 4 == 0 in [4, 128] (the head's range),
+ * 1 <= V <= XAS_TRI_MAX_VIEWS, 2 <= G <= 32, 1 <= levels <= 4, side_mm, beta and out_penalty finite and > 0, B*K < 2^31. */
+int xas_triangulate_volume(const float* const* logits, const int* chan, const float* trans_image, const float* k_mat,
+                           const float* pelvis, const float* rot_world, const float* trans_world, const float* init,
+                           const unsigned char* views, const float* weight, int B, int V, int K, int D, int G, int levels,
+                           float side_mm, float beta, float out_penalty, float image_size, float rect_width, float* xyz,
+                           float* cov, unsigned char* status, void* stream);
+
 /* Smallest (lambda_1 - lambda_0) / lambda_3 at which xas_multiview_consistency_bwd differentiates through X (below). */
 #define XAS_MV_MIN_GAP 1e-10
 /* Multi-view consistency loss of the training step (train.py --mv-2d / --mv-3d; the reference has no counterpart: its step

@@ -5,6 +5,7 @@
              [--batch_size B --worker W --multi_hypo best|confident] [--synthetic STEPS] [--ema] [--flip]
              [--tri dlt|robust --tri_thresh PX] [--resolve gt|views] [--tri-weight depth|spread]
              [--tri-refine none|lm --tri-huber PX] [--tri-skeleton --tri-sym W]
+             [--tri-volume --tri-vol-side MM --tri-vol-grid G --tri-vol-levels N]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -37,6 +38,17 @@ upper and lower arm and leg (ops_eval.triangulate_skeleton: one wave per sample,
 then says how long its mirror is, where a wrist or elbow is ill determined along the rays.  A joint that lm would pass through
 stays where it was and switches its limb pairs off.  Unknown: its effect on MPJPE, and the right --tri-sym; the default only
 puts a 1 mm mismatch on the scale of a 1 px residual at roughly 0.3 px per mm.
+
+--tri-volume (opt-in; model_params.tri_volume) runs after whatever the options above produced and starts from that point: a
+voxel grid round it (--tri-vol-side MM, --tri-vol-grid G voxels per side, --tri-vol-levels N, each level half the side of the
+one before, round its result) is looked up in every camera's heat-map cube, the log-probabilities are added (a product of
+experts) and the soft-argmax of the fused volume, in world space, replaces the point (ops_eval.triangulate_volume: one
+launch).  Every stage above sees ONE point per camera and joint, the soft-argmax of its heat-map, which lies between the
+modes of a two-mode heat-map; here the whole distributions meet and the other cameras choose the mode.  The cameras are those
+the triangulation used (--tri robust: its inliers), each reading the heat-map channel that the left/right decisions above
+assigned to the joint.  The detector's logits of all cameras stay alive until then: V x 604 MB at B = 32, D = 64, K = 18.
+Not with --flip.  Unknown: its effect on MPJPE (no checkpoint or dataset here), and the right grid: the defaults are read off
+the cell size (31 mm), not tuned.
 """
 import copy
 import os
@@ -53,9 +65,9 @@ from metrics import pose_errors
 from modules.keypoint_detector_integral import KPDetector3D as KPDetector3D_integral
 from modules.keypoint_detector_integral_multi import KPDetector3DMulti as KPDetector3DMulti_integral
 from modules.util import (convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_refined,
-                          triangulation_skeleton, triangulation_weighted)
+                          triangulation_skeleton, triangulation_volume, triangulation_weighted)
 from eval_utils import cal_per_class_error
-from xas_amd import ops_eval
+from xas_amd import ops_eval, ops_head
 from xas_amd.synthetic import synthetic_eval_batch
 
 ACTIONS = ('Directions', 'Discussion', 'Eating', 'Greeting', 'Phoning', 'Posing', 'Purchases', 'Sitting',
@@ -104,6 +116,13 @@ class Eval:
             if num_kp is not None and num_kp > ops_eval.SKEL_MAX_JOINTS:
                 raise ValueError("tri_refine='skeleton' couples at most {} joints; the detector has {}".format(
                     ops_eval.SKEL_MAX_JOINTS, num_kp))
+        tri_volume = bool(config['model_params'].get('tri_volume', False))     # --tri-volume; not a key of the shipped configs either
+        if tri_volume and flip_test:
+            raise ValueError('tri_volume fuses the heat-map cubes of the cameras; the flip test\'s head works on an average of two '
+                             'cubes that is never formed in memory: --tri-volume does not go with --flip')
+        if tri_volume and len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
+            raise ValueError('tri_volume fuses at most {} cameras; cam_id_list has {}'.format(
+                ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
         self.cam_id_list = config['model_params']['cam_id_list']
@@ -129,11 +148,23 @@ class Eval:
         self.refine_px, self.refine_gain, self.refine_batches = 0.0, 0.0, 0    # lm and skeleton, summed over the batches
         self.tri_sym = float(config['model_params'].get('tri_sym', ops_eval.TRI_SYM_W))    # skeleton only: --tri-sym, px^2 per mm^2
         self.sym_mm = np.zeros(2)                  # skeleton only: mean |limb a| - |limb b| in mm before and after, summed
+        self.tri_volume = tri_volume               # --tri-volume: the cameras' heat-map cubes fused round the triangulated point
+        mp = config['model_params']
+        self.vol_side = float(mp.get('tri_vol_side', ops_eval.TRI_VOL_SIDE_MM))
+        self.vol_grid, self.vol_levels = int(mp.get('tri_vol_grid', ops_eval.TRI_VOL_G)), int(mp.get('tri_vol_levels', ops_eval.TRI_VOL_LEVELS))
+        self.logits = None                         # volume only: the logits [B,K*D,D,D] of the latest detect()
+        self.vol_move, self.vol_sigma, self.vol_status, self.vol_batches = 0.0, 0.0, np.zeros(4), 0   # volume only, summed
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
         the average of each heat-map and the mirrored, left/right-swapped heat-map of the mirrored image).  With
-        tri_weight='spread' through forward_spread, which also leaves that heat-map's spread in self.spread."""
+        tri_weight='spread' through forward_spread, which also leaves that heat-map's spread in self.spread.  With tri_volume
+        through forward_logits, which leaves the logits in self.logits (never with flip_test)."""
+        if self.tri_volume:
+            kps, _, self.logits = self.detector.forward_logits(img)
+            if self.tri_weight == 'spread':
+                self.spread = ops_head.detector_spread(self.detector, self.logits, None)
+            return kps
         if self.tri_weight == 'spread':
             pairs = self.config['model_params']['flip_pairs'] if self.flip_test else None
             kps, _, self.spread = self.detector.forward_spread(img, pairs)
@@ -160,11 +191,14 @@ class Eval:
         cams = ['cam_{}'.format(c) for c in self.cam_id_list]
         sel, out, trans = {}, {}, None
         weights = {} if self.tri_weight == 'spread' else None
+        cubes, chan = ({}, []) if self.tri_volume else (None, None)
 
         def detect(m):                             # one camera's joints; spread: also its weights, which need the detector
-            kps = self.detect(x[m + '_img']) if kps_by_cam is None or weights is not None else None
+            kps = self.detect(x[m + '_img']) if kps_by_cam is None or weights is not None or cubes is not None else None
             if weights is not None:
                 weights[m] = spread_weight(self.spread, x[m + '_trans_image'])
+            if cubes is not None:
+                cubes[m] = self.logits             # every camera's logits stay alive until the fusion
             return kps if kps_by_cam is None else kps_by_cam[m]
 
         if self.resolve == 'views':
@@ -182,6 +216,9 @@ class Eval:
             before = torch.where(r['named'].bool(), count(r['valid']) - count(r['swap']), count(r['swap']))   # naming undone
             out['resolve_exchanged'] = (before * paired).sum() / (paired.sum().clamp(min=1.0) * B * len(cams))
             out['resolve_hyp0'] = (r['hyp'] == 0).float().mean()
+            if chan is not None:                   # view v read joint k from perm[k] where bit v of swap is set
+                own = torch.arange(K, device=shifts.device, dtype=torch.int32)
+                chan = [torch.where(((r['swap'].int() >> v) & 1).bool(), perm, own) for v in range(len(cams))]
         for m in ([] if self.resolve == 'views' else cams):
             kps = detect(m)
             s = ops_eval.eval_select(kps, x[m + '_joints'], image_size=self.img_size, mode=mode)
@@ -189,6 +226,10 @@ class Eval:
             out['err2d_' + m] = s['err2d']
             t = s['swapped'].float()
             trans = t if trans is None else trans + t
+            if chan is not None:                   # the joint was taken from its partner's channel where eval_select exchanged
+                K = s['swapped'].shape[1]
+                perm = ops_eval.switch_perm(K, ops_eval.SWITCH_PAIRS, kps.device)
+                chan.append(torch.where(s['swapped'].squeeze(-1), perm, torch.arange(K, device=kps.device, dtype=torch.int32)))
         out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
         gt = convert_patch_to_world(x['cam_0_joints'], x, 'cam_0', is_norm=False)          # eval.py:170
         if self.tri_refine == 'lm':                # the same solver, then the pixel error minimised over the views it used
@@ -214,6 +255,15 @@ class Eval:
             out['tri_inlier_views'] = torch.where(used == 0, len(cams), bits.sum(dim=-1)).float().mean()
         if weights is not None:
             out['tri_sigma'] = torch.stack([1.0 / weights[m] for m in cams]).mean()
+        if self.tri_volume:                        # from whatever point the options above produced, over the views they used
+            views = None
+            if self.tri == 'robust':               # a zero mask is the fallback: the DLT ran over all views, and so does the fusion
+                views = torch.where(used == 0, torch.full_like(used, (1 << len(cams)) - 1), used)
+            tri, r = triangulation_volume(tri, cubes, x, self.cam_id_list, torch.stack(chan, dim=0).contiguous(), views=views,
+                                          G=self.vol_grid, levels=self.vol_levels, side_mm=self.vol_side, want=('cov', 'status'))
+            out['tri_vol_move_mm'] = (tri - r['init']).norm(dim=-1).nanmean()
+            out['tri_vol_sigma_mm'] = (r['cov'][..., 0] + r['cov'][..., 3] + r['cov'][..., 5]).sqrt().nanmean()   # passed through: NaN
+            out['tri_vol_status'] = torch.stack([(r['status'] == c).float().mean() for c in range(4)])
         preds = {'tri': tri}
         for m in cams:
             preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
@@ -254,6 +304,11 @@ class Eval:
                 self.refine_batches += 1
             if 'tri_sym_mm' in host:
                 self.sym_mm += host['tri_sym_mm']
+            if 'tri_vol_status' in host:
+                self.vol_move += float(host['tri_vol_move_mm'])
+                self.vol_sigma += float(host['tri_vol_sigma_mm'])
+                self.vol_status += host['tri_vol_status']
+                self.vol_batches += 1
             if 'resolve_hyp0' in host:
                 self.res_exchanged += float(host['resolve_exchanged'])
                 self.res_hyp0 += float(host['resolve_hyp0'])
@@ -316,6 +371,12 @@ class Eval:
             n = max(self.refine_batches, 1)
             lines.append('TRI refine skeleton (huber {}, sym {}): reprojection RMS {} px, gained {} px, limb asymmetry {} -> {} mm'.format(
                 self.tri_huber, self.tri_sym, self.refine_px / n, self.refine_gain / n, self.sym_mm[0] / n, self.sym_mm[1] / n))
+        if self.tri_volume:                        # after everything else; without --tri-volume the file is as it was
+            n = max(self.vol_batches, 1)
+            lines.append('TRI volume (side {} mm, grid {}, levels {}): moved {} mm, sigma {} mm'.format(
+                self.vol_side, self.vol_grid, self.vol_levels, self.vol_move / n, self.vol_sigma / n))
+            lines.append('TRI volume status: fused {} , passed through {} , mode on a face {} , logits not finite {}'.format(
+                *(self.vol_status / n)))
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -411,11 +472,22 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
                        help='--tri-skeleton: weight of the squared length difference of a left/right limb pair, in px^2 '
                             'per mm^2 (sigma^2 per mm^2 with --tri-weight spread)')),
 )
+CLI_VOLUME = (  # --tri-volume and its grid, parsed after CLI (a table of their own: CLI's last entries are pinned by older tests)
+    ('--tri-volume', dict(default=False, action='store_true', dest='tri_volume',
+                          help="after everything above: fuse the cameras' heat-map cubes over a voxel grid round the triangulated "
+                               'point and take the soft-argmax of the fused volume in world space (not with --flip)')),
+    ('--tri-vol-side', dict(default=ops_eval.TRI_VOL_SIDE_MM, type=float, metavar='MM', dest='tri_vol_side',
+                            help='--tri-volume: side of the first grid in mm (untuned default)')),
+    ('--tri-vol-grid', dict(default=ops_eval.TRI_VOL_G, type=int, metavar='G', dest='tri_vol_grid',
+                            help='--tri-volume: voxels per side of every grid, 2..32 (untuned default)')),
+    ('--tri-vol-levels', dict(default=ops_eval.TRI_VOL_LEVELS, type=int, metavar='N', dest='tri_vol_levels',
+                              help='--tri-volume: grids, each half the side of the one before round its result, 1..4')),
+)
 
 
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI:
+    for flag, kw in CLI + CLI_VOLUME:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -425,6 +497,10 @@ def main():
     config['model_params']['tri_refine'] = 'skeleton' if opt.tri_skeleton else opt.tri_refine
     config['model_params']['tri_huber'] = opt.tri_huber
     config['model_params']['tri_sym'] = opt.tri_sym
+    config['model_params']['tri_volume'] = opt.tri_volume
+    config['model_params']['tri_vol_side'] = opt.tri_vol_side
+    config['model_params']['tri_vol_grid'] = opt.tri_vol_grid
+    config['model_params']['tri_vol_levels'] = opt.tri_vol_levels
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

@@ -23,6 +23,15 @@ class KPDetector3D(nn.Module):
         kps, depth_prob_map = ops_head.softargmax_single(self.net(x), self.num_kp)
         return kps, depth_prob_map          # kps [B, 1, num_kp, 3], aligned with the multi-hypothesis layout
 
+    @torch.no_grad()
+    def forward_logits(self, x):
+        """forward plus the logits the head ran on, [B, K*D, D, D] in its NHWC storage: see KPDetector3DMulti.forward_logits.
+        -> (kps, depth_prob_map, heatmap)."""
+        ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3D')
+        heatmap = self.net(x)
+        kps, depth_prob_map = ops_head.softargmax_single(heatmap, self.num_kp)
+        return kps, depth_prob_map, ops_head._nhwc_storage(heatmap)
+
     def forward_flip(self, x, flip_pairs):
         """Flip test (eval() only, no autograd): see KPDetector3DMulti.forward_flip.  -> what forward returns."""
         x2, perm = ops_head.detector_flip_input(self, x, flip_pairs, 'KPDetector3D')

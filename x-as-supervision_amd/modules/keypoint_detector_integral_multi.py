@@ -38,6 +38,16 @@ class KPDetector3DMulti(nn.Module):
         self.last_peak_indices = idx
         return kps, depth_prob_map
 
+    @torch.no_grad()
+    def forward_logits(self, x):
+        """forward plus the logits the head ran on: -> (kps, depth_prob_map, heatmap [B, K*D, D, D] in the head's NHWC
+        storage), for ops_eval.triangulate_volume.  The caller keeps the 604 MB (B = 32) alive.  For eval(): records no graph."""
+        ops_head.check_patch_size(x, self.depth_dim, 'KPDetector3DMulti')
+        heatmap = self.net(x)
+        kps, depth_prob_map, idx = ops_head.softargmax_multi(heatmap, self.num_kp, self.num_hypo, self.neighbor_size)
+        self.last_peak_indices = idx
+        return kps, depth_prob_map, ops_head._nhwc_storage(heatmap)
+
     def forward_flip(self, x, flip_pairs):
         """Flip test (eval() only, no autograd): x and its horizontal mirrors go through the network as ONE batch of 2B
         images - batch norm uses running statistics, so the mirrors change nothing for the originals - and the head runs on

@@ -163,6 +163,28 @@ def triangulation_skeleton(keypoints, params, cam_id_list, weights=None, is_norm
     return out['xyzw'][..., :3], out
 
 
+def triangulation_volume(sel_or_init, logits, params, cam_id_list, chan=None, views=None, RECT_WIDTH=2000,
+                         G=ops_eval.TRI_VOL_G, levels=ops_eval.TRI_VOL_LEVELS, side_mm=ops_eval.TRI_VOL_SIDE_MM, beta=1.0,
+                         out_penalty=1.0, want=()):
+    """Volumetric fusion of the cameras' heat-map cubes round a triangulated point (ops_eval.triangulate_volume).
+    `sel_or_init`: the start, world joints [B,K,3] (or [B,K,4]) from any triangulation or refinement, or {cam_key: [B,K,3]}
+    patch predictions, which are triangulated by the DLT first.  `logits`: {cam_key: [B,K*D,D,D]} of the detector's
+    forward_logits; `chan` [V,B,K] int32 (V in cam_id_list's order) the heat-map channel every camera reads for every joint,
+    None = the joint's own; `views` [B,K] uint8 (bit i = cam_id_list[i]) the cameras that take part, None = all.
+    -> (world joints [B,K,3], dict of ops_eval.triangulate_volume: xyz and the outputs in `want`, + `init`).  No reference
+    counterpart."""
+    modes = ['cam_{}'.format(c) for c in cam_id_list]
+    init = triangulation(sel_or_init, params, cam_id_list, RECT_WIDTH=RECT_WIDTH) if isinstance(sel_or_init, dict) else sel_or_init
+    init = init[..., :3].contiguous()
+    stack = lambda name: torch.stack([params['{}_{}'.format(m, name)].float() for m in modes], dim=0)
+    out = ops_eval.triangulate_volume([logits[m] for m in modes], chan, stack('trans_image'), stack('k_mat'), stack('pelvis'),
+                                      stack('rot_world'), stack('trans_world'), init, views=views, G=G, levels=levels,
+                                      side_mm=side_mm, beta=beta, out_penalty=out_penalty,
+                                      image_size=params['{}_img'.format(modes[0])].shape[-1], rect_width=RECT_WIDTH, want=want)
+    out['init'] = init
+    return out['xyz'], out
+
+
 def resolve_views(kps_by_cam, params, cam_id_list, pairs, gt=True, RECT_WIDTH=2000):
     """{cam_key: [B,Hy,K,3]} raw detections of all cameras -> ({cam_key: [B,K,3]} resolved joints, the other outputs of
     ops_eval.multiview_resolve).  The left/right exchange of every view and the depth hypothesis of every view and joint are

@@ -165,6 +165,7 @@ SIGNATURES = {
     'xas_multiview_resolve': ('ppppppiiiifpppppp', 'i'),
     'xas_triangulate_refine': ('ppppiiiifippppp', 'i'),
     'xas_triangulate_skeleton': ('ppppp' 'iiiii' 'ffi' 'pppppp', 'i'),
+    'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),
     'xas_multiview_consistency_fwd': ('pppppiiiiffipppppp', 'i'),
     'xas_multiview_consistency_bwd': ('pppppppiiiiffippp', 'i'),
     'xas_pose_metrics': ('pppiififppppp', 'i'),

@@ -198,6 +198,70 @@ def triangulate_skeleton(points, pmat, init, views=None, limbs=SYM_LIMBS, weight
     return out
 
 
+# Defaults of the volumetric fusion.  A starting point read off the cell size, NOT a tuned choice: at the shipped rig one
+# heat-map cell is about 31 mm (2000 mm over 64 cells), so 800 mm over 16 voxels gives 50 mm voxels at the first level and 25 mm
+# at the second.  No accuracy figure stands behind any of the three.
+TRI_VOL_G = 16
+TRI_VOL_LEVELS = 2
+TRI_VOL_SIDE_MM = 800.0
+
+
+def triangulate_volume(logits_by_view, chan, trans_image, k_mat, pelvis, rot_world, trans_world, init, views=None, weight=None,
+                       G=TRI_VOL_G, levels=TRI_VOL_LEVELS, side_mm=TRI_VOL_SIDE_MM, beta=1.0, out_penalty=1.0, image_size=256.0,
+                       rect_width=2000.0, want=()):
+    """Volumetric fusion of the views' heat-map cubes round a triangulated point (xas_triangulate_volume): the product of the
+    views' distributions over a G^3 voxel grid of side side_mm round `init`, refined `levels` times at half the side, and its
+    soft-argmax in world mm.  logits_by_view: V tensors [B, K*D, D, D] with NHWC storage (a detector's forward_logits), which
+    stay where they are: only their addresses are passed.  chan [V,B,K] int32 or None: the heat-map channel view v reads for
+    joint k.  trans_image [V,B,2,3], k_mat [V,B,3,3], pelvis [V,B,3], rot_world [V,B,3,3], trans_world [V,B,3]; init [B,K,3]
+    (or [B,K,4]: the first three); views [B,K] uint8 (bit v = view v takes part; None = all); weight [V,B,K] or None = 1.
+    -> dict: xyz [B,K,3] always; cov [B,K,6] (mm^2: xx xy xz yy yz zz) and status [B,K] uint8 (0 fused, 1 passed through, 2
+    fused with the mode on a face of the grid, 3 a logit that is not finite: passed through) as requested."""
+    from .ops_head import _nhwc_storage
+    V = len(logits_by_view)
+    if not 1 <= V <= TRI_MAX_VIEWS:
+        raise RuntimeError('triangulate_volume: V=%d views (needs 1 <= V <= XAS_TRI_MAX_VIEWS = %d)' % (V, TRI_MAX_VIEWS))
+    init = _f32(init[..., :3])
+    B, K, _ = init.shape
+    cubes = []
+    for v, t in enumerate(logits_by_view):
+        if t.dim() != 4 or t.dtype != torch.float32 or t.shape[0] != B or t.shape[1] % K or not (t.shape[1] // K == t.shape[2] == t.shape[3]):
+            raise RuntimeError('triangulate_volume: logits of view %d are %s %s, not float32 [B=%d, K*D, D, D] with K=%d' % (
+                v, tuple(t.shape), t.dtype, B, K))
+        cubes.append(_nhwc_storage(t.detach()))
+    D = cubes[0].shape[2]
+    if any(t.shape != cubes[0].shape for t in cubes):
+        raise RuntimeError('triangulate_volume: the views\' logits differ in shape: %s' % ([tuple(t.shape) for t in cubes],))
+    cams = [_f32(t) for t in (trans_image, k_mat, pelvis, rot_world, trans_world)]
+    for t, tail, name in zip(cams, ((2, 3), (3, 3), (3,), (3, 3), (3,)), ('trans_image', 'k_mat', 'pelvis', 'rot_world', 'trans_world')):
+        if t.shape != (V, B) + tail:
+            raise RuntimeError('triangulate_volume: %s %s is not [V=%d, B=%d, %s]' % (name, tuple(t.shape), V, B, ', '.join(map(str, tail))))
+    if chan is not None:
+        if chan.shape != (V, B, K) or chan.dtype != torch.int32:
+            raise RuntimeError('triangulate_volume: chan %s %s is not the [V,B,K] int32 channel table' % (tuple(chan.shape), chan.dtype))
+        chan = chan.contiguous()
+    if views is not None:
+        if views.shape != (B, K) or views.dtype != torch.uint8:
+            raise RuntimeError('triangulate_volume: views %s %s are not the [B,K] uint8 masks of init %s' % (
+                tuple(views.shape), views.dtype, tuple(init.shape)))
+        views = views.contiguous()
+    if weight is not None:
+        weight = _f32(weight)
+        if weight.shape != (V, B, K):
+            raise RuntimeError('triangulate_volume: weight %s is not [V,B,K]' % (tuple(weight.shape),))
+    dev = init.device
+    out = {'xyz': torch.empty(B, K, 3, device=dev)}
+    if 'cov' in want:
+        out['cov'] = torch.empty(B, K, 6, device=dev)
+    if 'status' in want:
+        out['status'] = torch.empty(B, K, device=dev, dtype=torch.uint8)
+    table = (ctypes.c_void_p * V)(*[ptr(t) for t in cubes])           # read by the host before the launch
+    call('xas_triangulate_volume', table, ptr(chan), *[ptr(t) for t in cams], ptr(init), ptr(views), ptr(weight), B, V, K, D, int(G),
+         int(levels), float(side_mm), float(beta), float(out_penalty), float(image_size), float(rect_width), ptr(out['xyz']),
+         ptr(out.get('cov')), ptr(out.get('status')))
+    return out
+
+
 def multiview_resolve(points, pmat, kps, world, pairs=SWITCH_PAIRS, gt=None, image_size=256.0,
                       want=('xyzw', 'swap', 'hyp', 'named')):
     """Left/right exchange and depth hypothesis of every view from the agreement of the views (xas_multiview_resolve).
