@@ -921,6 +921,38 @@ int xas_multiview_consistency_bwd(const float* kps_xy, const float* trans_image,
                                   int K, float image_size, float huber_px, int flags, float* grad_kps_xy,
                                   float* grad_world, void* stream);
 
+/* Z-buffered triangle rasteriser: the last stage of the online pseudo-image path (train.py --pseudo-online; the reference
+ * reads pre-rendered PNGs and has no renderer).  Forward only, no atomics, a pure function of its inputs bit for bit.
+ * Inputs, contiguous: verts [B][Nv][3] fp32 = (x px, y px of the patch with pixel centres at the integers 0 .. S - 1, depth in
+ * any unit, smaller = nearer); faces [F][3] int32 vertex indices shared by the batch; face_rgb [F][3] fp32 or NULL = white;
+ * light [3] fp32 on the DEVICE, the direction towards the light in (x, y, depth * depth_scale) space, or NULL = (0, 0, -1).
+ * SKIPPED faces (never read out of bounds, hit nothing): an index outside [0, Nv), a vertex coordinate that is not finite,
+ * area == 0 (below).  No back-face culling, no near plane (the caller marks vertices behind the camera NaN), no clipping but
+ * by the pixel grid, no antialiasing, no top-left rule: a pixel on a shared edge belongs to both faces and the depth decides.
+ * Everything below is in double precision from the fp32 numbers, each operation rounded on its own (no fused multiply-add),
+ * in the order written; tests/_render_oracle.py restates it.  For a face (a, b, c) and a pixel centre p:
+ *   E(q, s, t) = (s.x - q.x) (t.y - q.y) - (s.y - q.y) (t.x - q.x);   area = E(a, b, c);
+ *   w0 = E(b, c, p), w1 = E(c, a, p), w2 = E(a, b, p);
+ *   COVERED: p lies in the closed box of the three vertices, and w0, w1, w2 are all >= 0 if area > 0, all <= 0 if area < 0;
+ *   depth z = ((w0 a.z + w1 b.z) + w2 c.z) / area    (affine in the patch, not perspective-correct).
+ * The covering face of the smallest z keeps the pixel (comparison `z < best`: a z that is NaN or +inf never wins); of equal z
+ * the smallest face index.  Colour, flat per face: with e1 = b - a, e2 = c - a in (x, y, depth * depth_scale), n = e1 x e2
+ * negated if n.z > 0, |n| = sqrt((n.x^2 + n.y^2) + n.z^2), l = light / |light|, d = ((n.x / |n|) l.x + (n.y / |n|) l.y) +
+ * (n.z / |n|) l.z:   rgb = fp32(face_rgb * (ambient + (1 - ambient) * (d > 0 ? d : 0))), rounded once.
+ * ambient = 1: pure face colours; ambient < 1 on white faces: an untextured shaded body.
+ * Outputs, every element written by every call: img [B][3][S][S] (background where nothing was hit), mask [B][1][S][S]
+ * (1 / 0); zbuf [B][S][S] = fp32(z), +inf where nothing was hit, or NULL; face_id [B][S][S] int32, -1 where nothing was hit,
+ * or NULL.  workspace: xas_mesh_render_workspace_bytes(B, F, S) bytes, 16-byte aligned (per face and sample 8 bytes of pixel
+ * box and a 64-byte record); may be NULL when B * F == 0.
+ * Two launches: one thread per (sample, face) writes box and record; one workgroup of 256 threads per (sample, 16 x 16 tile)
+ * reads the boxes 256 at a time, compacts the records whose box meets the tile into LDS in face order and lets every thread
+ * resolve its pixel against them before the next 256: no capacity to overflow.  F == 0 writes the background, B == 0
+ * nothing.  1 <= S <= 4096, B <= 65535, B*F < 2^31; status 1 and xas_last_error() on any other shape or a null required buffer. */
+size_t xas_mesh_render_workspace_bytes(int B, int F, int S);
+int xas_mesh_render(const float* verts, const int* faces, const float* face_rgb, const float* light, float ambient,
+                    float depth_scale, float background, int B, int Nv, int F, int S, float* img, float* mask, float* zbuf,
+                    int* face_id, void* workspace, void* stream);
+
 /* Pose metrics, replaces metrics.py:5-244 (numpy, per-sample SVD on the host).
  * pred, gt [N][K][3]; both are divided by in_div on load (eval.py:52-53 passes mm / 1000 for PCK / AUC);
  * mask [N][K] (0/1) or NULL = all visible.  Outputs (each may be NULL):

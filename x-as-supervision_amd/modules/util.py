@@ -276,6 +276,58 @@ def project_smpl_to_patch_kps(global_rot_params, pose_params, shape_params,
                                    pelvis_origin=True)
 
 
+def normalise_patch_joints(kps, size, RECT_WIDTH=2000):
+    """Patch pixels [B,K,3] (project_smpl_to_patch_kps) -> the form the step expects of `<cam>_pseudo_joints`: x, y in [-1, 1]
+    over the pixel centres 0 .. size - 1, z in units of RECT_WIDTH (depth px * (RECT_WIDTH / size) mm / RECT_WIDTH = px / size:
+    what the reference's loader makes of a depth in metres, dataloader.py:227)."""
+    xy = kps[..., :2] / (size - 1.0) * 2.0 - 1.0
+    return torch.cat([xy, kps[..., 2:3] / float(size)], dim=-1)
+
+
+RENDER_LOOKS = ('shade', 'parts')     # untextured shaded body (smpl_pseudo_img) / pure body-part colours (smpl_part_seg_img)
+RENDER_AMBIENT = 0.35                 # untuned: no rendering of the authors' to match
+
+
+def render_smpl_to_patch(global_rot_params, pose_params, shape_params, smpl_layer, h36m_regressor, x, mode, look='shade',
+                         size=256):
+    """SMPL parameters -> a rendering of the body in the patch of camera `mode` and its joints:
+    (img [B,3,S,S] in [0,1], mask [B,1,S,S], joints [B,18,3] normalised by normalise_patch_joints).  No reference counterpart
+    (its pseudo-images are read from disk); no graph is kept.
+    The SMPL layer runs once.  The joints are project_smpl_to_patch_kps's, launch for launch; the vertices take its
+    convert_verts path to world mm and one more world->patch launch to patch pixels (x, y) and depth relative to the pelvis in
+    the patch's depth unit (RECT_WIDTH / size mm, about what a pixel spans at the pelvis), so depth_scale = 1 makes the three
+    axes of the shading normal commensurate.  Vertices at or behind the camera plane become NaN: the renderer drops their faces.
+    `look`: 'shade' = white faces, ambient RENDER_AMBIENT, lit from the viewer; 'parts' = ops_render.part_colours, ambient 1."""
+    from xas_amd import ops_render
+    if look not in RENDER_LOOKS:
+        raise ValueError('render_smpl_to_patch: look=%r (known: %s)' % (look, ', '.join(RENDER_LOOKS)))
+    faces = smpl_layer.th_faces
+    if faces.numel() == 0:
+        raise RuntimeError('render_smpl_to_patch: the SMPL layer has no faces (th_faces is empty)')
+    S_img = x['{}_img'.format(mode)].shape[-1]
+    with torch.no_grad():
+        full_pose = torch.cat([pose_params.new_zeros(pose_params.shape[0], 3), pose_params], dim=1)
+        verts, _ = smpl_layer(full_pose, shape_params)
+        if verts.shape[0] * verts.shape[1] > 0x7fffffff // 3:            # xas_world_to_patch_fwd: one thread per point, any K
+            raise RuntimeError('render_smpl_to_patch: %d x %d vertices exceed one world->patch launch' % tuple(verts.shape[:2]))
+        joints = ops_head.world_to_patch(smpl_to_h36m(verts, h36m_regressor), x, mode, is_norm=False,
+                                         pre_rot=global_rot_params, pre_scale=1000.0, pelvis_origin=True)
+        world = ops_head.world_to_patch(verts, x, mode, pre_rot=global_rot_params, pre_scale=1000.0, pelvis_origin=True,
+                                        stop_at_world=True)
+        pix = ops_head.world_to_patch(world, x, mode, is_norm=False)
+        unit = 2000.0 / S_img                                            # mm per depth unit (world_to_patch's RECT_WIDTH)
+        cam_z = pix[..., 2] * unit + x['{}_pelvis'.format(mode)][:, 2:3].float()
+        pix = torch.where((cam_z > 0).unsqueeze(-1), pix, pix.new_full((), float('nan')))
+        if size != S_img:                                                # pixel centres 0 .. S_img - 1 onto 0 .. size - 1
+            pix = pix * pix.new_tensor([(size - 1.0) / (S_img - 1.0), (size - 1.0) / (S_img - 1.0), float(size) / S_img])
+        if look == 'parts':
+            rgb, ambient = ops_render.part_colours(smpl_layer.th_weights, faces), 1.0
+        else:
+            rgb, ambient = None, RENDER_AMBIENT
+        r = ops_render.render_mesh(pix, faces, face_rgb=rgb, ambient=ambient, depth_scale=1.0, size=size)
+    return r['img'], r['mask'], normalise_patch_joints(joints, S_img)
+
+
 def random_rotation_3D(keypoints):
     """Random rotation about z in [-pi/4, pi/4] per sample (util.py:389-407; only with use_aug).  The angles are drawn
     from the CPU generator exactly as the reference does (torch.rand(B, 1)): same seed, same augmentation."""

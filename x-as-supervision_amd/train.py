@@ -4,6 +4,7 @@
     torchrun --nproc-per-node=N train.py --config config/HM36_Multi_SurS1.yaml [--checkpoint ... --finetune]
              [--batch_size B --epoch E --worker W --seed S --extra_tag T --log_dir D] [--synthetic STEPS]
              [--mv-2d W --mv-3d W --mv-huber PX --mv-detach]
+             [--pseudo-online BANK.npz --pseudo-look shade|parts --smpl-model ROOT]
 
 Differences from the reference, all outside the hot step: the two DistributedDataParallel wrappers are
 replaced by xas_amd.engine.TrainStep (flat gradient arenas + bucketed RCCL all-reduce on a side stream);
@@ -46,7 +47,8 @@ class Trainer:
     """Same constructor arguments as the reference Trainer (train.py:47-59)."""
 
     def __init__(self, config, unsup_model, unsup_disc, train_data, optimizer_detector, save_dir,
-                 checkpoint_path=None, optimizer_discriminator=None, mode='train'):
+                 checkpoint_path=None, optimizer_discriminator=None, mode='train', pseudo=None):
+        self.pseudo = pseudo               # xas_amd.pseudo.PseudoSynth (--pseudo-online) or None: the batch's own pseudo samples
         self.gpu_id = int(os.environ['LOCAL_RANK'])
         self.unsup_model = unsup_model.to(self.gpu_id)
         self.unsup_disc = unsup_disc.to(self.gpu_id)
@@ -133,6 +135,8 @@ class Trainer:
                 self.train_data.sampler.set_epoch(epoch)
             for it, x in enumerate(self.train_data):
                 x = self.convert_data_to_device(x)
+                if self.pseudo is not None:                          # rendered pseudo samples in place of the batch's
+                    self.pseudo.fill(x, ['cam_{}'.format(c) for c in self.config['dataset_params']['cam_id_list']])
                 loss_disc, loss_kp, total, output = self.step(x)
                 if self.gpu_id == 0 and tb_logger is not None:      # train.py:192-199: every step, total = None on steps
                     cur = epoch * len(self.train_data) + it          # where only the discriminator was updated
@@ -221,6 +225,29 @@ CLI = (  # same flags as the reference entry (train.py:305-315) + --synthetic
 )
 
 
+CLI_PSEUDO = (  # online pseudo samples, parsed after CLI (a table of their own: CLI's entries are pinned by older tests)
+    ('--pseudo-online', dict(default=None, metavar='BANK.npz', dest='pseudo_online',
+                             help='render the pseudo images and joints of every batch on the device from this bank of SMPL '
+                                  'poses (`pose` [N,72], optional `betas` [N,10]) in place of the ones the batch brings')),
+    ('--pseudo-look', dict(default='shade', choices=['shade', 'parts'], dest='pseudo_look',
+                           help='--pseudo-online: shaded untextured body, or pure body-part colours')),
+    ('--smpl-model', dict(default=None, metavar='ROOT', dest='smpl_model',
+                          help='directory of the SMPL model files (replaces model_params.smpl_layer_params.model_path), or an '
+                               '.npz of exported arrays with `h36m_regressor` and the faces `f`')),
+)
+
+
+def pseudo_source(opt, config, model):
+    """The PseudoSynth of --pseudo-online on `model`'s SMPL layer, or None without the flag (nothing is imported then)."""
+    if opt.pseudo_online is None:
+        return None
+    from xas_amd.pseudo import PseudoSynth
+    di = config['dataset_params'].get('dataiter') or {}
+    seed = max(opt.seed, 0) + int(os.environ.get('RANK', '0'))           # every rank draws bodies of its own
+    return PseudoSynth(opt.pseudo_online, model.smpl_layer, model.h36m_regressor, look=opt.pseudo_look, seed=seed,
+                       mean=di.get('mean'), std=di.get('std'))
+
+
 def multiview_entry(opt):
     """loss_config's `multiview_loss` entry of --mv-2d / --mv-3d / --mv-huber / --mv-detach, or None if neither weight is given."""
     if opt.mv_2d is None and opt.mv_3d is None:
@@ -230,7 +257,7 @@ def multiview_entry(opt):
 
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI:
+    for flag, kw in CLI + CLI_PSEUDO:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -245,10 +272,17 @@ def main():
     setup_seed(opt.seed)
     rank_local, world = int(os.environ['LOCAL_RANK']), int(os.environ['WORLD_SIZE'])
     save_dir, tb_logger = create_logger(opt)
-    nets = engine.prepare_model(config)
+    smpl_arrays = None
+    if opt.smpl_model is not None and opt.smpl_model.endswith('.npz'):
+        from xas_amd.pseudo import load_smpl_arrays
+        smpl_arrays = load_smpl_arrays(opt.smpl_model)
+    elif opt.smpl_model is not None:
+        config['model_params'].setdefault('smpl_layer_params', {})['model_path'] = opt.smpl_model
+    nets = engine.prepare_model(config, smpl_arrays)
     loader = prepare_data(config, world, opt.worker, opt.synthetic, torch.device('cuda', rank_local), opt.seed)
     trainer = Trainer(config, nets[0], nets[1], loader, nets[2], save_dir, checkpoint_path=opt.checkpoint,
-                      optimizer_discriminator=nets[3], mode='finetune' if opt.finetune else 'train')
+                      optimizer_discriminator=nets[3], mode='finetune' if opt.finetune else 'train',
+                      pseudo=pseudo_source(opt, config, nets[0]))
     trainer.train(tb_logger)
     if tb_logger is not None:
         tb_logger.close()

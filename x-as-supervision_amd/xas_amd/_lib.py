@@ -168,6 +168,8 @@ SIGNATURES = {
     'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),
     'xas_multiview_consistency_fwd': ('pppppiiiiffipppppp', 'i'),
     'xas_multiview_consistency_bwd': ('pppppppiiiiffippp', 'i'),
+    'xas_mesh_render_workspace_bytes': ('iii', 'z'),
+    'xas_mesh_render': ('pppp' 'fff' 'iiii' 'pppp' 'pp', 'i'),
     'xas_pose_metrics': ('pppiififppppp', 'i'),
 }
 
