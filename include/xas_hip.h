@@ -630,6 +630,55 @@ int xas_smpl_lbs_bwd(const float* pose, const float* betas, const float* v_templ
                      int V, int center_idx, const float* fwd_workspace, const float* d_verts, const float* d_joints,
                      float* d_pose, float* d_betas, float* workspace, void* stream);
 
+/* SMPL parameters from the 18 H36M joints of a sample (eval.py --fit-smpl; the reference has no counterpart): the inverse of
+ * project_smpl_to_patch_kps' model.  The layer runs with a zero root rotation:
+ *   verts = xas_smpl_lbs_fwd((0, 0, 0, theta), beta)[center_idx];   j = smpl_to_h36m(verts, h36m_regressor), 18 joints, root
+ *   centred (17 regressed rows, arms exchanged, joint 17 = (j_11 + j_14) / 2, minus joint 0);   Y_k = R(omega) (1000 j_k) + t.
+ * The 23 body rotations are the layer's rodrigues (unit quaternion of angle |a + 1e-8|); R(omega) is the plain exponential map
+ * I + sin(th) K + (1 - cos(th)) K^2, K the cross matrix of omega / th, th = |omega| (xas_amd.pseudo._rodrigues: pose[:, :3] =
+ * omega is what PseudoSynth reads); for th^2 < 1e-16 its series I + K(omega) + K(omega)^2 / 2, so the derivative exists at 0.
+ * UNKNOWNS x [85]: omega 3, t 3 (mm), theta 69, beta 10.  Inputs are fp32; everything after the loads is double.
+ * RESIDUALS r [133], in this order: 54 joint rows sqrt(w_k) (Y_k - target_k) in mm, row 3 k + c; 69 rows sqrt(pose_prior)
+ * theta_i; 10 rows sqrt(shape_prior) beta_i.  A joint is USED if w_k > 0 (NaN and negative weights count as 0); a joint not
+ * used has r = 0 and a zero row of J exactly, and its target is never read into arithmetic.  COST C = sum of r_i^2, i ascending.
+ * targets [B][18][3] world mm, joint_w [B][18], pose_prior, shape_prior >= 0 finite.  parents [24] int32 on the device (an entry
+ * that is not in [0, i) makes joint i a root).  center_idx: the layer's, -1 = none.
+ * h36m_regressor [17][V] dense.  reg_verts [V] int32 + reg_count (one int32), both on the device: the vertices that have a
+ * non-zero column come first in reg_verts and reg_count says how many; only those are visited, an index outside [0, V) is
+ * skipped.  Both NULL = every vertex.  The result does not depend on the list as long as it holds every non-zero column.
+ * xas_smpl_fit_linearise: r [B][133] and J = d r / d x [B][133][85] (double) at the given parameters, the exact derivative
+ * (forward mode through the Rodrigues formula, the pose blend shapes, the betas' effect on the rest joints, the chain and the
+ * skinning).
+ * xas_smpl_fit: Levenberg-Marquardt from the given parameters.  H = J^T J, g = J^T r.  A TRIAL is x + d with
+ * (H + lambda diag(H)) d = -g by Cholesky, lambda = 1e-3 at the start.  A trial is ACCEPTED if its cost is finite and strictly
+ * lower: x moves, lambda *= 0.1, and the fit has CONVERGED if the largest |d_i| of that step is under XAS_SMPLFIT_STEP_TOL
+ * (radians, mm and betas alike); otherwise, and at a pivot that is not positive, lambda *= 10.  The loop ends when converged,
+ * after max_iters trials (0 <= max_iters <= XAS_SMPLFIT_MAX_ITERS) or when lambda > 1e12.  So cost[1] <= cost[0], always.
+ * PASSED THROUGH: fewer than 6 joints used, or the cost at the given parameters is not finite.
+ * Outputs, every element written by every call (double unless noted): pose [B][72] = (omega, theta), betas [B][10], trans
+ * [B][3], joints [B][18][3] = Y at the result, cost [B][2] = C at the start and at the result, iters [B] int32 = trials made,
+ * status [B] bytes: 0 converged, 1 ran out of trials or lambda, 2 passed through (parameters = the inputs exactly, joints = Y
+ * there, cost[1] = cost[0], iters = 0).
+ * workspace: xas_smpl_fit_workspace_bytes(B, V) bytes, 16-byte aligned.  V >= 1 any size; B == 0 writes nothing.
+ * One workgroup of 256 threads per sample and the whole LM in one launch (plus one launch that forms j_regressor . v_template
+ * and j_regressor . shapedirs); no atomics, no host synchronisation: a pure function of the inputs bit for bit, per sample. */
+#define XAS_SMPLFIT_UNKNOWNS 85
+#define XAS_SMPLFIT_RESIDUALS 133
+#define XAS_SMPLFIT_MAX_ITERS 200
+#define XAS_SMPLFIT_STEP_TOL 1e-7
+size_t xas_smpl_fit_workspace_bytes(int B, int V);
+int xas_smpl_fit_linearise(const float* pose, const float* betas, const float* trans, const float* v_template,
+                           const float* shapedirs, const float* posedirs, const float* j_regressor, const float* weights,
+                           const int* parents, const float* h36m_regressor, const int* reg_verts, const int* reg_count,
+                           const float* targets, const float* joint_w, float pose_prior, float shape_prior, int B, int V,
+                           int center_idx, double* r, double* J, void* workspace, void* stream);
+int xas_smpl_fit(const float* pose, const float* betas, const float* trans, const float* v_template, const float* shapedirs,
+                 const float* posedirs, const float* j_regressor, const float* weights, const int* parents,
+                 const float* h36m_regressor, const int* reg_verts, const int* reg_count, const float* targets,
+                 const float* joint_w, float pose_prior, float shape_prior, int B, int V, int center_idx, int max_iters,
+                 double* pose_out, double* betas_out, double* trans_out, double* joints_out, double* cost, int* iters,
+                 unsigned char* status, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Fused multi-tensor Adam (train.py:257-264: betas (0.5, 0.999), eps 1e-8, no decay).
  * One launch updates a flat parameter arena: p, g, m, v are arenas of n floats.

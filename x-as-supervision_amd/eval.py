@@ -6,6 +6,7 @@
              [--tri dlt|robust --tri_thresh PX] [--resolve gt|views] [--tri-weight depth|spread]
              [--tri-refine none|lm --tri-huber PX] [--tri-skeleton --tri-sym W]
              [--tri-volume --tri-vol-side MM --tri-vol-grid G --tri-vol-levels N]
+             [--fit-smpl OUT.npz --smpl-model ROOT|.npz --fit-iters N --fit-pose-prior W --fit-shape-prior W]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -49,6 +50,14 @@ the triangulation used (--tri robust: its inliers), each reading the heat-map ch
 assigned to the joint.  The detector's logits of all cameras stay alive until then: V x 604 MB at B = 32, D = 64, K = 18.
 Not with --flip.  Unknown: its effect on MPJPE (no checkpoint or dataset here), and the right grid: the defaults are read off
 the cell size (31 mm), not tuned.
+
+--fit-smpl OUT.npz (opt-in; model_params.fit_smpl) runs after everything else, on the final world joints (the triangulated
+ones with several cameras, the selected hypothesis with one): SMPL parameters per sample by a double-precision
+Levenberg-Marquardt on the device (xas_amd.ops_smplfit.fit_smpl, one launch per batch).  A joint that is not finite or that a
+solver above passed through counts 0; with a covariance (--tri-volume, or --tri-refine lm with --tri-weight spread) a joint
+counts 1 / trace(cov), normalised to mean 1 per sample.  OUT.npz (`pose` [N,72], `betas`, `trans`, `cost`, `status`,
+`joint_rms_mm`) is a bank that train.py --pseudo-online reads as it is; eval_result.txt gains one last line.  Unknown: how good
+the fits are on real detections (no checkpoint or dataset here), and the prior weights, which are untuned guesses.
 """
 import copy
 import os
@@ -154,6 +163,56 @@ class Eval:
         self.vol_grid, self.vol_levels = int(mp.get('tri_vol_grid', ops_eval.TRI_VOL_G)), int(mp.get('tri_vol_levels', ops_eval.TRI_VOL_LEVELS))
         self.logits = None                         # volume only: the logits [B,K*D,D,D] of the latest detect()
         self.vol_move, self.vol_sigma, self.vol_status, self.vol_batches = 0.0, 0.0, np.zeros(4), 0   # volume only, summed
+        self.fit_smpl = mp.get('fit_smpl') or None     # --fit-smpl OUT.npz: SMPL parameters of the final world joints, a --pseudo-online bank
+        if self.fit_smpl:
+            smpl = prepare_smpl(mp)                  # (Eval's signature is pinned: the model comes through model_params.smpl_model)
+            if smpl[0] is None or smpl[1] is None:
+                raise ValueError('fit_smpl needs an SMPL layer and the H36M joint regressor (eval.py --smpl-model)')
+            from xas_amd import ops_smplfit          # only with the flag
+            self.smpl_layer, self.h36m_regressor = smpl[0].to(self.gpu_id), smpl[1].to(self.gpu_id)
+            self.fit_iters = int(mp.get('fit_iters', 30))
+            self.fit_pose_prior = float(mp.get('fit_pose_prior', ops_smplfit.POSE_PRIOR))      # untuned guesses, both
+            self.fit_shape_prior = float(mp.get('fit_shape_prior', ops_smplfit.SHAPE_PRIOR))
+            self.fit_rows = []                         # per batch: the host arrays of the file
+
+    def fit_batch(self, joints, bad, cov):
+        """--fit-smpl on the final world joints [B,18,3] of a batch.  A joint's weight is 0 where it is not finite or `bad`
+        [B,18] marks it (a triangulation that passed it through), else 1, or with `cov` [B,18,6] (xx xy xz yy yz zz, mm^2)
+        1 / trace(cov) normalised to mean 1 over the usable joints of the sample.  -> the file's rows, on the device."""
+        from xas_amd import ops_smplfit
+        ok = torch.isfinite(joints).all(dim=-1)
+        if bad is not None:
+            ok = ok & ~bad
+        w = ok.float()
+        if cov is not None:
+            tr = cov[..., 0] + cov[..., 3] + cov[..., 5]
+            ok = ok & torch.isfinite(tr) & (tr > 0)
+            inv = torch.where(ok, 1.0 / tr.clamp(min=1e-30), torch.zeros_like(tr))
+            w = inv / (inv.sum(dim=1, keepdim=True) / ok.float().sum(dim=1, keepdim=True).clamp(min=1.0)).clamp(min=1e-30)
+        r = ops_smplfit.fit_smpl(joints, w, self.smpl_layer, self.h36m_regressor, iters=self.fit_iters,
+                                 pose_prior=self.fit_pose_prior, shape_prior=self.fit_shape_prior)
+        d2 = ((r['joints'] - torch.where(ok.unsqueeze(-1), joints.double(), r['joints'])) ** 2).sum(dim=-1)
+        rms = (d2.sum(dim=1) / ok.double().sum(dim=1).clamp(min=1.0)).sqrt()
+        return {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
+                'fit_cost': r['cost'].float(), 'fit_status': r['status'], 'fit_joint_rms_mm': rms.float()}
+
+    def write_fit(self):
+        """Writes the --fit-smpl file (atomically: a temporary file beside it, then a rename); passed-through samples are kept
+        with their status.  -> the line of eval_result.txt."""
+        from xas_amd import ops_smplfit
+        shapes = {'pose': (0, 72), 'betas': (0, 10), 'trans': (0, 3), 'cost': (0, 2), 'status': (0,), 'joint_rms_mm': (0,)}
+        cols = {k: (np.concatenate([r[k] for r in self.fit_rows]) if self.fit_rows else np.zeros(sh, np.uint8 if k == 'status' else np.float32))
+                for k, sh in shapes.items()}
+        os.makedirs(os.path.dirname(os.path.abspath(self.fit_smpl)), exist_ok=True)
+        tmp = self.fit_smpl + '.tmp.npz'
+        np.savez(tmp, **cols)
+        os.replace(tmp, self.fit_smpl)
+        n = max(len(cols['status']), 1)
+        fitted = cols['status'] != ops_smplfit.STATUS_PASSED
+        rms = float(cols['joint_rms_mm'][fitted].mean()) if fitted.any() else float('nan')
+        share = ' , '.join('{} {}'.format(name, float((cols['status'] == c).sum()) / n) for c, name in enumerate(ops_smplfit.STATUS_NAMES))
+        return 'FIT smpl ({} trials, pose prior {}, shape prior {}): joint RMS {} mm; {}'.format(
+            self.fit_iters, self.fit_pose_prior, self.fit_shape_prior, rms, share)
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -232,19 +291,25 @@ class Eval:
                 chan.append(torch.where(s['swapped'].squeeze(-1), perm, torch.arange(K, device=kps.device, dtype=torch.int32)))
         out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
         gt = convert_patch_to_world(x['cam_0_joints'], x, 'cam_0', is_norm=False)          # eval.py:170
+        fit_bad = fit_cov = None                   # --fit-smpl only: joints a solver passed through, and a covariance if one came
+        fit_want = (('status',) + (('cov',) if weights is not None and self.tri_refine == 'lm' else ())) if self.fit_smpl else ()
         if self.tri_refine == 'lm':                # the same solver, then the pixel error minimised over the views it used
-            tri, r = triangulation_refined(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, want=('resid',),
+            tri, r = triangulation_refined(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, want=('resid',) + fit_want,
                                            robust_px=self.tri_thresh if self.tri == 'robust' else None)
             used = r.get('inliers')
             out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a joint passed through has no residual (NaN)
             out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
+            if self.fit_smpl:
+                fit_bad, fit_cov = r['status'] == 2, r.get('cov')
         elif self.tri_refine == 'skeleton':        # the same start and views, the joints of a sample refined together
             tri, r = triangulation_skeleton(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, sym_w=self.tri_sym,
-                                            want=('resid', 'sym'), robust_px=self.tri_thresh if self.tri == 'robust' else None)
+                                            want=('resid', 'sym') + fit_want, robust_px=self.tri_thresh if self.tri == 'robust' else None)
             used = r.get('inliers')
             out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a fixed joint has no residual (NaN)
             out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
             out['tri_sym_mm'] = r['sym'].abs().reshape(-1, 2).nanmean(dim=0)   # [2]: before, after; a pair switched off is NaN
+            if self.fit_smpl:
+                fit_bad = r['status'] == 2
         elif self.tri == 'robust':
             tri, used = triangulation_weighted(sel, x, self.cam_id_list, weights, robust_px=self.tri_thresh, return_inliers=True)
         else:
@@ -264,6 +329,8 @@ class Eval:
             out['tri_vol_move_mm'] = (tri - r['init']).norm(dim=-1).nanmean()
             out['tri_vol_sigma_mm'] = (r['cov'][..., 0] + r['cov'][..., 3] + r['cov'][..., 5]).sqrt().nanmean()   # passed through: NaN
             out['tri_vol_status'] = torch.stack([(r['status'] == c).float().mean() for c in range(4)])
+            if self.fit_smpl:                      # passed through (1, 3): the start came back and there is no covariance
+                fit_bad, fit_cov = (r['status'] == 1) | (r['status'] == 3), r['cov']
         preds = {'tri': tri}
         for m in cams:
             preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
@@ -276,6 +343,11 @@ class Eval:
                 out['pck_' + name] = q['pck'].mean()
                 out['auc_' + name] = (q['auc_hits'].sum(dim=0).float() / q['pck'].numel()).mean() * 100
         out['world_gt'], out['world_tri'] = gt, preds['tri']
+        if self.fit_smpl:                          # after everything else, on the final world joints
+            if len(cams) > 1:
+                out.update(self.fit_batch(preds['tri'][..., :3].contiguous(), fit_bad, fit_cov))
+            else:                                  # one camera: its selected hypothesis
+                out.update(self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None))
         return out
 
     def eval(self, tb_log, record_table, count_table, record_3d_table, count_3d_table, record_3d_tri_table,
@@ -309,6 +381,8 @@ class Eval:
                 self.vol_sigma += float(host['tri_vol_sigma_mm'])
                 self.vol_status += host['tri_vol_status']
                 self.vol_batches += 1
+            if 'fit_status' in host:
+                self.fit_rows.append({k[4:]: v for k, v in host.items() if k.startswith('fit_')})
             if 'resolve_hyp0' in host:
                 self.res_exchanged += float(host['resolve_exchanged'])
                 self.res_hyp0 += float(host['resolve_hyp0'])
@@ -377,6 +451,8 @@ class Eval:
                 self.vol_side, self.vol_grid, self.vol_levels, self.vol_move / n, self.vol_sigma / n))
             lines.append('TRI volume status: fused {} , passed through {} , mode on a face {} , logits not finite {}'.format(
                 *(self.vol_status / n)))
+        if self.fit_smpl:                          # after everything else; without --fit-smpl the file is as it was
+            lines.append(self.write_fit())
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -385,6 +461,21 @@ class Eval:
         print('Results saved in {}'.format(path))
         print('Ambiguity Ratio:{}'.format(ambiguity_ratio / len(self.eval_data) / len(self.cam_id_list)))
         return lines
+
+
+def prepare_smpl(mp):
+    """--fit-smpl: the SMPL layer and the H36M regressor, loaded the way train.py loads them (model_params.smpl_model, the
+    --smpl-model flag: a directory of the model files, or an .npz of exported arrays; None = smpl_layer_params.model_path)."""
+    from xas_amd.engine import _load_smpl
+    from xas_amd.pseudo import load_smpl_arrays
+    path, arrays = mp.get('smpl_model'), None
+    if path is not None and str(path).endswith('.npz'):
+        arrays = load_smpl_arrays(path)
+    elif path is not None:
+        mp.setdefault('smpl_layer_params', {})['model_path'] = path
+    elif not mp.get('smpl_layer_params', {}).get('model_path'):
+        return None, None
+    return _load_smpl(mp, arrays)
 
 
 def prepare_model(config, opt):
@@ -485,9 +576,32 @@ CLI_VOLUME = (  # --tri-volume and its grid, parsed after CLI (a table of their 
 )
 
 
+CLI_FIT = (  # --fit-smpl and its settings, parsed after CLI_VOLUME (a table of their own: older tests pin the tables above)
+    ('--fit-smpl', dict(default=None, metavar='OUT.npz', dest='fit_smpl',
+                        help='after everything above: fit SMPL parameters to the final world joints of every sample and write '
+                             'them as a bank that train.py --pseudo-online reads (needs --smpl-model)')),
+    ('--smpl-model', dict(default=None, metavar='ROOT', dest='smpl_model',
+                          help='--fit-smpl: directory of the SMPL model files, or an .npz of exported arrays with `h36m_regressor`')),
+    ('--fit-iters', dict(default=30, type=int, metavar='N', dest='fit_iters', help='--fit-smpl: Levenberg-Marquardt trials per sample')),
+    ('--fit-pose-prior', dict(default=None, type=float, metavar='W', dest='fit_pose_prior',
+                              help='--fit-smpl: weight of the squared body-pose angles against mm^2 (untuned default)')),
+    ('--fit-shape-prior', dict(default=None, type=float, metavar='W', dest='fit_shape_prior',
+                               help='--fit-smpl: weight of the squared betas against mm^2 (untuned default)')),
+)
+
+
+def mirror_fit_options(config, opt):
+    """The --fit-smpl flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_smplfit)."""
+    mp = config['model_params']
+    mp['fit_smpl'], mp['smpl_model'], mp['fit_iters'] = opt.fit_smpl, opt.smpl_model, opt.fit_iters
+    for key in ('fit_pose_prior', 'fit_shape_prior'):
+        if getattr(opt, key) is not None:
+            mp[key] = getattr(opt, key)
+
+
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -501,6 +615,7 @@ def main():
     config['model_params']['tri_vol_side'] = opt.tri_vol_side
     config['model_params']['tri_vol_grid'] = opt.tri_vol_grid
     config['model_params']['tri_vol_levels'] = opt.tri_vol_levels
+    mirror_fit_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

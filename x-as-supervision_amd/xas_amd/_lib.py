@@ -152,6 +152,9 @@ SIGNATURES = {
     'xas_smpl_lbs_fwd': ('ppppppppiiipppp', 'i'),
     'xas_smpl_lbs_bwd_workspace_floats': ('ii', 'z'),
     'xas_smpl_lbs_bwd': ('ppppppppiiippppppp', 'i'),
+    'xas_smpl_fit_workspace_bytes': ('ii', 'z'),
+    'xas_smpl_fit_linearise': ('p' * 14 + 'ff' + 'iii' + 'ppp' + 'p', 'i'),
+    'xas_smpl_fit': ('p' * 14 + 'ff' + 'iiii' + 'p' * 8 + 'p', 'i'),
     'xas_adam_step': ('pppplffffip', 'i'),
     'xas_grad_guard_workspace_bytes': ('l', 'z'),
     'xas_grad_guard': ('plfifffppp', 'i'),

@@ -1,0 +1,119 @@
+"""SMPL parameters from 18 world joints on the device (csrc/smplfit.hip, xas_smpl_fit): the inverse of
+modules.util.project_smpl_to_patch_kps' model, Y = R(omega) (1000 smpl_to_h36m(layer((0, theta), beta))) + t, solved by a
+double-precision Levenberg-Marquardt, one workgroup per sample.  include/xas_hip.h states the residual order and the schedule.
+Nothing here keeps state between calls or synchronises with the host.  No reference counterpart."""
+import torch
+
+from xas_amd._lib import call, ptr, query
+
+# Weights of the priors sqrt(w) theta_i (per radian^2, against mm^2 of the joint rows) and sqrt(w) beta_i.  UNTUNED GUESSES:
+# there is neither a dataset nor a checkpoint here to tune them on.  They keep the 85 unknowns determined by 54 joint rows.
+POSE_PRIOR = 100.0
+SHAPE_PRIOR = 25.0
+
+STATUS_CONVERGED, STATUS_LIMIT, STATUS_PASSED = 0, 1, 2
+STATUS_NAMES = ('converged', 'iteration limit', 'passed through')
+
+
+def _layer_arrays(smpl_layer, dev):
+    bufs = tuple(t.to(device=dev, dtype=torch.float32).contiguous() for t in (
+        smpl_layer.th_v_template.reshape(-1, 3), smpl_layer.th_shapedirs, smpl_layer.th_posedirs, smpl_layer.th_J_regressor,
+        smpl_layer.th_weights))
+    parents = smpl_layer._parents.to(device=dev, dtype=torch.int32).contiguous()
+    center = -1 if smpl_layer.center_idx is None else int(smpl_layer.center_idx)
+    return bufs, parents, center
+
+
+def compact_regressor(h36m_regressor):
+    """[17,V] -> (reg_verts [V] int32: the vertices with a non-zero column first, ascending; reg_count [1] int32), on the
+    regressor's device and without a host synchronisation (no nonzero())."""
+    used = (h36m_regressor != 0).any(dim=0)
+    order = torch.argsort((~used).to(torch.int32), stable=True).to(torch.int32).contiguous()
+    return order, used.sum().to(torch.int32).reshape(1)
+
+
+def _expmap_log(R):
+    """Rotation matrices [B,3,3] -> axis-angle [B,3] (angle in [0, pi); ill-conditioned towards pi, good enough for a start)."""
+    cos = ((R.diagonal(dim1=1, dim2=2).sum(1) - 1.0) * 0.5).clamp(-1.0, 1.0)
+    th = torch.acos(cos)
+    v = torch.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], dim=1)
+    s = v.norm(dim=1)
+    return v * (th / s.clamp(min=1e-12)).unsqueeze(1)
+
+
+def default_init(targets, weights, smpl_layer, h36m_regressor):
+    """Zero body pose and betas, t = the target pelvis (where it is not usable: what the rigid alignment gives), omega from the
+    weighted rigid (Kabsch) alignment of the zero-pose joints to the targets.  torch on the device, float64; not a hot path.
+    -> dict(pose [B,72], betas [B,10], trans [B,3]) float32."""
+    from modules.util import smpl_to_h36m
+    dev, B = targets.device, targets.shape[0]
+    with torch.no_grad():
+        verts, _ = smpl_layer.to(dev)(torch.zeros(1, 72, device=dev), torch.zeros(1, 10, device=dev))
+        src = smpl_to_h36m(verts, h36m_regressor.to(dev)).double() * 1000.0              # [1,18,3], root centred
+        w = torch.where(weights > 0, weights, torch.zeros_like(weights)).double()       # NaN and negative weights: 0
+        tgt = torch.where((w > 0).unsqueeze(-1), targets.double(), torch.zeros((), device=dev, dtype=torch.float64))
+        wn = w / w.sum(dim=1, keepdim=True).clamp(min=1e-300)
+        ca, cb = (wn.unsqueeze(-1) * src).sum(1, keepdim=True), (wn.unsqueeze(-1) * tgt).sum(1, keepdim=True)
+        M = torch.einsum('bk,bki,bkj->bij', wn, tgt - cb, src - ca)                      # sum w (b - cb)(a - ca)^T
+        U, _, Vh = torch.linalg.svd(M)
+        d = torch.sign(torch.linalg.det(U @ Vh))
+        D = torch.diag_embed(torch.stack([torch.ones_like(d), torch.ones_like(d), d], dim=1))
+        R = U @ D @ Vh
+        omega = _expmap_log(R)
+        t_rigid = cb[:, 0] - torch.einsum('bij,bj->bi', R, ca[:, 0].expand(B, 3))
+        pelvis_ok = (w[:, 0] > 0) & torch.isfinite(targets[:, 0]).all(dim=1)
+        t = torch.where(pelvis_ok.unsqueeze(1), tgt[:, 0], t_rigid)
+        pose = torch.cat([omega, torch.zeros(B, 69, device=dev, dtype=torch.float64)], dim=1)
+    return {'pose': pose.float(), 'betas': torch.zeros(B, 10, device=dev), 'trans': t.float()}
+
+
+def _prepare(targets, weights, smpl_layer, h36m_regressor, init):
+    if targets.dim() != 3 or tuple(targets.shape[1:]) != (18, 3) or tuple(weights.shape) != (targets.shape[0], 18):
+        raise RuntimeError('smpl fit: targets must be [B,18,3] and weights [B,18], got %s and %s'
+                           % (tuple(targets.shape), tuple(weights.shape)))
+    dev, B = targets.device, targets.shape[0]
+    targets = targets.detach().float().contiguous()
+    weights = weights.detach().to(device=dev, dtype=torch.float32).contiguous()
+    bufs, parents, center = _layer_arrays(smpl_layer, dev)
+    V = bufs[0].shape[0]
+    reg = h36m_regressor.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(reg.shape) != (17, V):
+        raise RuntimeError('smpl fit: h36m_regressor must be [17,%d], got %s' % (V, tuple(reg.shape)))
+    if init is None:
+        init = default_init(targets, weights, smpl_layer, reg)
+    pose, betas, trans = (init[k].detach().to(device=dev, dtype=torch.float32).contiguous() for k in ('pose', 'betas', 'trans'))
+    if tuple(pose.shape) != (B, 72) or tuple(betas.shape) != (B, 10) or tuple(trans.shape) != (B, 3):
+        raise RuntimeError('smpl fit: init needs pose [B,72], betas [B,10] and trans [B,3]')
+    rverts, rcount = compact_regressor(reg)
+    nbytes = query('xas_smpl_fit_workspace_bytes', B, V)
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    head = (ptr(pose), ptr(betas), ptr(trans), *(ptr(t) for t in bufs), ptr(parents), ptr(reg), ptr(rverts), ptr(rcount),
+            ptr(targets), ptr(weights))
+    keep = (pose, betas, trans, bufs, parents, reg, rverts, rcount, targets, weights)
+    return head, keep, ws, B, V, center, dev
+
+
+def linearise_smpl(targets, weights, smpl_layer, h36m_regressor, init, pose_prior=POSE_PRIOR, shape_prior=SHAPE_PRIOR):
+    """Residual r [B,133] and Jacobian J [B,133,85] (float64) at the parameters `init` (xas_smpl_fit_linearise); the unknowns
+    are ordered omega 3, t 3, body pose 69, betas 10."""
+    head, keep, ws, B, V, center, dev = _prepare(targets, weights, smpl_layer, h36m_regressor, init)
+    r = torch.empty(B, 133, device=dev, dtype=torch.float64)
+    J = torch.empty(B, 133, 85, device=dev, dtype=torch.float64)
+    call('xas_smpl_fit_linearise', *head, float(pose_prior), float(shape_prior), B, V, center, ptr(r), ptr(J), ptr(ws))
+    return r, J
+
+
+def fit_smpl(targets, weights, smpl_layer, h36m_regressor, init=None, iters=30, pose_prior=POSE_PRIOR,
+             shape_prior=SHAPE_PRIOR):
+    """targets [B,18,3] world mm, weights [B,18] >= 0 (0 = the joint is not used, its target may be anything) -> dict:
+    pose [B,72] (root axis-angle first: a PseudoSynth bank row), betas [B,10], trans [B,3] mm, joints [B,18,3] mm, cost [B,2]
+    (start, result), all float64; iters [B] int32; status [B] uint8 (STATUS_*).  init: dict(pose, betas, trans) or None =
+    default_init.  The semantics are those of include/xas_hip.h."""
+    head, keep, ws, B, V, center, dev = _prepare(targets, weights, smpl_layer, h36m_regressor, init)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'pose': f64(B, 72), 'betas': f64(B, 10), 'trans': f64(B, 3), 'joints': f64(B, 18, 3), 'cost': f64(B, 2),
+           'iters': torch.empty(B, device=dev, dtype=torch.int32), 'status': torch.empty(B, device=dev, dtype=torch.uint8)}
+    call('xas_smpl_fit', *head, float(pose_prior), float(shape_prior), B, V, center, int(iters), ptr(out['pose']),
+         ptr(out['betas']), ptr(out['trans']), ptr(out['joints']), ptr(out['cost']), ptr(out['iters']), ptr(out['status']),
+         ptr(ws))
+    return out
