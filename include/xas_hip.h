@@ -875,6 +875,73 @@ int xas_triangulate_skeleton(const float* points, const float* P, const float* i
                              int max_iter, float* out, float* resid, float* sym, float* cost,
                              unsigned char* status, void* stream);
 
+/* Bundle adjustment of the camera extrinsics over a whole evaluation set (eval.py --calibrate OUT.npz, applied by --calibration IN.npz; the reference has no
+ * counterpart: everything above holds the cameras fixed).  points [N][V][K][3], P [N][V][3][4], init [N][K][4] and views [N][K]
+ * (or NULL) are exactly as for xas_triangulate_refine, with its rules for VALID views, the views used F, BEHIND,
+ * XAS_REFINE_WEIGHTED (the only flag) and huber; N counts the samples of the whole set.  rig_start [R+1] int32, a HOST array read
+ * before the launch: samples rig_start[r] .. rig_start[r+1]-1 belong to rig r (non-decreasing, rig_start[0] = 0, rig_start[R] =
+ * N, otherwise an error; a rig may be empty).  free_mask: bit v set = camera v of every rig may move; bits >= V are ignored.
+ * UNKNOWNS of rig r, all double.  Per free camera v a correction delta_rv = (omega, tau) in R^6, a rigid motion of the world in
+ * front of that camera: X' = exp([omega]x) X + tau, then h = P_nv (X', 1); the corrected matrix is P T(delta), T = [exp omega,
+ * tau; 0 1], so nothing but P is needed.  exp is the plain exponential map I + sin(th) K / th + (1 - cos(th)) K^2 / th^2, K =
+ * [omega]x, th = |omega|; for th^2 < 1e-16 its series I + K + K^2 / 2.  Per FREE point X_nk in R^3; a point is free if
+ * xas_triangulate_refine would not pass it through, judged once at the start corrections (at least two views used, init finite,
+ * init' in front of every view used); otherwise it is FIXED: it leaves as init, bit for bit, and takes part in nothing.
+ * COST of rig r, in double from the fp32 inputs:
+ *   C = sum over free points and v in F of rho(s_v |r_v|)  +  prior_rot sum |omega_rv|^2  +  prior_trans sum |tau_rv|^2
+ * the first sum term for term the cost of xas_triangulate_refine once the corrections are 0, the prior sums over the free
+ * cameras; prior_rot in cost per rad^2, prior_trans in cost per mm^2, both >= 0 and finite.  The prior pulls towards the given
+ * calibration; with a camera held fixed it settles the gauge (scale only softly).
+ * LINEARISATION: the corrections are updated additively, delta <- delta + d, and the Jacobian is re-linearised about the
+ * current rotation with the exact derivative of the exponential map: d(u, v) / dX' = multiview.h's ju / jv,
+ * dX' / d tau = I, dX' / d omega = -[exp(omega) X]x Jl(omega), Jl = I + (1 - cos th) K / th^2 + (th - sin th) K^2 / th^3 the left
+ * Jacobian of SO(3) (series I + K / 2 + K^2 / 6), dX' / dX = exp(omega).  With psi and s of xas_triangulate_refine,
+ * H = sum psi s^2 J^T J and g = sum psi s^2 J^T r over the residuals, plus prior on the diagonal of H_cc and prior * delta in g_c.
+ * A TRIAL solves (H + lambda diag H) d = -g over all of the rig's unknowns exactly by eliminating the points: with A_p = H_pp +
+ * lambda diag H_pp (3x3, Cholesky) and B_p = H_cp (6 V_free x 3, rows of the views the point uses),
+ *   S = H_cc + lambda diag H_cc - sum_p B_p A_p^-1 B_p^T,  b = -g_c + sum_p B_p A_p^-1 g_p,  S d_c = b by Cholesky (S is at most
+ *   36 x 36; camera slots are the free cameras in ascending order, 6 rows each: omega, tau),  d_p = -A_p^-1 (g_p + B_p^T d_c).
+ * lambda = 1e-3 at the start.  A trial is ACCEPTED if the rig's C strictly decreases and no free point lies behind a view it
+ * uses: the state moves, lambda *= 0.1; otherwise, and at a pivot of S that is not positive, lambda *= 10.  The loop stops when
+ * an accepted step changes every point coordinate by less than 1e-5 (mm), every omega component by less than
+ * XAS_CALIB_STEP_TOL_ROT (rad) and every tau component by less than XAS_CALIB_STEP_TOL_TRANS (mm); after max_iter trials
+ * (1 <= max_iter <= 64); or when lambda > 1e12.  So C(out) <= C(start), always.  Rigs are independent: each has its own lambda,
+ * stop and status, and its result does not depend on the other rigs, bit for bit.
+ * xas_calibrate_bundle.  delta [R][V][6] double (required) is read as the start (0, or an earlier result; entries of fixed
+ * cameras are taken as 0) and written with the result (fixed cameras: 0).  out [N][K][4] (required, must not overlap init) =
+ * the point rounded to fp32 and init's fourth entry.  Each of the others may be NULL:
+ *   cost [R][2] double    C at the start and at the result
+ *   rms [R][2] double     RMS of |r_v| in px, unweighted, over the views used of the free points, at the start and at the
+ *                         result; NaN for a rig with no free point
+ *   cam_cov [R][6V][6V]   double: the inverse of S at the result with lambda = 0, rows and columns by view (6 v + (omega, tau));
+ *                         those of fixed cameras are 0; NaN where S has no positive pivot.  A large entry = a camera parameter
+ *                         that the data (and the prior) did not determine.
+ *   status [R] bytes      0 = stopped on the step rule, 1 = ran out of trials or lambda, 2 = the rig has no free point:
+ *                         everything passed through, delta = the start.  With no free camera (free_mask = 0) the free points
+ *                         alone are solved (S is empty, d_p = -A_p^-1 g_p): xas_triangulate_refine's problem per point under
+ *                         one lambda and one stop per rig
+ *   trials [R][2] int32   trials made and trials accepted (what the tests compare with the oracle's schedule)
+ * xas_calibrate_linearise: one linearisation at the state (delta, the points of init) with the given lambda >= 0: S [R][n][n]
+ * (dense, symmetric, n = 6 * the number of free cameras), b [R][n] and C [R], all double and required (S and b may be NULL
+ * when n = 0).  It exists so that the
+ * Schur assembly can be tested on its own.
+ * workspace: xas_calibrate_workspace_bytes(N, V, K, R) bytes (0 for a shape outside the limits), 16-byte aligned.
+ * Limits: 2 <= V <= XAS_TRI_MAX_VIEWS, K >= 1, N > 0, N*K < 2^31, 1 <= R <= XAS_CALIB_MAX_RIGS.
+ * Four launches per trial, all enqueued up front (a stopped rig's blocks return at once), no host synchronisation, no atomics,
+ * every sum in one order: two calls on the same inputs give the same bits in every output. */
+#define XAS_CALIB_MAX_RIGS 16
+#define XAS_CALIB_STEP_TOL_ROT 1e-9     /* rad: 1e-5 mm at 10 m.  Untuned. */
+#define XAS_CALIB_STEP_TOL_TRANS 1e-5   /* mm, the points' tolerance.  Untuned. */
+size_t xas_calibrate_workspace_bytes(int N, int V, int K, int R);
+int xas_calibrate_linearise(const float* points, const float* P, const float* init, const unsigned char* views,
+                            const int* rig_start, int N, int V, int K, int R, int free_mask, int flags, float huber,
+                            double prior_rot, double prior_trans, double lambda, const double* delta, double* S, double* b,
+                            double* C, void* workspace, void* stream);
+int xas_calibrate_bundle(const float* points, const float* P, const float* init, const unsigned char* views,
+                         const int* rig_start, int N, int V, int K, int R, int free_mask, int flags, float huber,
+                         double prior_rot, double prior_trans, int max_iter, double* delta, float* out, double* cost,
+                         double* rms, double* cam_cov, unsigned char* status, int* trials, void* workspace, void* stream);
+
 /* Volumetric fusion of the views' heat-map cubes (eval.py --tri-volume; the reference has no counterpart).  Every other
  * triangulation here starts from ONE point per view, the soft-argmax of that view's heat-map; this one multiplies the views'
  * whole distributions over a voxel grid round the triangulated point (a product of experts) and takes the soft-argmax of the

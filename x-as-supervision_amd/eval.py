@@ -73,8 +73,8 @@ from torch.distributed import destroy_process_group, init_process_group
 from metrics import pose_errors
 from modules.keypoint_detector_integral import KPDetector3D as KPDetector3D_integral
 from modules.keypoint_detector_integral_multi import KPDetector3DMulti as KPDetector3DMulti_integral
-from modules.util import (convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_refined,
-                          triangulation_skeleton, triangulation_volume, triangulation_weighted)
+from modules.util import (apply_calibration, convert_patch_to_world, resolve_views_weighted, spread_weight, triangulation_inputs,
+                          triangulation_refined, triangulation_skeleton, triangulation_volume, triangulation_weighted)
 from eval_utils import cal_per_class_error
 from xas_amd import ops_eval, ops_head
 from xas_amd.synthetic import synthetic_eval_batch
@@ -174,6 +174,54 @@ class Eval:
             self.fit_pose_prior = float(mp.get('fit_pose_prior', ops_smplfit.POSE_PRIOR))      # untuned guesses, both
             self.fit_shape_prior = float(mp.get('fit_shape_prior', ops_smplfit.SHAPE_PRIOR))
             self.fit_rows = []                         # per batch: the host arrays of the file
+        self.calibrate = mp.get('calibrate') or None   # --calibrate OUT.npz: bundle adjustment of the extrinsics over the whole set
+        self.calibration = mp.get('calibration') or None   # --calibration IN.npz: every batch's cameras corrected by such a file
+        if self.calibrate and self.calibration:
+            raise ValueError('calibrate estimates corrections of the given cameras and calibration applies earlier ones: '
+                             '--calibrate and --calibration do not go together')
+        if self.calibrate:
+            if not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
+                raise ValueError('calibrate needs 2 to {} cameras; cam_id_list has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
+            if int(os.environ.get('WORLD_SIZE', 1)) != 1:
+                raise ValueError('calibrate needs WORLD_SIZE == 1: a rank sees only its shard of the set, and a bundle over '
+                                 'several ranks is not built')
+            from xas_amd import ops_calib              # only with the flag
+            self.calib_iters = int(mp.get('calib_iters', 30))
+            self.calib_prior_rot = float(mp.get('calib_prior_rot', ops_calib.CALIB_PRIOR_ROT))        # untuned guesses, both
+            self.calib_prior_trans = float(mp.get('calib_prior_trans', ops_calib.CALIB_PRIOR_TRANS))
+            self.calib_free = mp.get('calib_free')     # mask of the cameras that may move; None = all but camera 0
+            self.calib_rows = []                       # per batch, on the device: points, pmat, init, views
+        if self.calibration:
+            with np.load(self.calibration) as f:
+                self.calib_keys = torch.from_numpy(f['keys']).to(self.gpu_id)
+                self.calib_delta = torch.from_numpy(f['delta']).to(self.gpu_id)
+
+    def write_calibration(self):
+        """--calibrate: one bundle adjustment over everything the batches kept, the file (atomically: a temporary file beside
+        it, then a rename) and -> the lines of eval_result.txt, one per rig."""
+        from xas_amd import ops_calib
+        cat = lambda k: torch.cat([r[k] for r in self.calib_rows])
+        points, pmat, init = cat('points'), cat('pmat'), cat('init')
+        views = cat('views') if self.calib_rows[0]['views'] is not None else None
+        rig, keys = ops_calib.rigs_of(pmat)
+        r = ops_calib.calibrate_bundle(points, pmat, init, rig, views=views, free=self.calib_free,
+                                       weighted=self.tri_weight == 'spread', huber_px=self.tri_huber,
+                                       prior_rot=self.calib_prior_rot, prior_trans=self.calib_prior_trans,
+                                       max_iter=self.calib_iters, num_rigs=keys.shape[0])
+        cols = {k: r[k].cpu().numpy() for k in ('delta', 'cost', 'rms', 'status', 'cam_cov')}
+        made = r['trials'].cpu().numpy()
+        cols['keys'] = keys.cpu().numpy()
+        os.makedirs(os.path.dirname(os.path.abspath(self.calibrate)), exist_ok=True)
+        tmp = self.calibrate + '.tmp.npz'
+        np.savez(tmp, **cols)
+        os.replace(tmp, self.calibrate)
+        d = cols['delta']
+        return ['CALIBRATE rig {} ({} of {} trials, prior rot {}, prior trans {}): reprojection RMS {} -> {} px, largest |omega| {} deg, '
+                'largest |tau| {} mm, {}'.format(i, int(made[i, 0]), self.calib_iters, self.calib_prior_rot, self.calib_prior_trans,
+                                                 cols['rms'][i, 0], cols['rms'][i, 1],
+                                                 float(np.degrees(np.linalg.norm(d[i, :, :3], axis=-1).max())),
+                                                 float(np.linalg.norm(d[i, :, 3:], axis=-1).max()),
+                                                 ops_calib.STATUS_NAMES[int(cols['status'][i])]) for i in range(len(d))]
 
     def fit_batch(self, joints, bad, cov):
         """--fit-smpl on the final world joints [B,18,3] of a batch.  A joint's weight is 0 where it is not finite or `bad`
@@ -249,6 +297,9 @@ class Eval:
         the cameras' agreement picks the hypotheses."""
         cams = ['cam_{}'.format(c) for c in self.cam_id_list]
         sel, out, trans = {}, {}, None
+        given = x                                  # the ground truth reads the cameras as given; --calibration corrects the predictions'
+        if self.calibration:
+            x = apply_calibration(x, self.cam_id_list, self.calib_keys, self.calib_delta)
         weights = {} if self.tri_weight == 'spread' else None
         cubes, chan = ({}, []) if self.tri_volume else (None, None)
 
@@ -290,7 +341,7 @@ class Eval:
                 perm = ops_eval.switch_perm(K, ops_eval.SWITCH_PAIRS, kps.device)
                 chan.append(torch.where(s['swapped'].squeeze(-1), perm, torch.arange(K, device=kps.device, dtype=torch.int32)))
         out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
-        gt = convert_patch_to_world(x['cam_0_joints'], x, 'cam_0', is_norm=False)          # eval.py:170
+        gt = convert_patch_to_world(given['cam_0_joints'], given, 'cam_0', is_norm=False)  # eval.py:170
         fit_bad = fit_cov = None                   # --fit-smpl only: joints a solver passed through, and a covariance if one came
         fit_want = (('status',) + (('cov',) if weights is not None and self.tri_refine == 'lm' else ())) if self.fit_smpl else ()
         if self.tri_refine == 'lm':                # the same solver, then the pixel error minimised over the views it used
@@ -331,6 +382,10 @@ class Eval:
             out['tri_vol_status'] = torch.stack([(r['status'] == c).float().mean() for c in range(4)])
             if self.fit_smpl:                      # passed through (1, 3): the start came back and there is no covariance
                 fit_bad, fit_cov = (r['status'] == 1) | (r['status'] == 3), r['cov']
+        if self.calibrate:                         # kept on the device for the one bundle after the loop: the final point, the views it used
+            pts, pm = triangulation_inputs(sel, x, self.cam_id_list, weights)
+            self.calib_rows.append({'points': pts, 'pmat': pm, 'views': used if self.tri == 'robust' else None,
+                                    'init': torch.cat([tri[..., :3], torch.ones_like(tri[..., :1])], dim=-1).contiguous()})
         preds = {'tri': tri}
         for m in cams:
             preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
@@ -453,6 +508,8 @@ class Eval:
                 *(self.vol_status / n)))
         if self.fit_smpl:                          # after everything else; without --fit-smpl the file is as it was
             lines.append(self.write_fit())
+        if self.calibrate:                         # after everything else; without --calibrate the file is as it was
+            lines.extend(self.write_calibration())
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -599,9 +656,36 @@ def mirror_fit_options(config, opt):
             mp[key] = getattr(opt, key)
 
 
+CLI_CALIB = (  # --calibrate / --calibration and their settings, parsed after CLI_FIT (a table of their own, as above)
+    ('--calibrate', dict(default=None, metavar='OUT.npz', dest='calibrate',
+                         help='after everything above: bundle adjustment of the camera extrinsics over the whole set, per rig, '
+                              'written as corrections that --calibration applies (needs 2+ cameras and one rank)')),
+    ('--calibration', dict(default=None, metavar='IN.npz', dest='calibration',
+                           help='correct every batch\'s cameras by a --calibrate file before triangulation (not with --calibrate)')),
+    ('--calib-iters', dict(default=30, type=int, metavar='N', dest='calib_iters', help='--calibrate: Levenberg-Marquardt trials per rig')),
+    ('--calib-prior-rot', dict(default=None, type=float, metavar='W', dest='calib_prior_rot',
+                               help='--calibrate: weight of the squared rotation corrections, cost per rad^2 (untuned default)')),
+    ('--calib-prior-trans', dict(default=None, type=float, metavar='W', dest='calib_prior_trans',
+                                 help='--calibrate: weight of the squared translation corrections, cost per mm^2 (untuned default)')),
+    ('--calib-free', dict(default=None, type=int, metavar='MASK', dest='calib_free',
+                          help='--calibrate: bit v set = camera v may move (default: every camera but the first)')),
+)
+
+
+def mirror_calib_options(config, opt):
+    """The --calibrate / --calibration flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_calib)."""
+    if opt.calibrate and opt.calibration:
+        raise ValueError('--calibrate and --calibration do not go together')
+    mp = config['model_params']
+    mp['calibrate'], mp['calibration'], mp['calib_iters'] = opt.calibrate, opt.calibration, opt.calib_iters
+    for key in ('calib_prior_rot', 'calib_prior_trans', 'calib_free'):
+        if getattr(opt, key) is not None:
+            mp[key] = getattr(opt, key)
+
+
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -616,6 +700,7 @@ def main():
     config['model_params']['tri_vol_grid'] = opt.tri_vol_grid
     config['model_params']['tri_vol_levels'] = opt.tri_vol_levels
     mirror_fit_options(config, opt)
+    mirror_calib_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

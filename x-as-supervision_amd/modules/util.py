@@ -123,6 +123,56 @@ def _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT
     return _stack_points(pts, weights, ['cam_{}'.format(c) for c in cam_id_list]), torch.stack(pm, dim=1)
 
 
+def correction_matrix(delta):
+    """delta [...,6] = (omega rad, tau mm) -> T [...,4,4] float64 = [exp([omega]x), tau; 0 1], the rigid motion of the world in
+    front of a camera that xas_calibrate_bundle estimates (P T is the corrected matrix).  The exponential map as in
+    include/xas_hip.h: its series I + K + K^2 / 2 for |omega|^2 < 1e-16."""
+    delta = delta.double()
+    w = delta[..., :3]
+    th2 = (w * w).sum(-1)
+    small = th2 < 1e-16
+    t2 = torch.where(small, torch.ones_like(th2), th2)
+    th = t2.sqrt()
+    a = torch.where(small, torch.ones_like(th), torch.sin(th) / th)[..., None, None]
+    b = torch.where(small, torch.full_like(th, 0.5), (1.0 - torch.cos(th)) / t2)[..., None, None]
+    z = torch.zeros_like(th2)
+    K = torch.stack([z, -w[..., 2], w[..., 1], w[..., 2], z, -w[..., 0], -w[..., 1], w[..., 0], z], -1).reshape(w.shape[:-1] + (3, 3))
+    T = torch.zeros(w.shape[:-1] + (4, 4), dtype=torch.float64, device=delta.device)
+    T[..., :3, :3] = torch.eye(3, dtype=torch.float64, device=delta.device) + a * K + b * (K @ K)
+    T[..., :3, 3] = delta[..., 3:]
+    T[..., 3, 3] = 1.0
+    return T
+
+
+def apply_calibration(params, cam_id_list, keys, delta):
+    """A shallow copy of the batch dict with the corrections of xas_amd.ops_calib.calibrate_bundle applied: keys [R,V,3,4] are
+    the rigs' projection matrices (ops_calib.rigs_of) and delta [R,V,6] their corrections.  A sample belongs to the rig whose
+    matrices its own equal bit for bit; one that matches no rig raises.  With P = K [R | t] (projection_kernel) and T(delta) =
+    [E, tau; 0 1], P T = K [R E | R tau + t]: cam_*_rot_world becomes R E and cam_*_trans_world R tau + t, formed in double and
+    rounded once, so that ops_eval.projection_matrix of the copy is P T to fp32 rounding.  The original dict is untouched: the
+    ground truth keeps reading it."""
+    modes = ['cam_{}'.format(c) for c in cam_id_list]
+    pm = torch.stack([ops_eval.projection_matrix(params[m + '_k_mat'], params[m + '_rot_world'], params[m + '_trans_world'])
+                      for m in modes], dim=1)
+    B, R = pm.shape[0], keys.shape[0]
+    keys = keys.to(device=pm.device, dtype=torch.float32).contiguous()
+    match = (pm.contiguous().view(torch.int32).reshape(B, 1, -1) == keys.view(torch.int32).reshape(1, R, -1)).all(dim=-1)
+    if not bool(match.any(dim=1).all()):
+        raise RuntimeError('apply_calibration: a sample whose cameras match none of the %d calibrated rigs bit for bit' % R)
+    T = correction_matrix(delta.to(pm.device))[match.float().argmax(dim=1)]              # [B,V,4,4]
+    out = dict(params)
+    for i, m in enumerate(modes):
+        rot, t = params[m + '_rot_world'].double().reshape(B, 3, 3), params[m + '_trans_world'].double().reshape(B, 3)
+        out[m + '_rot_world'] = (rot @ T[:, i, :3, :3]).float().reshape(params[m + '_rot_world'].shape)
+        out[m + '_trans_world'] = (torch.einsum('bij,bj->bi', rot, T[:, i, :3, 3]) + t).float().reshape(params[m + '_trans_world'].shape)
+    return out
+
+
+def triangulation_inputs(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000):
+    """points [B,V,K,3] and projection matrices [B,V,3,4] as every triangulation above forms them (eval.py --calibrate keeps them)."""
+    return _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+
+
 def triangulation_refined(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000, robust_px=None,
                           huber_px=0.0, want=()):
     """triangulation_weighted, then Levenberg-Marquardt on the reprojection error in pixels from its point, over the views it

@@ -168,6 +168,9 @@ SIGNATURES = {
     'xas_multiview_resolve': ('ppppppiiiifpppppp', 'i'),
     'xas_triangulate_refine': ('ppppiiiifippppp', 'i'),
     'xas_triangulate_skeleton': ('ppppp' 'iiiii' 'ffi' 'pppppp', 'i'),
+    'xas_calibrate_workspace_bytes': ('iiii', 'z'),
+    'xas_calibrate_linearise': ('ppppp' 'iiiiii' 'f' 'ddd' 'pppp' 'pp', 'i'),
+    'xas_calibrate_bundle': ('ppppp' 'iiiiii' 'f' 'dd' 'i' 'ppppppp' 'pp', 'i'),
     'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),
     'xas_multiview_consistency_fwd': ('pppppiiiiffipppppp', 'i'),
     'xas_multiview_consistency_bwd': ('pppppppiiiiffippp', 'i'),
