@@ -942,6 +942,58 @@ int xas_calibrate_bundle(const float* points, const float* P, const float* init,
                          double prior_rot, double prior_trans, int max_iter, double* delta, float* out, double* cost,
                          double* rms, double* cam_cov, unsigned char* status, int* trials, void* workspace, void* stream);
 
+/* Temporal smoothing of triangulated joint tracks over a whole evaluation set (eval.py --smooth OUT.npz; the reference has no
+ * counterpart: everything above works inside one frame).  points [N][V][K][3], P [N][V][3][4], init [N][K][4] and views [N][K]
+ * (or NULL) are exactly as for xas_triangulate_refine, with its rules for VALID views, the views used F, BEHIND,
+ * XAS_REFINE_WEIGHTED (the only flag) and huber; N counts the samples of the whole set, sorted by track and frame.
+ * start [S+1] int32, a HOST array read before the launch: samples start[s] .. start[s+1]-1 are track s (start[0] = 0, start[S]
+ * = N, increasing: every track has a sample; otherwise an error).  frame [N] int32 on the device: the frame number tau of every
+ * sample, strictly increasing inside a track (the caller's duty: the kernel does not check it; a repeated frame gives a step
+ * h = 0, a cost that is not finite, no accepted trial and out = the start).  acc_w >= 0 and finite, in px^2 per
+ * (mm^2 / frame^3) (sigma^2 with XAS_REFINE_WEIGHTED).
+ * Per (track, joint), T = the track's length: a frame is a DATA frame if xas_triangulate_refine would not pass it through (at
+ * least two views used, x, y and z of init finite, init behind no view used).  Every other frame is a GAP frame: it has no
+ * reprojection term, and it starts on the line in tau through the nearest data frames on either side, X_l + (X_r - X_l)
+ * (tau - tau_l) / (tau_r - tau_l); beyond the ends of the data at the nearest data frame's point.  A (track, joint) with fewer
+ * than two data frames is PASSED THROUGH: out = init bit for bit (NaN stays NaN).
+ * COST, in double from the fp32 inputs, over X_t in R^3, t = 0 .. T-1:
+ *   C = sum over data t and v in F_t of rho(s_v |r_v(X_t)|)            (term for term the cost of xas_triangulate_refine)
+ *     + acc_w sum_{t=1..T-2} 2 / (h0 + h1) |(X_t+1 - X_t) / h1 - (X_t - X_t-1) / h0|^2,  h0 = tau_t - tau_t-1, h1 = tau_t+1 - tau_t
+ * the second sum the discretised integral of |X''|^2 of a cubic smoothing spline on a non-uniform grid: X^T (A x I3) X with A
+ * pentadiagonal, A = sum_t 2 / (h0 + h1) c_t c_t^T, c_t = (1 / h0 at t-1, -(1 / h0 + 1 / h1) at t, 1 / h1 at t+1).
+ * Levenberg-Marquardt on all 3 T coordinates at once, in double.  H = the 3x3 blocks of xas_triangulate_refine on the diagonal
+ * of the data frames (with its psi) + acc_w (A x I3), g = its g per data frame + acc_w (A x I3) X.  A TRIAL is X + d with
+ * (H + lambda diag H) d = -g by a block-pentadiagonal Cholesky (3x3 blocks, half-bandwidth 8); lambda = 1e-3 at the start.  A
+ * trial is ACCEPTED if C strictly decreases and no data frame's point lies behind a view it uses: X moves, lambda *= 0.1;
+ * otherwise, and at a pivot that is not positive, lambda *= 10.  The loop stops when the longest per-frame step |d_t| of an
+ * accepted trial is under 1e-5 (mm), after max_iter trials (1 <= max_iter <= 64), or when lambda > 1e12.  So C(out) <=
+ * C(start), always.  With acc_w = 0 a gap frame has a zero pivot: every trial is rejected and out = the start.
+ * xas_track_smooth.  out [N][K][4] (required, must not overlap init) = (X, Y, Z) rounded to fp32 and init's fourth entry bit
+ * for bit.  Each of the others may be NULL:
+ *   status [N][K] bytes        0 = data frame smoothed, 1 = gap frame filled, 2 = passed through
+ *   resid [N][K][2]            RMS of |r_v| over F (px, unweighted) at the start and at the result; NaN for gap and
+ *                              passed-through frames
+ *   track_status [S][K] bytes  0 = stopped on the step rule, 1 = ran out of trials or lambda, 2 = passed through
+ *   cost [S][K][2] double      C at the start and at the result (0 where passed through)
+ *   trials [S][K] int32        trials made (0 where passed through)
+ * xas_track_linearise: one linearisation at the start (the points of init, gap frames filled) with the given lambda >= 0, all
+ * double and required: band [N][K][3][9], entry [n][k][c][o] = element (i, i - o) of H + lambda diag H for row i = 3 t + c
+ * of the (track, joint) that sample n is frame t of (0 where i - o < 0, and where the column lies outside the block row);
+ * g [N][K][3]; C [S][K].  Passed through: band, g and C are 0.  It exists so that the assembly can be tested on its own.
+ * workspace: xas_track_smooth_workspace_bytes(N, K) bytes (0 for a shape outside the limits), 16-byte aligned; its content
+ * before the call does not matter.  The band's factor, g, d, X and the trial point live there: no bound on T beyond N.
+ * Limits: 2 <= V <= XAS_TRI_MAX_VIEWS, K >= 1, N > 0, N*K < 2^31, 1 <= S <= N, S*K < 2^31.
+ * One wave per (track, joint); one launch after the copy of start (one small launch per 512 tracks), all enqueued up front,
+ * no host synchronisation, no atomics, every sum in one order: two calls on the same inputs give the same bits in every output. */
+size_t xas_track_smooth_workspace_bytes(int N, int K);
+int xas_track_linearise(const float* points, const float* P, const float* init, const unsigned char* views, const int* start,
+                        const int* frame, int N, int V, int K, int S, int flags, float huber, double acc_w, double lambda,
+                        double* band, double* g, double* C, void* workspace, void* stream);
+int xas_track_smooth(const float* points, const float* P, const float* init, const unsigned char* views, const int* start,
+                     const int* frame, int N, int V, int K, int S, int flags, float huber, double acc_w, int max_iter,
+                     float* out, unsigned char* status, float* resid, unsigned char* track_status, double* cost, int* trials,
+                     void* workspace, void* stream);
+
 /* Volumetric fusion of the views' heat-map cubes (eval.py --tri-volume; the reference has no counterpart).  Every other
  * triangulation here starts from ONE point per view, the soft-argmax of that view's heat-map; this one multiplies the views'
  * whole distributions over a voxel grid round the triangulated point (a product of experts) and takes the soft-argmax of the

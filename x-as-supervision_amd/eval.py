@@ -191,6 +191,18 @@ class Eval:
             self.calib_prior_trans = float(mp.get('calib_prior_trans', ops_calib.CALIB_PRIOR_TRANS))
             self.calib_free = mp.get('calib_free')     # mask of the cameras that may move; None = all but camera 0
             self.calib_rows = []                       # per batch, on the device: points, pmat, init, views
+        self.smooth = mp.get('smooth') or None         # --smooth OUT.npz: the joint tracks smoothed over time, over the whole set
+        if self.smooth:
+            if not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
+                raise ValueError('smooth needs 2 to {} cameras; cam_id_list has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
+            if int(os.environ.get('WORLD_SIZE', 1)) != 1:
+                raise ValueError('smooth needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out over '
+                                 'the ranks, and no rank sees a track')
+            from xas_amd import ops_track              # only with the flag
+            self.smooth_acc = float(mp.get('smooth_acc', ops_track.TRACK_ACC_W))                     # untuned guesses, both
+            self.smooth_gap = int(mp.get('smooth_gap', ops_track.TRACK_MAX_GAP))
+            self.smooth_iters = int(mp.get('smooth_iters', 30))
+            self.smooth_rows = []                      # per batch, on the device: points, pmat, init, views, gt; and the paths
         if self.calibration:
             with np.load(self.calibration) as f:
                 self.calib_keys = torch.from_numpy(f['keys']).to(self.gpu_id)
@@ -222,6 +234,40 @@ class Eval:
                                                  float(np.degrees(np.linalg.norm(d[i, :, :3], axis=-1).max())),
                                                  float(np.linalg.norm(d[i, :, 3:], axis=-1).max()),
                                                  ops_calib.STATUS_NAMES[int(cols['status'][i])]) for i in range(len(d))]
+
+    def write_smooth(self):
+        """--smooth: one track_smooth over everything the batches kept, the file (atomically: a temporary file beside it, then
+        a rename) and -> the two lines of eval_result.txt."""
+        from xas_amd import ops_track
+        rows = self.smooth_rows
+        cat = lambda k: torch.cat([r[k] for r in rows])
+        points, pmat, init, gt = cat('points'), cat('pmat'), cat('init'), cat('gt')
+        views = cat('views') if rows[0]['views'] is not None else None
+        paths = [p for r in rows for p in r['paths']] if rows[0]['paths'] is not None else None
+        track, frame = ops_track.tracks_of(paths, self.smooth_gap, count=len(points))
+        r = ops_track.track_smooth(points, pmat, init, track, frame, views=views, weighted=self.tri_weight == 'spread',
+                                   huber_px=self.tri_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
+        joints, status = r['xyzw'][..., :3].contiguous(), r['status']
+        both = torch.isfinite(joints).all(-1) & torch.isfinite(init[..., :3]).all(-1)                  # [N,K]
+        err = lambda p: pose_errors(torch.where(torch.isfinite(p), p, torch.zeros_like(p)), gt, want=('err',))['err'][0]   # [N,K] mm, no alignment
+        e_before, e_after = err(init[..., :3].contiguous()), err(joints)
+        mean = lambda e, m: float(e[m].mean()) if bool(m.any()) else float('nan')
+        filled = (status == ops_track.STATUS_FILLED) & torch.isfinite(joints).all(-1)
+        rms = lambda c: float(torch.sqrt((r['resid'][..., c] ** 2).nanmean()))
+        cols = {'joints': joints, 'status': status, 'track_status': r['track_status'], 'cost': r['cost'], 'trials': r['trials']}
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        cols['track'], cols['frame'] = track, frame
+        os.makedirs(os.path.dirname(os.path.abspath(self.smooth)), exist_ok=True)
+        tmp = self.smooth + '.tmp.npz'
+        np.savez(tmp, **cols)
+        os.replace(tmp, self.smooth)
+        S = len(r['tracks'])
+        return ['SMOOTH {} tracks of mean length {} (acc {}, gap {}, {} trials): TRI MPJPE {} -> {} mm, reprojection RMS {} -> {} px, '
+                'gaps filled {} , passed through {}'.format(S, len(points) / S, self.smooth_acc, self.smooth_gap, self.smooth_iters,
+                                                            mean(e_before, both), mean(e_after, both), rms(0), rms(1),
+                                                            float((status == ops_track.STATUS_FILLED).float().mean()),
+                                                            float((status == ops_track.STATUS_PASSED).float().mean())),
+                'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(mean(e_after, filled), int(filled.sum()))]
 
     def fit_batch(self, joints, bad, cov):
         """--fit-smpl on the final world joints [B,18,3] of a batch.  A joint's weight is 0 where it is not finite or `bad`
@@ -386,6 +432,12 @@ class Eval:
             pts, pm = triangulation_inputs(sel, x, self.cam_id_list, weights)
             self.calib_rows.append({'points': pts, 'pmat': pm, 'views': used if self.tri == 'robust' else None,
                                     'init': torch.cat([tri[..., :3], torch.ones_like(tri[..., :1])], dim=-1).contiguous()})
+        if self.smooth:                            # kept on the device for the one smoothing after the loop, as --calibrate keeps its rows
+            pts, pm = triangulation_inputs(sel, x, self.cam_id_list, weights)
+            paths = x.get(cams[0] + '_img_path')
+            self.smooth_rows.append({'points': pts, 'pmat': pm, 'views': used if self.tri == 'robust' else None, 'gt': gt[..., :3].contiguous(),
+                                     'init': torch.cat([tri[..., :3], torch.ones_like(tri[..., :1])], dim=-1).contiguous(),
+                                     'paths': None if paths is None else [str(p) for p in paths]})
         preds = {'tri': tri}
         for m in cams:
             preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
@@ -510,6 +562,8 @@ class Eval:
             lines.append(self.write_fit())
         if self.calibrate:                         # after everything else; without --calibrate the file is as it was
             lines.extend(self.write_calibration())
+        if self.smooth:                            # after everything else; without --smooth the file is as it was
+            lines.extend(self.write_smooth())
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -683,9 +737,30 @@ def mirror_calib_options(config, opt):
             mp[key] = getattr(opt, key)
 
 
+CLI_SMOOTH = (  # --smooth and its settings, parsed after CLI_CALIB (a table of their own, as above)
+    ('--smooth', dict(default=None, metavar='OUT.npz', dest='smooth',
+                      help='after everything above: smooth every joint\'s triangulated track over the frames of its sequence '
+                           '(reprojection cost + acceleration penalty) and fill frames without data (needs 2+ cameras and one rank)')),
+    ('--smooth-acc', dict(default=None, type=float, metavar='W', dest='smooth_acc',
+                          help='--smooth: weight of the squared acceleration, px^2 per (mm^2 / frame^3) (untuned default)')),
+    ('--smooth-gap', dict(default=None, type=int, metavar='FRAMES', dest='smooth_gap',
+                          help='--smooth: frames of a sequence further apart than this start a new track (untuned default)')),
+    ('--smooth-iters', dict(default=30, type=int, metavar='N', dest='smooth_iters', help='--smooth: Levenberg-Marquardt trials per track')),
+)
+
+
+def mirror_smooth_options(config, opt):
+    """The --smooth flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_track)."""
+    mp = config['model_params']
+    mp['smooth'], mp['smooth_iters'] = opt.smooth, opt.smooth_iters
+    for key in ('smooth_acc', 'smooth_gap'):
+        if getattr(opt, key) is not None:
+            mp[key] = getattr(opt, key)
+
+
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -701,6 +776,7 @@ def main():
     config['model_params']['tri_vol_levels'] = opt.tri_vol_levels
     mirror_fit_options(config, opt)
     mirror_calib_options(config, opt)
+    mirror_smooth_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

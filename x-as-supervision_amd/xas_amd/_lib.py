@@ -171,6 +171,9 @@ SIGNATURES = {
     'xas_calibrate_workspace_bytes': ('iiii', 'z'),
     'xas_calibrate_linearise': ('ppppp' 'iiiiii' 'f' 'ddd' 'pppp' 'pp', 'i'),
     'xas_calibrate_bundle': ('ppppp' 'iiiiii' 'f' 'dd' 'i' 'ppppppp' 'pp', 'i'),
+    'xas_track_smooth_workspace_bytes': ('ii', 'z'),
+    'xas_track_linearise': ('pppppp' 'iiiii' 'f' 'dd' 'ppp' 'pp', 'i'),
+    'xas_track_smooth': ('pppppp' 'iiiii' 'f' 'd' 'i' 'pppppp' 'pp', 'i'),
     'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),
     'xas_multiview_consistency_fwd': ('pppppiiiiffipppppp', 'i'),
     'xas_multiview_consistency_bwd': ('pppppppiiiiffippp', 'i'),

@@ -1,0 +1,155 @@
+"""Temporal smoothing of triangulated joint tracks on the device (csrc/track_smooth.hip, xas_track_smooth): per (track, joint)
+the reprojection cost of ops_eval.triangulate_refine in every frame that has data plus a penalty on the acceleration, by a
+double-precision Levenberg-Marquardt over all frames of the track at once (block-pentadiagonal Cholesky); frames without data
+are filled in from their neighbours.  include/xas_hip.h states the problem and the schedule.  Imported only when eval.py is given
+--smooth.  No reference counterpart."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import torch
+
+from xas_amd._lib import call, ptr, query
+
+# Weight of the squared acceleration, in px^2 per (mm^2 / frame^3): about 4 mm / frame^2 of acceleration on the scale of a 1 px
+# residual (0.05 * 4.5^2 = 1).  AN UNTUNED GUESS: there is neither a dataset nor a checkpoint here to tune it on.
+TRACK_ACC_W = 0.05
+# Consecutive frames of a sequence further apart than this start a new track.  Untuned as well.
+TRACK_MAX_GAP = 8
+REFINE_WEIGHTED = 1      # xas_hip.h XAS_REFINE_WEIGHTED
+
+STATUS_SMOOTHED, STATUS_FILLED, STATUS_PASSED = 0, 1, 2
+STATUS_NAMES = ('smoothed', 'gap filled', 'passed through')
+TRACK_STATUS_NAMES = ('converged', 'trial limit', 'passed through')
+
+_LAST_DIGITS = re.compile(r'(\d+)(?!.*\d)', re.S)
+
+
+def tracks_of(paths, max_gap=TRACK_MAX_GAP, count=None):
+    """paths: one image path per sample, or None with `count` samples -> (track [N] int64, frame [N] int64), numpy.
+    The sequence key of a path is the path with the last run of digits of its basename removed, the frame that run as an
+    integer (H36M: ..._ca_01_000123.jpg -> frame 123).  Consecutive frames of a key more than `max_gap` apart start a new track.
+    Tracks are numbered by the first appearance of their key, then by frame.  A frame that a key holds twice is an error.
+    Without paths all samples form one key and the frame is the running index."""
+    if paths is None:
+        keys, frames = [''] * int(count), list(range(int(count)))
+    else:
+        keys, frames = [], []
+        for p in paths:
+            head, base = os.path.split(str(p))
+            m = _LAST_DIGITS.search(base)
+            if m is None:
+                raise RuntimeError('tracks_of: no frame number in %r' % (p,))
+            keys.append(os.path.join(head, base[:m.start(1)] + base[m.end(1):]))
+            frames.append(int(m.group(1)))
+    by_key = {}
+    for i, k in enumerate(keys):
+        by_key.setdefault(k, []).append(i)
+    track, frame, next_id = np.zeros(len(keys), np.int64), np.asarray(frames, np.int64).reshape(-1), 0
+    for k, idx in by_key.items():                                      # dicts keep the order of first appearance
+        idx.sort(key=lambda i: frames[i])
+        for j, i in enumerate(idx):
+            if j:
+                step = frames[i] - frames[idx[j - 1]]
+                if step == 0:
+                    raise RuntimeError('tracks_of: frame %d of %r is there twice' % (frames[i], k))
+                if step > max_gap:
+                    next_id += 1
+            track[i] = next_id
+        next_id += 1
+    return track, frame
+
+
+def _prepare(name, points, pmat, init, track, frame, views):
+    points, pmat, init = (t.detach().float().contiguous() for t in (points, pmat, init))
+    if points.dim() != 4 or points.shape[-1] != 3:
+        raise RuntimeError('%s: points must be [N,V,K,3], got %s' % (name, tuple(points.shape)))
+    N, V, K, _ = points.shape
+    if pmat.shape != (N, V, 3, 4):
+        raise RuntimeError('%s: projection matrices %s do not match points %s' % (name, tuple(pmat.shape), tuple(points.shape)))
+    if init.shape != (N, K, 4):
+        raise RuntimeError('%s: start points %s do not match points %s' % (name, tuple(init.shape), tuple(points.shape)))
+    dev = points.device
+    track, frame = (torch.as_tensor(t).to(device=dev, dtype=torch.int64) for t in (track, frame))
+    if track.shape != (N,) or frame.shape != (N,):
+        raise RuntimeError('%s: track %s and frame %s are not one number per sample of points %s' % (
+            name, tuple(track.shape), tuple(frame.shape), tuple(points.shape)))
+    if views is not None and (views.shape != (N, K) or views.dtype != torch.uint8):
+        raise RuntimeError('%s: views %s %s are not the [N,K] uint8 masks of points %s' % (
+            name, tuple(views.shape), views.dtype, tuple(points.shape)))
+    order = torch.argsort(frame, stable=True)
+    order = order[torch.argsort(track[order], stable=True)]            # by (track, frame)
+    ts, fs = track[order], frame[order]
+    if N > 1 and bool(((ts[1:] == ts[:-1]) & (fs[1:] <= fs[:-1])).any()):
+        raise RuntimeError('%s: a track holds a frame twice (frame numbers must differ inside a track)' % name)
+    if int(fs.abs().max()) >= 1 << 31:
+        raise RuntimeError('%s: frame numbers must fit 32 bits' % name)
+    ids, counts = torch.unique_consecutive(ts, return_counts=True)     # the host reads: start is a host array
+    start = [0]
+    for c in counts.tolist():
+        start.append(start[-1] + int(c))
+    S = len(start) - 1
+    table = (ctypes.c_int * (S + 1))(*start)
+    points, pmat, init = points[order].contiguous(), pmat[order].contiguous(), init[order].contiguous()
+    views = None if views is None else views[order].contiguous()
+    ws = torch.empty(max(query('xas_track_smooth_workspace_bytes', N, K), 16), device=dev, dtype=torch.uint8)
+    return points, pmat, init, views, fs.to(torch.int32).contiguous(), order, ids, table, ws, N, V, K, S
+
+
+def _scatter(order, t):
+    out = torch.empty_like(t)
+    out[order] = t
+    return out
+
+
+def track_linearise(points, pmat, init, track, frame, views=None, weighted=False, huber_px=0.0, acc_w=TRACK_ACC_W, lam=0.0,
+                    workspace=None):
+    """One linearisation at the points of init (gap frames filled) with damping `lam` (xas_track_linearise) -> dict, float64:
+    band [N,K,3,9] (entry [n,k,c,o] = element (3 t + c, 3 t + c - o) of H + lam diag H, t = the position of sample n in its
+    track) and g [N,K,3] in the order given, C [S,K] and tracks [S] (the track numbers, ascending)."""
+    points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S = _prepare('track_linearise', points, pmat, init, track,
+                                                                                  frame, views)
+    dev = points.device
+    band = torch.empty(N, K, 3, 9, device=dev, dtype=torch.float64)
+    g = torch.empty(N, K, 3, device=dev, dtype=torch.float64)
+    C = torch.empty(S, K, device=dev, dtype=torch.float64)
+    call('xas_track_linearise', ptr(points), ptr(pmat), ptr(init), ptr(views), table, ptr(frame), N, V, K, S,
+         REFINE_WEIGHTED if weighted else 0, float(huber_px), float(acc_w), float(lam), ptr(band), ptr(g), ptr(C),
+         ptr(ws if workspace is None else workspace))
+    return {'band': _scatter(order, band), 'g': _scatter(order, g), 'C': C, 'tracks': ids}
+
+
+def track_smooth(points, pmat, init, track, frame, views=None, weighted=False, huber_px=0.0, acc_w=TRACK_ACC_W, max_iter=30,
+                 want=('status', 'resid', 'track_status', 'cost', 'trials'), workspace=None):
+    """points [N,V,K,3] (u, v, weight), pmat [N,V,3,4], init [N,K,4] and views [N,K] uint8 (or None) as for
+    ops_eval.triangulate_refine, over the whole evaluation set; track [N] and frame [N] integers in any order (tracks_of): the
+    samples are sorted by (track, frame) for the kernel and the per-sample results put back in the order given.  A frame twice in
+    a track is an error.  acc_w: weight of the squared acceleration, px^2 per (mm^2 / frame^3) (TRACK_ACC_W is an untuned guess).
+    `workspace`: a uint8 tensor of xas_track_smooth_workspace_bytes(N, K) bytes to use instead of a fresh one (tests).
+    -> dict: xyzw [N,K,4]; tracks [S] int64 (the track numbers, ascending: the rows of the per-track outputs); status [N,K]
+    uint8 (STATUS_*), resid [N,K,2] (px, before and after; NaN where there is no data), track_status [S,K] uint8, cost [S,K,2]
+    float64, trials [S,K] int32 as requested.  The semantics are those of include/xas_hip.h."""
+    points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S = _prepare('track_smooth', points, pmat, init, track,
+                                                                                  frame, views)
+    dev = points.device
+    sorted_out = torch.empty(N, K, 4, device=dev)
+    per_sample, out = {}, {'tracks': ids}
+    if 'status' in want:
+        per_sample['status'] = torch.empty(N, K, device=dev, dtype=torch.uint8)
+    if 'resid' in want:
+        per_sample['resid'] = torch.empty(N, K, 2, device=dev)
+    if 'track_status' in want:
+        out['track_status'] = torch.empty(S, K, device=dev, dtype=torch.uint8)
+    if 'cost' in want:
+        out['cost'] = torch.empty(S, K, 2, device=dev, dtype=torch.float64)
+    if 'trials' in want:
+        out['trials'] = torch.empty(S, K, device=dev, dtype=torch.int32)
+    call('xas_track_smooth', ptr(points), ptr(pmat), ptr(init), ptr(views), table, ptr(frame), N, V, K, S,
+         REFINE_WEIGHTED if weighted else 0, float(huber_px), float(acc_w), int(max_iter), ptr(sorted_out),
+         ptr(per_sample.get('status')), ptr(per_sample.get('resid')), ptr(out.get('track_status')), ptr(out.get('cost')),
+         ptr(out.get('trials')), ptr(ws if workspace is None else workspace))
+    out['xyzw'] = _scatter(order, sorted_out)
+    for k, v in per_sample.items():
+        out[k] = _scatter(order, v)
+    return out
