@@ -217,6 +217,10 @@ int xas_world_to_patch_bwd(const float* pts, const float* grad_out, const float*
  * parents/children: L int32 each (device).  fine_mask: bit l set -> exponent x2
  * (modules/util.py:50-53, applied by the host when L >= 21).
  * mask [B][1][S][S].   partial: workspace B*nblk*K*2 floats, nblk = xas_lines_nblk(S).
+ * Both passes take a pixel's line by one rule: the first line with a NaN exponent if there is
+ * one, else the first maximum.  A NaN or infinite joint therefore makes the whole mask of its
+ * sample NaN, and the backward sends NaN to both end points of every line that touches it
+ * (what exp, torch.max and autograd give); other samples are not affected.
  * ---------------------------------------------------------------------------------- */
 int xas_lines_nblk(int S);
 int xas_draw_lines_max_fwd(const float* kps, long kp_stride_b, long kp_stride_j, int B, int K,

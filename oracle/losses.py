@@ -6,13 +6,15 @@ _BONE_A = [16, 15, 13, 12, 3, 2, 6, 5]   # loss_func.py:20
 _BONE_B = [15, 14, 12, 11, 2, 1, 5, 4]
 
 
-def mask_recon(mask, gt, weight=None, use_clip=False):
+def mask_recon(mask, gt, weight=None, use_clip=False, clip_at=0.1):
     """loss_func.py:4-16.  NB: weight=None & use_clip=True returns a TENSOR
-    (scalar MSE x clip mask), reduced later by .mean() at train.py:182."""
+    (scalar MSE x clip mask), reduced later by .mean() at train.py:182.
+    `clip_at`: the threshold as the program's dtype sees it - on a float32 mask the literal 0.1 is
+    float32(0.1), which a float64 run has to be given explicitly to decide that one value alike."""
     sq = (mask - gt) ** 2
     loss = sq.mean() if weight is None else sq
     if use_clip:
-        loss = loss * (mask > 0.1).to(mask.dtype)
+        loss = loss * (mask > clip_at).to(mask.dtype)
     if weight is not None:
         loss = (loss * weight).mean()
     return loss

@@ -8,6 +8,8 @@
 //                  max_l exp(e_l) == exp(max_l e_l): one exp per pixel, nothing but the
 //                  [B,1,S,S] mask ever reaches HBM (the reference keeps ten 419 MB
 //                  intermediates for autograd).  Backward recomputes the winner line.
+#include <float.h>
+
 #include "common.h"
 
 namespace xas {
@@ -312,6 +314,20 @@ __device__ __forceinline__ float seg_exponent(const LineSeg& s, float gx, float 
   return (-d2 / body_width) * s.scale;
 }
 
+// The line a pixel takes its value from, for both passes: the first line whose exponent is NaN if there is one (a non-finite
+// joint makes the whole mask of its sample NaN, as exp(...) followed by torch.max gives), else the first maximum.
+struct LineWinner { float e, t; int line; };
+
+__device__ __forceinline__ LineWinner winning_line(const LineSeg* segs, int L, float gx, float gy, float body_width) {
+  LineWinner w = {-INFINITY, 0.f, 0};
+  for (int l = 0; l < L; ++l) {
+    float t;
+    const float ex = seg_exponent(segs[l], gx, gy, body_width, &t);
+    if (ex > w.e || (ex != ex && w.e == w.e)) { w.e = ex; w.t = t; w.line = l; }      // a NaN wins and stays
+  }
+  return w;
+}
+
 __global__ void draw_lines_max_fwd_kernel(const float* __restrict__ kps, long sb, long sj, const int* parents,
                                           const int* children, int L, unsigned fine, float body_width, int S,
                                           float* __restrict__ mask) {
@@ -326,9 +342,7 @@ __global__ void draw_lines_max_fwd_kernel(const float* __restrict__ kps, long sb
   for (int q = 0; q < kPixPerThread; ++q) {
     const int pix = pix0 + q;
     const float gx = 2.f * ((float)(pix % S) / fs) - 1.f, gy = 2.f * ((float)(pix / S) / fs) - 1.f;
-    float best = -INFINITY, t;
-    for (int l = 0; l < L; ++l) best = fmaxf(best, seg_exponent(segs[l], gx, gy, body_width, &t));
-    out[q] = __expf(best);
+    out[q] = __expf(winning_line(segs, L, gx, gy, body_width).e);
   }
   float* o = mask + (size_t)b * S * S + pix0;
   if (pix0 + kPixPerThread <= S * S && ((S * S) % kPixPerThread) == 0) {
@@ -363,16 +377,12 @@ __global__ void draw_lines_max_bwd_kernel(const float* __restrict__ kps, long sb
     if (pix < S * S) {
       const float go = gmask[(size_t)b * S * S + pix];
       const float gx = 2.f * ((float)(pix % S) / fs) - 1.f, gy = 2.f * ((float)(pix / S) / fs) - 1.f;
-      float best = -INFINITY, bt = 0.f, t;
-      int win = 0;
-      for (int l = 0; l < L; ++l) {
-        const float ex = seg_exponent(segs[l], gx, gy, body_width, &t);
-        if (ex > best) { best = ex; win = l; bt = t; }     // first maximum wins, as torch.max
-      }
-      const float ge = go * __expf(best);
+      const LineWinner w = winning_line(segs, L, gx, gy, body_width);
+      const float bt = w.t;
+      const float ge = go * __expf(w.e);
       if (ge != 0.f) {
-        bl = win;
-        const LineSeg s = segs[win];
+        bl = w.line;
+        const LineSeg s = segs[w.line];
         const float gd2 = -ge * s.scale / body_width;
         if (bt <= 0.f) {
           gax = -2.f * (gx - s.ax) * gd2; gay = -2.f * (gy - s.ay) * gd2;
@@ -401,6 +411,9 @@ __global__ void draw_lines_max_bwd_kernel(const float* __restrict__ kps, long sb
       if (rec_line[e] == l) { s0 += rec_g[0][e]; s1 += rec_g[1][e]; s2 += rec_g[2][e]; s3 += rec_g[3][e]; }
     }
     s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
+    // A line with a non-finite end point (den is then non-finite too) has a NaN exponent at every pixel; autograd sends NaN to
+    // both its end points whether or not it is the winner (0 * NaN), and so does this.
+    if (!(fabsf(segs[l].den) <= FLT_MAX)) s0 = s1 = s2 = s3 = NAN;
     if (lane == 0) { line_sum[l][0] = s0; line_sum[l][1] = s1; line_sum[l][2] = s2; line_sum[l][3] = s3; }
   }
   __syncthreads();
@@ -516,7 +529,9 @@ extern "C" int xas_draw_lines_max_bwd(const float* kps, long kp_stride_b, long k
                                       float body_width, int S, const float* grad_mask, float* partial,
                                       float* grad_kps_xy, void* stream) {
   XAS_REQUIRE(kps && parents && children && grad_mask && partial && grad_kps_xy, "draw_lines bwd: null buffer");
-  XAS_REQUIRE(L >= 1 && L <= kMaxLines && K >= 1 && K <= 64 && S >= 2 && B >= 1, "draw_lines bwd: bad shape");
+  XAS_REQUIRE(L >= 1 && L <= kMaxLines && K >= 1 && K <= 64 && S >= 2 && B >= 1, "draw_lines bwd: bad shape L=%d K=%d S=%d", L, K,
+              S);
+  XAS_REQUIRE(body_width > 0.f, "draw_lines bwd: body_width must be > 0");
   const int nblk = xas_lines_nblk(S);
   hipLaunchKernelGGL(draw_lines_max_bwd_kernel, dim3(nblk, B), dim3(kLineThreads), 0, as_stream(stream), kps,
                      kp_stride_b, kp_stride_j, parents, children, L, fine_mask, body_width, S, K, grad_mask, partial);
