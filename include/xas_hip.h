@@ -998,6 +998,42 @@ int xas_track_smooth(const float* points, const float* P, const float* init, con
                      float* out, unsigned char* status, float* resid, unsigned char* track_status, double* cost, int* trials,
                      void* workspace, void* stream);
 
+/* Depth hypothesis and left/right exchange of ONE camera chosen over time (eval.py --resolve-track OUT.npz; the reference has
+ * no counterpart, and no labels are read).  kps [N][Hy][K][3] the detector's patch-normalised joints, world [N][Hy][K][3] their
+ * single-view world points in mm, unary [N][Hy][K] an extra cost per candidate or NULL (= 0), all fp32 on the device; N counts
+ * the samples of the whole set, sorted by track and frame; start [S+1] and frame [N] exactly as for xas_track_smooth.
+ * perm [K] int32, a HOST array like start, read before the launch (the kernel receives it by value, so no device copy exists
+ * that could differ from what was checked): an involution, perm[perm[k]] = k, as ops_eval.switch_perm builds it.
+ * A UNIT is a pair (a, b = perm[a]), a < b, or a joint k = perm[k].  The state of a pair at a frame is (e, h0, h1), e in
+ * {0, 1}, h0 and h1 in [0, Hy), index e Hy^2 + h0 Hy + h1: joint a is candidate h0 of channel (e ? b : a), joint b candidate
+ * h1 of channel (e ? a : b).  The state of a single joint is h.  A frame is USABLE for a unit if every coordinate of every
+ * candidate of the unit's channels in world, and every such value of unary if given, is finite.  Over the usable frames
+ * t0 < t1 < ... of the track, in double from the fp32 inputs, with Xa, Xb the world points the state reads and ua, ub their
+ * unary values,
+ *   C = sum_t [ hyp_w (h0 + h1) + swap_w e + ua + ub ]
+ *     + vel_w sum over consecutive usable (t', t) of (|Xa_t - Xa_t'|^2 + |Xb_t - Xb_t'|^2) / (frame_t - frame_t')
+ * (a random walk: an unusable frame is bridged with the variance of the gap; a single joint has no e and no b terms).  The
+ * result is an exact minimiser (Viterbi); among equal costs the smallest predecessor index at every frame and the smallest end
+ * state.  A unit with fewer than two usable frames is PASSED THROUGH: hypothesis 0, not exchanged, status 1, cost 0; so is an
+ * unusable frame of a resolved unit, for that frame only.
+ *   sel [N][K][3] (required)   the chosen candidate's entry of kps, bit for bit: the layout of xas_eval_select's sel3d
+ *   hyp, swap, status [N][K] bytes, each may be NULL: the hypothesis, the exchange bit (both joints of a pair carry it),
+ *                              0 = resolved / 1 = passed through
+ *   cost [S][K] double or NULL C of the unit (both joints of a pair carry it)
+ * workspace: xas_track_resolve_workspace_bytes(N, Hy, K) bytes (0 for a shape outside the limits, else a multiple of 16),
+ * 16-byte aligned; its content before the call does not matter.  It holds start and one back-pointer byte per frame and state.
+ * Limits: 1 <= Hy <= XAS_TRACK_MAX_HYPO (2 Hy^2 states are the lanes of one wave), 1 <= K <= XAS_TRACK_MAX_JOINTS, N > 0,
+ * N*K < 2^31, 1 <= S <= N; vel_w, hyp_w, swap_w finite and >= 0; no output may overlap kps, world, unary or frame.
+ * One wave per (track, unit); one launch after the copy of start, no host synchronisation, no atomics: two calls on the same
+ * inputs give the same bits in every output, and the inputs are not written. */
+#define XAS_TRACK_MAX_HYPO 5
+#define XAS_TRACK_MAX_JOINTS 64
+size_t xas_track_resolve_workspace_bytes(int N, int Hy, int K);
+int xas_track_resolve(const float* kps, const float* world, const float* unary, const int* perm, const int* start,
+                      const int* frame, int N, int Hy, int K, int S, double vel_w, double hyp_w, double swap_w, float* sel,
+                      unsigned char* hyp, unsigned char* swap, unsigned char* status, double* cost, void* workspace,
+                      void* stream);
+
 /* Volumetric fusion of the views' heat-map cubes (eval.py --tri-volume; the reference has no counterpart).  Every other
  * triangulation here starts from ONE point per view, the soft-argmax of that view's heat-map; this one multiplies the views'
  * whole distributions over a voxel grid round the triangulated point (a product of experts) and takes the soft-argmax of the

@@ -20,10 +20,11 @@
 #include <math.h>
 
 #include "multiview.h"
+#include "track_start.h"
 
 namespace xas {
 
-constexpr int kTsV = XAS_TRI_MAX_VIEWS, kTsChunk = 512;
+constexpr int kTsV = XAS_TRI_MAX_VIEWS;
 // offsets of the arrays of a wave's record, in units of T doubles
 constexpr int kTsX = 0, kTsD = 6, kTsG = 18, kTsR2 = 24, kTsA = 26, kTsL = 29, kTsDX = 53, kTsUsed = 56, kTsRec = 57;
 enum { TS_SMOOTH, TS_LINEARISE };
@@ -43,14 +44,6 @@ struct TsOut {
   int* trials;
   double *band, *g, *C, lambda;                                       // linearise
 };
-struct TsStart {
-  int v[kTsChunk];
-};
-
-__global__ __launch_bounds__(256) void track_start_kernel(TsStart c, int first, int count, int* __restrict__ dst) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) dst[first + i] = c.v[i];
-}
 
 // A frame's observations in registers, every loop over the views unrolled and predicated as in triangulate_refine_kernel.
 struct TsObs {
@@ -479,9 +472,6 @@ __global__ __launch_bounds__(64) void track_smooth_kernel(TsArgs a, TsOut o, int
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-static inline size_t ts_align(size_t b) { return (b + 15) & ~(size_t)15; }
-static inline size_t ts_table_bytes(long N) { return ts_align((size_t)(N + 1) * sizeof(int)); }
-
 // The checks the two entry points share, the copy of `start` into the workspace and the kernel's arguments.
 static int ts_plan(const char* who, const float* points, const float* P, const float* init, const unsigned char* views,
                    const int* start, const int* frame, int N, int V, int K, int S, int flags, float huber, double acc_w,
@@ -489,25 +479,14 @@ static int ts_plan(const char* who, const float* points, const float* P, const f
   XAS_REQUIRE(points && P && init && start && frame && workspace,
               "%s: null buffer (points, P, init, start, frame and workspace are required)", who);
   if (tri_check_views(who, V, 2) || tri_check_shape(who, N, K, "N > 0, K >= 1")) return 1;
-  XAS_REQUIRE(S >= 1 && S <= N && (long)S * K <= 0x7fffffffL, "%s: S=%d tracks (needs 1 <= S <= N = %d, S*K < 2^31)", who, S, N);
-  XAS_REQUIRE(start[0] == 0 && start[S] == N, "%s: start runs from %d to %d (needs start[0] = 0 and start[S] = N = %d)", who,
-              start[0], start[S], N);
-  for (int t = 0; t < S; ++t)
-    XAS_REQUIRE(start[t] < start[t + 1], "%s: start[%d] = %d >= start[%d] = %d (needs an increasing start: every track has a sample)",
-                who, t, start[t], t + 1, start[t + 1]);
+  if (track_check_start(who, start, N, K, S)) return 1;
   XAS_REQUIRE((flags & ~XAS_REFINE_WEIGHTED) == 0, "%s: unknown flag bits 0x%x (XAS_REFINE_WEIGHTED = %d is the only flag)", who,
               flags & ~XAS_REFINE_WEIGHTED, XAS_REFINE_WEIGHTED);
   XAS_REQUIRE(acc_w >= 0.0 && acc_w < INFINITY, "%s: acc_w %f (needs a finite acc_w >= 0)", who, acc_w);
   XAS_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace is not 16-byte aligned", who);
   int* table = (int*)workspace;
-  for (int first = 0; first <= S; first += kTsChunk) {
-    TsStart c;
-    const int count = S + 1 - first < kTsChunk ? S + 1 - first : kTsChunk;
-    for (int i = 0; i < kTsChunk; ++i) c.v[i] = i < count ? start[first + i] : 0;
-    hipLaunchKernelGGL(track_start_kernel, dim3((unsigned)cdiv(count, 256)), dim3(256), 0, s, c, first, count, table);
-    XAS_LAUNCH_CHECK();
-  }
-  a = TsArgs{points, P, init, views, frame, table, (double*)((char*)workspace + ts_table_bytes(N)), N, V, K, S, flags, 1,
+  if (int e = track_copy_start(start, S, table, s)) return e;
+  a = TsArgs{points, P, init, views, frame, table, (double*)((char*)workspace + track_table_bytes(N)), N, V, K, S, flags, 1,
              (double)huber, acc_w};
   return 0;
 }
@@ -518,7 +497,7 @@ using namespace xas;
 
 extern "C" size_t xas_track_smooth_workspace_bytes(int N, int K) {
   if (!(N > 0 && K > 0 && (long)N * K <= 0x7fffffffL)) return 0;
-  return ts_table_bytes(N) + (size_t)N * K * kTsRec * sizeof(double);
+  return track_table_bytes(N) + (size_t)N * K * kTsRec * sizeof(double);
 }
 
 extern "C" int xas_track_linearise(const float* points, const float* P, const float* init, const unsigned char* views,

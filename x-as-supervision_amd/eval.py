@@ -203,6 +203,17 @@ class Eval:
             self.smooth_gap = int(mp.get('smooth_gap', ops_track.TRACK_MAX_GAP))
             self.smooth_iters = int(mp.get('smooth_iters', 30))
             self.smooth_rows = []                      # per batch, on the device: points, pmat, init, views, gt; and the paths
+        self.resolve_track = mp.get('resolve_track') or None   # --resolve-track OUT.npz: hypothesis and exchange chosen over time, per camera
+        if self.resolve_track:
+            if int(os.environ.get('WORLD_SIZE', 1)) != 1:
+                raise ValueError('resolve_track needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out '
+                                 'over the ranks, and no rank sees a track')
+            from xas_amd import ops_track              # only with the flag
+            self.rt_vel = float(mp.get('rt_vel', ops_track.TRACK_VEL_W))                             # untuned guesses, all four
+            self.rt_hyp = float(mp.get('rt_hyp', ops_track.TRACK_HYP_W))
+            self.rt_swap = float(mp.get('rt_swap', ops_track.TRACK_SWAP_W))
+            self.rt_gap = int(mp.get('rt_gap', ops_track.TRACK_MAX_GAP))
+            self.rt_rows = []                          # per batch, on the device: per camera kps, world, labels, view; gt; and the paths
         if self.calibration:
             with np.load(self.calibration) as f:
                 self.calib_keys = torch.from_numpy(f['keys']).to(self.gpu_id)
@@ -268,6 +279,44 @@ class Eval:
                                                             float((status == ops_track.STATUS_FILLED).float().mean()),
                                                             float((status == ops_track.STATUS_PASSED).float().mean())),
                 'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(mean(e_after, filled), int(filled.sum()))]
+
+    def write_resolve_track(self):
+        """--resolve-track: one track_resolve per camera over everything the batches kept, the file (atomically: a temporary
+        file beside it, then a rename) and -> the lines of eval_result.txt, one per camera."""
+        from xas_amd import ops_track
+        rows = self.rt_rows
+        gt = torch.cat([r['gt'] for r in rows])
+        err = lambda p: pose_errors(torch.where(torch.isfinite(p), p, torch.zeros_like(p)), gt, want=('err',))['err'][0]   # [N,K] mm, no alignment
+        mean = lambda e, m: float(e[m].mean()) if bool(m.any()) else float('nan')
+        cols, lines = {}, []
+        for c in self.cam_id_list:
+            m = 'cam_{}'.format(c)
+            cat = lambda k: torch.cat([r[m][k] for r in rows])
+            kps, world, view = cat('kps'), cat('world'), cat('view')
+            paths = [p for r in rows for p in r[m]['paths']] if rows[0][m]['paths'] is not None else None
+            track, frame = ops_track.tracks_of(paths, self.rt_gap, count=len(kps))
+            r = ops_track.track_resolve(kps, world, track, frame, vel_w=self.rt_vel, hyp_w=self.rt_hyp, swap_w=self.rt_swap,
+                                        gt=cat('labels'), image_size=self.img_size)
+            perm = ops_eval.switch_perm(kps.shape[2], ops_eval.SWITCH_PAIRS, kps.device)
+            joints = ops_track.resolved_gather(world, r['hyp'], r['swap'], perm)[..., :3].contiguous()
+            first = world[:, 0, :, :3].contiguous()
+            ok = torch.isfinite(joints).all(-1) & torch.isfinite(first).all(-1) & torch.isfinite(view).all(-1)
+            for k, v in (('joints', joints), ('sel', r['sel']), ('hyp', r['hyp']), ('swap', r['swap']), ('status', r['status']),
+                         ('cost', r['cost']), ('named', r['named'])):
+                cols['{}_{}'.format(m, k)] = v.cpu().numpy()
+            cols[m + '_track'], cols[m + '_frame'] = track, frame
+            S = len(r['tracks'])
+            paired = perm.long() != torch.arange(len(perm), device=perm.device)
+            lines.append('RESOLVE track {}: {} tracks of mean length {} (vel {}, hyp {}, swap {}, gap {}): MPJPE hypothesis 0 as given {} '
+                         '-> {} mm ({} with labels: {} mm), exchanged {} , hypothesis 0 kept {} , passed through {}'.format(
+                             m, S, len(kps) / S, self.rt_vel, self.rt_hyp, self.rt_swap, self.rt_gap, mean(err(first), ok),
+                             mean(err(joints), ok), rows[0]['mode'], mean(err(view), ok), float(r['swap'][:, paired].float().mean()),
+                             float((r['hyp'] == 0).float().mean()), float((r['status'] == ops_track.RESOLVE_PASSED).float().mean())))
+        os.makedirs(os.path.dirname(os.path.abspath(self.resolve_track)), exist_ok=True)
+        tmp = self.resolve_track + '.tmp.npz'
+        np.savez(tmp, **cols)
+        os.replace(tmp, self.resolve_track)
+        return lines
 
     def fit_batch(self, joints, bad, cov):
         """--fit-smpl on the final world joints [B,18,3] of a batch.  A joint's weight is 0 where it is not finite or `bad`
@@ -348,6 +397,7 @@ class Eval:
             x = apply_calibration(x, self.cam_id_list, self.calib_keys, self.calib_delta)
         weights = {} if self.tri_weight == 'spread' else None
         cubes, chan = ({}, []) if self.tri_volume else (None, None)
+        raw_kps = {} if self.resolve_track else None   # --resolve-track: every camera's detections as they came
 
         def detect(m):                             # one camera's joints; spread: also its weights, which need the detector
             kps = self.detect(x[m + '_img']) if kps_by_cam is None or weights is not None or cubes is not None else None
@@ -359,6 +409,8 @@ class Eval:
 
         if self.resolve == 'views':
             raw = {m: detect(m) for m in cams}
+            if raw_kps is not None:
+                raw_kps.update(raw)
             sel, r = resolve_views_weighted(raw, x, self.cam_id_list, ops_eval.SWITCH_PAIRS, weights, gt=True)   # None: the depth
             for m in cams:                         # the labels' part from here on: measuring, no longer choosing
                 out['err2d_' + m] = ops_eval.eval_select(sel[m].unsqueeze(1), x[m + '_joints'], image_size=self.img_size,
@@ -377,6 +429,8 @@ class Eval:
                 chan = [torch.where(((r['swap'].int() >> v) & 1).bool(), perm, own) for v in range(len(cams))]
         for m in ([] if self.resolve == 'views' else cams):
             kps = detect(m)
+            if raw_kps is not None:
+                raw_kps[m] = kps
             s = ops_eval.eval_select(kps, x[m + '_joints'], image_size=self.img_size, mode=mode)
             sel[m] = s['sel3d']
             out['err2d_' + m] = s['err2d']
@@ -390,7 +444,9 @@ class Eval:
         gt = convert_patch_to_world(given['cam_0_joints'], given, 'cam_0', is_norm=False)  # eval.py:170
         fit_bad = fit_cov = None                   # --fit-smpl only: joints a solver passed through, and a covariance if one came
         fit_want = (('status',) + (('cov',) if weights is not None and self.tri_refine == 'lm' else ())) if self.fit_smpl else ()
-        if self.tri_refine == 'lm':                # the same solver, then the pixel error minimised over the views it used
+        if len(cams) == 1 and self.tri == 'dlt' and self.tri_refine == 'none':     # one camera: nothing to triangulate, its own point
+            tri = convert_patch_to_world(sel[cams[0]], x, cams[0], is_norm=True)[..., :3]            # (the DLT refuses one view)
+        elif self.tri_refine == 'lm':              # the same solver, then the pixel error minimised over the views it used
             tri, r = triangulation_refined(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, want=('resid',) + fit_want,
                                            robust_px=self.tri_thresh if self.tri == 'robust' else None)
             used = r.get('inliers')
@@ -450,6 +506,16 @@ class Eval:
                 out['pck_' + name] = q['pck'].mean()
                 out['auc_' + name] = (q['auc_hits'].sum(dim=0).float() / q['pck'].numel()).mean() * 100
         out['world_gt'], out['world_tri'] = gt, preds['tri']
+        if self.resolve_track:                     # kept on the device for the one pass per camera after the loop, as --smooth keeps its rows
+            row = {'gt': gt[..., :3].contiguous(), 'mode': 'views' if self.resolve == 'views' else mode}
+            for m in cams:
+                paths = x.get(m + '_img_path')
+                if paths is None:                  # the cameras of a sample show the same frame
+                    paths = x.get(cams[0] + '_img_path')
+                row[m] = {'kps': raw_kps[m].detach().float().contiguous(), 'labels': x[m + '_joints'],
+                          'world': convert_patch_to_world(raw_kps[m], x, m, is_norm=True)[..., :3].contiguous(),
+                          'view': preds['view_' + m][..., :3].contiguous(), 'paths': None if paths is None else [str(p) for p in paths]}
+            self.rt_rows.append(row)
         if self.fit_smpl:                          # after everything else, on the final world joints
             if len(cams) > 1:
                 out.update(self.fit_batch(preds['tri'][..., :3].contiguous(), fit_bad, fit_cov))
@@ -564,6 +630,8 @@ class Eval:
             lines.extend(self.write_calibration())
         if self.smooth:                            # after everything else; without --smooth the file is as it was
             lines.extend(self.write_smooth())
+        if self.resolve_track:                     # after everything else; without --resolve-track the file is as it was
+            lines.extend(self.write_resolve_track())
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -758,9 +826,32 @@ def mirror_smooth_options(config, opt):
             mp[key] = getattr(opt, key)
 
 
+CLI_RESOLVE_TRACK = (  # --resolve-track and its settings, parsed after CLI_SMOOTH (a table of their own, as above)
+    ('--resolve-track', dict(default=None, metavar='OUT.npz', dest='resolve_track',
+                             help='after everything above, per camera and without labels: choose every joint\'s depth hypothesis '
+                                  'and every limb pair\'s left/right exchange over the frames of its sequence (motion cost + priors, '
+                                  'exact by dynamic programming; works with one camera; needs one rank)')),
+    ('--rt-vel', dict(default=None, type=float, metavar='W', dest='rt_vel',
+                      help='--resolve-track: weight of the squared jump between frames, cost per (mm^2 / frame) (untuned default)')),
+    ('--rt-hyp', dict(default=None, type=float, metavar='W', dest='rt_hyp',
+                      help='--resolve-track: cost of one rank step away from hypothesis 0 (untuned default)')),
+    ('--rt-swap', dict(default=None, type=float, metavar='W', dest='rt_swap',
+                       help='--resolve-track: cost of an exchanged pair in a frame (untuned default)')),
+    ('--rt-gap', dict(default=None, type=int, metavar='FRAMES', dest='rt_gap',
+                      help='--resolve-track: frames of a sequence further apart than this start a new track (untuned default)')),
+)
+
+
+def mirror_resolve_track_options(config, opt):
+    """The --resolve-track flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_track)."""
+    for key in ('resolve_track', 'rt_vel', 'rt_hyp', 'rt_swap', 'rt_gap'):
+        if getattr(opt, key) is not None:
+            config['model_params'][key] = getattr(opt, key)
+
+
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -777,6 +868,7 @@ def main():
     mirror_fit_options(config, opt)
     mirror_calib_options(config, opt)
     mirror_smooth_options(config, opt)
+    mirror_resolve_track_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

@@ -174,6 +174,8 @@ SIGNATURES = {
     'xas_track_smooth_workspace_bytes': ('ii', 'z'),
     'xas_track_linearise': ('pppppp' 'iiiii' 'f' 'dd' 'ppp' 'pp', 'i'),
     'xas_track_smooth': ('pppppp' 'iiiii' 'f' 'd' 'i' 'pppppp' 'pp', 'i'),
+    'xas_track_resolve_workspace_bytes': ('iii', 'z'),
+    'xas_track_resolve': ('pppppp' 'iiii' 'ddd' 'ppppp' 'pp', 'i'),
     'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),
     'xas_multiview_consistency_fwd': ('pppppiiiiffipppppp', 'i'),
     'xas_multiview_consistency_bwd': ('pppppppiiiiffippp', 'i'),

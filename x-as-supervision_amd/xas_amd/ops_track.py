@@ -1,8 +1,9 @@
 """Temporal smoothing of triangulated joint tracks on the device (csrc/track_smooth.hip, xas_track_smooth): per (track, joint)
 the reprojection cost of ops_eval.triangulate_refine in every frame that has data plus a penalty on the acceleration, by a
 double-precision Levenberg-Marquardt over all frames of the track at once (block-pentadiagonal Cholesky); frames without data
-are filled in from their neighbours.  include/xas_hip.h states the problem and the schedule.  Imported only when eval.py is given
---smooth.  No reference counterpart."""
+are filled in from their neighbours.  include/xas_hip.h states the problem and the schedule.  Below it, one camera's depth
+hypothesis and left/right exchange chosen over the frames of a track (csrc/track_resolve.hip, xas_track_resolve).  Imported only
+when eval.py is given --smooth or --resolve-track.  No reference counterpart."""
 import ctypes
 import os
 import re
@@ -11,6 +12,7 @@ import numpy as np
 import torch
 
 from xas_amd._lib import call, ptr, query
+from xas_amd.ops_eval import SWITCH_PAIRS, switch_perm
 
 # Weight of the squared acceleration, in px^2 per (mm^2 / frame^3): about 4 mm / frame^2 of acceleration on the scale of a 1 px
 # residual (0.05 * 4.5^2 = 1).  AN UNTUNED GUESS: there is neither a dataset nor a checkpoint here to tune it on.
@@ -61,6 +63,25 @@ def tracks_of(paths, max_gap=TRACK_MAX_GAP, count=None):
     return track, frame
 
 
+def _by_track(name, track, frame):
+    """track, frame [N] int64 on the device -> (order [N]: the samples by (track, frame); frame[order] as int32; the track
+    numbers, ascending; start [S+1] as the HOST array the kernels take; S).  A frame twice in a track is an error."""
+    N = track.shape[0]
+    order = torch.argsort(frame, stable=True)
+    order = order[torch.argsort(track[order], stable=True)]            # by (track, frame)
+    ts, fs = track[order], frame[order]
+    if N > 1 and bool(((ts[1:] == ts[:-1]) & (fs[1:] <= fs[:-1])).any()):
+        raise RuntimeError('%s: a track holds a frame twice (frame numbers must differ inside a track)' % name)
+    if int(fs.abs().max()) >= 1 << 31:
+        raise RuntimeError('%s: frame numbers must fit 32 bits' % name)
+    ids, counts = torch.unique_consecutive(ts, return_counts=True)     # the host reads: start is a host array
+    start = [0]
+    for c in counts.tolist():
+        start.append(start[-1] + int(c))
+    S = len(start) - 1
+    return order, fs.to(torch.int32).contiguous(), ids, (ctypes.c_int * (S + 1))(*start), S
+
+
 def _prepare(name, points, pmat, init, track, frame, views):
     points, pmat, init = (t.detach().float().contiguous() for t in (points, pmat, init))
     if points.dim() != 4 or points.shape[-1] != 3:
@@ -78,23 +99,11 @@ def _prepare(name, points, pmat, init, track, frame, views):
     if views is not None and (views.shape != (N, K) or views.dtype != torch.uint8):
         raise RuntimeError('%s: views %s %s are not the [N,K] uint8 masks of points %s' % (
             name, tuple(views.shape), views.dtype, tuple(points.shape)))
-    order = torch.argsort(frame, stable=True)
-    order = order[torch.argsort(track[order], stable=True)]            # by (track, frame)
-    ts, fs = track[order], frame[order]
-    if N > 1 and bool(((ts[1:] == ts[:-1]) & (fs[1:] <= fs[:-1])).any()):
-        raise RuntimeError('%s: a track holds a frame twice (frame numbers must differ inside a track)' % name)
-    if int(fs.abs().max()) >= 1 << 31:
-        raise RuntimeError('%s: frame numbers must fit 32 bits' % name)
-    ids, counts = torch.unique_consecutive(ts, return_counts=True)     # the host reads: start is a host array
-    start = [0]
-    for c in counts.tolist():
-        start.append(start[-1] + int(c))
-    S = len(start) - 1
-    table = (ctypes.c_int * (S + 1))(*start)
+    order, frame, ids, table, S = _by_track(name, track, frame)
     points, pmat, init = points[order].contiguous(), pmat[order].contiguous(), init[order].contiguous()
     views = None if views is None else views[order].contiguous()
     ws = torch.empty(max(query('xas_track_smooth_workspace_bytes', N, K), 16), device=dev, dtype=torch.uint8)
-    return points, pmat, init, views, fs.to(torch.int32).contiguous(), order, ids, table, ws, N, V, K, S
+    return points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S
 
 
 def _scatter(order, t):
@@ -152,4 +161,94 @@ def track_smooth(points, pmat, init, track, frame, views=None, weighted=False, h
     out['xyzw'] = _scatter(order, sorted_out)
     for k, v in per_sample.items():
         out[k] = _scatter(order, v)
+    return out
+
+
+# ---- depth hypothesis and left/right exchange over time (csrc/track_resolve.hip, xas_track_resolve) --------------------------
+# One camera, no labels: per track and unit (a left/right pair, or a joint without partner) the exact minimum over all
+# labellings of a motion cost in world mm plus priors towards hypothesis 0 and towards "not exchanged".  The weights: one rank
+# step or one exchange costs what a jump of 20 mm between consecutive frames costs (400 = 20^2).  UNTUNED GUESSES from a
+# synthetic float64 experiment (decoys 250-600 mm along the ray, 5 mm noise): there is neither a dataset nor a checkpoint here.
+TRACK_VEL_W = 1.0
+TRACK_HYP_W = 400.0
+TRACK_SWAP_W = 400.0
+TRACK_MAX_HYPO = 5       # xas_hip.h XAS_TRACK_MAX_HYPO
+RESOLVE_RESOLVED, RESOLVE_PASSED = 0, 1
+RESOLVE_STATUS_NAMES = ('resolved', 'passed through')
+
+
+def resolved_gather(x, hyp, swap, perm):
+    """x [N,Hy,K,C] -> [N,K,C]: joint k from hypothesis hyp[n,k] of channel perm[k] where swap[n,k], else of channel k."""
+    N, _, K, _ = x.shape
+    own = torch.arange(K, device=x.device)
+    chan = torch.where(swap.bool(), perm.long().unsqueeze(0), own.unsqueeze(0))
+    return x[torch.arange(N, device=x.device).unsqueeze(1), hyp.long(), chan]
+
+
+def track_resolve(kps, world, track, frame, pairs=SWITCH_PAIRS, unary=None, vel_w=TRACK_VEL_W, hyp_w=TRACK_HYP_W,
+                  swap_w=TRACK_SWAP_W, gt=None, image_size=256.0, want=('hyp', 'swap', 'status', 'cost'), workspace=None):
+    """kps [N,Hy,K,3] (one camera's patch-normalised joints) and world [N,Hy,K,3] (their single-view world points, mm) over the
+    whole evaluation set, unary [N,Hy,K] an extra cost per candidate or None; track [N] and frame [N] integers in any order
+    (tracks_of): the samples are sorted by (track, frame) for the kernel and the per-sample results put back in the order
+    given.  A frame twice in a track is an error.  The cost, the states and the rules are those of include/xas_hip.h.
+    gt [N,K,>=2] labels in patch pixels or None.  They only NAME each pair, once per track: if the track's summed |dx| + |dy|
+    of both joints against the labels (normalised with image_size as eval_select does; the measure of switch_points) is
+    strictly smaller with every exchange bit of the track flipped, all are flipped (passed-through frames too) and
+    named[s, a] = named[s, b] = 1.  Flipped means the mirror labelling, which costs the same motion: the two curves stay as
+    chosen and trade their names, so sel and hyp of a and b trade places.  One bit per (track, pair), never per frame; a
+    few torch ops on the device.
+    `workspace`: a uint8 tensor of xas_track_resolve_workspace_bytes(N, Hy, K) bytes to use instead of a fresh one (tests).
+    -> dict: sel [N,K,3]; tracks [S] int64 (the track numbers, ascending: the rows of the per-track outputs); hyp, swap, status
+    [N,K] uint8 (RESOLVE_*) and cost [S,K] float64 as requested; named [S,K] uint8 with gt."""
+    kps, world = (t.detach().float().contiguous() for t in (kps, world))
+    if kps.dim() != 4 or kps.shape[-1] != 3:
+        raise RuntimeError('track_resolve: kps must be [N,Hy,K,3], got %s' % (tuple(kps.shape),))
+    N, Hy, K, _ = kps.shape
+    if world.shape != kps.shape:
+        raise RuntimeError('track_resolve: world %s and kps %s differ' % (tuple(world.shape), tuple(kps.shape)))
+    if unary is not None and unary.shape != (N, Hy, K):
+        raise RuntimeError('track_resolve: unary %s is not one value per candidate of kps %s' % (tuple(unary.shape), tuple(kps.shape)))
+    if gt is not None and (gt.dim() != 3 or gt.shape[:2] != (N, K) or gt.shape[2] < 2):
+        raise RuntimeError('track_resolve: labels %s do not match kps %s' % (tuple(gt.shape), tuple(kps.shape)))
+    dev = kps.device
+    track, frame = (torch.as_tensor(t).to(device=dev, dtype=torch.int64) for t in (track, frame))
+    if track.shape != (N,) or frame.shape != (N,):
+        raise RuntimeError('track_resolve: track %s and frame %s are not one number per sample of kps %s' % (
+            tuple(track.shape), tuple(frame.shape), tuple(kps.shape)))
+    order, frame, ids, table, S = _by_track('track_resolve', track, frame)
+    kps, world = kps[order].contiguous(), world[order].contiguous()
+    unary = None if unary is None else unary.detach().float()[order].contiguous()
+    perm = switch_perm(K, pairs, dev)
+    host_perm = (ctypes.c_int * K)(*perm.tolist())                     # a HOST array, like start (xas_hip.h)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(query('xas_track_resolve_workspace_bytes', N, Hy, K), 16), device=dev, dtype=torch.uint8)
+    sel = torch.empty(N, K, 3, device=dev)
+    byte = lambda name: torch.empty(N, K, device=dev, dtype=torch.uint8) if name in want or (gt is not None and name != 'status') else None
+    hyp, swap, status = byte('hyp'), byte('swap'), byte('status')
+    cost = torch.empty(S, K, device=dev, dtype=torch.float64) if 'cost' in want else None
+    call('xas_track_resolve', ptr(kps), ptr(world), ptr(unary), host_perm, table, ptr(frame), N, Hy, K, S, float(vel_w),
+         float(hyp_w), float(swap_w), ptr(sel), ptr(hyp), ptr(swap), ptr(status), ptr(cost), ptr(ws))
+    out = {'tracks': ids}
+    if gt is not None:
+        g = gt.detach().float()[order][..., :2] / (float(image_size) - 1.0) * 2.0 - 1.0
+        paired = (perm.long() != torch.arange(K, device=dev)).unsqueeze(0)                           # [1,K]
+        flipped = sel[:, perm.long()]
+        l1 = lambda p: (p[..., :2] - g).abs().sum(-1).double()
+        d = l1(flipped) - l1(sel)                                       # [N,K] < 0: the flipped frame lies closer
+        d = torch.where(torch.isfinite(d), d, torch.zeros_like(d))
+        d = d + d[:, perm.long()]                                       # both joints of the pair, the same sum on either
+        run = torch.cat([torch.zeros(1, K, device=dev, dtype=torch.float64), d.cumsum(0)])
+        start = torch.tensor(list(table), device=dev)
+        named = ((run[start[1:]] - run[start[:-1]]) < 0) & paired      # [S,K]
+        rows = torch.repeat_interleave(named, start[1:] - start[:-1], dim=0)                          # [N,K]
+        swap = swap ^ rows.to(torch.uint8)
+        sel, hyp = torch.where(rows.unsqueeze(-1), flipped, sel), torch.where(rows, hyp[:, perm.long()], hyp)
+        out['named'] = named.to(torch.uint8)
+    out['sel'] = _scatter(order, sel)
+    for name, t in (('hyp', hyp), ('swap', swap), ('status', status)):
+        if name in want:
+            out[name] = _scatter(order, t)
+    if cost is not None:
+        out['cost'] = cost
     return out
