@@ -55,7 +55,6 @@ __device__ __forceinline__ int cal_view_of(int free_mask, int slot) {
     if (slot == 0) { v = __ffs(m) - 1; break; }
   return v;
 }
-__device__ __forceinline__ int cal_idx(int i, int j) { return i * (i + 1) / 2 + j; }       // j <= i
 
 // c [21] of a correction d = (omega, tau): R = exp([omega]x) row-major, tau, and the left Jacobian Jl of the exponential map,
 // d (R X) / d omega = -[R X]x Jl.  th^2 < 1e-16: the series R = I + K + K^2 / 2, Jl = I + K / 2 + K^2 / 6.
@@ -108,75 +107,25 @@ __device__ __forceinline__ void cal_view(const float* __restrict__ Pm, const dou
   }
 }
 
-// A point's observations in registers, every loop over the views unrolled and predicated as in triangulate_refine_kernel.
-struct CalObs {
-  float pu[kCalV], pv[kCalV], ps[kCalV];
-  int valid;
-};
-__device__ __forceinline__ void cal_load(const CalArgs& a, int b, int k, CalObs& o) {
-  o.valid = 0;
-#pragma unroll
-  for (int v = 0; v < kCalV; ++v) {
-    o.pu[v] = 0.f; o.pv[v] = 0.f; o.ps[v] = 0.f;
-    if (v < a.V) {
-      const float* q = a.pts + (((size_t)b * a.V + v) * a.K + k) * 3;
-      o.pu[v] = q[0]; o.pv[v] = q[1];
-      o.ps[v] = (a.flags & XAS_REFINE_WEIGHTED) ? q[2] : 1.f;
-      o.valid |= view_valid(q[2]) ? 1 << v : 0;
-    }
-  }
-}
-
-// Cost, |r|^2 and "in front of every view used" of the point X under the cameras cam [V][21].
-__device__ __forceinline__ bool cal_cost(const CalArgs& a, const float* Pb, const double (*cam)[kCalCam], const CalObs& o, int used,
-                                         const double (&X)[3], double& C, double& r2) {
-  C = 0.0; r2 = 0.0;
-  bool front = true;
-#pragma unroll
-  for (int v = 0; v < kCalV; ++v) {
-    if (!((used >> v) & 1)) continue;
+// The fit (multiview.h's PointFit) of the point X under the cameras cam [V][21]: cal_view's terms, summed as everywhere else.
+__device__ __forceinline__ bool cal_fit(const CalArgs& a, const float* Pb, const double (*cam)[kCalCam], const ViewObs& o, int used,
+                                        const double (&X)[3], PointFit& f) {
+  return fit_views(used, a.huber, [&](int v) {
     CalView w;
     cal_view(Pb + v * 12, cam[v], X, (double)o.pu[v], (double)o.pv[v], (double)o.ps[v], a.huber, false, w);
-    front = w.t.front && front;
-    r2 += w.t.rr;
-    C += w.t.tail ? 2.0 * a.huber * w.t.e - a.huber * a.huber : w.t.e * w.t.e;
-  }
-  return front;
+    return w.t;
+  }, f);
 }
 
-// The point's own 3x3 system at X: A = H_pp + lambda diag H_pp factored, L (00 10 11 20 21 22) L^T = A, and y = L^-1 g_p.
-// A pivot that is not positive leaves NaN, which no later comparison passes.
-__device__ __forceinline__ void cal_point_system(const CalArgs& a, const float* Pb, const double (*cam)[kCalCam], const CalObs& o,
+// The point's own 3x3 system at X: A = H_pp + lambda diag H_pp factored, L L^T = A (chol3: a pivot that is not positive leaves
+// NaN, which no later comparison passes), and y = L^-1 g_p.
+__device__ __forceinline__ void cal_point_system(const CalArgs& a, const float* Pb, const double (*cam)[kCalCam], const ViewObs& o,
                                                  int used, const double (&X)[3], double lambda, double (&L)[6], double (&y)[3]) {
-  double A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-  for (int v = 0; v < kCalV; ++v) {
-    if (!((used >> v) & 1)) continue;
-    CalView w;
-    cal_view(Pb + v * 12, cam[v], X, (double)o.pu[v], (double)o.pv[v], (double)o.ps[v], a.huber, false, w);
-    double blk[6];
-    reproj_block(w.t, blk);
-#pragma unroll
-    for (int n = 0; n < 3; ++n) g[n] += w.t.w * w.t.grad(n);
-#pragma unroll
-    for (int n = 0; n < 6; ++n) A[n] += blk[n];
-  }
-  A[0] *= 1.0 + lambda; A[3] *= 1.0 + lambda; A[5] *= 1.0 + lambda;
-  L[0] = sqrt(A[0]);
-  L[1] = A[1] / L[0];
-  L[2] = sqrt(A[3] - L[1] * L[1]);
-  L[3] = A[2] / L[0];
-  L[4] = (A[4] - L[3] * L[1]) / L[2];
-  L[5] = sqrt(A[5] - L[3] * L[3] - L[4] * L[4]);
-  y[0] = g[0] / L[0];
-  y[1] = (g[1] - L[1] * y[0]) / L[2];
-  y[2] = (g[2] - L[3] * y[0] - L[4] * y[1]) / L[5];
-}
-// x = L^-1 b
-__device__ __forceinline__ void cal_lsolve(const double (&L)[6], const double (&b)[3], double (&x)[3]) {
-  x[0] = b[0] / L[0];
-  x[1] = (b[1] - L[1] * x[0]) / L[2];
-  x[2] = (b[2] - L[3] * x[0] - L[4] * x[1]) / L[5];
+  PointFit f;
+  cal_fit(a, Pb, cam, o, used, X, f);
+  f.H[0] *= 1.0 + lambda; f.H[3] *= 1.0 + lambda; f.H[5] *= 1.0 + lambda;
+  chol3(f.H, L);
+  lsolve3(L, f.g, y);
 }
 
 struct CalRec {
@@ -223,8 +172,8 @@ __global__ __launch_bounds__(kCalBlock) void calib_assemble_kernel(CalArgs a, Ca
       if (used) {
         const int b = i / a.K, k = i - b * a.K;
         const float* Pb = a.P + (size_t)b * a.V * 12;
-        CalObs o;
-        cal_load(a, b, k, o);
+        ViewObs o;
+        load_obs(a.pts, b, a.V, a.K, k, a.flags, o);
         const double* xp = w.X + ((size_t)cur * NK + i) * 3;
         const double X[3] = {xp[0], xp[1], xp[2]};
         double L[6], y[3];
@@ -245,7 +194,7 @@ __global__ __launch_bounds__(kCalBlock) void calib_assemble_kernel(CalArgs a, Ca
                                  vw.t.w * (vw.cu[m] * vw.t.ju[1] + vw.cv[m] * vw.t.jv[1]),
                                  vw.t.w * (vw.cu[m] * vw.t.ju[2] + vw.cv[m] * vw.t.jv[2])};
             double W[3];
-            cal_lsolve(L, B, W);
+            lsolve3(L, B, W);
             q.W[sl][m][0] = W[0]; q.W[sl][m][1] = W[1]; q.W[sl][m][2] = W[2];
           }
           cams |= 1 << sl;
@@ -285,13 +234,13 @@ __global__ __launch_bounds__(kCalBlock) void calib_assemble_kernel(CalArgs a, Ca
 __device__ __forceinline__ void cal_chol_solve(const double* Lm, int n, double* x) {
   for (int i = 0; i < n; ++i) {
     double s = x[i];
-    for (int k = 0; k < i; ++k) s -= Lm[cal_idx(i, k)] * x[k];
-    x[i] = s / Lm[cal_idx(i, i)];
+    for (int k = 0; k < i; ++k) s -= Lm[tri_idx(i, k)] * x[k];
+    x[i] = s / Lm[tri_idx(i, i)];
   }
   for (int i = n - 1; i >= 0; --i) {
     double s = x[i];
-    for (int k = i + 1; k < n; ++k) s -= Lm[cal_idx(k, i)] * x[k];
-    x[i] = s / Lm[cal_idx(i, i)];
+    for (int k = i + 1; k < n; ++k) s -= Lm[tri_idx(k, i)] * x[k];
+    x[i] = s / Lm[tri_idx(i, i)];
   }
 }
 
@@ -313,14 +262,14 @@ __global__ __launch_bounds__(kCalBlock) void calib_solve_kernel(CalArgs a, CalRi
   if (tid < n) {
     const int v = cal_view_of(a.free_mask, tid / 6), c = tid % 6;
     const double p = c < 3 ? a.prior_rot : a.prior_trans;
-    T[cal_idx(tid, tid)] += p + lambda * (T[nT + n + tid] + p);
+    T[tri_idx(tid, tid)] += p + lambda * (T[nT + n + tid] + p);
     gv[tid] = T[nT + tid] + p * dcur[v * 6 + c];
   }
   __syncthreads();
   if (mode == CAL_EXPORT) {                                           // S [R][n][n] symmetric, b = -g [R][n], C [R]
     for (int e = tid; e < n * n; e += kCalBlock) {
       const int i = e / n, j = e - i * n;
-      o0[(size_t)r * n * n + e] = T[i >= j ? cal_idx(i, j) : cal_idx(j, i)];
+      o0[(size_t)r * n * n + e] = T[i >= j ? tri_idx(i, j) : tri_idx(j, i)];
     }
     if (tid < n) o1[(size_t)r * n + tid] = -gv[tid];
     if (tid == 0) o2[r] = w.rs[r * kCalRs + RS_C];
@@ -329,8 +278,8 @@ __global__ __launch_bounds__(kCalBlock) void calib_solve_kernel(CalArgs a, CalRi
   bool ok = true;                                                     // Cholesky in place, left-looking, thread = row
   for (int j = 0; j < n; ++j) {
     if (tid == 0) {
-      double d = T[cal_idx(j, j)];
-      for (int k = 0; k < j; ++k) d -= T[cal_idx(j, k)] * T[cal_idx(j, k)];
+      double d = T[tri_idx(j, j)];
+      for (int k = 0; k < j; ++k) d -= T[tri_idx(j, k)] * T[tri_idx(j, k)];
       piv = d;
     }
     __syncthreads();
@@ -338,12 +287,12 @@ __global__ __launch_bounds__(kCalBlock) void calib_solve_kernel(CalArgs a, CalRi
     if (!(d > 0.0)) { ok = false; break; }                            // the same d on every thread; NaN fails too
     const double sd = sqrt(d);
     if (tid > j && tid < n) {
-      double s = T[cal_idx(tid, j)];
-      for (int k = 0; k < j; ++k) s -= T[cal_idx(tid, k)] * T[cal_idx(j, k)];
-      T[cal_idx(tid, j)] = s / sd;
+      double s = T[tri_idx(tid, j)];
+      for (int k = 0; k < j; ++k) s -= T[tri_idx(tid, k)] * T[tri_idx(j, k)];
+      T[tri_idx(tid, j)] = s / sd;
     }
     __syncthreads();
-    if (tid == 0) T[cal_idx(j, j)] = sd;
+    if (tid == 0) T[tri_idx(j, j)] = sd;
     __syncthreads();
   }
   if (mode == CAL_COV) {                                              // o0 = cam_cov [R][6V][6V]: the inverse, by view
@@ -393,16 +342,15 @@ __global__ __launch_bounds__(kCalBlock) void calib_cost_kernel(CalArgs a, CalRig
   if (i < g.start[r + 1] * a.K) {
     const int b = i / a.K, k = i - b * a.K;
     const float* Pb = a.P + (size_t)b * a.V * 12;
-    CalObs o;
-    cal_load(a, b, k, o);
-    if (init_mode) {                                                  // free = triangulate_refine would not pass it through
+    ViewObs o;
+    load_obs(a.pts, b, a.V, a.K, k, a.flags, o);
+    if (init_mode) {                                                  // free by multiview.h's pass-through rule
       const int used = views_used(o.valid, a.views ? a.views[i] : 0), nused = __popc(used);
       const float* in = a.init + (size_t)i * 4;
       const double X[3] = {(double)in[0], (double)in[1], (double)in[2]};
-      const bool finite = fabs(X[0]) < INFINITY && fabs(X[1]) < INFINITY && fabs(X[2]) < INFINITY;
-      bool isfree = nused >= 2 && finite;
-      if (isfree) isfree = cal_cost(a, Pb, cam[0], o, used, X, C, r2);
-      if (!isfree) { C = 0.0; r2 = 0.0; } else cnt = (double)nused;
+      PointFit f;
+      const bool isfree = point_startable(nused, X) && cal_fit(a, Pb, cam[0], o, used, X, f);
+      if (isfree) { C = f.C; r2 = f.r2; cnt = (double)nused; }
       w.free[i] = isfree ? used : 0;
       double* xp = w.X + (size_t)i * 3;
       xp[0] = X[0]; xp[1] = X[1]; xp[2] = X[2];
@@ -425,21 +373,22 @@ __global__ __launch_bounds__(kCalBlock) void calib_cost_kernel(CalArgs a, CalRig
                                  vw.t.w * (vw.cu[m] * vw.t.ju[1] + vw.cv[m] * vw.t.jv[1]),
                                  vw.t.w * (vw.cu[m] * vw.t.ju[2] + vw.cv[m] * vw.t.jv[2])};
             double W[3];
-            cal_lsolve(L, B, W);
+            lsolve3(L, B, W);
             const double d = dc[6 * sl + m];
             z[0] += W[0] * d; z[1] += W[1] * d; z[2] += W[2] * d;
           }
         }
+        const double nz[3] = {-z[0], -z[1], -z[2]};
         double d[3];                                                  // d_p = -L^-T z
-        d[2] = -z[2] / L[5];
-        d[1] = (-z[1] - L[4] * d[2]) / L[2];
-        d[0] = (-z[0] - L[1] * d[1] - L[3] * d[2]) / L[0];
+        ltsolve3(L, nz, d);
         const double Xt[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
         double* xo = w.X + ((size_t)dst * NK + i) * 3;
         xo[0] = Xt[0]; xo[1] = Xt[1]; xo[2] = Xt[2];
         step = fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2])));
         if (!(step == step)) bad = 1.0;                               // a NaN step: fmax would drop it
-        if (!cal_cost(a, Pb, cam[1], o, used, Xt, C, r2)) bad = 1.0;
+        PointFit f;
+        if (!cal_fit(a, Pb, cam[1], o, used, Xt, f)) bad = 1.0;
+        C = f.C; r2 = f.r2;
         cnt = (double)__popc(used);
       }
     }
@@ -555,7 +504,6 @@ __global__ __launch_bounds__(kCalBlock) void calib_report_kernel(CalArgs a, CalW
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-static inline size_t cal_align(size_t b) { return (b + 15) & ~(size_t)15; }
 struct CalLayout {
   size_t X, part, cpart, rs, delta, dc, free, ri, total;
 };
@@ -563,14 +511,14 @@ static inline CalLayout cal_layout(long N, int K, int R) {
   const size_t NK = (size_t)N * K, NB = (NK + kCalBlock - 1) / kCalBlock + R;   // a rig's last block may be partial
   CalLayout l;
   size_t o = 0;
-  l.X = o; o += cal_align(2 * NK * 3 * sizeof(double));
-  l.part = o; o += cal_align(NB * kCalE * sizeof(double));
-  l.cpart = o; o += cal_align(NB * kCalCp * sizeof(double));
-  l.rs = o; o += cal_align((size_t)R * kCalRs * sizeof(double));
-  l.delta = o; o += cal_align((size_t)2 * R * kCalN * sizeof(double));
-  l.dc = o; o += cal_align((size_t)R * kCalN * sizeof(double));
-  l.free = o; o += cal_align(NK * sizeof(int));
-  l.ri = o; o += cal_align((size_t)R * kCalRi * sizeof(int));
+  l.X = o; o += align16(2 * NK * 3 * sizeof(double));
+  l.part = o; o += align16(NB * kCalE * sizeof(double));
+  l.cpart = o; o += align16(NB * kCalCp * sizeof(double));
+  l.rs = o; o += align16((size_t)R * kCalRs * sizeof(double));
+  l.delta = o; o += align16((size_t)2 * R * kCalN * sizeof(double));
+  l.dc = o; o += align16((size_t)R * kCalN * sizeof(double));
+  l.free = o; o += align16(NK * sizeof(int));
+  l.ri = o; o += align16((size_t)R * kCalRi * sizeof(int));
   l.total = o;
   return l;
 }
@@ -597,8 +545,7 @@ static int cal_plan(const char* who, const float* points, const float* P, const 
   for (int r = 0; r < R; ++r)
     XAS_REQUIRE(rig_start[r] <= rig_start[r + 1], "%s: rig_start[%d] = %d > rig_start[%d] = %d (needs a non-decreasing rig_start)", who,
                 r, rig_start[r], r + 1, rig_start[r + 1]);
-  XAS_REQUIRE((flags & ~XAS_REFINE_WEIGHTED) == 0, "%s: unknown flag bits 0x%x (XAS_REFINE_WEIGHTED = %d is the only flag)", who,
-              flags & ~XAS_REFINE_WEIGHTED, XAS_REFINE_WEIGHTED);
+  if (tri_check_flags(who, flags)) return 1;
   XAS_REQUIRE(free_mask >= 0, "%s: free_mask=%d (needs a mask of cameras >= 0; bits >= V are ignored)", who, free_mask);
   XAS_REQUIRE(prior_rot >= 0.0 && prior_rot < INFINITY && prior_trans >= 0.0 && prior_trans < INFINITY,
               "%s: priors %f, %f (needs finite prior_rot, prior_trans >= 0)", who, prior_rot, prior_trans);
@@ -672,7 +619,7 @@ extern "C" int xas_calibrate_bundle(const float* points, const float* P, const f
                workspace, p))
     return 1;
   XAS_REQUIRE(delta && out, "calibrate_bundle: null buffer (delta and out are required)");
-  XAS_REQUIRE(max_iter >= 1 && max_iter <= 64, "calibrate_bundle: max_iter=%d trials (needs 1 <= max_iter <= 64)", max_iter);
+  if (tri_check_iter("calibrate_bundle", max_iter)) return 1;
   const size_t nout = (size_t)N * K * 4;
   XAS_REQUIRE(out + nout <= init || init + nout <= out, "calibrate_bundle: out must not overlap init (a fixed point is copied from it)");
   hipStream_t s = as_stream(stream);

@@ -123,5 +123,6 @@ __device__ __forceinline__ float read_amax(const float* amax) {
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+static inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }   // a piece of a workspace: rounded up to 16 bytes
 
 }  // namespace xas

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void track_resolve_kernel(TrArgs a, TrOut o) {
 static inline bool tr_shape_ok(int N, int Hy, int K) {
   return N > 0 && Hy >= 1 && Hy <= kTrHy && K >= 1 && K <= kTrK && (long)N * K <= 0x7fffffffL;
 }
-static inline size_t tr_back_bytes(int N, int Hy, int K) { return track_align((size_t)N * K * 2 * Hy * Hy); }
+static inline size_t tr_back_bytes(int N, int Hy, int K) { return align16((size_t)N * K * 2 * Hy * Hy); }
 static inline bool tr_overlap(const void* p, size_t np, const void* q, size_t nq) {
   return p && q && (const char*)p < (const char*)q + nq && (const char*)q < (const char*)p + np;
 }
@@ -216,7 +216,7 @@ using namespace xas;
 
 extern "C" size_t xas_track_resolve_workspace_bytes(int N, int Hy, int K) {
   if (!tr_shape_ok(N, Hy, K)) return 0;
-  return track_table_bytes(N) + tr_back_bytes(N, Hy, K) + track_align((size_t)N * K);
+  return track_table_bytes(N) + tr_back_bytes(N, Hy, K) + align16((size_t)N * K);
 }
 
 extern "C" int xas_track_resolve(const float* kps, const float* world, const float* unary, const int* perm, const int* start,

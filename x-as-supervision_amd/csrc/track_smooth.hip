@@ -24,7 +24,6 @@
 
 namespace xas {
 
-constexpr int kTsV = XAS_TRI_MAX_VIEWS;
 // offsets of the arrays of a wave's record, in units of T doubles
 constexpr int kTsX = 0, kTsD = 6, kTsG = 18, kTsR2 = 24, kTsA = 26, kTsL = 29, kTsDX = 53, kTsUsed = 56, kTsRec = 57;
 enum { TS_SMOOTH, TS_LINEARISE };
@@ -45,56 +44,6 @@ struct TsOut {
   double *band, *g, *C, lambda;                                       // linearise
 };
 
-// A frame's observations in registers, every loop over the views unrolled and predicated as in triangulate_refine_kernel.
-struct TsObs {
-  float pu[kTsV], pv[kTsV], ps[kTsV];
-  int valid;
-};
-__device__ __forceinline__ void ts_load(const TsArgs& a, int n, int k, TsObs& o) {
-  o.valid = 0;
-#pragma unroll
-  for (int v = 0; v < kTsV; ++v) {
-    o.pu[v] = 0.f; o.pv[v] = 0.f; o.ps[v] = 0.f;
-    if (v < a.V) {
-      const float* q = a.pts + (((size_t)n * a.V + v) * a.K + k) * 3;
-      o.pu[v] = q[0]; o.pv[v] = q[1];
-      o.ps[v] = (a.flags & XAS_REFINE_WEIGHTED) ? q[2] : 1.f;
-      o.valid |= view_valid(q[2]) ? 1 << v : 0;
-    }
-  }
-}
-
-// The data of one frame at X: cost, |r|^2, block (upper triangle) and gradient over the views used, term for term
-// triangulate_refine's.  false if X lies behind a view used.
-struct TsFit {
-  double C, r2, H[6], g[3];
-};
-__device__ __forceinline__ bool ts_fit(const float* __restrict__ Pb, const TsObs& o, int used, double huber, const double (&X)[3],
-                                       TsFit& f) {
-  f.C = 0.0; f.r2 = 0.0;
-#pragma unroll
-  for (int n = 0; n < 6; ++n) f.H[n] = 0.0;
-#pragma unroll
-  for (int n = 0; n < 3; ++n) f.g[n] = 0.0;
-  const double Xh[4] = {X[0], X[1], X[2], 1.0};
-  bool front = true;
-#pragma unroll
-  for (int v = 0; v < kTsV; ++v) {
-    if (!((used >> v) & 1)) continue;
-    const ReprojTerm t = reproj_term(Pb + v * 12, Xh, (double)o.pu[v], (double)o.pv[v], (double)o.ps[v], huber);
-    front = t.front && front;
-    f.r2 += t.rr;
-    f.C += t.tail ? 2.0 * huber * t.e - huber * huber : t.e * t.e;
-    double blk[6];
-    reproj_block(t, blk);
-#pragma unroll
-    for (int n = 0; n < 3; ++n) f.g[n] += t.w * t.grad(n);
-#pragma unroll
-    for (int n = 0; n < 6; ++n) f.H[n] += blk[n];
-  }
-  return front;
-}
-
 // The acceleration stencil centred at frame s (1 <= s <= T - 2): q_s = cm X_s-1 + c0 X_s + cp X_s+1 is the difference of the
 // two slopes, ws = 2 / (h0 + h1) its weight in the prior.
 struct TsStencil {
@@ -106,18 +55,6 @@ __device__ __forceinline__ TsStencil ts_stencil(const int* __restrict__ fr, int 
   TsStencil c;
   c.cm = 1.0 / h0; c.cp = 1.0 / h1; c.c0 = -(c.cm + c.cp); c.ws = 2.0 / (h0 + h1);
   return c;
-}
-
-// x = L^-1 b and x = L^-T b, L lower 00 10 11 20 21 22.
-__device__ __forceinline__ void ts_lsolve(const double (&L)[6], const double (&b)[3], double (&x)[3]) {
-  x[0] = b[0] / L[0];
-  x[1] = (b[1] - L[1] * x[0]) / L[2];
-  x[2] = (b[2] - L[3] * x[0] - L[4] * x[1]) / L[5];
-}
-__device__ __forceinline__ void ts_ltsolve(const double (&L)[6], const double (&b)[3], double (&x)[3]) {
-  x[2] = b[2] / L[5];
-  x[1] = (b[1] - L[4] * x[2]) / L[2];
-  x[0] = (b[0] - L[1] * x[1] - L[3] * x[2]) / L[0];
 }
 
 // Cost, data blocks and gradients of every frame at X[src] -> D[src], G[src], R2[src]; C = the track's cost, bad = a data frame
@@ -149,17 +86,13 @@ __device__ __forceinline__ void ts_eval(const TsArgs& a, double* w, const int* _
       if (s == t) cp = c.ws * qq;
     }
     const int used = usedw[t];
-    TsFit f;
-    f.C = 0.0; f.r2 = 0.0;
-#pragma unroll
-    for (int m = 0; m < 6; ++m) f.H[m] = 0.0;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) f.g[m] = 0.0;
+    PointFit f;
+    f.clear();                                                        // a gap frame: no data
     if (used) {
-      TsObs o;
-      ts_load(a, n0 + t, k, o);
+      ViewObs o;
+      load_obs(a.pts, n0 + t, a.V, a.K, k, a.flags, o);
       const double Xt[3] = {X[3 * t], X[3 * t + 1], X[3 * t + 2]};
-      if (!ts_fit(a.P + (size_t)(n0 + t) * a.V * 12, o, used, a.huber, Xt, f)) behind = 1;
+      if (!point_fit(a.P + (size_t)(n0 + t) * a.V * 12, o, used, a.huber, Xt, f)) behind = 1;
     }
 #pragma unroll
     for (int m = 0; m < 6; ++m) D[6 * t + m] = f.H[m];
@@ -208,7 +141,7 @@ __device__ bool ts_factor(double* w, int T, int cur, double lambda, double acc_w
     for (int r = 0; r < 3; ++r) {
       const double row[3] = {r == 0 ? b2 : 0.0, r == 1 ? b2 : 0.0, r == 2 ? b2 : 0.0};
       double x[3];
-      ts_lsolve(p2, row, x);
+      lsolve3(p2, row, x);
       l2[3 * r] = x[0]; l2[3 * r + 1] = x[1]; l2[3 * r + 2] = x[2];
     }
 #pragma unroll
@@ -218,7 +151,7 @@ __device__ bool ts_factor(double* w, int T, int cur, double lambda, double acc_w
       for (int c = 0; c < 3; ++c)
         row[c] = (r == c ? b1 : 0.0) - (l2[3 * r] * q1[3 * c] + l2[3 * r + 1] * q1[3 * c + 1] + l2[3 * r + 2] * q1[3 * c + 2]);
       double x[3];
-      ts_lsolve(p1, row, x);
+      lsolve3(p1, row, x);
       l1[3 * r] = x[0]; l1[3 * r + 1] = x[1]; l1[3 * r + 2] = x[2];
     }
     auto dot = [&](int r, int c) {
@@ -227,7 +160,7 @@ __device__ bool ts_factor(double* w, int T, int cur, double lambda, double acc_w
     };
     const double m00 = (d[0] + b0) * (1.0 + lambda) - dot(0, 0), m10 = d[1] - dot(1, 0), m11 = (d[3] + b0) * (1.0 + lambda) - dot(1, 1);
     const double m20 = d[2] - dot(2, 0), m21 = d[4] - dot(2, 1), m22 = (d[5] + b0) * (1.0 + lambda) - dot(2, 2);
-    double l0[6];
+    double l0[6];                                                     // chol3's factor, with a test at every pivot
     if (!(m00 > 0.0)) return false;
     l0[0] = sqrt(m00);
     l0[1] = m10 / l0[0];
@@ -244,7 +177,7 @@ __device__ bool ts_factor(double* w, int T, int cur, double lambda, double acc_w
     for (int r = 0; r < 3; ++r)
       rhs[r] = -g[r] - (l1[3 * r] * y1[0] + l1[3 * r + 1] * y1[1] + l1[3 * r + 2] * y1[2]) -
                (l2[3 * r] * y2[0] + l2[3 * r + 1] * y2[1] + l2[3 * r + 2] * y2[2]);
-    ts_lsolve(l0, rhs, y);
+    lsolve3(l0, rhs, y);
     if (lane == 0) {
       double* o = L + (size_t)24 * t;
 #pragma unroll
@@ -292,7 +225,7 @@ __device__ void ts_back(double* w, int T, int lane) {
     for (int c = 0; c < 3; ++c)
       rhs[c] = y[c] - (a1[c] * d1[0] + a1[3 + c] * d1[1] + a1[6 + c] * d1[2]) - (a2[c] * d2[0] + a2[3 + c] * d2[1] + a2[6 + c] * d2[2]);
     const double l0[6] = {l[0], l[1], l[2], l[3], l[4], l[5]};
-    ts_ltsolve(l0, rhs, d);
+    ltsolve3(l0, rhs, d);
     if (lane == 0) { Y[3 * t] = d[0]; Y[3 * t + 1] = d[1]; Y[3 * t + 2] = d[2]; }
 #pragma unroll
     for (int m = 0; m < 9; ++m) { a2[m] = a2n[m]; a2n[m] = l[15 + m]; a1[m] = l[6 + m]; }
@@ -310,20 +243,17 @@ __global__ __launch_bounds__(64) void track_smooth_kernel(TsArgs a, TsOut o, int
   int* usedw = (int*)(w + (size_t)kTsUsed * T);
   double* X0 = w + (size_t)kTsX * T;
 
-  // which frames have data (triangulate_refine would not pass them through), and their start
+  // which frames have data (multiview.h's pass-through rule: a frame with data is a free point), and their start
   double cnt = 0.0;
   for (int t = lane; t < T; t += 64) {
     const size_t i = (size_t)(n0 + t) * a.K + k;
-    TsObs ob;
-    ts_load(a, n0 + t, k, ob);
+    ViewObs ob;
+    load_obs(a.pts, n0 + t, a.V, a.K, k, a.flags, ob);
     const int used = views_used(ob.valid, a.views ? a.views[i] : 0);
     const float* in = a.init + i * 4;
     const double X[3] = {(double)in[0], (double)in[1], (double)in[2]};
-    bool data = __popc(used) >= 2 && fabs(X[0]) < INFINITY && fabs(X[1]) < INFINITY && fabs(X[2]) < INFINITY;
-    if (data) {
-      TsFit f;
-      data = ts_fit(a.P + (size_t)(n0 + t) * a.V * 12, ob, used, a.huber, X, f);
-    }
+    PointFit f;
+    const bool data = point_startable(__popc(used), X) && point_fit(a.P + (size_t)(n0 + t) * a.V * 12, ob, used, a.huber, X, f);
     usedw[t] = data ? used : 0;
     X0[3 * t] = X[0]; X0[3 * t + 1] = X[1]; X0[3 * t + 2] = X[2];
     cnt += data ? 1.0 : 0.0;
@@ -480,8 +410,7 @@ static int ts_plan(const char* who, const float* points, const float* P, const f
               "%s: null buffer (points, P, init, start, frame and workspace are required)", who);
   if (tri_check_views(who, V, 2) || tri_check_shape(who, N, K, "N > 0, K >= 1")) return 1;
   if (track_check_start(who, start, N, K, S)) return 1;
-  XAS_REQUIRE((flags & ~XAS_REFINE_WEIGHTED) == 0, "%s: unknown flag bits 0x%x (XAS_REFINE_WEIGHTED = %d is the only flag)", who,
-              flags & ~XAS_REFINE_WEIGHTED, XAS_REFINE_WEIGHTED);
+  if (tri_check_flags(who, flags)) return 1;
   XAS_REQUIRE(acc_w >= 0.0 && acc_w < INFINITY, "%s: acc_w %f (needs a finite acc_w >= 0)", who, acc_w);
   XAS_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace is not 16-byte aligned", who);
   int* table = (int*)workspace;
@@ -521,7 +450,7 @@ extern "C" int xas_track_smooth(const float* points, const float* P, const float
                                 double acc_w, int max_iter, float* out, unsigned char* status, float* resid,
                                 unsigned char* track_status, double* cost, int* trials, void* workspace, void* stream) {
   XAS_REQUIRE(out, "track_smooth: null buffer (out is required)");
-  XAS_REQUIRE(max_iter >= 1 && max_iter <= 64, "track_smooth: max_iter=%d trials (needs 1 <= max_iter <= 64)", max_iter);
+  if (tri_check_iter("track_smooth", max_iter)) return 1;
   if (init && N > 0 && K > 0) {
     const size_t nout = (size_t)N * K * 4;
     XAS_REQUIRE(out + nout <= init || init + nout <= out, "track_smooth: out must not overlap init (a passed-through frame is copied from it)");

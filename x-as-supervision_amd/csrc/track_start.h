@@ -15,8 +15,7 @@ static __global__ __launch_bounds__(256) void track_start_kernel(TrackStart c, i
   if (i < count) dst[first + i] = c.v[i];
 }
 
-static inline size_t track_align(size_t b) { return (b + 15) & ~(size_t)15; }
-static inline size_t track_table_bytes(long N) { return track_align((size_t)(N + 1) * sizeof(int)); }
+static inline size_t track_table_bytes(long N) { return align16((size_t)(N + 1) * sizeof(int)); }
 
 // 1 <= S <= N, S*K < 2^31, start[0] = 0 < ... < start[S] = N.
 static inline int track_check_start(const char* who, const int* start, int N, int K, int S) {

@@ -1,6 +1,7 @@
 // Refinement of triangulated joints on the device (gfx950): Levenberg-Marquardt on the weighted reprojection error in pixels,
-// from the DLT or robust point of triangulate.hip.  The two kernels share multiview.h's reprojection term, LM schedule and view
-// rules; their loops differ in what is uniform over the wave and where the barriers sit, so each keeps its own.
+// from the DLT or robust point of triangulate.hip.  The two kernels share multiview.h's solver layer: the observations, the fit of
+// a point, the pass-through rule, the LM schedule.  Their loops differ in what is uniform over the wave and where the barriers
+// sit, so each keeps its own.
 //   triangulate_refine : per joint, thread per (b, joint) (no reference counterpart: eval.py --tri-refine lm)
 //   triangulate_skeleton : the joints of a sample coupled by left/right limb symmetry, one wave per sample (eval.py --tri-skeleton)
 #include "multiview.h"
@@ -11,51 +12,7 @@ namespace xas {
 // (b, joint) as triangulate_kernel.  A few hundred joints of 3x3 algebra in double: latency-bound, no throughput to win.
 // A thread keeps its V points (u, v, scale) in registers and re-reads the sample's projection matrices at every
 // linearisation: at most 72 floats that all threads of a sample share, so they stay in the caches, where holding them
-// would cost every thread 72 more registers.  Every loop over the views is unrolled to XAS_TRI_MAX_VIEWS and predicated by
-// the mask of the views used, so no array is indexed at run time and no view >= V is ever read.
-// Inverse of the symmetric 3x3 a (upper triangle 00 01 02 11 12 22) by its adjugate.  A singular a gives inf / NaN.
-__device__ __forceinline__ void sym3_inverse(const double (&a)[6], double (&inv)[6]) {
-  const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
-  const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
-  inv[0] = c00 / det; inv[1] = c01 / det; inv[2] = c02 / det;
-  inv[3] = (a[0] * a[5] - a[2] * a[2]) / det;
-  inv[4] = (a[1] * a[2] - a[0] * a[4]) / det;
-  inv[5] = (a[0] * a[3] - a[1] * a[1]) / det;
-}
-
-// The problem at one point X: cost C, sum of the squared unweighted pixel residuals r2, Gauss-Newton Hessian H (upper
-// triangle) and gradient g with the IRLS weights of X itself.  false if X lies behind a view used.
-struct RefineFit {
-  double C, r2, H[6], g[3];
-};
-
-__device__ __forceinline__ bool refine_linearise(const float* __restrict__ Pb, int used, const float (&pu)[XAS_TRI_MAX_VIEWS],
-                                                 const float (&pv)[XAS_TRI_MAX_VIEWS], const float (&ps)[XAS_TRI_MAX_VIEWS],
-                                                 double huber, const double (&X)[3], RefineFit& f) {
-  f.C = 0.0; f.r2 = 0.0;
-#pragma unroll
-  for (int n = 0; n < 6; ++n) f.H[n] = 0.0;
-#pragma unroll
-  for (int n = 0; n < 3; ++n) f.g[n] = 0.0;
-  const double Xh[4] = {X[0], X[1], X[2], 1.0};
-  bool front = true;
-#pragma unroll
-  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
-    if (!((used >> v) & 1)) continue;
-    const ReprojTerm t = reproj_term(Pb + v * 12, Xh, (double)pu[v], (double)pv[v], (double)ps[v], huber);
-    front = t.front && front;
-    f.r2 += t.rr;
-    f.C += t.tail ? 2.0 * huber * t.e - huber * huber : t.e * t.e;
-    double blk[6];
-    reproj_block(t, blk);
-#pragma unroll
-    for (int n = 0; n < 3; ++n) f.g[n] += t.w * t.grad(n);
-#pragma unroll
-    for (int n = 0; n < 6; ++n) f.H[n] += blk[n];
-  }
-  return front;
-}
-
+// would cost every thread 72 more registers.
 __global__ __launch_bounds__(64) void triangulate_refine_kernel(const float* __restrict__ pts, const float* __restrict__ P,
                                                                 const float* __restrict__ init,
                                                                 const unsigned char* __restrict__ views, int B, int V, int K,
@@ -66,28 +23,17 @@ __global__ __launch_bounds__(64) void triangulate_refine_kernel(const float* __r
   if (i >= B * K) return;
   const int b = i / K, k = i % K;
   const float* Pb = P + (size_t)b * V * 12;
-  float pu[XAS_TRI_MAX_VIEWS], pv[XAS_TRI_MAX_VIEWS], ps[XAS_TRI_MAX_VIEWS];
-  int valid = 0;
-#pragma unroll
-  for (int v = 0; v < XAS_TRI_MAX_VIEWS; ++v) {
-    pu[v] = 0.f; pv[v] = 0.f; ps[v] = 0.f;
-    if (v < V) {
-      const float* q = pts + (((size_t)b * V + v) * K + k) * 3;
-      pu[v] = q[0]; pv[v] = q[1];
-      ps[v] = (flags & XAS_REFINE_WEIGHTED) ? q[2] : 1.f;
-      valid |= view_valid(q[2]) ? 1 << v : 0;
-    }
-  }
-  const int used = views_used(valid, views ? views[i] : 0);
+  ViewObs obs;
+  load_obs(pts, b, V, K, k, flags, obs);
+  const int used = views_used(obs.valid, views ? views[i] : 0);
   const int nused = __popc(used);
   const double huber = (double)huber_;
 
   const float* in = init + (size_t)i * 4;
   const float x0 = in[0], x1 = in[1], x2 = in[2];
   double X[3] = {(double)x0, (double)x1, (double)x2};
-  RefineFit fit;
-  const bool finite = fabs(X[0]) < INFINITY && fabs(X[1]) < INFINITY && fabs(X[2]) < INFINITY;
-  const bool solve = nused >= 2 && finite && refine_linearise(Pb, used, pu, pv, ps, huber, X, fit);
+  PointFit fit;
+  const bool solve = point_startable(nused, X) && point_fit(Pb, obs, used, huber, X, fit);   // multiview.h's pass-through rule
   float* o = out + (size_t)i * 4;
   o[3] = in[3];
   if (!solve) {                                                       // passed through: init bit for bit, NaN stays NaN
@@ -110,8 +56,8 @@ __global__ __launch_bounds__(64) void triangulate_refine_kernel(const float* __r
                          -(inv[1] * fit.g[0] + inv[3] * fit.g[1] + inv[4] * fit.g[2]),
                          -(inv[2] * fit.g[0] + inv[4] * fit.g[1] + inv[5] * fit.g[2])};
     const double Xt[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
-    RefineFit trial;
-    const bool front = refine_linearise(Pb, used, pu, pv, ps, huber, Xt, trial);
+    PointFit trial;
+    const bool front = point_fit(Pb, obs, used, huber, Xt, trial);
     if (front && trial.C < fit.C) {                                   // NaN never passes
       X[0] = Xt[0]; X[1] = Xt[1]; X[2] = Xt[2];
       fit = trial;
@@ -175,8 +121,6 @@ struct SkShared {
 };
 static_assert(sizeof(SkShared) <= 64 * 1024, "triangulate_skeleton: static LDS of one block");
 
-__device__ __forceinline__ int sk_idx(int i, int j) { return i * (i + 1) / 2 + j; }        // j <= i
-
 // The residual terms of the joints in `mask` at X[src], then each joint's sums on its own lane: cost, |r|^2 and whether it lies
 // in front of every view it uses.  Starts with a barrier (X[src] was just written, `term` may still be read) and ends past one.
 __device__ __forceinline__ void sk_reproj(SkShared& s, int src, int V, int K, unsigned mask, double huber, int lane, double& Ck,
@@ -188,7 +132,7 @@ __device__ __forceinline__ void sk_reproj(SkShared& s, int src, int V, int K, un
     const double Xh[4] = {s.X[src][k][0], s.X[src][k][1], s.X[src][k][2], 1.0};
     const ReprojTerm r = reproj_term(s.P[v], Xh, (double)s.pu[k][v], (double)s.pv[k][v], (double)s.ps[k][v], huber);
     double* o = s.term[k][v];
-    o[0] = r.tail ? 2.0 * huber * r.e - huber * huber : r.e * r.e;
+    o[0] = huber_cost(r, huber);
     o[1] = r.rr;
 #pragma unroll
     for (int n = 0; n < 3; ++n) o[8 + n] = r.w * r.grad(n);
@@ -275,7 +219,7 @@ __device__ __forceinline__ void sk_assemble(SkShared& s, int src, int V, int nfr
     for (int r = 0; r < 3; ++r)
 #pragma unroll
       for (int c = 0; c < 3; ++c)
-        if (bi > bj || c <= r) s.H[sk_idx(3 * bi + r, 3 * bj + c)] = h[r][c];
+        if (bi > bj || c <= r) s.H[tri_idx(3 * bi + r, 3 * bj + c)] = h[r][c];
   }
   for (int i = lane; i < 3 * nfree; i += 64) {
     const int k = s.joint[i / 3], c = i % 3;
@@ -303,9 +247,9 @@ __device__ __forceinline__ bool sk_factor(SkShared& s, int n, double lambda, int
       if (i < j || i >= n) continue;
       const int fi = 3 * s.first[i / 3];
       if (j < fi) continue;                                           // outside the envelope: L_ij = 0
-      double a = s.H[sk_idx(i, j)];
+      double a = s.H[tri_idx(i, j)];
       if (i == j) a *= 1.0 + lambda;
-      for (int k = fi > fj ? fi : fj; k < j; ++k) a -= s.Lm[sk_idx(i, k)] * s.Lm[sk_idx(j, k)];
+      for (int k = fi > fj ? fi : fj; k < j; ++k) a -= s.Lm[tri_idx(i, k)] * s.Lm[tri_idx(j, k)];
       v[h] = a;
     }
     const double d = j < 64 ? __shfl(v[0], j, 64) : __shfl(v[1], j - 64, 64);
@@ -315,7 +259,7 @@ __device__ __forceinline__ bool sk_factor(SkShared& s, int n, double lambda, int
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
       if (i < j || i >= n) continue;
-      s.Lm[sk_idx(i, j)] = i == j ? sd : v[h] / sd;
+      s.Lm[tri_idx(i, j)] = i == j ? sd : v[h] / sd;
       if (i == j) inv[h] = 1.0 / sd;
     }
   }
@@ -329,8 +273,8 @@ __device__ __forceinline__ void sk_solve(const SkShared& s, int n, int lane, con
   const int i0 = lane, i1 = lane + 64;
   d[0] = i0 < n ? -s.g[i0] : 0.0;
   d[1] = i1 < n ? -s.g[i1] : 0.0;
-  auto below = [&](int i, int j) { return i > j && i < n ? s.Lm[sk_idx(i, j)] : 0.0; };   // L_ij, column j
-  auto left = [&](int i, int j) { return i < j ? s.Lm[sk_idx(j, i)] : 0.0; };             // L_ji, row j
+  auto below = [&](int i, int j) { return i > j && i < n ? s.Lm[tri_idx(i, j)] : 0.0; };   // L_ij, column j
+  auto left = [&](int i, int j) { return i < j ? s.Lm[tri_idx(j, i)] : 0.0; };             // L_ji, row j
   double c0 = below(i0, 0), c1 = below(i1, 0);
   for (int j = 0; j < n; ++j) {
     const double n0 = below(i0, j + 1), n1 = below(i1, j + 1);
@@ -368,7 +312,7 @@ __global__ __launch_bounds__(64) void triangulate_skeleton_kernel(const float* _
   bool cand = false;
   if (lane < K) {
     int valid = 0;
-    for (int v = 0; v < V; ++v) {
+    for (int v = 0; v < V; ++v) {                                     // load_obs's per-view body, staged to LDS
       const float* q = pts + (((size_t)b * V + v) * K + lane) * 3;
       s.pu[lane][v] = q[0]; s.pv[lane][v] = q[1];
       s.ps[lane][v] = (flags & XAS_REFINE_WEIGHTED) ? q[2] : 1.f;
@@ -380,13 +324,13 @@ __global__ __launch_bounds__(64) void triangulate_skeleton_kernel(const float* _
     const float* in = init + i * 4;
     x0 = in[0]; x1 = in[1]; x2 = in[2]; x3 = in[3];
     s.X[0][lane][0] = (double)x0; s.X[0][lane][1] = (double)x1; s.X[0][lane][2] = (double)x2;
-    cand = nused >= 2 && fabsf(x0) < INFINITY && fabsf(x1) < INFINITY && fabsf(x2) < INFINITY;
+    cand = nused >= 2 && fabsf(x0) < INFINITY && fabsf(x1) < INFINITY && fabsf(x2) < INFINITY;   // point_startable, on the floats
   }
   const unsigned candmask = (unsigned)__ballot(cand);
   double Ck, r2k;
   bool frontk;
   sk_reproj(s, 0, V, K, candmask, huber, lane, Ck, r2k, frontk);      // its first barrier publishes the staging above
-  const bool isfree = cand && frontk;                                 // FREE: triangulate_refine would not pass it through
+  const bool isfree = cand && frontk;                                 // FREE by multiview.h's pass-through rule
   const unsigned freemask = (unsigned)__ballot(isfree);
   const int nfree = __popc(freemask), n = 3 * nfree;
   const int myslot = __popc(freemask & ((1u << (lane & 31)) - 1u));    // read where lane < K <= 24 only

@@ -7,6 +7,7 @@ import ctypes
 import torch
 
 from xas_amd._lib import call, ptr, query
+from xas_amd.ops_eval import _scatter, _solver_inputs, _sorted
 
 # Weights of the priors on the corrections, in cost per rad^2 and per mm^2: sigma = 0.01 rad and 10 mm at a 1 px residual.
 # UNTUNED GUESSES: there is neither a dataset nor a checkpoint here to tune them on.  With camera 0 fixed they settle the gauge.
@@ -38,17 +39,9 @@ def default_free(V):
 
 
 def _prepare(name, points, pmat, init, rig, views, num_rigs):
-    points, pmat, init = (t.detach().float().contiguous() for t in (points, pmat, init))
-    N, V, K, _ = points.shape
-    if pmat.shape != (N, V, 3, 4):
-        raise RuntimeError('%s: projection matrices %s do not match points %s' % (name, tuple(pmat.shape), tuple(points.shape)))
-    if init.shape != (N, K, 4):
-        raise RuntimeError('%s: start points %s do not match points %s' % (name, tuple(init.shape), tuple(points.shape)))
+    points, pmat, init, views, N, V, K = _solver_inputs(name, points, pmat, init, views, 'N')
     if rig.shape != (N,):
         raise RuntimeError('%s: rig %s is not one index per sample of points %s' % (name, tuple(rig.shape), tuple(points.shape)))
-    if views is not None and (views.shape != (N, K) or views.dtype != torch.uint8):
-        raise RuntimeError('%s: views %s %s are not the [N,K] uint8 masks of points %s' % (
-            name, tuple(views.shape), views.dtype, tuple(points.shape)))
     rig = rig.to(device=points.device, dtype=torch.int64)
     R = int(num_rigs) if num_rigs is not None else int(rig.max()) + 1
     order = torch.argsort(rig, stable=True)
@@ -59,8 +52,7 @@ def _prepare(name, points, pmat, init, rig, views, num_rigs):
     for c in counts:
         start.append(start[-1] + int(c))
     table = (ctypes.c_int * (R + 1))(*start)
-    points, pmat, init = points[order].contiguous(), pmat[order].contiguous(), init[order].contiguous()
-    views = None if views is None else views[order].contiguous()
+    points, pmat, init, views = _sorted(order, points, pmat, init, views)
     ws = torch.empty(max(query('xas_calibrate_workspace_bytes', N, V, K, R), 16), device=points.device, dtype=torch.uint8)
     return points, pmat, init, views, order, table, ws, N, V, K, R
 
@@ -119,6 +111,5 @@ def calibrate_bundle(points, pmat, init, rig, views=None, free=None, weighted=Fa
          REFINE_WEIGHTED if weighted else 0, float(huber_px), float(prior_rot), float(prior_trans), int(max_iter), ptr(out['delta']),
          ptr(sorted_out), ptr(out.get('cost')), ptr(out.get('rms')), ptr(out.get('cam_cov')), ptr(out.get('status')),
          ptr(out.get('trials')), ptr(ws))
-    out['xyzw'] = torch.empty_like(sorted_out)
-    out['xyzw'][order] = sorted_out
+    out['xyzw'] = _scatter(order, sorted_out)
     return out

@@ -117,6 +117,36 @@ def triangulate_robust(points, pmat, threshold_px=TRI_ROBUST_PX, want=('inliers'
 REFINE_WEIGHTED = 1      # xas_hip.h XAS_REFINE_WEIGHTED
 
 
+def _solver_inputs(name, points, pmat, init, views, batch='B'):
+    """The inputs that the four solvers share (triangulate_refine, triangulate_skeleton, ops_calib, ops_track): points
+    [B,V,K,3], pmat [B,V,3,4] and init [B,K,4] as contiguous float32, views [B,K] uint8 or None -> them and B, V, K.  `batch` is
+    the letter the caller's documentation has for B."""
+    points, pmat, init = _f32(points), _f32(pmat), _f32(init)
+    B, V, K, _ = points.shape
+    if pmat.shape != (B, V, 3, 4):
+        raise RuntimeError('%s: projection matrices %s do not match points %s' % (name, tuple(pmat.shape), tuple(points.shape)))
+    if init.shape != (B, K, 4):
+        raise RuntimeError('%s: start points %s do not match points %s' % (name, tuple(init.shape), tuple(points.shape)))
+    if views is not None:
+        if views.shape != (B, K) or views.dtype != torch.uint8:
+            raise RuntimeError('%s: views %s %s are not the [%s,K] uint8 masks of points %s' % (
+                name, tuple(views.shape), views.dtype, batch, tuple(points.shape)))
+        views = views.contiguous()
+    return points, pmat, init, views, B, V, K
+
+
+def _sorted(order, *tensors):
+    """Every tensor (None stays None) with its samples in the order `order`, for a kernel that takes them sorted by a host table."""
+    return tuple(None if t is None else t[order].contiguous() for t in tensors)
+
+
+def _scatter(order, t):
+    """The result t of such a kernel put back in the order given."""
+    out = torch.empty_like(t)
+    out[order] = t
+    return out
+
+
 def triangulate_refine(points, pmat, init, views=None, weighted=False, huber_px=0.0, max_iter=20, want=('resid',)):
     """Levenberg-Marquardt on the reprojection error from a triangulated point (xas_triangulate_refine).  points [B,V,K,3]
     (u, v, weight), pmat [B,V,3,4], init [B,K,4] (triangulate_dlt, or xyzw of triangulate_robust), views [B,K] uint8 (inliers of
@@ -125,17 +155,7 @@ def triangulate_refine(points, pmat, init, views=None, weighted=False, huber_px=
     -> dict: xyzw [B,K,4] always; resid [B,K,2] (RMS pixel residual over the views used, before and after), cov [B,K,6] (upper
     triangle of the inverse Gauss-Newton Hessian), status [B,K] uint8 (0 converged, 1 out of trials, 2 passed through) as
     requested."""
-    points, pmat, init = _f32(points), _f32(pmat), _f32(init)
-    B, V, K, _ = points.shape
-    if pmat.shape != (B, V, 3, 4):
-        raise RuntimeError('triangulate_refine: projection matrices %s do not match points %s' % (tuple(pmat.shape), tuple(points.shape)))
-    if init.shape != (B, K, 4):
-        raise RuntimeError('triangulate_refine: start points %s do not match points %s' % (tuple(init.shape), tuple(points.shape)))
-    if views is not None:
-        if views.shape != (B, K) or views.dtype != torch.uint8:
-            raise RuntimeError('triangulate_refine: views %s %s are not the [B,K] uint8 masks of points %s' % (
-                tuple(views.shape), views.dtype, tuple(points.shape)))
-        views = views.contiguous()
+    points, pmat, init, views, B, V, K = _solver_inputs('triangulate_refine', points, pmat, init, views)
     dev = points.device
     out = {'xyzw': torch.empty(B, K, 4, device=dev)}
     if 'resid' in want:
@@ -166,17 +186,7 @@ def triangulate_skeleton(points, pmat, init, views=None, limbs=SYM_LIMBS, weight
     -> dict: xyzw [B,K,4] always; resid [B,K,2] (RMS pixel residual before and after; NaN for a fixed joint), sym [B,L,2]
     (|limb a| - |limb b| in mm before and after; NaN where the pair is off), cost [B,2], status [B,K] uint8 (0 the sample
     converged, 1 out of trials, 2 fixed joint) as requested."""
-    points, pmat, init = _f32(points), _f32(pmat), _f32(init)
-    B, V, K, _ = points.shape
-    if pmat.shape != (B, V, 3, 4):
-        raise RuntimeError('triangulate_skeleton: projection matrices %s do not match points %s' % (tuple(pmat.shape), tuple(points.shape)))
-    if init.shape != (B, K, 4):
-        raise RuntimeError('triangulate_skeleton: start points %s do not match points %s' % (tuple(init.shape), tuple(points.shape)))
-    if views is not None:
-        if views.shape != (B, K) or views.dtype != torch.uint8:
-            raise RuntimeError('triangulate_skeleton: views %s %s are not the [B,K] uint8 masks of points %s' % (
-                tuple(views.shape), views.dtype, tuple(points.shape)))
-        views = views.contiguous()
+    points, pmat, init, views, B, V, K = _solver_inputs('triangulate_skeleton', points, pmat, init, views)
     limbs = [tuple(int(j) for j in row) for row in limbs]
     if any(len(row) != 4 for row in limbs):
         raise RuntimeError('triangulate_skeleton: every limb pair is (far_a, near_a, far_b, near_b); got %s' % (limbs,))

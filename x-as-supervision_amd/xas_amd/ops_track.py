@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from xas_amd._lib import call, ptr, query
-from xas_amd.ops_eval import SWITCH_PAIRS, switch_perm
+from xas_amd.ops_eval import SWITCH_PAIRS, _scatter, _solver_inputs, _sorted, switch_perm
 
 # Weight of the squared acceleration, in px^2 per (mm^2 / frame^3): about 4 mm / frame^2 of acceleration on the scale of a 1 px
 # residual (0.05 * 4.5^2 = 1).  AN UNTUNED GUESS: there is neither a dataset nor a checkpoint here to tune it on.
@@ -83,33 +83,18 @@ def _by_track(name, track, frame):
 
 
 def _prepare(name, points, pmat, init, track, frame, views):
-    points, pmat, init = (t.detach().float().contiguous() for t in (points, pmat, init))
     if points.dim() != 4 or points.shape[-1] != 3:
         raise RuntimeError('%s: points must be [N,V,K,3], got %s' % (name, tuple(points.shape)))
-    N, V, K, _ = points.shape
-    if pmat.shape != (N, V, 3, 4):
-        raise RuntimeError('%s: projection matrices %s do not match points %s' % (name, tuple(pmat.shape), tuple(points.shape)))
-    if init.shape != (N, K, 4):
-        raise RuntimeError('%s: start points %s do not match points %s' % (name, tuple(init.shape), tuple(points.shape)))
+    points, pmat, init, views, N, V, K = _solver_inputs(name, points, pmat, init, views, 'N')
     dev = points.device
     track, frame = (torch.as_tensor(t).to(device=dev, dtype=torch.int64) for t in (track, frame))
     if track.shape != (N,) or frame.shape != (N,):
         raise RuntimeError('%s: track %s and frame %s are not one number per sample of points %s' % (
             name, tuple(track.shape), tuple(frame.shape), tuple(points.shape)))
-    if views is not None and (views.shape != (N, K) or views.dtype != torch.uint8):
-        raise RuntimeError('%s: views %s %s are not the [N,K] uint8 masks of points %s' % (
-            name, tuple(views.shape), views.dtype, tuple(points.shape)))
     order, frame, ids, table, S = _by_track(name, track, frame)
-    points, pmat, init = points[order].contiguous(), pmat[order].contiguous(), init[order].contiguous()
-    views = None if views is None else views[order].contiguous()
+    points, pmat, init, views = _sorted(order, points, pmat, init, views)
     ws = torch.empty(max(query('xas_track_smooth_workspace_bytes', N, K), 16), device=dev, dtype=torch.uint8)
     return points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S
-
-
-def _scatter(order, t):
-    out = torch.empty_like(t)
-    out[order] = t
-    return out
 
 
 def track_linearise(points, pmat, init, track, frame, views=None, weighted=False, huber_px=0.0, acc_w=TRACK_ACC_W, lam=0.0,
