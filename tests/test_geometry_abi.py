@@ -1,4 +1,4 @@
-"""The patch->world, line-mask and mask-loss entry points of csrc/geometry.hip and csrc/misc.hip in the C ABI, without a GPU:
+"""The patch->world, line-mask and mask-loss entry points of csrc/geometry.hip and csrc/losses.hip in the C ABI, without a GPU:
 they are exported by the built library, declared in include/xas_hip.h and bound by the ctypes table; the two block-count
 queries state the launch geometry the kernels use; every bad-argument call answers 1 with a message before any launch
 (xas_draw_lines_max_bwd checks what xas_draw_lines_max_fwd checks, body_width included)."""

@@ -1,4 +1,4 @@
-"""The discriminator and joint-loss kernels of csrc/misc.hip alone, through the C ABI, against plain float64 torch on the CPU
+"""The discriminator and joint-loss kernels of csrc/gcn.hip and csrc/losses.hip alone, through the C ABI, against plain float64 torch on the CPU
 computed from the same fp32 inputs: graph_aggregate, the six gln_* kernels (graph LayerNorm + ReLU + residual, both ways),
 pose_loss_fwd/bwd (kinds 0, 1, 2) and lsgan_fwd/bwd - at the shapes where each guard, stride loop and grid cap is taken, with
 every output buffer filled with NaN before the launch.

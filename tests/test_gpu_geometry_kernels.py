@@ -1,7 +1,7 @@
 """The kernels between the detector and the loss alone, against the float64 run of the oracle on the same fp32 inputs:
 patch_to_world fwd/bwd (csrc/geometry.hip) on skewed cameras and every flag combination, the one-block-per-sample reduction
 of world_to_patch's backward past its 256 threads, draw_lines_max fwd/bwd at every launch edge (store tail, ragged last block,
-L = 1, L = 32, many lines per joint, strides, fine bits, NaN / infinite joints) and the mask-loss kernels of csrc/misc.hip
+L = 1, L = 32, many lines per joint, strides, fine bits, NaN / infinite joints) and the mask-loss kernels of csrc/losses.hip
 around their block boundaries and at the clip threshold.
 
 Bounds.  Every case runs the oracle twice on the CPU, in float64 (the reference) and in float32, and takes

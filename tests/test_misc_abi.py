@@ -1,4 +1,4 @@
-"""The discriminator and joint-loss entry points of csrc/misc.hip in the C ABI, without a GPU: they are exported by the
+"""The discriminator and joint-loss entry points of csrc/gcn.hip and csrc/losses.hip in the C ABI, without a GPU: they are exported by the
 built library, declared in include/xas_hip.h and bound by the ctypes table; the graph-LayerNorm workspace query states the
 layout that the forward and the backward carve out of it; every bad-argument call answers 1 with a message before any
 launch (xas_pose_loss_bwd checks what xas_pose_loss_fwd checks)."""

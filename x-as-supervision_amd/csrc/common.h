@@ -124,5 +124,10 @@ __device__ __forceinline__ float read_amax(const float* amax) {
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 static inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }   // a piece of a workspace: rounded up to 16 bytes
+// blocks of a grid-stride element-wise launch over n elements: one per `per_block` of them, 1 .. 4096
+static inline unsigned ew_grid(long n, int per_block = 256) {
+  long b = cdiv(n, per_block);
+  return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
 
 }  // namespace xas

@@ -1,4 +1,5 @@
-"""Mask losses, graph ops for the GCN discriminator, SMPL skinning: autograd ops over the C ABI."""
+"""Mask and joint losses (csrc/losses.hip), graph ops for the GCN discriminator (csrc/gcn.hip), SMPL skinning
+(csrc/smpl_lbs.hip): autograd ops over the C ABI."""
 import torch
 
 from ._lib import call, ptr, query
@@ -105,7 +106,7 @@ class _SmplLbs(torch.autograd.Function):
         bufs = tuple(t.contiguous() for t in (v_template, shapedirs, posedirs, j_regressor, weights))
         verts = torch.empty(B, V, 3, device=dev, dtype=torch.float32)
         joints = torch.empty(B, 24, 3, device=dev, dtype=torch.float32)
-        ws = torch.empty(B * (72 + 24 * 16 + 207), device=dev, dtype=torch.float32)
+        ws = torch.empty(B * (24 * 3 + 24 * 16 + 207), device=dev, dtype=torch.float32)      # xas_hip.h: xas_smpl_lbs_fwd
         c = -1 if center_idx is None else int(center_idx)
         call('xas_smpl_lbs_fwd', ptr(pose), ptr(betas), *(ptr(t) for t in bufs), ptr(parents), B, V, c, ptr(verts),
              ptr(joints), ptr(ws))

@@ -1,6 +1,7 @@
 """Layer ops (conv / conv-transpose / linear / batch-norm / pool / upsample / sigmoid) as
 autograd Functions over the C ABI.  Activations are torch channels_last tensors: logically
-[N,C,H,W] like the reference, physically NHWC like the kernels want."""
+[N,C,H,W] like the reference, physically NHWC like the kernels want.  Kernels: csrc/conv*.hip, csrc/bn.hip (batch norm),
+csrc/layers.hip (pool / upsample / sigmoid), csrc/layout.hip (NCHW <-> NHWC, the mirrored pair)."""
 import os
 
 import torch

@@ -2,7 +2,8 @@
 
 Parameters of one optimizer are re-homed into ONE contiguous fp32 arena (each nn.Parameter becomes a view),
 gradients into a second arena (`.grad` views, so autograd accumulates in place), moments into two more.
-`step()` is one kernel launch over the arena; `zero_grad()` is one memset.  The contiguous gradient arena
+`step()` is one kernel launch over the arena (csrc/optim.hip: one kernel template for the plain, guarded and averaged
+forms); `zero_grad()` is one memset.  The contiguous gradient arena
 is also what the data-parallel reducer all-reduces in large buckets (xas_amd/dp.py).
 state_dict()/load_state_dict() speak torch.optim.Adam's format so reference checkpoints resume.
 
