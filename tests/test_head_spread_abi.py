@@ -76,7 +76,7 @@ def test_weighted_variants_stand_beside_the_old_signatures():
     p = inspect.signature(mu.triangulation).parameters
     assert list(p) == ['keypoints', 'params', 'cam_id_list', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers']
     q = inspect.signature(mu.triangulation_weighted).parameters
-    assert list(q) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers']
+    assert list(q) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers', 'inputs']
     assert all(q[n].default == p[n].default for n in list(p)[3:])
     p = inspect.signature(mu.resolve_views).parameters
     assert list(p) == ['kps_by_cam', 'params', 'cam_id_list', 'pairs', 'gt', 'RECT_WIDTH']

@@ -127,9 +127,9 @@ def test_signatures():
     p = inspect.signature(mu.triangulation).parameters
     assert list(p) == ['keypoints', 'params', 'cam_id_list', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers']
     p = inspect.signature(mu.triangulation_weighted).parameters
-    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers']
+    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers', 'inputs']
     p = inspect.signature(mu.triangulation_refined).parameters
-    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'huber_px', 'want']
+    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'huber_px', 'want', 'inputs']
 
 
 def test_model_refuses_a_camera_count_it_cannot_triangulate():

@@ -106,10 +106,10 @@ def test_util_signatures_are_unchanged_and_the_new_one_stands_beside_them():
     p = inspect.signature(mu.triangulation).parameters
     assert list(p) == ['keypoints', 'params', 'cam_id_list', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers']
     p = inspect.signature(mu.triangulation_weighted).parameters
-    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers']
+    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'return_inliers', 'inputs']
     p = inspect.signature(mu.triangulation_refined).parameters
-    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'huber_px', 'want']
-    assert [p[n].default for n in list(p)[3:]] == [None, True, 2000, None, 0.0, ()]
+    assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'huber_px', 'want', 'inputs']
+    assert [p[n].default for n in list(p)[3:]] == [None, True, 2000, None, 0.0, (), None]
 
 
 def _names():

@@ -118,8 +118,8 @@ def test_eval_knows_the_choice_and_the_weight():
     assert list(p) == ['self', 'config', 'detector', 'eval_data', 'log_dir', 'img_size', 'flip_test', 'tri', 'tri_thresh', 'resolve']
     p = inspect.signature(mu.triangulation_skeleton).parameters
     assert list(p) == ['keypoints', 'params', 'cam_id_list', 'weights', 'is_norm', 'RECT_WIDTH', 'robust_px', 'huber_px', 'sym_w',
-                       'limbs', 'want']
-    assert [p[n].default for n in list(p)[3:]] == [None, True, 2000, None, 0.0, 0.1, ops_eval.SYM_LIMBS, ()]
+                       'limbs', 'want', 'inputs']
+    assert [p[n].default for n in list(p)[3:]] == [None, True, 2000, None, 0.0, 0.1, ops_eval.SYM_LIMBS, (), None]
 
 
 def test_oracle_reprojection_terms_are_the_per_joint_oracles():

@@ -7,6 +7,10 @@
              [--tri-refine none|lm --tri-huber PX] [--tri-skeleton --tri-sym W]
              [--tri-volume --tri-vol-side MM --tri-vol-grid G --tri-vol-levels N]
              [--fit-smpl OUT.npz --smpl-model ROOT|.npz --fit-iters N --fit-pose-prior W --fit-shape-prior W]
+             [--calibrate OUT.npz --calib-iters N --calib-prior-rot W --calib-prior-trans W --calib-free MASK]
+             [--calibration IN.npz]
+             [--smooth OUT.npz --smooth-acc W --smooth-gap FRAMES --smooth-iters N]
+             [--resolve-track OUT.npz --rt-vel W --rt-hyp W --rt-swap W --rt-gap FRAMES]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -58,10 +62,35 @@ solver above passed through counts 0; with a covariance (--tri-volume, or --tri-
 counts 1 / trace(cov), normalised to mean 1 per sample.  OUT.npz (`pose` [N,72], `betas`, `trans`, `cost`, `status`,
 `joint_rms_mm`) is a bank that train.py --pseudo-online reads as it is; eval_result.txt gains one last line.  Unknown: how good
 the fits are on real detections (no checkpoint or dataset here), and the prior weights, which are untuned guesses.
+
+--calibrate OUT.npz (opt-in; model_params.calibrate; 2+ cameras, one rank) keeps every batch's triangulation inputs, final
+points and the views they used on the device and, after the loop, runs one bundle adjustment of the camera extrinsics per rig
+(xas_amd.ops_calib.calibrate_bundle).  OUT.npz holds the rigs' projection matrices (`keys`) and their corrections (`delta`:
+rotation vector in rad, translation in mm) with `cost`, `rms`, `status` and `cam_cov`; eval_result.txt gains one line per rig.
+--calibration IN.npz (model_params.calibration; not with --calibrate) applies such a file: the cameras of every batch are
+corrected before anything is predicted from them (modules.util.apply_calibration), while the ground truth keeps reading the
+cameras as given.  Unknown: what either does to MPJPE on real rigs, and the prior weights.
+
+--smooth OUT.npz (opt-in; model_params.smooth; 2+ cameras, one rank) keeps the same rows plus the ground truth and the image
+paths, which name the sequence and frame of every sample, and after the loop smooths every joint's triangulated track over the
+frames of its sequence: reprojection cost plus --smooth-acc times the squared acceleration, frames without data filled
+(xas_amd.ops_track.track_smooth).  OUT.npz holds `joints`, `status`, `track`, `frame`, `track_status`, `cost` and `trials`;
+eval_result.txt gains two lines.  Unknown: its effect on MPJPE on real sequences, and the right --smooth-acc.
+
+--resolve-track OUT.npz (opt-in; model_params.resolve_track; one rank, any number of cameras) keeps every camera's raw
+detections and, after the loop and without labels, chooses per camera every joint's depth hypothesis and every limb pair's
+left/right exchange over the frames of its sequence: motion cost plus priors, exact by dynamic programming
+(xas_amd.ops_track.track_resolve).  OUT.npz holds per camera `joints`, `sel`, `hyp`, `swap`, `status`, `cost`, `named`,
+`track` and `frame`; eval_result.txt gains one line per camera, which also states the MPJPE of the choice made with labels.
+Unknown: its accuracy on real detections, and the weights, untuned guesses all four.
+
+The post-loop options keep their rows in the plain lists fit_rows, calib_rows, smooth_rows and rt_rows and write their files
+(atomically) from record().
 """
 import copy
 import os
 from argparse import ArgumentParser
+from collections import namedtuple
 
 import numpy as np
 
@@ -99,42 +128,99 @@ def ddp_setup():
     torch.cuda.set_device(int(os.environ['LOCAL_RANK']))
 
 
+# What the stages of Eval.eval_batch hand on.  A field is None where the options that ran produce none.
+#   sel {cam: [B,K,3]} the selected joints in the patch; trans [B,K,1] the views that exchanged each joint; chan, per camera,
+#   [B,K] int32 the heat-map channel each joint was read from (tri_volume); raw {cam: [B,Hy,K,3]} the detections as they came;
+#   weights {cam: [B,K]} (tri_weight='spread'); cubes {cam: logits} (tri_volume); out: the stage's entries of the result
+Selection = namedtuple('Selection', 'sel trans chan raw weights cubes out')
+#   point [B,K,3] world mm; used [B,K] uint8 the views behind it (tri='robust'); bad [B,K] joints a solver passed through and
+#   cov [B,K,6] mm^2 (both fit_smpl only); inputs (points [B,V,K,3], projection matrices [B,V,3,4]), formed once per batch
+Triangulated = namedtuple('Triangulated', 'point used bad cov inputs out')
+
+# the per-batch figures of eval_batch's result that eval() sums and the lines of eval_result.txt report as means over the batches
+MEANS = ('tri_inlier_views', 'resolve_exchanged', 'resolve_hyp0', 'tri_sigma', 'tri_refine_px', 'tri_refine_gain_px', 'tri_sym_mm',
+         'tri_vol_move_mm', 'tri_vol_sigma_mm', 'tri_vol_status')
+
+
+def check_cameras(cam_id_list, message, least=0):
+    """An option's bound on the cameras, `least` to ops_eval.TRI_MAX_VIEWS of them: outside it a ValueError of `message`, formatted
+    with that maximum and the number of cameras."""
+    if not least <= len(cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
+        raise ValueError(message.format(ops_eval.TRI_MAX_VIEWS, len(cam_id_list)))
+
+
+def check_single_rank(message):
+    """An option that needs the whole set on one rank: a ValueError of `message` unless WORLD_SIZE is 1 or unset."""
+    if int(os.environ.get('WORLD_SIZE', 1)) != 1:
+        raise ValueError(message)
+
+
+def save_npz(path, cols):
+    """np.savez of `cols` at `path`, atomically: a temporary file beside it, then a rename."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + '.tmp.npz'
+    np.savez(tmp, **cols)
+    os.replace(tmp, path)
+
+
+def cat_rows(rows, key):
+    """Column `key` of the rows that the batches kept, as one: tensors concatenated, lists (the image paths) chained, and None
+    where the rows hold None (no views, no paths)."""
+    first = rows[0][key]
+    if first is None:
+        return None
+    return [p for r in rows for p in r[key]] if isinstance(first, list) else torch.cat([r[key] for r in rows])
+
+
+def joint_errors(joints, gt):
+    """[N,K] mm between `joints` and `gt` without alignment (the MPJPE's terms); a joint that is not finite counts as the origin
+    and is for the caller to mask out."""
+    return pose_errors(torch.where(torch.isfinite(joints), joints, torch.zeros_like(joints)), gt, want=('err',))['err'][0]
+
+
+def masked_mean(errors, mask):
+    """Mean of errors[mask] as a float, NaN where the mask is empty."""
+    return float(errors[mask].mean()) if bool(mask.any()) else float('nan')
+
+
+def homogeneous(point):
+    """[...,3+] -> [...,4]: the first three coordinates and a one, the form the solvers take their start in."""
+    return torch.cat([point[..., :3], torch.ones_like(point[..., :1])], dim=-1).contiguous()
+
+
 class Eval:
     """Same constructor and method signatures as the reference Eval (eval.py:63-107)."""
 
     def __init__(self, config, detector, eval_data, log_dir, img_size=256.0, flip_test=False, tri='dlt',
                  tri_thresh=ops_eval.TRI_ROBUST_PX, resolve='gt'):
+        mp = config['model_params']                # the options after --resolve are no keys of the shipped configs: eval.py's flags
+        cam_id_list = mp['cam_id_list']
         if tri not in ('dlt', 'robust'):
             raise ValueError('Unknown triangulation: {}'.format(tri))
         if resolve not in ('gt', 'views'):
             raise ValueError('Unknown resolve mode: {}'.format(resolve))
-        tri_weight = config['model_params'].get('tri_weight', 'depth')         # --tri-weight; not a key of the shipped configs
+        tri_weight = mp.get('tri_weight', 'depth')
         if tri_weight not in ('depth', 'spread'):
             raise ValueError('Unknown triangulation weight: {}'.format(tri_weight))
-        tri_refine = config['model_params'].get('tri_refine', 'none')          # --tri-refine / --tri-huber; not keys of the shipped configs either
+        tri_refine = mp.get('tri_refine', 'none')
         if tri_refine not in ('none', 'lm', 'skeleton'):
             raise ValueError('Unknown triangulation refinement: {}'.format(tri_refine))
-        if tri_refine == 'lm' and len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
-            raise ValueError("tri_refine='lm' refines over at most {} cameras; cam_id_list has {}".format(
-                ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
+        if tri_refine != 'none':
+            check_cameras(cam_id_list, "tri_refine='" + tri_refine + "' refines over at most {} cameras; cam_id_list has {}")
         if tri_refine == 'skeleton':
-            if len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
-                raise ValueError("tri_refine='skeleton' refines over at most {} cameras; cam_id_list has {}".format(
-                    ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
-            num_kp = getattr(detector, 'num_kp', config['model_params'].get('detector_params', {}).get('num_kp'))
+            num_kp = getattr(detector, 'num_kp', mp.get('detector_params', {}).get('num_kp'))
             if num_kp is not None and num_kp > ops_eval.SKEL_MAX_JOINTS:
                 raise ValueError("tri_refine='skeleton' couples at most {} joints; the detector has {}".format(
                     ops_eval.SKEL_MAX_JOINTS, num_kp))
-        tri_volume = bool(config['model_params'].get('tri_volume', False))     # --tri-volume; not a key of the shipped configs either
+        tri_volume = bool(mp.get('tri_volume', False))
         if tri_volume and flip_test:
             raise ValueError('tri_volume fuses the heat-map cubes of the cameras; the flip test\'s head works on an average of two '
                              'cubes that is never formed in memory: --tri-volume does not go with --flip')
-        if tri_volume and len(config['model_params']['cam_id_list']) > ops_eval.TRI_MAX_VIEWS:
-            raise ValueError('tri_volume fuses at most {} cameras; cam_id_list has {}'.format(
-                ops_eval.TRI_MAX_VIEWS, len(config['model_params']['cam_id_list'])))
+        if tri_volume:
+            check_cameras(cam_id_list, 'tri_volume fuses at most {} cameras; cam_id_list has {}')
         self.gpu_id = int(os.environ.get('LOCAL_RANK', 0))
         self.config = config
-        self.cam_id_list = config['model_params']['cam_id_list']
+        self.cam_id_list = cam_id_list
         self.cal_per_act = config['dataset_params']['dataset']['name'] != 'mpi_inf_3dhp'
         self.detector = detector.to(self.gpu_id)
         self.detector.eval()                       # BN uses running statistics; no DDP wrapper is needed to evaluate
@@ -143,26 +229,20 @@ class Eval:
         self.img_size = img_size
         self.flip_test = bool(flip_test)           # --flip: every image is evaluated together with its horizontal mirror
         self.tri, self.tri_thresh = tri, float(tri_thresh)   # --tri robust: DLT over the views that agree within tri_thresh px
-        self.tri_views, self.tri_batches = 0.0, 0  # robust only: mean views used per joint, summed over the batches
         self.resolve = resolve                     # --resolve views: exchange and hypothesis by the cameras' agreement
-        if resolve == 'views' and not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
-            raise ValueError("resolve='views' decides by the agreement of the cameras and needs 2 to {} of them; cam_id_list "
-                             'has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
-        self.res_exchanged, self.res_hyp0, self.res_batches = 0.0, 0.0, 0      # views only, summed over the batches
+        if resolve == 'views':
+            check_cameras(cam_id_list, "resolve='views' decides by the agreement of the cameras and needs 2 to {} of them; "
+                                       'cam_id_list has {}', least=2)
+        self.sums = {}                             # key of MEANS -> [sum over the batches, batches]: see add() and mean()
         self.tri_weight = tri_weight               # --tri-weight spread: a view counts by its heat-map's 1 / sigma, not its depth
         self.spread = None                         # spread only: heat-map spread [B,K,5] of the latest detect()
-        self.tri_sigma, self.sigma_batches = 0.0, 0    # spread only: mean sigma in pixels, summed over the batches
         self.tri_refine = tri_refine               # --tri-refine lm: the triangulated point minimises the reprojection error in pixels
-        self.tri_huber = float(config['model_params'].get('tri_huber', 0.0))   # lm only: Huber's delta, 0 = plain least squares
-        self.refine_px, self.refine_gain, self.refine_batches = 0.0, 0.0, 0    # lm and skeleton, summed over the batches
-        self.tri_sym = float(config['model_params'].get('tri_sym', ops_eval.TRI_SYM_W))    # skeleton only: --tri-sym, px^2 per mm^2
-        self.sym_mm = np.zeros(2)                  # skeleton only: mean |limb a| - |limb b| in mm before and after, summed
+        self.tri_huber = float(mp.get('tri_huber', 0.0))   # lm and skeleton: Huber's delta, 0 = plain least squares
+        self.tri_sym = float(mp.get('tri_sym', ops_eval.TRI_SYM_W))    # skeleton only: --tri-sym, px^2 per mm^2
         self.tri_volume = tri_volume               # --tri-volume: the cameras' heat-map cubes fused round the triangulated point
-        mp = config['model_params']
         self.vol_side = float(mp.get('tri_vol_side', ops_eval.TRI_VOL_SIDE_MM))
         self.vol_grid, self.vol_levels = int(mp.get('tri_vol_grid', ops_eval.TRI_VOL_G)), int(mp.get('tri_vol_levels', ops_eval.TRI_VOL_LEVELS))
         self.logits = None                         # volume only: the logits [B,K*D,D,D] of the latest detect()
-        self.vol_move, self.vol_sigma, self.vol_status, self.vol_batches = 0.0, 0.0, np.zeros(4), 0   # volume only, summed
         self.fit_smpl = mp.get('fit_smpl') or None     # --fit-smpl OUT.npz: SMPL parameters of the final world joints, a --pseudo-online bank
         if self.fit_smpl:
             smpl = prepare_smpl(mp)                  # (Eval's signature is pinned: the model comes through model_params.smpl_model)
@@ -180,11 +260,9 @@ class Eval:
             raise ValueError('calibrate estimates corrections of the given cameras and calibration applies earlier ones: '
                              '--calibrate and --calibration do not go together')
         if self.calibrate:
-            if not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
-                raise ValueError('calibrate needs 2 to {} cameras; cam_id_list has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
-            if int(os.environ.get('WORLD_SIZE', 1)) != 1:
-                raise ValueError('calibrate needs WORLD_SIZE == 1: a rank sees only its shard of the set, and a bundle over '
-                                 'several ranks is not built')
+            check_cameras(cam_id_list, 'calibrate needs 2 to {} cameras; cam_id_list has {}', least=2)
+            check_single_rank('calibrate needs WORLD_SIZE == 1: a rank sees only its shard of the set, and a bundle over '
+                              'several ranks is not built')
             from xas_amd import ops_calib              # only with the flag
             self.calib_iters = int(mp.get('calib_iters', 30))
             self.calib_prior_rot = float(mp.get('calib_prior_rot', ops_calib.CALIB_PRIOR_ROT))        # untuned guesses, both
@@ -193,11 +271,9 @@ class Eval:
             self.calib_rows = []                       # per batch, on the device: points, pmat, init, views
         self.smooth = mp.get('smooth') or None         # --smooth OUT.npz: the joint tracks smoothed over time, over the whole set
         if self.smooth:
-            if not 2 <= len(self.cam_id_list) <= ops_eval.TRI_MAX_VIEWS:
-                raise ValueError('smooth needs 2 to {} cameras; cam_id_list has {}'.format(ops_eval.TRI_MAX_VIEWS, len(self.cam_id_list)))
-            if int(os.environ.get('WORLD_SIZE', 1)) != 1:
-                raise ValueError('smooth needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out over '
-                                 'the ranks, and no rank sees a track')
+            check_cameras(cam_id_list, 'smooth needs 2 to {} cameras; cam_id_list has {}', least=2)
+            check_single_rank('smooth needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out over '
+                              'the ranks, and no rank sees a track')
             from xas_amd import ops_track              # only with the flag
             self.smooth_acc = float(mp.get('smooth_acc', ops_track.TRACK_ACC_W))                     # untuned guesses, both
             self.smooth_gap = int(mp.get('smooth_gap', ops_track.TRACK_MAX_GAP))
@@ -205,9 +281,8 @@ class Eval:
             self.smooth_rows = []                      # per batch, on the device: points, pmat, init, views, gt; and the paths
         self.resolve_track = mp.get('resolve_track') or None   # --resolve-track OUT.npz: hypothesis and exchange chosen over time, per camera
         if self.resolve_track:
-            if int(os.environ.get('WORLD_SIZE', 1)) != 1:
-                raise ValueError('resolve_track needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out '
-                                 'over the ranks, and no rank sees a track')
+            check_single_rank('resolve_track needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out '
+                              'over the ranks, and no rank sees a track')
             from xas_amd import ops_track              # only with the flag
             self.rt_vel = float(mp.get('rt_vel', ops_track.TRACK_VEL_W))                             # untuned guesses, all four
             self.rt_hyp = float(mp.get('rt_hyp', ops_track.TRACK_HYP_W))
@@ -219,13 +294,53 @@ class Eval:
                 self.calib_keys = torch.from_numpy(f['keys']).to(self.gpu_id)
                 self.calib_delta = torch.from_numpy(f['delta']).to(self.gpu_id)
 
+    def add(self, key, value):
+        """One batch's figure (a scalar, or a vector such as tri_sym_mm [2] and tri_vol_status [4]) into the sum of `key`, in double."""
+        value = float(value) if np.ndim(value) == 0 else np.asarray(value, dtype=np.float64)
+        entry = self.sums.setdefault(key, [0.0, 0])
+        entry[0], entry[1] = entry[0] + value, entry[1] + 1
+
+    def mean(self, key, size=None):
+        """Mean of `key` over the batches that produced it; without any, 0.0 (np.zeros(size) for a vector of that size)."""
+        total, n = self.sums.get(key, (0.0 if size is None else np.zeros(size), 0))
+        return total / max(n, 1)
+
+    def option_lines(self):
+        """The lines that the options add to eval_result.txt after the reference's, in their fixed order.  An option that is off
+        adds none, so the file is then as it was; the post-loop options also write their files here."""
+        lines, cams = [], len(self.cam_id_list)
+        if self.tri == 'robust':
+            lines.append('TRI inlier views ({} px): {} of {}'.format(self.tri_thresh, self.mean('tri_inlier_views'), cams))
+        if self.resolve == 'views':
+            lines.append('RESOLVE views: exchanged {} , hypothesis 0 kept {}'.format(self.mean('resolve_exchanged'), self.mean('resolve_hyp0')))
+        if self.tri_weight == 'spread':
+            lines.append('TRI weight spread: mean sigma {} px'.format(self.mean('tri_sigma')))
+        if self.tri_refine == 'lm':
+            lines.append('TRI refine lm (huber {}): reprojection RMS {} px, gained {} px'.format(
+                self.tri_huber, self.mean('tri_refine_px'), self.mean('tri_refine_gain_px')))
+        if self.tri_refine == 'skeleton':
+            lines.append('TRI refine skeleton (huber {}, sym {}): reprojection RMS {} px, gained {} px, limb asymmetry {} -> {} mm'.format(
+                self.tri_huber, self.tri_sym, self.mean('tri_refine_px'), self.mean('tri_refine_gain_px'), *self.mean('tri_sym_mm', 2)))
+        if self.tri_volume:
+            lines.append('TRI volume (side {} mm, grid {}, levels {}): moved {} mm, sigma {} mm'.format(
+                self.vol_side, self.vol_grid, self.vol_levels, self.mean('tri_vol_move_mm'), self.mean('tri_vol_sigma_mm')))
+            lines.append('TRI volume status: fused {} , passed through {} , mode on a face {} , logits not finite {}'.format(
+                *self.mean('tri_vol_status', 4)))
+        if self.fit_smpl:
+            lines.append(self.write_fit())
+        if self.calibrate:
+            lines.extend(self.write_calibration())
+        if self.smooth:
+            lines.extend(self.write_smooth())
+        if self.resolve_track:
+            lines.extend(self.write_resolve_track())
+        return lines
+
     def write_calibration(self):
-        """--calibrate: one bundle adjustment over everything the batches kept, the file (atomically: a temporary file beside
-        it, then a rename) and -> the lines of eval_result.txt, one per rig."""
+        """--calibrate: one bundle adjustment over everything the batches kept, the file and -> the lines of eval_result.txt,
+        one per rig."""
         from xas_amd import ops_calib
-        cat = lambda k: torch.cat([r[k] for r in self.calib_rows])
-        points, pmat, init = cat('points'), cat('pmat'), cat('init')
-        views = cat('views') if self.calib_rows[0]['views'] is not None else None
+        points, pmat, init, views = (cat_rows(self.calib_rows, k) for k in ('points', 'pmat', 'init', 'views'))
         rig, keys = ops_calib.rigs_of(pmat)
         r = ops_calib.calibrate_bundle(points, pmat, init, rig, views=views, free=self.calib_free,
                                        weighted=self.tri_weight == 'spread', huber_px=self.tri_huber,
@@ -234,10 +349,7 @@ class Eval:
         cols = {k: r[k].cpu().numpy() for k in ('delta', 'cost', 'rms', 'status', 'cam_cov')}
         made = r['trials'].cpu().numpy()
         cols['keys'] = keys.cpu().numpy()
-        os.makedirs(os.path.dirname(os.path.abspath(self.calibrate)), exist_ok=True)
-        tmp = self.calibrate + '.tmp.npz'
-        np.savez(tmp, **cols)
-        os.replace(tmp, self.calibrate)
+        save_npz(self.calibrate, cols)
         d = cols['delta']
         return ['CALIBRATE rig {} ({} of {} trials, prior rot {}, prior trans {}): reprojection RMS {} -> {} px, largest |omega| {} deg, '
                 'largest |tau| {} mm, {}'.format(i, int(made[i, 0]), self.calib_iters, self.calib_prior_rot, self.calib_prior_trans,
@@ -247,56 +359,42 @@ class Eval:
                                                  ops_calib.STATUS_NAMES[int(cols['status'][i])]) for i in range(len(d))]
 
     def write_smooth(self):
-        """--smooth: one track_smooth over everything the batches kept, the file (atomically: a temporary file beside it, then
-        a rename) and -> the two lines of eval_result.txt."""
+        """--smooth: one track_smooth over everything the batches kept, the file and -> the two lines of eval_result.txt."""
         from xas_amd import ops_track
-        rows = self.smooth_rows
-        cat = lambda k: torch.cat([r[k] for r in rows])
-        points, pmat, init, gt = cat('points'), cat('pmat'), cat('init'), cat('gt')
-        views = cat('views') if rows[0]['views'] is not None else None
-        paths = [p for r in rows for p in r['paths']] if rows[0]['paths'] is not None else None
+        points, pmat, init, gt, views, paths = (cat_rows(self.smooth_rows, k) for k in ('points', 'pmat', 'init', 'gt', 'views', 'paths'))
         track, frame = ops_track.tracks_of(paths, self.smooth_gap, count=len(points))
         r = ops_track.track_smooth(points, pmat, init, track, frame, views=views, weighted=self.tri_weight == 'spread',
                                    huber_px=self.tri_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
         joints, status = r['xyzw'][..., :3].contiguous(), r['status']
         both = torch.isfinite(joints).all(-1) & torch.isfinite(init[..., :3]).all(-1)                  # [N,K]
-        err = lambda p: pose_errors(torch.where(torch.isfinite(p), p, torch.zeros_like(p)), gt, want=('err',))['err'][0]   # [N,K] mm, no alignment
-        e_before, e_after = err(init[..., :3].contiguous()), err(joints)
-        mean = lambda e, m: float(e[m].mean()) if bool(m.any()) else float('nan')
+        e_before, e_after = joint_errors(init[..., :3].contiguous(), gt), joint_errors(joints, gt)
         filled = (status == ops_track.STATUS_FILLED) & torch.isfinite(joints).all(-1)
         rms = lambda c: float(torch.sqrt((r['resid'][..., c] ** 2).nanmean()))
         cols = {'joints': joints, 'status': status, 'track_status': r['track_status'], 'cost': r['cost'], 'trials': r['trials']}
         cols = {k: v.cpu().numpy() for k, v in cols.items()}
         cols['track'], cols['frame'] = track, frame
-        os.makedirs(os.path.dirname(os.path.abspath(self.smooth)), exist_ok=True)
-        tmp = self.smooth + '.tmp.npz'
-        np.savez(tmp, **cols)
-        os.replace(tmp, self.smooth)
+        save_npz(self.smooth, cols)
         S = len(r['tracks'])
         return ['SMOOTH {} tracks of mean length {} (acc {}, gap {}, {} trials): TRI MPJPE {} -> {} mm, reprojection RMS {} -> {} px, '
                 'gaps filled {} , passed through {}'.format(S, len(points) / S, self.smooth_acc, self.smooth_gap, self.smooth_iters,
-                                                            mean(e_before, both), mean(e_after, both), rms(0), rms(1),
+                                                            masked_mean(e_before, both), masked_mean(e_after, both), rms(0), rms(1),
                                                             float((status == ops_track.STATUS_FILLED).float().mean()),
                                                             float((status == ops_track.STATUS_PASSED).float().mean())),
-                'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(mean(e_after, filled), int(filled.sum()))]
+                'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))]
 
     def write_resolve_track(self):
-        """--resolve-track: one track_resolve per camera over everything the batches kept, the file (atomically: a temporary
-        file beside it, then a rename) and -> the lines of eval_result.txt, one per camera."""
+        """--resolve-track: one track_resolve per camera over everything the batches kept, the file and -> the lines of
+        eval_result.txt, one per camera."""
         from xas_amd import ops_track
         rows = self.rt_rows
-        gt = torch.cat([r['gt'] for r in rows])
-        err = lambda p: pose_errors(torch.where(torch.isfinite(p), p, torch.zeros_like(p)), gt, want=('err',))['err'][0]   # [N,K] mm, no alignment
-        mean = lambda e, m: float(e[m].mean()) if bool(m.any()) else float('nan')
+        gt = cat_rows(rows, 'gt')
         cols, lines = {}, []
         for c in self.cam_id_list:
             m = 'cam_{}'.format(c)
-            cat = lambda k: torch.cat([r[m][k] for r in rows])
-            kps, world, view = cat('kps'), cat('world'), cat('view')
-            paths = [p for r in rows for p in r[m]['paths']] if rows[0][m]['paths'] is not None else None
+            kps, world, view, labels, paths = (cat_rows([r[m] for r in rows], k) for k in ('kps', 'world', 'view', 'labels', 'paths'))
             track, frame = ops_track.tracks_of(paths, self.rt_gap, count=len(kps))
             r = ops_track.track_resolve(kps, world, track, frame, vel_w=self.rt_vel, hyp_w=self.rt_hyp, swap_w=self.rt_swap,
-                                        gt=cat('labels'), image_size=self.img_size)
+                                        gt=labels, image_size=self.img_size)
             perm = ops_eval.switch_perm(kps.shape[2], ops_eval.SWITCH_PAIRS, kps.device)
             joints = ops_track.resolved_gather(world, r['hyp'], r['swap'], perm)[..., :3].contiguous()
             first = world[:, 0, :, :3].contiguous()
@@ -309,13 +407,11 @@ class Eval:
             paired = perm.long() != torch.arange(len(perm), device=perm.device)
             lines.append('RESOLVE track {}: {} tracks of mean length {} (vel {}, hyp {}, swap {}, gap {}): MPJPE hypothesis 0 as given {} '
                          '-> {} mm ({} with labels: {} mm), exchanged {} , hypothesis 0 kept {} , passed through {}'.format(
-                             m, S, len(kps) / S, self.rt_vel, self.rt_hyp, self.rt_swap, self.rt_gap, mean(err(first), ok),
-                             mean(err(joints), ok), rows[0]['mode'], mean(err(view), ok), float(r['swap'][:, paired].float().mean()),
-                             float((r['hyp'] == 0).float().mean()), float((r['status'] == ops_track.RESOLVE_PASSED).float().mean())))
-        os.makedirs(os.path.dirname(os.path.abspath(self.resolve_track)), exist_ok=True)
-        tmp = self.resolve_track + '.tmp.npz'
-        np.savez(tmp, **cols)
-        os.replace(tmp, self.resolve_track)
+                             m, S, len(kps) / S, self.rt_vel, self.rt_hyp, self.rt_swap, self.rt_gap, masked_mean(joint_errors(first, gt), ok),
+                             masked_mean(joint_errors(joints, gt), ok), rows[0]['mode'], masked_mean(joint_errors(view, gt), ok),
+                             float(r['swap'][:, paired].float().mean()), float((r['hyp'] == 0).float().mean()),
+                             float((r['status'] == ops_track.RESOLVE_PASSED).float().mean())))
+        save_npz(self.resolve_track, cols)
         return lines
 
     def fit_batch(self, joints, bad, cov):
@@ -339,17 +435,19 @@ class Eval:
         return {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
                 'fit_cost': r['cost'].float(), 'fit_status': r['status'], 'fit_joint_rms_mm': rms.float()}
 
+    def keep_fit_rows(self, host):
+        """--fit-smpl: the fit_* entries of a batch's host arrays as one row of the file (none without the flag: no row)."""
+        row = {k[4:]: v for k, v in host.items() if k.startswith('fit_')}
+        if row:
+            self.fit_rows.append(row)
+
     def write_fit(self):
-        """Writes the --fit-smpl file (atomically: a temporary file beside it, then a rename); passed-through samples are kept
-        with their status.  -> the line of eval_result.txt."""
+        """Writes the --fit-smpl file; passed-through samples are kept with their status.  -> the line of eval_result.txt."""
         from xas_amd import ops_smplfit
         shapes = {'pose': (0, 72), 'betas': (0, 10), 'trans': (0, 3), 'cost': (0, 2), 'status': (0,), 'joint_rms_mm': (0,)}
         cols = {k: (np.concatenate([r[k] for r in self.fit_rows]) if self.fit_rows else np.zeros(sh, np.uint8 if k == 'status' else np.float32))
                 for k, sh in shapes.items()}
-        os.makedirs(os.path.dirname(os.path.abspath(self.fit_smpl)), exist_ok=True)
-        tmp = self.fit_smpl + '.tmp.npz'
-        np.savez(tmp, **cols)
-        os.replace(tmp, self.fit_smpl)
+        save_npz(self.fit_smpl, cols)
         n = max(len(cols['status']), 1)
         fitted = cols['status'] != ops_smplfit.STATUS_PASSED
         rms = float(cols['joint_rms_mm'][fitted].mean()) if fitted.any() else float('nan')
@@ -385,52 +483,30 @@ class Eval:
                 x[key] = torch.from_numpy(v).to(self.gpu_id)
         return x
 
-    @torch.no_grad()
-    def eval_batch(self, x, mode='best', kps_by_cam=None):
-        """Device part of one iteration of eval.py:111-204.  Returns ({name: tensor on the device}, layout) where
-        every tensor is per sample [B] (errors), or a scalar (ambiguity, pck, auc).  With resolve='views' `mode` is ignored:
-        the cameras' agreement picks the hypotheses."""
-        cams = ['cam_{}'.format(c) for c in self.cam_id_list]
-        sel, out, trans = {}, {}, None
-        given = x                                  # the ground truth reads the cameras as given; --calibration corrects the predictions'
-        if self.calibration:
-            x = apply_calibration(x, self.cam_id_list, self.calib_keys, self.calib_delta)
-        weights = {} if self.tri_weight == 'spread' else None
-        cubes, chan = ({}, []) if self.tri_volume else (None, None)
-        raw_kps = {} if self.resolve_track else None   # --resolve-track: every camera's detections as they came
+    # ---- the stages of one batch, in the order eval_batch calls them ----
 
-        def detect(m):                             # one camera's joints; spread: also its weights, which need the detector
-            kps = self.detect(x[m + '_img']) if kps_by_cam is None or weights is not None or cubes is not None else None
-            if weights is not None:
-                weights[m] = spread_weight(self.spread, x[m + '_trans_image'])
-            if cubes is not None:
-                cubes[m] = self.logits             # every camera's logits stay alive until the fusion
-            return kps if kps_by_cam is None else kps_by_cam[m]
+    def calibrated(self, x):
+        """-> the batch the predictions read: `x` itself, or with --calibration a shallow copy whose cameras are corrected."""
+        return apply_calibration(x, self.cam_id_list, self.calib_keys, self.calib_delta) if self.calibration else x
 
-        if self.resolve == 'views':
-            raw = {m: detect(m) for m in cams}
-            if raw_kps is not None:
-                raw_kps.update(raw)
-            sel, r = resolve_views_weighted(raw, x, self.cam_id_list, ops_eval.SWITCH_PAIRS, weights, gt=True)   # None: the depth
-            for m in cams:                         # the labels' part from here on: measuring, no longer choosing
-                out['err2d_' + m] = ops_eval.eval_select(sel[m].unsqueeze(1), x[m + '_joints'], image_size=self.img_size,
-                                                         mode='confident', no_switch=True, want=('err2d',))['err2d']
-            shifts = torch.arange(len(cams), device=r['swap'].device, dtype=torch.int32)
-            count = lambda mask: ((mask.unsqueeze(-1).int() >> shifts) & 1).sum(dim=-1).float()     # [B,K] bits set
-            trans = count(r['swap']).unsqueeze(-1)
-            B, K = r['swap'].shape
-            perm = ops_eval.switch_perm(K, ops_eval.SWITCH_PAIRS, shifts.device)
-            paired = (perm != torch.arange(K, device=shifts.device, dtype=torch.int32)).float()       # [K], both of a pair
-            before = torch.where(r['named'].bool(), count(r['valid']) - count(r['swap']), count(r['swap']))   # naming undone
-            out['resolve_exchanged'] = (before * paired).sum() / (paired.sum().clamp(min=1.0) * B * len(cams))
-            out['resolve_hyp0'] = (r['hyp'] == 0).float().mean()
-            if chan is not None:                   # view v read joint k from perm[k] where bit v of swap is set
-                own = torch.arange(K, device=shifts.device, dtype=torch.int32)
-                chan = [torch.where(((r['swap'].int() >> v) & 1).bool(), perm, own) for v in range(len(cams))]
-        for m in ([] if self.resolve == 'views' else cams):
-            kps = detect(m)
-            if raw_kps is not None:
-                raw_kps[m] = kps
+    def detect_camera(self, x, m, kps_by_cam, weights, cubes):
+        """-> the detections [B,Hy,K,3] of camera `m`: the planted kps_by_cam[m] where given, else the detector's.  Under planted
+        detections the detector still runs when the spread or the logits are needed, and only then: `weights` and `cubes`
+        (None where the options want none) gain the camera's entry."""
+        kps = self.detect(x[m + '_img']) if kps_by_cam is None or weights is not None or cubes is not None else None
+        if weights is not None:
+            weights[m] = spread_weight(self.spread, x[m + '_trans_image'])
+        if cubes is not None:
+            cubes[m] = self.logits                 # every camera's logits stay alive until the fusion
+        return kps if kps_by_cam is None else kps_by_cam[m]
+
+    def select_by_labels(self, x, cams, mode, kps_by_cam):
+        """The reference's selection: left/right exchange and hypothesis of every view by its labels (ops_eval.eval_select, one
+        launch per camera).  -> Selection; out: err2d_<cam> [B]."""
+        weights, cubes = {} if self.tri_weight == 'spread' else None, {} if self.tri_volume else None
+        sel, raw, out, trans, chan = {}, {}, {}, None, [] if self.tri_volume else None
+        for m in cams:
+            raw[m] = kps = self.detect_camera(x, m, kps_by_cam, weights, cubes)
             s = ops_eval.eval_select(kps, x[m + '_joints'], image_size=self.img_size, mode=mode)
             sel[m] = s['sel3d']
             out['err2d_' + m] = s['err2d']
@@ -440,63 +516,108 @@ class Eval:
                 K = s['swapped'].shape[1]
                 perm = ops_eval.switch_perm(K, ops_eval.SWITCH_PAIRS, kps.device)
                 chan.append(torch.where(s['swapped'].squeeze(-1), perm, torch.arange(K, device=kps.device, dtype=torch.int32)))
-        out['ambiguity'] = torch.minimum(trans, len(cams) - trans).mean()                  # eval.py:164-167
-        gt = convert_patch_to_world(given['cam_0_joints'], given, 'cam_0', is_norm=False)  # eval.py:170
-        fit_bad = fit_cov = None                   # --fit-smpl only: joints a solver passed through, and a covariance if one came
-        fit_want = (('status',) + (('cov',) if weights is not None and self.tri_refine == 'lm' else ())) if self.fit_smpl else ()
-        if len(cams) == 1 and self.tri == 'dlt' and self.tri_refine == 'none':     # one camera: nothing to triangulate, its own point
-            tri = convert_patch_to_world(sel[cams[0]], x, cams[0], is_norm=True)[..., :3]            # (the DLT refuses one view)
-        elif self.tri_refine == 'lm':              # the same solver, then the pixel error minimised over the views it used
-            tri, r = triangulation_refined(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, want=('resid',) + fit_want,
-                                           robust_px=self.tri_thresh if self.tri == 'robust' else None)
+        return Selection(sel, trans, chan, raw, weights, cubes, out)
+
+    def select_by_views(self, x, cams, kps_by_cam):
+        """--resolve views: exchange and hypothesis of all views by the cameras' agreement in one launch; the labels only name
+        each pair and then measure.  -> Selection; out: err2d_<cam> [B], resolve_exchanged and resolve_hyp0 (scalars)."""
+        weights, cubes = {} if self.tri_weight == 'spread' else None, {} if self.tri_volume else None
+        raw = {m: self.detect_camera(x, m, kps_by_cam, weights, cubes) for m in cams}
+        sel, r = resolve_views_weighted(raw, x, self.cam_id_list, ops_eval.SWITCH_PAIRS, weights, gt=True)   # None: the depth
+        out = {}
+        for m in cams:                             # the labels' part from here on: measuring, no longer choosing
+            out['err2d_' + m] = ops_eval.eval_select(sel[m].unsqueeze(1), x[m + '_joints'], image_size=self.img_size,
+                                                     mode='confident', no_switch=True, want=('err2d',))['err2d']
+        shifts = torch.arange(len(cams), device=r['swap'].device, dtype=torch.int32)
+        count = lambda mask: ((mask.unsqueeze(-1).int() >> shifts) & 1).sum(dim=-1).float()     # [B,K] bits set
+        trans = count(r['swap']).unsqueeze(-1)
+        B, K = r['swap'].shape
+        own = torch.arange(K, device=shifts.device, dtype=torch.int32)
+        perm = ops_eval.switch_perm(K, ops_eval.SWITCH_PAIRS, shifts.device)
+        paired = (perm != own).float()                                                            # [K], both of a pair
+        before = torch.where(r['named'].bool(), count(r['valid']) - count(r['swap']), count(r['swap']))   # naming undone
+        out['resolve_exchanged'] = (before * paired).sum() / (paired.sum().clamp(min=1.0) * B * len(cams))
+        out['resolve_hyp0'] = (r['hyp'] == 0).float().mean()
+        chan = None
+        if self.tri_volume:                        # view v read joint k from perm[k] where bit v of swap is set
+            chan = [torch.where(((r['swap'].int() >> v) & 1).bool(), perm, own) for v in range(len(cams))]
+        return Selection(sel, trans, chan, raw, weights, cubes, out)
+
+    def triangulate(self, s, x, cams):
+        """The world joints of the selected views: the DLT or the robust DLT over inputs formed once, then --tri-refine lm or
+        skeleton from its point.  One camera without robust or refinement: that view's own point, and no inputs.
+        -> Triangulated; out: tri_refine_px, tri_refine_gain_px, tri_sym_mm [2], tri_inlier_views, tri_sigma, each with its option."""
+        robust_px = self.tri_thresh if self.tri == 'robust' else None
+        out, inputs, used, bad, cov = {}, None, None, None, None
+        if len(cams) == 1 and self.tri == 'dlt' and self.tri_refine == 'none':      # nothing to triangulate (the DLT refuses one view)
+            tri = convert_patch_to_world(s.sel[cams[0]], x, cams[0], is_norm=True)[..., :3]
+        elif self.tri_refine == 'none':
+            inputs = triangulation_inputs(s.sel, x, self.cam_id_list, s.weights)
+            tri, used = triangulation_weighted(s.sel, x, self.cam_id_list, s.weights, robust_px=robust_px, return_inliers=True, inputs=inputs)
+        else:                                      # the same start, then the pixel error minimised over the views it used
+            inputs = triangulation_inputs(s.sel, x, self.cam_id_list, s.weights)
+            want = ('resid',)
+            if self.fit_smpl:                      # the joints passed through, and a covariance where the solver has a meaningful one
+                want += ('status', 'cov') if self.tri_refine == 'lm' and s.weights is not None else ('status',)
+            if self.tri_refine == 'lm':
+                tri, r = triangulation_refined(s.sel, x, self.cam_id_list, s.weights, huber_px=self.tri_huber, want=want,
+                                               robust_px=robust_px, inputs=inputs)
+            else:                                  # the joints of a sample refined together
+                tri, r = triangulation_skeleton(s.sel, x, self.cam_id_list, s.weights, huber_px=self.tri_huber, sym_w=self.tri_sym,
+                                                want=want + ('sym',), robust_px=robust_px, inputs=inputs)
             used = r.get('inliers')
-            out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a joint passed through has no residual (NaN)
+            out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a joint passed through or fixed has no residual (NaN)
             out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
+            if self.tri_refine == 'skeleton':
+                out['tri_sym_mm'] = r['sym'].abs().reshape(-1, 2).nanmean(dim=0)   # [2]: before, after; a pair switched off is NaN
             if self.fit_smpl:
-                fit_bad, fit_cov = r['status'] == 2, r.get('cov')
-        elif self.tri_refine == 'skeleton':        # the same start and views, the joints of a sample refined together
-            tri, r = triangulation_skeleton(sel, x, self.cam_id_list, weights, huber_px=self.tri_huber, sym_w=self.tri_sym,
-                                            want=('resid', 'sym') + fit_want, robust_px=self.tri_thresh if self.tri == 'robust' else None)
-            used = r.get('inliers')
-            out['tri_refine_px'] = r['resid'][..., 1].nanmean()            # a fixed joint has no residual (NaN)
-            out['tri_refine_gain_px'] = (r['resid'][..., 0] - r['resid'][..., 1]).nanmean()
-            out['tri_sym_mm'] = r['sym'].abs().reshape(-1, 2).nanmean(dim=0)   # [2]: before, after; a pair switched off is NaN
-            if self.fit_smpl:
-                fit_bad = r['status'] == 2
-        elif self.tri == 'robust':
-            tri, used = triangulation_weighted(sel, x, self.cam_id_list, weights, robust_px=self.tri_thresh, return_inliers=True)
-        else:
-            tri = triangulation_weighted(sel, x, self.cam_id_list, weights)
+                bad, cov = r['status'] == 2, r.get('cov')
         if self.tri == 'robust':
             bits = (used.unsqueeze(-1).int() >> torch.arange(len(cams), device=used.device, dtype=torch.int32)) & 1
             # a zero mask is the fallback: no two views agreed, the DLT ran over all of them
             out['tri_inlier_views'] = torch.where(used == 0, len(cams), bits.sum(dim=-1)).float().mean()
-        if weights is not None:
-            out['tri_sigma'] = torch.stack([1.0 / weights[m] for m in cams]).mean()
-        if self.tri_volume:                        # from whatever point the options above produced, over the views they used
-            views = None
-            if self.tri == 'robust':               # a zero mask is the fallback: the DLT ran over all views, and so does the fusion
-                views = torch.where(used == 0, torch.full_like(used, (1 << len(cams)) - 1), used)
-            tri, r = triangulation_volume(tri, cubes, x, self.cam_id_list, torch.stack(chan, dim=0).contiguous(), views=views,
-                                          G=self.vol_grid, levels=self.vol_levels, side_mm=self.vol_side, want=('cov', 'status'))
-            out['tri_vol_move_mm'] = (tri - r['init']).norm(dim=-1).nanmean()
-            out['tri_vol_sigma_mm'] = (r['cov'][..., 0] + r['cov'][..., 3] + r['cov'][..., 5]).sqrt().nanmean()   # passed through: NaN
-            out['tri_vol_status'] = torch.stack([(r['status'] == c).float().mean() for c in range(4)])
-            if self.fit_smpl:                      # passed through (1, 3): the start came back and there is no covariance
-                fit_bad, fit_cov = (r['status'] == 1) | (r['status'] == 3), r['cov']
-        if self.calibrate:                         # kept on the device for the one bundle after the loop: the final point, the views it used
-            pts, pm = triangulation_inputs(sel, x, self.cam_id_list, weights)
-            self.calib_rows.append({'points': pts, 'pmat': pm, 'views': used if self.tri == 'robust' else None,
-                                    'init': torch.cat([tri[..., :3], torch.ones_like(tri[..., :1])], dim=-1).contiguous()})
-        if self.smooth:                            # kept on the device for the one smoothing after the loop, as --calibrate keeps its rows
-            pts, pm = triangulation_inputs(sel, x, self.cam_id_list, weights)
+        if s.weights is not None:
+            out['tri_sigma'] = torch.stack([1.0 / s.weights[m] for m in cams]).mean()
+        return Triangulated(tri, used, bad, cov, inputs, out)
+
+    def fuse(self, t, s, x, cams):
+        """--tri-volume: the cameras' heat-map cubes fused round the triangulated point, over the views that produced it.
+        -> Triangulated with the fused point (and for fit_smpl its pass-through marks and covariance) in place of t's, `t` itself
+        without the option; out gains tri_vol_move_mm, tri_vol_sigma_mm, tri_vol_status [4]."""
+        if not self.tri_volume:
+            return t
+        views = None
+        if self.tri == 'robust':                   # a zero mask is the fallback: the DLT ran over all views, and so does the fusion
+            views = torch.where(t.used == 0, torch.full_like(t.used, (1 << len(cams)) - 1), t.used)
+        tri, r = triangulation_volume(t.point, s.cubes, x, self.cam_id_list, torch.stack(s.chan, dim=0).contiguous(), views=views,
+                                      G=self.vol_grid, levels=self.vol_levels, side_mm=self.vol_side, want=('cov', 'status'))
+        out = dict(t.out)
+        out['tri_vol_move_mm'] = (tri - r['init']).norm(dim=-1).nanmean()
+        out['tri_vol_sigma_mm'] = (r['cov'][..., 0] + r['cov'][..., 3] + r['cov'][..., 5]).sqrt().nanmean()   # passed through: NaN
+        out['tri_vol_status'] = torch.stack([(r['status'] == c).float().mean() for c in range(4)])
+        if self.fit_smpl:                          # passed through (1, 3): the start came back and there is no covariance
+            return t._replace(point=tri, bad=(r['status'] == 1) | (r['status'] == 3), cov=r['cov'], out=out)
+        return t._replace(point=tri, out=out)
+
+    def keep_solver_rows(self, t, x, gt, cams):
+        """--calibrate and --smooth: one row each of what their solver reads after the loop, kept on the device: the batch's
+        triangulation inputs, the final point as the start (formed once, shared by the two) and the views it used."""
+        if not (self.calibrate or self.smooth):
+            return
+        row = {'points': t.inputs[0], 'pmat': t.inputs[1], 'views': t.used if self.tri == 'robust' else None, 'init': homogeneous(t.point)}
+        if self.calibrate:
+            self.calib_rows.append(dict(row))
+        if self.smooth:
             paths = x.get(cams[0] + '_img_path')
-            self.smooth_rows.append({'points': pts, 'pmat': pm, 'views': used if self.tri == 'robust' else None, 'gt': gt[..., :3].contiguous(),
-                                     'init': torch.cat([tri[..., :3], torch.ones_like(tri[..., :1])], dim=-1).contiguous(),
-                                     'paths': None if paths is None else [str(p) for p in paths]})
-        preds = {'tri': tri}
+            self.smooth_rows.append(dict(row, gt=gt[..., :3].contiguous(), paths=None if paths is None else [str(p) for p in paths]))
+
+    def measure(self, s, t, x, gt, cams):
+        """The triangulated joints and every view's own against the ground truth (one pose_errors launch per set and kind).
+        -> (preds {'tri', 'view_<cam>': world joints}, out: mpjpe_ / n-mpjpe_ / p-mpjpe_<set> [B], without per-action tables
+        pck_ / auc_<set> (scalars), world_gt and world_tri)."""
+        preds, out = {'tri': t.point}, {}
         for m in cams:
-            preds['view_' + m] = convert_patch_to_world(sel[m], x, m, is_norm=True)
+            preds['view_' + m] = convert_patch_to_world(s.sel[m], x, m, is_norm=True)
         for name, p in preds.items():
             e = pose_errors(p, gt, want=('err',))['err'].mean(dim=2)                       # [3,B]
             for metric, a in METRICS_3D:
@@ -506,21 +627,49 @@ class Eval:
                 out['pck_' + name] = q['pck'].mean()
                 out['auc_' + name] = (q['auc_hits'].sum(dim=0).float() / q['pck'].numel()).mean() * 100
         out['world_gt'], out['world_tri'] = gt, preds['tri']
-        if self.resolve_track:                     # kept on the device for the one pass per camera after the loop, as --smooth keeps its rows
-            row = {'gt': gt[..., :3].contiguous(), 'mode': 'views' if self.resolve == 'views' else mode}
-            for m in cams:
-                paths = x.get(m + '_img_path')
-                if paths is None:                  # the cameras of a sample show the same frame
-                    paths = x.get(cams[0] + '_img_path')
-                row[m] = {'kps': raw_kps[m].detach().float().contiguous(), 'labels': x[m + '_joints'],
-                          'world': convert_patch_to_world(raw_kps[m], x, m, is_norm=True)[..., :3].contiguous(),
-                          'view': preds['view_' + m][..., :3].contiguous(), 'paths': None if paths is None else [str(p) for p in paths]}
-            self.rt_rows.append(row)
-        if self.fit_smpl:                          # after everything else, on the final world joints
-            if len(cams) > 1:
-                out.update(self.fit_batch(preds['tri'][..., :3].contiguous(), fit_bad, fit_cov))
-            else:                                  # one camera: its selected hypothesis
-                out.update(self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None))
+        return preds, out
+
+    def keep_track_rows(self, s, x, gt, preds, cams, mode):
+        """--resolve-track: one row of what track_resolve reads per camera after the loop, kept on the device: the detections as
+        they came, in the patch and in the world, the labels, the view as selected with them, the paths; and the ground truth."""
+        if not self.resolve_track:
+            return
+        row = {'gt': gt[..., :3].contiguous(), 'mode': 'views' if self.resolve == 'views' else mode}
+        for m in cams:
+            paths = x.get(m + '_img_path')
+            if paths is None:                      # the cameras of a sample show the same frame
+                paths = x.get(cams[0] + '_img_path')
+            row[m] = {'kps': s.raw[m].detach().float().contiguous(), 'labels': x[m + '_joints'],
+                      'world': convert_patch_to_world(s.raw[m], x, m, is_norm=True)[..., :3].contiguous(),
+                      'view': preds['view_' + m][..., :3].contiguous(), 'paths': None if paths is None else [str(p) for p in paths]}
+        self.rt_rows.append(row)
+
+    def fit(self, t, preds, cams):
+        """--fit-smpl, after everything else, on the final world joints: the triangulated ones with their pass-through marks and
+        covariance, or with one camera that view's selected hypothesis.  -> out: the fit_* rows of fit_batch, {} without the option."""
+        if not self.fit_smpl:
+            return {}
+        if len(cams) > 1:
+            return self.fit_batch(preds['tri'][..., :3].contiguous(), t.bad, t.cov)
+        return self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None)
+
+    @torch.no_grad()
+    def eval_batch(self, x, mode='best', kps_by_cam=None):
+        """Device part of one iteration of eval.py:111-204.  Returns ({name: tensor on the device}, layout) where
+        every tensor is per sample [B] (errors), or a scalar (ambiguity, pck, auc).  With resolve='views' `mode` is ignored:
+        the cameras' agreement picks the hypotheses."""
+        cams = ['cam_{}'.format(c) for c in self.cam_id_list]
+        given, x = x, self.calibrated(x)           # the ground truth reads the cameras as given; --calibration corrects the predictions'
+        s = self.select_by_views(x, cams, kps_by_cam) if self.resolve == 'views' else self.select_by_labels(x, cams, mode, kps_by_cam)
+        out = dict(s.out, ambiguity=torch.minimum(s.trans, len(cams) - s.trans).mean())    # eval.py:164-167
+        gt = convert_patch_to_world(given['cam_0_joints'], given, 'cam_0', is_norm=False)  # eval.py:170
+        t = self.fuse(self.triangulate(s, x, cams), s, x, cams)
+        out.update(t.out)
+        self.keep_solver_rows(t, x, gt, cams)
+        preds, errors = self.measure(s, t, x, gt, cams)
+        out.update(errors)
+        self.keep_track_rows(s, x, gt, preds, cams, mode)
+        out.update(self.fit(t, preds, cams))
         return out
 
     def eval(self, tb_log, record_table, count_table, record_3d_table, count_3d_table, record_3d_tri_table,
@@ -537,29 +686,10 @@ class Eval:
                     record_table = record_table + host['err2d_' + m]
                     count_table += 1
             ambiguity_ratio = ambiguity_ratio + float(host['ambiguity'])
-            if 'tri_inlier_views' in host:
-                self.tri_views += float(host['tri_inlier_views'])
-                self.tri_batches += 1
-            if 'tri_sigma' in host:
-                self.tri_sigma += float(host['tri_sigma'])
-                self.sigma_batches += 1
-            if 'tri_refine_px' in host:
-                self.refine_px += float(host['tri_refine_px'])
-                self.refine_gain += float(host['tri_refine_gain_px'])
-                self.refine_batches += 1
-            if 'tri_sym_mm' in host:
-                self.sym_mm += host['tri_sym_mm']
-            if 'tri_vol_status' in host:
-                self.vol_move += float(host['tri_vol_move_mm'])
-                self.vol_sigma += float(host['tri_vol_sigma_mm'])
-                self.vol_status += host['tri_vol_status']
-                self.vol_batches += 1
-            if 'fit_status' in host:
-                self.fit_rows.append({k[4:]: v for k, v in host.items() if k.startswith('fit_')})
-            if 'resolve_hyp0' in host:
-                self.res_exchanged += float(host['resolve_exchanged'])
-                self.res_hyp0 += float(host['resolve_hyp0'])
-                self.res_batches += 1
+            for key in MEANS:                      # whatever the options of this run produce
+                if key in host:
+                    self.add(key, host[key])
+            self.keep_fit_rows(host)
             for table, count, names in ((record_3d_tri_table, count_3d_tri_table, ['tri']),
                                         (record_3d_table, count_3d_table, ['view_' + m for m in cams])):
                 for name in names:
@@ -579,7 +709,7 @@ class Eval:
 
     def record(self, record_table, count_table, record_3d_table, count_3d_table, record_3d_tri_table,
                count_3d_tri_table, ambiguity_ratio):
-        """Prints and writes <log_dir>/eval/eval_result.txt with the reference's lines (eval.py:206-296)."""
+        """Prints and writes <log_dir>/eval/eval_result.txt with the reference's lines (eval.py:206-296), then the options'."""
         lines = []
         if self.cal_per_act:
             full2d, sel2d = cal_per_class_error(record_table, count_table)
@@ -602,36 +732,7 @@ class Eval:
                         lines.append('{}: {} %'.format(key, float(tbl[key] / cnt[key])))
                     else:
                         lines.append('{}: {}'.format(key, float(np.mean(tbl[key]) / cnt[key])))
-        if self.tri == 'robust':                   # after the reference's lines; --tri dlt leaves the file as it was
-            lines.append('TRI inlier views ({} px): {} of {}'.format(self.tri_thresh, self.tri_views / max(self.tri_batches, 1),
-                                                                     len(self.cam_id_list)))
-        if self.resolve == 'views':                # after everything else; --resolve gt leaves the file as it was
-            n = max(self.res_batches, 1)
-            lines.append('RESOLVE views: exchanged {} , hypothesis 0 kept {}'.format(self.res_exchanged / n, self.res_hyp0 / n))
-        if self.tri_weight == 'spread':            # after everything else; --tri-weight depth leaves the file as it was
-            lines.append('TRI weight spread: mean sigma {} px'.format(self.tri_sigma / max(self.sigma_batches, 1)))
-        if self.tri_refine == 'lm':                # after everything else; --tri-refine none leaves the file as it was
-            n = max(self.refine_batches, 1)
-            lines.append('TRI refine lm (huber {}): reprojection RMS {} px, gained {} px'.format(
-                self.tri_huber, self.refine_px / n, self.refine_gain / n))
-        if self.tri_refine == 'skeleton':          # after everything else; none and lm leave the file as it was
-            n = max(self.refine_batches, 1)
-            lines.append('TRI refine skeleton (huber {}, sym {}): reprojection RMS {} px, gained {} px, limb asymmetry {} -> {} mm'.format(
-                self.tri_huber, self.tri_sym, self.refine_px / n, self.refine_gain / n, self.sym_mm[0] / n, self.sym_mm[1] / n))
-        if self.tri_volume:                        # after everything else; without --tri-volume the file is as it was
-            n = max(self.vol_batches, 1)
-            lines.append('TRI volume (side {} mm, grid {}, levels {}): moved {} mm, sigma {} mm'.format(
-                self.vol_side, self.vol_grid, self.vol_levels, self.vol_move / n, self.vol_sigma / n))
-            lines.append('TRI volume status: fused {} , passed through {} , mode on a face {} , logits not finite {}'.format(
-                *(self.vol_status / n)))
-        if self.fit_smpl:                          # after everything else; without --fit-smpl the file is as it was
-            lines.append(self.write_fit())
-        if self.calibrate:                         # after everything else; without --calibrate the file is as it was
-            lines.extend(self.write_calibration())
-        if self.smooth:                            # after everything else; without --smooth the file is as it was
-            lines.extend(self.write_smooth())
-        if self.resolve_track:                     # after everything else; without --resolve-track the file is as it was
-            lines.extend(self.write_resolve_track())
+        lines.extend(self.option_lines())
         print('\n'.join(lines))
         os.makedirs(os.path.join(self.log_dir, 'eval'), exist_ok=True)
         path = os.path.join(self.log_dir, 'eval', 'eval_result.txt')
@@ -742,7 +843,8 @@ CLI = (  # same flags as the reference entry (eval.py:326-334) + --synthetic
                        help='--tri-skeleton: weight of the squared length difference of a left/right limb pair, in px^2 '
                             'per mm^2 (sigma^2 per mm^2 with --tri-weight spread)')),
 )
-CLI_VOLUME = (  # --tri-volume and its grid, parsed after CLI (a table of their own: CLI's last entries are pinned by older tests)
+CLI_VOLUME = (  # --tri-volume and its grid, parsed after CLI (a table per option: each names what one option adds, a test per
+    # option pins its table, and --help lists the tables in this order)
     ('--tri-volume', dict(default=False, action='store_true', dest='tri_volume',
                           help="after everything above: fuse the cameras' heat-map cubes over a voxel grid round the triangulated "
                                'point and take the soft-argmax of the fused volume in world space (not with --flip)')),
@@ -755,7 +857,7 @@ CLI_VOLUME = (  # --tri-volume and its grid, parsed after CLI (a table of their 
 )
 
 
-CLI_FIT = (  # --fit-smpl and its settings, parsed after CLI_VOLUME (a table of their own: older tests pin the tables above)
+CLI_FIT = (  # --fit-smpl and its settings, parsed after CLI_VOLUME (a table per option, as above)
     ('--fit-smpl', dict(default=None, metavar='OUT.npz', dest='fit_smpl',
                         help='after everything above: fit SMPL parameters to the final world joints of every sample and write '
                              'them as a bank that train.py --pseudo-online reads (needs --smpl-model)')),
@@ -769,16 +871,31 @@ CLI_FIT = (  # --fit-smpl and its settings, parsed after CLI_VOLUME (a table of 
 )
 
 
-def mirror_fit_options(config, opt):
-    """The --fit-smpl flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_smplfit)."""
+def mirror_options(config, opt, always=(), given=()):
+    """Parsed flags as model_params keys, which is where Eval reads its options: the keys of `always` as they are, those of
+    `given` only where the flag was given (not None), so that their defaults stay where the option's module has them."""
     mp = config['model_params']
-    mp['fit_smpl'], mp['smpl_model'], mp['fit_iters'] = opt.fit_smpl, opt.smpl_model, opt.fit_iters
-    for key in ('fit_pose_prior', 'fit_shape_prior'):
+    for key in always:
+        mp[key] = getattr(opt, key)
+    for key in given:
         if getattr(opt, key) is not None:
             mp[key] = getattr(opt, key)
 
 
-CLI_CALIB = (  # --calibrate / --calibration and their settings, parsed after CLI_FIT (a table of their own, as above)
+def mirror_tri_options(config, opt):
+    """The --tri-* flags of CLI and CLI_VOLUME as model_params keys; --tri-skeleton is the third choice of tri_refine."""
+    mirror_options(config, opt, always=('tri_weight', 'tri_refine', 'tri_huber', 'tri_sym', 'tri_volume', 'tri_vol_side', 'tri_vol_grid',
+                                        'tri_vol_levels'))
+    if opt.tri_skeleton:
+        config['model_params']['tri_refine'] = 'skeleton'
+
+
+def mirror_fit_options(config, opt):
+    """The --fit-smpl flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_smplfit)."""
+    mirror_options(config, opt, always=('fit_smpl', 'smpl_model', 'fit_iters'), given=('fit_pose_prior', 'fit_shape_prior'))
+
+
+CLI_CALIB = (  # --calibrate / --calibration and their settings, parsed after CLI_FIT (a table per option, as above)
     ('--calibrate', dict(default=None, metavar='OUT.npz', dest='calibrate',
                          help='after everything above: bundle adjustment of the camera extrinsics over the whole set, per rig, '
                               'written as corrections that --calibration applies (needs 2+ cameras and one rank)')),
@@ -798,14 +915,10 @@ def mirror_calib_options(config, opt):
     """The --calibrate / --calibration flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_calib)."""
     if opt.calibrate and opt.calibration:
         raise ValueError('--calibrate and --calibration do not go together')
-    mp = config['model_params']
-    mp['calibrate'], mp['calibration'], mp['calib_iters'] = opt.calibrate, opt.calibration, opt.calib_iters
-    for key in ('calib_prior_rot', 'calib_prior_trans', 'calib_free'):
-        if getattr(opt, key) is not None:
-            mp[key] = getattr(opt, key)
+    mirror_options(config, opt, always=('calibrate', 'calibration', 'calib_iters'), given=('calib_prior_rot', 'calib_prior_trans', 'calib_free'))
 
 
-CLI_SMOOTH = (  # --smooth and its settings, parsed after CLI_CALIB (a table of their own, as above)
+CLI_SMOOTH = (  # --smooth and its settings, parsed after CLI_CALIB (a table per option, as above)
     ('--smooth', dict(default=None, metavar='OUT.npz', dest='smooth',
                       help='after everything above: smooth every joint\'s triangulated track over the frames of its sequence '
                            '(reprojection cost + acceleration penalty) and fill frames without data (needs 2+ cameras and one rank)')),
@@ -819,14 +932,10 @@ CLI_SMOOTH = (  # --smooth and its settings, parsed after CLI_CALIB (a table of 
 
 def mirror_smooth_options(config, opt):
     """The --smooth flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_track)."""
-    mp = config['model_params']
-    mp['smooth'], mp['smooth_iters'] = opt.smooth, opt.smooth_iters
-    for key in ('smooth_acc', 'smooth_gap'):
-        if getattr(opt, key) is not None:
-            mp[key] = getattr(opt, key)
+    mirror_options(config, opt, always=('smooth', 'smooth_iters'), given=('smooth_acc', 'smooth_gap'))
 
 
-CLI_RESOLVE_TRACK = (  # --resolve-track and its settings, parsed after CLI_SMOOTH (a table of their own, as above)
+CLI_RESOLVE_TRACK = (  # --resolve-track and its settings, parsed after CLI_SMOOTH (a table per option, as above)
     ('--resolve-track', dict(default=None, metavar='OUT.npz', dest='resolve_track',
                              help='after everything above, per camera and without labels: choose every joint\'s depth hypothesis '
                                   'and every limb pair\'s left/right exchange over the frames of its sequence (motion cost + priors, '
@@ -844,9 +953,7 @@ CLI_RESOLVE_TRACK = (  # --resolve-track and its settings, parsed after CLI_SMOO
 
 def mirror_resolve_track_options(config, opt):
     """The --resolve-track flags as model_params keys (only the ones given: the defaults live in xas_amd.ops_track)."""
-    for key in ('resolve_track', 'rt_vel', 'rt_hyp', 'rt_swap', 'rt_gap'):
-        if getattr(opt, key) is not None:
-            config['model_params'][key] = getattr(opt, key)
+    mirror_options(config, opt, given=('resolve_track', 'rt_vel', 'rt_hyp', 'rt_swap', 'rt_gap'))
 
 
 def main():
@@ -857,14 +964,7 @@ def main():
     with open(opt.config) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     config['model_params']['cam_id_list'] = config['dataset_params']['cam_id_list']
-    config['model_params']['tri_weight'] = opt.tri_weight
-    config['model_params']['tri_refine'] = 'skeleton' if opt.tri_skeleton else opt.tri_refine
-    config['model_params']['tri_huber'] = opt.tri_huber
-    config['model_params']['tri_sym'] = opt.tri_sym
-    config['model_params']['tri_volume'] = opt.tri_volume
-    config['model_params']['tri_vol_side'] = opt.tri_vol_side
-    config['model_params']['tri_vol_grid'] = opt.tri_vol_grid
-    config['model_params']['tri_vol_levels'] = opt.tri_vol_levels
+    mirror_tri_options(config, opt)
     mirror_fit_options(config, opt)
     mirror_calib_options(config, opt)
     mirror_smooth_options(config, opt)

@@ -97,16 +97,23 @@ def triangulation(keypoints, params, cam_id_list, is_norm=True, RECT_WIDTH=2000,
 
 
 def triangulation_weighted(keypoints, params, cam_id_list, weights, is_norm=True, RECT_WIDTH=2000, robust_px=None,
-                           return_inliers=False):
+                           return_inliers=False, *, inputs=None):
     """triangulation with `weights`, {cam_key: [B,K]}: the weight of every view and joint (spread_weight) in place of the
     reference's, which is the joint's depth in mm.  A weight that is not finite or not positive marks the view invalid for that
-    joint, by the kernels' rule for the third column.  None: the reference's weights, bit for bit.  No reference counterpart."""
-    pts, pm = _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+    joint, by the kernels' rule for the third column.  None: the reference's weights, bit for bit.  `inputs`: the
+    (points, projection matrices) of triangulation_inputs where the caller has them already.  No reference counterpart."""
+    pts, pm = inputs or _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+    init, used = _triangulation_start(pts, pm, robust_px)
+    return (init[..., :3], used) if return_inliers else init[..., :3]
+
+
+def _triangulation_start(pts, pm, robust_px):
+    """Where triangulation_weighted ends and the refinements begin: the DLT over all views, or with `robust_px` over the largest
+    set of views that agree within it.  -> (init [B,K,4], used: the [B,K] uint8 masks of those views, None without robust_px)."""
     if robust_px is None:
-        tri = batch_triangulate(pts, pm)[..., :3]
-        return (tri, None) if return_inliers else tri
-    r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',) if return_inliers else ())
-    return (r['xyzw'][..., :3], r['inliers']) if return_inliers else r['xyzw'][..., :3]
+        return batch_triangulate(pts, pm), None
+    r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',))
+    return r['xyzw'], r['inliers']
 
 
 def _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH):
@@ -169,24 +176,22 @@ def apply_calibration(params, cam_id_list, keys, delta):
 
 
 def triangulation_inputs(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000):
-    """points [B,V,K,3] and projection matrices [B,V,3,4] as every triangulation above forms them (eval.py --calibrate keeps them)."""
+    """points [B,V,K,3] and projection matrices [B,V,3,4] as every triangulation above forms them: eval.py forms them once per
+    batch, hands them to the solver that runs as its `inputs` and keeps them for --calibrate and --smooth."""
     return _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
 
 
 def triangulation_refined(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000, robust_px=None,
-                          huber_px=0.0, want=()):
+                          huber_px=0.0, want=(), *, inputs=None):
     """triangulation_weighted, then Levenberg-Marquardt on the reprojection error in pixels from its point, over the views it
     used (ops_eval.triangulate_refine).  With `weights` every view's residual is scaled by its weight, so with spread_weight
     (1 / sigma in pixels) the cost is the detections' negative log-likelihood and `cov` the joint's covariance in mm^2; without,
     the residuals count in plain pixels (the depth in mm is no scale of a pixel error).  `huber_px` > 0: Huber's loss.
+    `inputs`: as in triangulation_weighted.
     -> (world joints [B,K,3], dict of ops_eval.triangulate_refine: xyzw and the outputs in `want`, + `inliers` with
     robust_px).  No reference counterpart."""
-    pts, pm = _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
-    if robust_px is None:
-        init, used = batch_triangulate(pts, pm), None
-    else:
-        r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',))
-        init, used = r['xyzw'], r['inliers']
+    pts, pm = inputs or _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+    init, used = _triangulation_start(pts, pm, robust_px)
     out = ops_eval.triangulate_refine(pts, pm, init, views=used, weighted=weights is not None, huber_px=huber_px, want=want)
     if used is not None:
         out['inliers'] = used
@@ -194,18 +199,16 @@ def triangulation_refined(keypoints, params, cam_id_list, weights=None, is_norm=
 
 
 def triangulation_skeleton(keypoints, params, cam_id_list, weights=None, is_norm=True, RECT_WIDTH=2000, robust_px=None,
-                           huber_px=0.0, sym_w=ops_eval.TRI_SYM_W, limbs=ops_eval.SYM_LIMBS, want=()):
+                           huber_px=0.0, sym_w=ops_eval.TRI_SYM_W, limbs=ops_eval.SYM_LIMBS, want=(), *,
+                           inputs=None):
     """triangulation_refined with the joints of every sample refined together under left/right limb symmetry
     (ops_eval.triangulate_skeleton): the same inputs, the same start (the DLT, or the robust point and its inlier masks with
     robust_px), the same weights; `sym_w` px^2 per mm^2 on the squared difference of each limb pair's lengths.
+    `inputs`: as in triangulation_weighted.
     -> (world joints [B,K,3], dict of ops_eval.triangulate_skeleton: xyzw and the outputs in `want`, + `inliers` with
     robust_px).  No reference counterpart."""
-    pts, pm = _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
-    if robust_px is None:
-        init, used = batch_triangulate(pts, pm), None
-    else:
-        r = ops_eval.triangulate_robust(pts, pm, threshold_px=robust_px, want=('inliers',))
-        init, used = r['xyzw'], r['inliers']
+    pts, pm = inputs or _triangulation_inputs(keypoints, params, cam_id_list, weights, is_norm, RECT_WIDTH)
+    init, used = _triangulation_start(pts, pm, robust_px)
     out = ops_eval.triangulate_skeleton(pts, pm, init, views=used, limbs=limbs, weighted=weights is not None, huber_px=huber_px,
                                         sym_w=sym_w, want=want)
     if used is not None:
