@@ -998,6 +998,44 @@ int xas_track_smooth(const float* points, const float* P, const float* init, con
                      float* out, unsigned char* status, float* resid, unsigned char* track_status, double* cost, int* trials,
                      void* workspace, void* stream);
 
+/* xas_track_smooth with one more kind of observation, a 3-D ANCHOR per frame and joint (eval.py --smooth --smooth-data anchor;
+ * the reference has no counterpart): a point A with a symmetric 3x3 information matrix W.  One camera's chosen point on its ray
+ * is one (W = depth_w r r^T along the ray r: the pixels know the point across the ray, the anchor along it), the point of
+ * xas_triangulate_volume with the inverse of its covariance another.  Everything not said here is exactly as xas_track_smooth
+ * and xas_track_linearise state it: points, P, init, views, start, frame, flags, huber, acc_w, the gap frames' start line, the
+ * pass-through of a (track, joint) with fewer than two data frames, the prior, the lambda schedule, the acceptance and stop
+ * rules, every output, "C(out) <= C(start)", the workspace (xas_track_anchor_workspace_bytes(N, K), the same number) and the
+ * limits, except that 1 <= V <= XAS_TRI_MAX_VIEWS.
+ * anchor [N][K][3] fp32 (mm) and info [N][K][6] fp32, the entries xx, xy, xz, yy, yz, zz of W in cost units per mm^2 (px^2, or
+ * sigma^2 with XAS_REFINE_WEIGHTED, like the reprojection term beside it): both NULL or both given, otherwise an error.  W
+ * positive semi-definite is the caller's duty, as an increasing `frame` is.  anchor_huber >= 0 and finite; 0 = squared.
+ * A frame's anchor is USABLE if its nine numbers are finite, no diagonal entry of W is negative and trace W > 0.
+ * The START of a frame is init's point if its x, y and z are finite, otherwise the usable anchor.
+ * Without a usable anchor a frame is a data frame by xas_track_smooth's rule.  With one it is ALWAYS a data frame: its
+ * reprojection term runs over the views F that xas_triangulate_refine would use (VALID views, and `views`: a zero byte stands
+ * for all valid views here too, so the term is switched off by weights of 0, not by `views`), however few; if the start lies
+ * behind one of them, F is empty and the frame keeps its anchor term only.
+ * COST of a data frame, in double from the fp32 inputs: sum_{v in F} rho(s_v |r_v(X_t)|) + rho_a(m_t), m_t = sqrt(max(e_t^T W_t
+ * e_t, 0)), e_t = X_t - A_t, rho_a the Huber function of the reprojection term with delta anchor_huber (the clamp: a
+ * rank-deficient W rounded to fp32 may be indefinite in its last bit).  The anchor term adds psi(m) W to the frame's
+ * Gauss-Newton block and psi(m) W e to its gradient, psi = 1 on the quadratic part and anchor_huber / m on the linear one, as
+ * xas_triangulate_refine weights its own Huber.
+ * Outputs as there; resid's two entries stay the pixel RMS over F and are NaN where F is empty; status 0 = data frame (with or
+ * without an anchor).  With NULL anchors and V >= 2 every output of both entry points equals xas_track_smooth's and
+ * xas_track_linearise's bit for bit: the schedule is one piece of code (csrc/track_band.h).
+ * One wave per (track, joint); one launch after the copy of start, no host synchronisation, no atomics, every sum in one
+ * order: two calls on the same inputs give the same bits in every output. */
+size_t xas_track_anchor_workspace_bytes(int N, int K);
+int xas_track_anchor_linearise(const float* points, const float* P, const float* init, const unsigned char* views,
+                               const float* anchor, const float* info, const int* start, const int* frame, int N, int V, int K,
+                               int S, int flags, float huber, double anchor_huber, double acc_w, double lambda, double* band,
+                               double* g, double* C, void* workspace, void* stream);
+int xas_track_anchor_smooth(const float* points, const float* P, const float* init, const unsigned char* views,
+                            const float* anchor, const float* info, const int* start, const int* frame, int N, int V, int K,
+                            int S, int flags, float huber, double anchor_huber, double acc_w, int max_iter, float* out,
+                            unsigned char* status, float* resid, unsigned char* track_status, double* cost, int* trials,
+                            void* workspace, void* stream);
+
 /* Depth hypothesis and left/right exchange of ONE camera chosen over time (eval.py --resolve-track OUT.npz; the reference has
  * no counterpart, and no labels are read).  kps [N][Hy][K][3] the detector's patch-normalised joints, world [N][Hy][K][3] their
  * single-view world points in mm, unary [N][Hy][K] an extra cost per candidate or NULL (= 0), all fp32 on the device; N counts

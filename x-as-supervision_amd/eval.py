@@ -11,6 +11,7 @@
              [--calibration IN.npz]
              [--smooth OUT.npz --smooth-acc W --smooth-gap FRAMES --smooth-iters N]
              [--resolve-track OUT.npz --rt-vel W --rt-hyp W --rt-swap W --rt-gap FRAMES]
+             [--smooth-data reproj|anchor --smooth-depth W --smooth-anchor-huber D]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -83,6 +84,14 @@ left/right exchange over the frames of its sequence: motion cost plus priors, ex
 (xas_amd.ops_track.track_resolve).  OUT.npz holds per camera `joints`, `sel`, `hyp`, `swap`, `status`, `cost`, `named`,
 `track` and `frame`; eval_result.txt gains one line per camera, which also states the MPJPE of the choice made with labels.
 Unknown: its accuracy on real detections, and the weights, untuned guesses all four.
+
+--smooth-data anchor (opt-in with --smooth; model_params.smooth_data; the default, reproj, makes exactly the calls above) holds
+the tracks by a 3-D anchor per frame and joint (xas_amd.ops_track.track_anchor_smooth), which lets --smooth run with ONE camera:
+that camera's pixels, known across the ray, plus its selected world point (--resolve-track's choice, `cam_<c>_joints`, when that
+flag is given too), known --smooth-depth W along it, under Huber's loss (--smooth-anchor-huber D) so that a wrongly chosen
+hypothesis is an outlier.  With 2+ cameras it needs --tri-volume and smooths the fused points with the inverse of their
+covariance, no pixels: the cost is then in sigma^2, and --smooth-acc weighs against it, not against pixels.  OUT.npz gains
+`anchored`; the two SMOOTH lines name the mode.  Unknown: its accuracy on real detections; both new constants are untuned.
 
 The post-loop options keep their rows in the plain lists fit_rows, calib_rows, smooth_rows and rt_rows and write their files
 (atomically) from record().
@@ -270,15 +279,26 @@ class Eval:
             self.calib_free = mp.get('calib_free')     # mask of the cameras that may move; None = all but camera 0
             self.calib_rows = []                       # per batch, on the device: points, pmat, init, views
         self.smooth = mp.get('smooth') or None         # --smooth OUT.npz: the joint tracks smoothed over time, over the whole set
+        self.smooth_data = mp.get('smooth_data') or 'reproj'   # --smooth-data anchor: the tracks are held by 3-D anchors
         if self.smooth:
-            check_cameras(cam_id_list, 'smooth needs 2 to {} cameras; cam_id_list has {}', least=2)
+            if self.smooth_data not in ('reproj', 'anchor'):
+                raise ValueError('Unknown smoothing data: {}'.format(self.smooth_data))
+            if self.smooth_data == 'reproj':
+                check_cameras(cam_id_list, 'smooth needs 2 to {} cameras; cam_id_list has {}', least=2)
+            else:
+                check_cameras(cam_id_list, "smooth_data='anchor' smooths 1 to {} cameras; cam_id_list has {}", least=1)
+                if len(cam_id_list) > 1 and not tri_volume:
+                    raise ValueError("smooth_data='anchor' with two or more cameras smooths the fused points of the volume with "
+                                     'their covariance: it needs --tri-volume (model_params.tri_volume)')
             check_single_rank('smooth needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out over '
                               'the ranks, and no rank sees a track')
             from xas_amd import ops_track              # only with the flag
             self.smooth_acc = float(mp.get('smooth_acc', ops_track.TRACK_ACC_W))                     # untuned guesses, both
             self.smooth_gap = int(mp.get('smooth_gap', ops_track.TRACK_MAX_GAP))
             self.smooth_iters = int(mp.get('smooth_iters', 30))
-            self.smooth_rows = []                      # per batch, on the device: points, pmat, init, views, gt; and the paths
+            self.smooth_depth = float(mp.get('smooth_depth', ops_track.TRACK_DEPTH_W))               # anchor only; untuned too
+            self.smooth_anchor_huber = float(mp.get('smooth_anchor_huber', ops_track.TRACK_ANCHOR_HUBER))
+            self.smooth_rows = []                      # per batch, on the device: points, pmat, init, views, gt (anchor, info); and the paths
         self.resolve_track = mp.get('resolve_track') or None   # --resolve-track OUT.npz: hypothesis and exchange chosen over time, per camera
         if self.resolve_track:
             check_single_rank('resolve_track needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out '
@@ -289,6 +309,7 @@ class Eval:
             self.rt_swap = float(mp.get('rt_swap', ops_track.TRACK_SWAP_W))
             self.rt_gap = int(mp.get('rt_gap', ops_track.TRACK_MAX_GAP))
             self.rt_rows = []                          # per batch, on the device: per camera kps, world, labels, view; gt; and the paths
+            self.rt_joints = {}                        # after the loop: camera -> the chosen world joints of the whole set
         if self.calibration:
             with np.load(self.calibration) as f:
                 self.calib_keys = torch.from_numpy(f['keys']).to(self.gpu_id)
@@ -330,11 +351,12 @@ class Eval:
             lines.append(self.write_fit())
         if self.calibrate:
             lines.extend(self.write_calibration())
+        # --resolve-track's step runs before --smooth's, which with --smooth-data anchor and one camera takes its choice as the
+        # anchors; its lines stay the last ones
+        track_lines = self.write_resolve_track() if self.resolve_track else []
         if self.smooth:
             lines.extend(self.write_smooth())
-        if self.resolve_track:
-            lines.extend(self.write_resolve_track())
-        return lines
+        return lines + track_lines
 
     def write_calibration(self):
         """--calibrate: one bundle adjustment over everything the batches kept, the file and -> the lines of eval_result.txt,
@@ -363,6 +385,8 @@ class Eval:
         from xas_amd import ops_track
         points, pmat, init, gt, views, paths = (cat_rows(self.smooth_rows, k) for k in ('points', 'pmat', 'init', 'gt', 'views', 'paths'))
         track, frame = ops_track.tracks_of(paths, self.smooth_gap, count=len(points))
+        if self.smooth_data == 'anchor':
+            return self.write_smooth_anchor(points, pmat, init, gt, views, track, frame)
         r = ops_track.track_smooth(points, pmat, init, track, frame, views=views, weighted=self.tri_weight == 'spread',
                                    huber_px=self.tri_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
         joints, status = r['xyzw'][..., :3].contiguous(), r['status']
@@ -382,6 +406,43 @@ class Eval:
                                                             float((status == ops_track.STATUS_PASSED).float().mean())),
                 'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))]
 
+    def write_smooth_anchor(self, points, pmat, init, gt, views, track, frame):
+        """--smooth --smooth-data anchor: one track_anchor_smooth over everything the batches kept, the file (write_smooth's
+        columns and `anchored` [N,K]: the joint had a usable anchor) and -> the two lines.  One camera: the anchors are
+        --resolve-track's choice where that ran, else the evaluation's own selected points, with information along the ray."""
+        from xas_amd import ops_track
+        anchor, one = cat_rows(self.smooth_rows, 'anchor'), len(self.cam_id_list) == 1
+        if one:
+            if self.resolve_track:
+                anchor = self.rt_joints['cam_{}'.format(self.cam_id_list[0])]
+                init = homogeneous(anchor)
+            info = ops_track.ray_information(pmat[:, 0], anchor, self.smooth_depth)
+        else:
+            info = cat_rows(self.smooth_rows, 'info')
+        r = ops_track.track_anchor_smooth(points, pmat, init, track, frame, anchor=anchor, info=info, views=views,
+                                          weighted=self.tri_weight == 'spread', huber_px=self.tri_huber,
+                                          anchor_huber=self.smooth_anchor_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
+        joints, status = r['xyzw'][..., :3].contiguous(), r['status']
+        anchored = torch.isfinite(anchor).all(-1) & torch.isfinite(info).all(-1) & (info[..., 0] + info[..., 3] + info[..., 5] > 0)
+        both = torch.isfinite(joints).all(-1) & torch.isfinite(init[..., :3]).all(-1)
+        e_before, e_after = joint_errors(init[..., :3].contiguous(), gt), joint_errors(joints, gt)
+        filled = (status == ops_track.STATUS_FILLED) & torch.isfinite(joints).all(-1)
+        rms = lambda c: float(torch.sqrt((r['resid'][..., c] ** 2).nanmean()))
+        cols = {'joints': joints, 'status': status, 'track_status': r['track_status'], 'cost': r['cost'], 'trials': r['trials'],
+                'anchored': anchored.to(torch.uint8)}
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        cols['track'], cols['frame'] = track, frame
+        save_npz(self.smooth, cols)
+        S = len(r['tracks'])
+        what = 'one camera, depth {}'.format(self.smooth_depth) if one else 'fused points'
+        return ['SMOOTH anchor ({}, huber {}) {} tracks of mean length {} (acc {}, gap {}, {} trials): {} MPJPE {} -> {} mm, '
+                'reprojection RMS {} -> {} px, anchored {} , gaps filled {} , passed through {}'.format(
+                    what, self.smooth_anchor_huber, S, len(points) / S, self.smooth_acc, self.smooth_gap, self.smooth_iters,
+                    'VIEW' if one else 'TRI', masked_mean(e_before, both), masked_mean(e_after, both), rms(0), rms(1),
+                    float(anchored.float().mean()), float((status == ops_track.STATUS_FILLED).float().mean()),
+                    float((status == ops_track.STATUS_PASSED).float().mean())),
+                'SMOOTH filled gap joints (anchor): MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))]
+
     def write_resolve_track(self):
         """--resolve-track: one track_resolve per camera over everything the batches kept, the file and -> the lines of
         eval_result.txt, one per camera."""
@@ -397,6 +458,7 @@ class Eval:
                                         gt=labels, image_size=self.img_size)
             perm = ops_eval.switch_perm(kps.shape[2], ops_eval.SWITCH_PAIRS, kps.device)
             joints = ops_track.resolved_gather(world, r['hyp'], r['swap'], perm)[..., :3].contiguous()
+            self.rt_joints[m] = joints                 # cam_<c>_joints, on the device: what write_smooth anchors one camera's tracks on
             first = world[:, 0, :, :3].contiguous()
             ok = torch.isfinite(joints).all(-1) & torch.isfinite(first).all(-1) & torch.isfinite(view).all(-1)
             for k, v in (('joints', joints), ('sel', r['sel']), ('hyp', r['hyp']), ('swap', r['swap']), ('status', r['status']),
@@ -595,21 +657,39 @@ class Eval:
         out['tri_vol_move_mm'] = (tri - r['init']).norm(dim=-1).nanmean()
         out['tri_vol_sigma_mm'] = (r['cov'][..., 0] + r['cov'][..., 3] + r['cov'][..., 5]).sqrt().nanmean()   # passed through: NaN
         out['tri_vol_status'] = torch.stack([(r['status'] == c).float().mean() for c in range(4)])
-        if self.fit_smpl:                          # passed through (1, 3): the start came back and there is no covariance
+        # passed through (1, 3): the start came back and there is no covariance.  --smooth-data anchor reads both as --fit-smpl does
+        if self.fit_smpl or (self.smooth and self.smooth_data == 'anchor'):
             return t._replace(point=tri, bad=(r['status'] == 1) | (r['status'] == 3), cov=r['cov'], out=out)
         return t._replace(point=tri, out=out)
 
-    def keep_solver_rows(self, t, x, gt, cams):
+    def keep_solver_rows(self, t, s, x, gt, cams):
         """--calibrate and --smooth: one row each of what their solver reads after the loop, kept on the device: the batch's
-        triangulation inputs, the final point as the start (formed once, shared by the two) and the views it used."""
+        triangulation inputs, the final point as the start (formed once, shared by the two) and the views it used.
+        --smooth-data anchor adds the anchors.  One camera: its pixel points and matrix (formed here where nothing was
+        triangulated) and its selected world point, whose information along the ray write_smooth forms.  More: the fused point
+        with the inverse of its covariance, NaN where the volume passed the joint through, and weights of 0, which switch the
+        reprojection term off."""
         if not (self.calibrate or self.smooth):
             return
-        row = {'points': t.inputs[0], 'pmat': t.inputs[1], 'views': t.used if self.tri == 'robust' else None, 'init': homogeneous(t.point)}
+        inputs = t.inputs if t.inputs is not None else triangulation_inputs(s.sel, x, self.cam_id_list, s.weights)
+        row = {'points': inputs[0], 'pmat': inputs[1], 'views': t.used if self.tri == 'robust' else None, 'init': homogeneous(t.point)}
         if self.calibrate:
             self.calib_rows.append(dict(row))
         if self.smooth:
             paths = x.get(cams[0] + '_img_path')
-            self.smooth_rows.append(dict(row, gt=gt[..., :3].contiguous(), paths=None if paths is None else [str(p) for p in paths]))
+            row = dict(row, gt=gt[..., :3].contiguous(), paths=None if paths is None else [str(p) for p in paths])
+            if self.smooth_data == 'anchor':
+                row['anchor'] = t.point[..., :3].contiguous()
+                if len(cams) > 1:
+                    from xas_amd import ops_track
+                    c = t.cov
+                    cov = torch.stack([c[..., 0], c[..., 1], c[..., 2], c[..., 1], c[..., 3], c[..., 4], c[..., 2], c[..., 4], c[..., 5]],
+                                      dim=-1).reshape(c.shape[:-1] + (3, 3))
+                    row['info'] = ops_track.covariance_information(cov)
+                    row['anchor'] = torch.where(t.bad.unsqueeze(-1), torch.full_like(row['anchor'], float('nan')), row['anchor'])
+                    row['points'] = torch.cat([inputs[0][..., :2], torch.zeros_like(inputs[0][..., 2:])], dim=-1)
+                    row['views'] = torch.zeros(t.bad.shape, dtype=torch.uint8, device=t.bad.device)
+            self.smooth_rows.append(row)
 
     def measure(self, s, t, x, gt, cams):
         """The triangulated joints and every view's own against the ground truth (one pose_errors launch per set and kind).
@@ -665,7 +745,7 @@ class Eval:
         gt = convert_patch_to_world(given['cam_0_joints'], given, 'cam_0', is_norm=False)  # eval.py:170
         t = self.fuse(self.triangulate(s, x, cams), s, x, cams)
         out.update(t.out)
-        self.keep_solver_rows(t, x, gt, cams)
+        self.keep_solver_rows(t, s, x, gt, cams)
         preds, errors = self.measure(s, t, x, gt, cams)
         out.update(errors)
         self.keep_track_rows(s, x, gt, preds, cams, mode)
@@ -956,9 +1036,30 @@ def mirror_resolve_track_options(config, opt):
     mirror_options(config, opt, given=('resolve_track', 'rt_vel', 'rt_hyp', 'rt_swap', 'rt_gap'))
 
 
+CLI_SMOOTH_ANCHOR = (  # --smooth-data and its settings, parsed after CLI_RESOLVE_TRACK (a table per option, as above)
+    ('--smooth-data', dict(default=None, choices=('reproj', 'anchor'), dest='smooth_data',
+                           help='--smooth: what holds the tracks.  reproj (the default): the pixels of 2+ cameras.  anchor: a 3-D '
+                                'point per frame and joint with an information matrix.  With one camera its pixels plus its '
+                                'selected world point (--resolve-track\'s choice if that is given too), known --smooth-depth '
+                                'along the ray.  With 2+ cameras it needs --tri-volume and smooths the fused points with the '
+                                'inverse of their covariance alone, no pixels: the cost is then in sigma^2, so --smooth-acc is '
+                                'in sigma^2 per (mm^2 / frame^3) and weighs against mm-scale covariances, not pixels')),
+    ('--smooth-depth', dict(default=None, type=float, metavar='W', dest='smooth_depth',
+                            help='--smooth-data anchor, one camera: information along the ray, px^2 per mm^2 (untuned default)')),
+    ('--smooth-anchor-huber', dict(default=None, type=float, metavar='D', dest='smooth_anchor_huber',
+                                   help='--smooth-data anchor: Huber delta of the anchor term, in sqrt(e^T W e); 0 = squared '
+                                        '(untuned default)')),
+)
+
+
+def mirror_smooth_anchor_options(config, opt):
+    """The --smooth-data flags as model_params keys (only the ones given: the defaults live in Eval and xas_amd.ops_track)."""
+    mirror_options(config, opt, given=('smooth_data', 'smooth_depth', 'smooth_anchor_huber'))
+
+
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -969,6 +1070,7 @@ def main():
     mirror_calib_options(config, opt)
     mirror_smooth_options(config, opt)
     mirror_resolve_track_options(config, opt)
+    mirror_smooth_anchor_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

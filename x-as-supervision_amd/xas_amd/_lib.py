@@ -174,6 +174,9 @@ SIGNATURES = {
     'xas_track_smooth_workspace_bytes': ('ii', 'z'),
     'xas_track_linearise': ('pppppp' 'iiiii' 'f' 'dd' 'ppp' 'pp', 'i'),
     'xas_track_smooth': ('pppppp' 'iiiii' 'f' 'd' 'i' 'pppppp' 'pp', 'i'),
+    'xas_track_anchor_workspace_bytes': ('ii', 'z'),
+    'xas_track_anchor_linearise': ('pppppppp' 'iiiii' 'f' 'ddd' 'ppp' 'pp', 'i'),
+    'xas_track_anchor_smooth': ('pppppppp' 'iiiii' 'f' 'dd' 'i' 'pppppp' 'pp', 'i'),
     'xas_track_resolve_workspace_bytes': ('iii', 'z'),
     'xas_track_resolve': ('pppppp' 'iiii' 'ddd' 'ppppp' 'pp', 'i'),
     'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),

@@ -1,9 +1,11 @@
 """Temporal smoothing of triangulated joint tracks on the device (csrc/track_smooth.hip, xas_track_smooth): per (track, joint)
 the reprojection cost of ops_eval.triangulate_refine in every frame that has data plus a penalty on the acceleration, by a
 double-precision Levenberg-Marquardt over all frames of the track at once (block-pentadiagonal Cholesky); frames without data
-are filled in from their neighbours.  include/xas_hip.h states the problem and the schedule.  Below it, one camera's depth
-hypothesis and left/right exchange chosen over the frames of a track (csrc/track_resolve.hip, xas_track_resolve).  Imported only
-when eval.py is given --smooth or --resolve-track.  No reference counterpart."""
+are filled in from their neighbours.  include/xas_hip.h states the problem and the schedule.  Below it, the same smoother with a
+3-D anchor and its information matrix per frame and joint, for one camera or after a volume fusion (csrc/track_anchor.hip,
+xas_track_anchor_smooth), and one camera's depth hypothesis and left/right exchange chosen over the frames of a track
+(csrc/track_resolve.hip, xas_track_resolve).  Imported only when eval.py is given --smooth or --resolve-track.  No reference
+counterpart."""
 import ctypes
 import os
 import re
@@ -143,6 +145,110 @@ def track_smooth(points, pmat, init, track, frame, views=None, weighted=False, h
          REFINE_WEIGHTED if weighted else 0, float(huber_px), float(acc_w), int(max_iter), ptr(sorted_out),
          ptr(per_sample.get('status')), ptr(per_sample.get('resid')), ptr(out.get('track_status')), ptr(out.get('cost')),
          ptr(out.get('trials')), ptr(ws if workspace is None else workspace))
+    out['xyzw'] = _scatter(order, sorted_out)
+    for k, v in per_sample.items():
+        out[k] = _scatter(order, v)
+    return out
+
+
+# ---- smoothing on 3-D anchors (csrc/track_anchor.hip, xas_track_anchor_smooth) ------------------------------------------------
+# The smoother above with one more observation per frame and joint: a 3-D point with a 3x3 information matrix.
+# Information along the ray of a single camera's point, in px^2 per mm^2: a depth error of 50 mm weighs like a residual of 1 px
+# (4e-4 * 50^2 = 1).  AN UNTUNED GUESS: there is neither a dataset nor a checkpoint here to tune it on.
+TRACK_DEPTH_W = 4e-4
+# Huber delta of the anchor term, in the unit of sqrt(e^T W e): with TRACK_DEPTH_W an anchor 150 mm down its ray, and a fused
+# point 3 sigma away, are where the pull stops growing.  Untuned as well.
+TRACK_ANCHOR_HUBER = 3.0
+
+
+def ray_information(pmat, anchor, depth_w=TRACK_DEPTH_W):
+    """pmat [N,3,4] (one view's projection matrices) and anchor [N,K,3] (world mm) -> info [N,K,6] float32, the entries xx, xy,
+    xz, yy, yz, zz of depth_w r r^T with r the unit vector from the camera centre (-M^-1 p4 of P = [M | p4], in float64) to the
+    anchor: what a point on that camera's ray says about its own depth.  Rows of non-finite anchors (or centres) are NaN."""
+    P = pmat.detach().double()
+    centre = -torch.linalg.solve(P[:, :, :3], P[:, :, 3:])[..., 0]                                  # [N,3]
+    r = anchor.detach().double() - centre.unsqueeze(1)
+    r = r / r.norm(dim=-1, keepdim=True)
+    rows, cols = (0, 0, 0, 1, 1, 2), (0, 1, 2, 1, 2, 2)
+    info = float(depth_w) * r[..., rows] * r[..., cols]
+    bad = ~torch.isfinite(info).all(-1, keepdim=True)
+    return torch.where(bad, torch.full_like(info, float('nan')), info).float().contiguous()
+
+
+def covariance_information(cov):
+    """cov [N,K,3,3] (mm^2) -> info [N,K,6] float32: the upper triangle of its inverse in float64, NaN rows where cov is not
+    finite or not positive definite."""
+    c = cov.detach().double()
+    finite = torch.isfinite(c).all(-1).all(-1)
+    c = torch.where(finite[..., None, None], 0.5 * (c + c.transpose(-1, -2)), torch.eye(3, dtype=c.dtype, device=c.device))
+    L, fail = torch.linalg.cholesky_ex(c)
+    ok = finite & (fail == 0)
+    L = torch.where(ok[..., None, None], L, torch.eye(3, dtype=c.dtype, device=c.device))
+    inv = torch.cholesky_inverse(L)
+    rows, cols = (0, 0, 0, 1, 1, 2), (0, 1, 2, 1, 2, 2)
+    info = inv[..., rows, cols]
+    return torch.where(ok.unsqueeze(-1), info, torch.full_like(info, float('nan'))).float().contiguous()
+
+
+def _anchors(name, anchor, info, order, N, K):
+    if (anchor is None) != (info is None):
+        raise RuntimeError('%s: anchor and info come together (both given, or both None)' % name)
+    if anchor is None:
+        return None, None
+    anchor, info = (t.detach().float() for t in (anchor, info))
+    if anchor.shape != (N, K, 3) or info.shape != (N, K, 6):
+        raise RuntimeError('%s: anchor %s and info %s are not [N,K,3] and [N,K,6] of %d samples and %d joints' % (
+            name, tuple(anchor.shape), tuple(info.shape), N, K))
+    return _sorted(order, anchor, info)
+
+
+def track_anchor_linearise(points, pmat, init, track, frame, anchor=None, info=None, views=None, weighted=False, huber_px=0.0,
+                           anchor_huber=TRACK_ANCHOR_HUBER, acc_w=TRACK_ACC_W, lam=0.0, workspace=None):
+    """track_linearise with anchors (xas_track_anchor_linearise): the same dict."""
+    name = 'track_anchor_linearise'
+    points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S = _prepare(name, points, pmat, init, track, frame, views)
+    anchor, info = _anchors(name, anchor, info, order, N, K)
+    dev = points.device
+    band = torch.empty(N, K, 3, 9, device=dev, dtype=torch.float64)
+    g = torch.empty(N, K, 3, device=dev, dtype=torch.float64)
+    C = torch.empty(S, K, device=dev, dtype=torch.float64)
+    call('xas_track_anchor_linearise', ptr(points), ptr(pmat), ptr(init), ptr(views), ptr(anchor), ptr(info), table, ptr(frame),
+         N, V, K, S, REFINE_WEIGHTED if weighted else 0, float(huber_px), float(anchor_huber), float(acc_w), float(lam),
+         ptr(band), ptr(g), ptr(C), ptr(ws if workspace is None else workspace))
+    return {'band': _scatter(order, band), 'g': _scatter(order, g), 'C': C, 'tracks': ids}
+
+
+def track_anchor_smooth(points, pmat, init, track, frame, anchor=None, info=None, views=None, weighted=False, huber_px=0.0,
+                        anchor_huber=TRACK_ANCHOR_HUBER, acc_w=TRACK_ACC_W, max_iter=30,
+                        want=('status', 'resid', 'track_status', 'cost', 'trials'), workspace=None):
+    """track_smooth with a 3-D anchor per frame and joint (xas_track_anchor_smooth), for one camera or more (V >= 1): anchor
+    [N,K,3] (world mm) and info [N,K,6] (xx, xy, xz, yy, yz, zz of the anchor's information matrix; ray_information,
+    covariance_information), or neither: then and with V >= 2 this is track_smooth bit for bit.  A frame with a usable anchor
+    (finite, trace > 0) is a data frame whatever its views say, and starts at the anchor where init is not finite; the anchor
+    term is Huber's loss of sqrt(e^T W e) with delta anchor_huber (0 = squared; TRACK_ANCHOR_HUBER is an untuned guess).  A
+    zero `views` byte stands for all valid views, as in track_smooth: to smooth on the anchors alone give weights of 0.
+    Everything else, the sorting by (track, frame) and the dict returned included, as track_smooth; resid is NaN where a frame
+    uses no view.  The semantics are those of include/xas_hip.h."""
+    name = 'track_anchor_smooth'
+    points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S = _prepare(name, points, pmat, init, track, frame, views)
+    anchor, info = _anchors(name, anchor, info, order, N, K)
+    dev = points.device
+    sorted_out = torch.empty(N, K, 4, device=dev)
+    per_sample, out = {}, {'tracks': ids}
+    if 'status' in want:
+        per_sample['status'] = torch.empty(N, K, device=dev, dtype=torch.uint8)
+    if 'resid' in want:
+        per_sample['resid'] = torch.empty(N, K, 2, device=dev)
+    if 'track_status' in want:
+        out['track_status'] = torch.empty(S, K, device=dev, dtype=torch.uint8)
+    if 'cost' in want:
+        out['cost'] = torch.empty(S, K, 2, device=dev, dtype=torch.float64)
+    if 'trials' in want:
+        out['trials'] = torch.empty(S, K, device=dev, dtype=torch.int32)
+    call('xas_track_anchor_smooth', ptr(points), ptr(pmat), ptr(init), ptr(views), ptr(anchor), ptr(info), table, ptr(frame),
+         N, V, K, S, REFINE_WEIGHTED if weighted else 0, float(huber_px), float(anchor_huber), float(acc_w), int(max_iter),
+         ptr(sorted_out), ptr(per_sample.get('status')), ptr(per_sample.get('resid')), ptr(out.get('track_status')),
+         ptr(out.get('cost')), ptr(out.get('trials')), ptr(ws if workspace is None else workspace))
     out['xyzw'] = _scatter(order, sorted_out)
     for k, v in per_sample.items():
         out[k] = _scatter(order, v)
