@@ -1036,6 +1036,64 @@ int xas_track_anchor_smooth(const float* points, const float* P, const float* in
                             unsigned char* status, float* resid, unsigned char* track_status, double* cost, int* trials,
                             void* workspace, void* stream);
 
+/* xas_track_anchor_smooth for all joints of a track at once, COUPLED BY THE LENGTHS OF THE BONES (eval.py --smooth
+ * --smooth-bones; the reference has no counterpart).  points, P, init, views, anchor, info, start, frame, N, V, K, S, flags,
+ * huber, anchor_huber and acc_w are exactly those of xas_track_anchor_smooth, with its rules word for word: valid views, the
+ * views used, BEHIND, data and gap frames, the start of a frame, the start line of a gap frame, the prior, XAS_REFINE_WEIGHTED.
+ * bones [Bn][2] int32, a HOST array read before the launch like limbs of xas_triangulate_skeleton: joint indices in [0, K); an
+ * index outside, or a bone from a joint to itself, is an error; NULL with Bn = 0.  length [S][Bn] fp32 on the device: the
+ * bone's length in mm for that track.  bone_w >= 0 and finite, in cost units per mm^2 (px^2, or sigma^2 with the flag).
+ * A (track, joint) that xas_track_anchor_smooth would pass through (fewer than two data frames) is FIXED: out = init bit for
+ * bit in every frame, and it takes part in nothing.  Every other is FREE.  A bone is ACTIVE in a track if both its joints are
+ * free and its length is finite and > 0; an active bone acts in EVERY frame of the track, gap frames included.
+ * COST of a track, in double from the fp32 inputs, over the free joints X[t,k]:
+ *   C = sum over free k of C_k                      (term for term the cost of xas_track_anchor_smooth for that joint)
+ *     + bone_w sum over active b = (i, j) and all t of e^2,  e = |X[t,i] - X[t,j]| - length[s][b]
+ * The Gauss-Newton row of a bone is +u at i and -u at j, u = d / |d|, d = X[t,i] - X[t,j]; where |d| < 1e-9 mm the residual
+ * counts but the row is zero and nothing is divided by |d| (the rule of xas_triangulate_skeleton).
+ * ONE Levenberg-Marquardt problem per track over all free joints and frames.  A TRIAL is X + d with (H + lambda diag H) d = -g;
+ * the lambda schedule, the acceptance rule and the stop rule are those of xas_track_smooth (lambda from 1e-3; accepted if C
+ * strictly decreases and no data frame's point lies behind a view it uses, then lambda *= 0.1, otherwise and at a pivot that is
+ * not positive lambda *= 10; stop when the longest |d[t,k]| of an accepted trial is under 1e-5 mm, after max_iter trials, 1 <=
+ * max_iter <= 64, or when lambda > 1e12).  So C(out) <= C(start), always.
+ * With the unknown 3K t + 3k + c the matrix is block-pentadiagonal with blocks of side n = 3K: the diagonal block of frame t
+ * holds the joints' 3x3 data blocks and acc_w A_tt on its diagonal plus bone_w sum J^T J, which couples the joints of that
+ * frame; the blocks (t, t-1) and (t, t-2) are acc_w A_t,t-1 and acc_w A_t,t-2 times the identity on the free joints.  It is
+ * solved by a block Cholesky with a forward and a back substitution over the frames.  A fixed joint's rows are identity rows
+ * with a zero right-hand side: the other unknowns do not feel them.
+ * xas_track_skeleton_smooth.  out [N][K][4] (required, must not overlap init), status [N][K] and resid [N][K][2] as
+ * xas_track_smooth (2 and NaN for a fixed joint).  Each but out may be NULL:
+ *   bone [N][Bn][2] fp32       e in mm at the start and at the result; NaN where the bone is not active in that track
+ *   track_status [S] bytes     0 = stopped on the step rule, 1 = ran out of trials or lambda, 2 = no free joint
+ *   cost [S][2] double         C at the start and at the result (0 with no free joint)
+ *   trials [S] int32           trials made (0 with no free joint)
+ * xas_track_skeleton_linearise: one linearisation at the start with the given lambda >= 0, all double and required: g
+ * [N][K][3]; hdiag [N][3K][3K], the diagonal block of H + lambda diag H of that sample's frame, rows and columns of fixed
+ * joints 0; hoff [N][2], the scalars acc_w A_t,t-1 and acc_w A_t,t-2 (0 where t-1 or t-2 lies outside the track); d [N][K][3],
+ * the solution of the trial system, 0 for fixed joints, NaN for the whole track if a pivot was not positive; C [S].  d is there
+ * so that the block factorisation can be tested apart from the loop.
+ * workspace: xas_track_skeleton_workspace_bytes(N, K) bytes (0 for a shape outside the limits or a size that does not fit
+ * size_t, else a multiple of 16), 16-byte aligned; its content before the call does not matter.  Per frame it holds the three
+ * factor blocks L_tt, L_t,t-1 and L_t,t-2 (3 n^2 doubles) and 10 n + 3 doubles of X, the trial point, g, d and the data
+ * blocks: 74,328 bytes per frame at K = 18, 69,984 of them the factor.  T is bounded by N alone.
+ * Limits: 1 <= V <= XAS_TRI_MAX_VIEWS, 1 <= K <= XAS_SKEL_MAX_JOINTS, 0 <= Bn <= XAS_TRACK_MAX_BONES, N > 0, 1 <= S <= N.
+ * One workgroup of 256 threads per track, the block in work and its factor in LDS (125 KB static); one launch after the copy
+ * of start, no host synchronisation, no atomics, every sum in one order: two calls on the same inputs give the same bits in
+ * every output. */
+#define XAS_TRACK_MAX_BONES 32
+size_t xas_track_skeleton_workspace_bytes(int N, int K);
+int xas_track_skeleton_linearise(const float* points, const float* P, const float* init, const unsigned char* views,
+                                 const float* anchor, const float* info, const int* bones, const float* length,
+                                 const int* start, const int* frame, int N, int V, int K, int S, int Bn, int flags, float huber,
+                                 double anchor_huber, double acc_w, double bone_w, double lambda, double* g, double* hdiag,
+                                 double* hoff, double* d, double* C, void* workspace, void* stream);
+int xas_track_skeleton_smooth(const float* points, const float* P, const float* init, const unsigned char* views,
+                              const float* anchor, const float* info, const int* bones, const float* length, const int* start,
+                              const int* frame, int N, int V, int K, int S, int Bn, int flags, float huber, double anchor_huber,
+                              double acc_w, double bone_w, int max_iter, float* out, unsigned char* status, float* resid,
+                              float* bone, unsigned char* track_status, double* cost, int* trials, void* workspace,
+                              void* stream);
+
 /* Depth hypothesis and left/right exchange of ONE camera chosen over time (eval.py --resolve-track OUT.npz; the reference has
  * no counterpart, and no labels are read).  kps [N][Hy][K][3] the detector's patch-normalised joints, world [N][Hy][K][3] their
  * single-view world points in mm, unary [N][Hy][K] an extra cost per candidate or NULL (= 0), all fp32 on the device; N counts

@@ -93,6 +93,14 @@ hypothesis is an outlier.  With 2+ cameras it needs --tri-volume and smooths the
 covariance, no pixels: the cost is then in sigma^2, and --smooth-acc weighs against it, not against pixels.  OUT.npz gains
 `anchored`; the two SMOOTH lines name the mode.  Unknown: its accuracy on real detections; both new constants are untuned.
 
+--smooth-bones [W] (opt-in with --smooth and either --smooth-data; model_params.smooth_bones; without it exactly the calls above)
+makes the one call after the loop xas_amd.ops_track.track_skeleton_smooth on the same kept tensors: all joints of a track at
+once, coupled in every frame, gap frames included, by the lengths of the bones of model_params.parent_ids (the per-track
+medians of the points the smoother starts from, track_bone_lengths).  OUT.npz gains `bones`, `bone_length` and `bone_err`, its
+`track_status`, `cost` and `trials` are per track, and the two SMOOTH lines end with the bone-length RMS before and after (over
+all active bones; over the bones at a filled joint).
+Unknown: its accuracy on real detections; W is an untuned guess; the workspace is 74 KB per frame at K = 18.
+
 The post-loop options keep their rows in the plain lists fit_rows, calib_rows, smooth_rows and rt_rows and write their files
 (atomically) from record().
 """
@@ -299,6 +307,14 @@ class Eval:
             self.smooth_depth = float(mp.get('smooth_depth', ops_track.TRACK_DEPTH_W))               # anchor only; untuned too
             self.smooth_anchor_huber = float(mp.get('smooth_anchor_huber', ops_track.TRACK_ANCHOR_HUBER))
             self.smooth_rows = []                      # per batch, on the device: points, pmat, init, views, gt (anchor, info); and the paths
+            self.smooth_bones = mp.get('smooth_bones')         # --smooth-bones [W]: all joints of a track at once, coupled by bone lengths
+            if self.smooth_bones is False:             # `smooth_bones: false` in a config is off, like no key
+                self.smooth_bones = None
+            if self.smooth_bones is not None:
+                self.smooth_bones = ops_track.TRACK_BONE_W if self.smooth_bones is True else float(self.smooth_bones)   # an untuned guess
+                self.bones = ops_track.bones_of(mp['parent_ids'])
+        elif mp.get('smooth_bones') is not None and mp.get('smooth_bones') is not False:
+            raise ValueError('smooth_bones couples the joints of --smooth: it needs smooth (model_params.smooth)')
         self.resolve_track = mp.get('resolve_track') or None   # --resolve-track OUT.npz: hypothesis and exchange chosen over time, per camera
         if self.resolve_track:
             check_single_rank('resolve_track needs WORLD_SIZE == 1: a DistributedSampler deals the frames of a sequence out '
@@ -387,8 +403,11 @@ class Eval:
         track, frame = ops_track.tracks_of(paths, self.smooth_gap, count=len(points))
         if self.smooth_data == 'anchor':
             return self.write_smooth_anchor(points, pmat, init, gt, views, track, frame)
-        r = ops_track.track_smooth(points, pmat, init, track, frame, views=views, weighted=self.tri_weight == 'spread',
-                                   huber_px=self.tri_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
+        if self.smooth_bones is not None:
+            r = self.smooth_skeleton(points, pmat, init, track, frame, views)
+        else:
+            r = ops_track.track_smooth(points, pmat, init, track, frame, views=views, weighted=self.tri_weight == 'spread',
+                                       huber_px=self.tri_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
         joints, status = r['xyzw'][..., :3].contiguous(), r['status']
         both = torch.isfinite(joints).all(-1) & torch.isfinite(init[..., :3]).all(-1)                  # [N,K]
         e_before, e_after = joint_errors(init[..., :3].contiguous(), gt), joint_errors(joints, gt)
@@ -397,14 +416,16 @@ class Eval:
         cols = {'joints': joints, 'status': status, 'track_status': r['track_status'], 'cost': r['cost'], 'trials': r['trials']}
         cols = {k: v.cpu().numpy() for k, v in cols.items()}
         cols['track'], cols['frame'] = track, frame
+        cols.update(self.bone_columns(r))
         save_npz(self.smooth, cols)
         S = len(r['tracks'])
-        return ['SMOOTH {} tracks of mean length {} (acc {}, gap {}, {} trials): TRI MPJPE {} -> {} mm, reprojection RMS {} -> {} px, '
+        return [line + words for line, words in zip(['SMOOTH {} tracks of mean length {} (acc {}, gap {}, {} trials): TRI MPJPE {} -> {} mm, reprojection RMS {} -> {} px, '
                 'gaps filled {} , passed through {}'.format(S, len(points) / S, self.smooth_acc, self.smooth_gap, self.smooth_iters,
                                                             masked_mean(e_before, both), masked_mean(e_after, both), rms(0), rms(1),
                                                             float((status == ops_track.STATUS_FILLED).float().mean()),
                                                             float((status == ops_track.STATUS_PASSED).float().mean())),
-                'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))]
+                'SMOOTH filled gap joints: MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))],
+            self.bone_words(r, filled))]
 
     def write_smooth_anchor(self, points, pmat, init, gt, views, track, frame):
         """--smooth --smooth-data anchor: one track_anchor_smooth over everything the batches kept, the file (write_smooth's
@@ -419,9 +440,13 @@ class Eval:
             info = ops_track.ray_information(pmat[:, 0], anchor, self.smooth_depth)
         else:
             info = cat_rows(self.smooth_rows, 'info')
-        r = ops_track.track_anchor_smooth(points, pmat, init, track, frame, anchor=anchor, info=info, views=views,
-                                          weighted=self.tri_weight == 'spread', huber_px=self.tri_huber,
-                                          anchor_huber=self.smooth_anchor_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
+        if self.smooth_bones is not None:
+            r = self.smooth_skeleton(points, pmat, init, track, frame, views, anchor=anchor, info=info,
+                                     anchor_huber=self.smooth_anchor_huber)
+        else:
+            r = ops_track.track_anchor_smooth(points, pmat, init, track, frame, anchor=anchor, info=info, views=views,
+                                              weighted=self.tri_weight == 'spread', huber_px=self.tri_huber,
+                                              anchor_huber=self.smooth_anchor_huber, acc_w=self.smooth_acc, max_iter=self.smooth_iters)
         joints, status = r['xyzw'][..., :3].contiguous(), r['status']
         anchored = torch.isfinite(anchor).all(-1) & torch.isfinite(info).all(-1) & (info[..., 0] + info[..., 3] + info[..., 5] > 0)
         both = torch.isfinite(joints).all(-1) & torch.isfinite(init[..., :3]).all(-1)
@@ -432,16 +457,51 @@ class Eval:
                 'anchored': anchored.to(torch.uint8)}
         cols = {k: v.cpu().numpy() for k, v in cols.items()}
         cols['track'], cols['frame'] = track, frame
+        cols.update(self.bone_columns(r))
         save_npz(self.smooth, cols)
         S = len(r['tracks'])
         what = 'one camera, depth {}'.format(self.smooth_depth) if one else 'fused points'
-        return ['SMOOTH anchor ({}, huber {}) {} tracks of mean length {} (acc {}, gap {}, {} trials): {} MPJPE {} -> {} mm, '
+        return [line + words for line, words in zip(['SMOOTH anchor ({}, huber {}) {} tracks of mean length {} (acc {}, gap {}, {} trials): {} MPJPE {} -> {} mm, '
                 'reprojection RMS {} -> {} px, anchored {} , gaps filled {} , passed through {}'.format(
                     what, self.smooth_anchor_huber, S, len(points) / S, self.smooth_acc, self.smooth_gap, self.smooth_iters,
                     'VIEW' if one else 'TRI', masked_mean(e_before, both), masked_mean(e_after, both), rms(0), rms(1),
                     float(anchored.float().mean()), float((status == ops_track.STATUS_FILLED).float().mean()),
                     float((status == ops_track.STATUS_PASSED).float().mean())),
-                'SMOOTH filled gap joints (anchor): MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))]
+                'SMOOTH filled gap joints (anchor): MPJPE {} mm over {} joints'.format(masked_mean(e_after, filled), int(filled.sum()))],
+            self.bone_words(r, filled))]
+
+    SKELETON_WORKSPACE_WARN = 1 << 30        # bytes: above this smooth_skeleton says what it is about to allocate
+
+    def smooth_skeleton(self, points, pmat, init, track, frame, views, **anchors):
+        """--smooth-bones: the one call of --smooth as track_skeleton_smooth, the lengths the per-track medians of the points it
+        starts from.  Its track_status, cost and trials are per track, not per (track, joint)."""
+        from xas_amd import _lib, ops_track
+        nbytes = _lib.query('xas_track_skeleton_workspace_bytes', points.shape[0], points.shape[2])
+        if nbytes > self.SKELETON_WORKSPACE_WARN:
+            print('SMOOTH bones: the solver keeps its factor per frame, a workspace of {:.1f} GB for {} frames'.format(
+                nbytes / 1e9, points.shape[0]), flush=True)
+        length = ops_track.track_bone_lengths(init, track, frame, self.bones)
+        return ops_track.track_skeleton_smooth(points, pmat, init, track, frame, self.bones, length=length, views=views,
+                                               weighted=self.tri_weight == 'spread', huber_px=self.tri_huber, acc_w=self.smooth_acc,
+                                               bone_w=self.smooth_bones, max_iter=self.smooth_iters, **anchors)
+
+    def bone_columns(self, r):
+        """What --smooth-bones adds to the file: bones [Bn,2], bone_length [S,Bn], bone_err [N,Bn,2].  Nothing without it."""
+        if self.smooth_bones is None:
+            return {}
+        return {'bones': self.bones, 'bone_length': r['length'].cpu().numpy(), 'bone_err': r['bone'].cpu().numpy()}
+
+    def bone_words(self, r, filled):
+        """What --smooth-bones appends to the two SMOOTH lines: the RMS over active bones and frames of (length in the frame -
+        length of the track) before and after, and the same over the bones with a filled joint (filled [N,K]) in that frame.
+        Nothing without it."""
+        if self.smooth_bones is None:
+            return '', ''
+        bones = torch.as_tensor(self.bones, dtype=torch.long, device=filled.device)
+        at_gap = (filled[:, bones[:, 0]] | filled[:, bones[:, 1]]).unsqueeze(-1)                          # [N,Bn,1]
+        rms = lambda e: [float(torch.sqrt((e[..., c] ** 2).nanmean())) for c in (0, 1)]
+        return (', bones ({} of weight {}): length RMS {} -> {} mm'.format(len(self.bones), self.smooth_bones, *rms(r['bone'])),
+                ', bone length RMS at them {} -> {} mm'.format(*rms(torch.where(at_gap, r['bone'], torch.full_like(r['bone'], float('nan'))))))
 
     def write_resolve_track(self):
         """--resolve-track: one track_resolve per camera over everything the batches kept, the file and -> the lines of
@@ -1057,9 +1117,24 @@ def mirror_smooth_anchor_options(config, opt):
     mirror_options(config, opt, given=('smooth_data', 'smooth_depth', 'smooth_anchor_huber'))
 
 
+CLI_SMOOTH_BONES = (  # --smooth-bones, parsed after CLI_SMOOTH_ANCHOR (a table per option, as above)
+    ('--smooth-bones', dict(default=None, nargs='?', const=True, type=float, metavar='W', dest='smooth_bones',
+                            help='--smooth (with either --smooth-data): smooth all joints of a track at once, coupled in every '
+                                 'frame by the lengths of the bones of model_params.parent_ids (the per-track medians of the start); '
+                                 'W = weight of a squared length error, px^2 per mm^2 (untuned default)')),
+)
+
+
+def mirror_smooth_bones_options(config, opt):
+    """--smooth-bones as a model_params key (only if given: True stands for the default weight of xas_amd.ops_track)."""
+    if opt.smooth_bones is not None and not opt.smooth:
+        raise ValueError('--smooth-bones couples the joints of --smooth: it needs --smooth')
+    mirror_options(config, opt, given=('smooth_bones',))
+
+
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -1071,6 +1146,7 @@ def main():
     mirror_smooth_options(config, opt)
     mirror_resolve_track_options(config, opt)
     mirror_smooth_anchor_options(config, opt)
+    mirror_smooth_bones_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

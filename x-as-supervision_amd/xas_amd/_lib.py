@@ -177,6 +177,9 @@ SIGNATURES = {
     'xas_track_anchor_workspace_bytes': ('ii', 'z'),
     'xas_track_anchor_linearise': ('pppppppp' 'iiiii' 'f' 'ddd' 'ppp' 'pp', 'i'),
     'xas_track_anchor_smooth': ('pppppppp' 'iiiii' 'f' 'dd' 'i' 'pppppp' 'pp', 'i'),
+    'xas_track_skeleton_workspace_bytes': ('ii', 'z'),
+    'xas_track_skeleton_linearise': ('pppppppppp' 'iiiiii' 'f' 'dddd' 'ppppp' 'pp', 'i'),
+    'xas_track_skeleton_smooth': ('pppppppppp' 'iiiiii' 'f' 'ddd' 'i' 'ppppppp' 'pp', 'i'),
     'xas_track_resolve_workspace_bytes': ('iii', 'z'),
     'xas_track_resolve': ('pppppp' 'iiii' 'ddd' 'ppppp' 'pp', 'i'),
     'xas_triangulate_volume': ('pppppppppp' 'iiiiii' 'fffff' 'pppp', 'i'),

@@ -3,8 +3,9 @@ the reprojection cost of ops_eval.triangulate_refine in every frame that has dat
 double-precision Levenberg-Marquardt over all frames of the track at once (block-pentadiagonal Cholesky); frames without data
 are filled in from their neighbours.  include/xas_hip.h states the problem and the schedule.  Below it, the same smoother with a
 3-D anchor and its information matrix per frame and joint, for one camera or after a volume fusion (csrc/track_anchor.hip,
-xas_track_anchor_smooth), and one camera's depth hypothesis and left/right exchange chosen over the frames of a track
-(csrc/track_resolve.hip, xas_track_resolve).  Imported only when eval.py is given --smooth or --resolve-track.  No reference
+xas_track_anchor_smooth), that smoother for all joints of a track at once, coupled by the lengths of the bones
+(csrc/track_skeleton.hip, xas_track_skeleton_smooth), and one camera's depth hypothesis and left/right exchange chosen over the
+frames of a track (csrc/track_resolve.hip, xas_track_resolve).  Imported only when eval.py is given --smooth or --resolve-track.  No reference
 counterpart."""
 import ctypes
 import os
@@ -84,7 +85,7 @@ def _by_track(name, track, frame):
     return order, fs.to(torch.int32).contiguous(), ids, (ctypes.c_int * (S + 1))(*start), S
 
 
-def _prepare(name, points, pmat, init, track, frame, views):
+def _prepare(name, points, pmat, init, track, frame, views, workspace_of='xas_track_smooth_workspace_bytes'):
     if points.dim() != 4 or points.shape[-1] != 3:
         raise RuntimeError('%s: points must be [N,V,K,3], got %s' % (name, tuple(points.shape)))
     points, pmat, init, views, N, V, K = _solver_inputs(name, points, pmat, init, views, 'N')
@@ -95,7 +96,7 @@ def _prepare(name, points, pmat, init, track, frame, views):
             name, tuple(track.shape), tuple(frame.shape), tuple(points.shape)))
     order, frame, ids, table, S = _by_track(name, track, frame)
     points, pmat, init, views = _sorted(order, points, pmat, init, views)
-    ws = torch.empty(max(query('xas_track_smooth_workspace_bytes', N, K), 16), device=dev, dtype=torch.uint8)
+    ws = torch.empty(max(query(workspace_of, N, K), 16), device=dev, dtype=torch.uint8)
     return points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S
 
 
@@ -249,6 +250,138 @@ def track_anchor_smooth(points, pmat, init, track, frame, anchor=None, info=None
          N, V, K, S, REFINE_WEIGHTED if weighted else 0, float(huber_px), float(anchor_huber), float(acc_w), int(max_iter),
          ptr(sorted_out), ptr(per_sample.get('status')), ptr(per_sample.get('resid')), ptr(out.get('track_status')),
          ptr(out.get('cost')), ptr(out.get('trials')), ptr(ws if workspace is None else workspace))
+    out['xyzw'] = _scatter(order, sorted_out)
+    for k, v in per_sample.items():
+        out[k] = _scatter(order, v)
+    return out
+
+
+# ---- all joints of a track at once, coupled by bone lengths (csrc/track_skeleton.hip, xas_track_skeleton_smooth) -------------
+# Weight of a squared bone-length error, in px^2 per mm^2: 3 mm of length error weigh like a residual of 1 px (0.1 * 3.2^2 = 1),
+# the reasoning of ops_eval.TRI_SYM_W.  AN UNTUNED GUESS: there is neither a dataset nor a checkpoint here to tune it on.
+TRACK_BONE_W = 0.1
+TRACK_MAX_BONES = 32     # xas_hip.h XAS_TRACK_MAX_BONES
+SKELETON_TRACK_STATUS_NAMES = ('converged', 'trial limit', 'no free joint')
+
+
+def bones_of(parent_ids):
+    """parent_ids [K] (model_params.parent_ids) -> the rows (k, parent_ids[k]) of the joints that have a parent other than
+    themselves (parent_ids[k] >= 0 and != k), as an int32 numpy array [Bn,2]."""
+    rows = [(k, int(p)) for k, p in enumerate(parent_ids) if int(p) >= 0 and int(p) != k]
+    return np.asarray(rows, np.int32).reshape(-1, 2)
+
+
+def track_bone_lengths(init, track, frame, bones, usable=None):
+    """init [N,K,>=3] (mm), track [N] and frame [N] integers (frame is not read: the argument list is the smoothers'), bones
+    [Bn,2] -> length [S,Bn] float32 on init's device, row s for the s-th track number in ascending order: the median of
+    |init_i - init_j| over the track's frames where both joints are finite (and `usable` [N,K] holds for both, if given), the
+    mean of the two middle values for an even count; NaN where no frame qualifies.  Set-up in plain torch, not hot path."""
+    x = init.detach()[..., :3].double()
+    bones = torch.as_tensor(np.asarray(bones, np.int64).reshape(-1, 2), device=x.device)
+    track = torch.as_tensor(track).to(device=x.device, dtype=torch.int64)
+    ids, inv = torch.unique(track, return_inverse=True)
+    ok = torch.isfinite(x).all(-1)
+    if usable is not None:
+        ok = ok & usable.to(x.device).bool()
+    okb = ok[:, bones[:, 0]] & ok[:, bones[:, 1]]                                                  # [N,Bn]
+    length = (x[:, bones[:, 0]] - x[:, bones[:, 1]]).norm(dim=-1)
+    length = torch.where(okb, length, torch.full_like(length, float('nan')))
+    out = torch.full((len(ids), bones.shape[0]), float('nan'), dtype=torch.float64, device=x.device)
+    for s in range(len(ids)):
+        rows, cnt = torch.sort(length[inv == s], dim=0).values, okb[inv == s].sum(0)                 # NaN sorts last
+        lo, hi = ((cnt - 1).clamp(min=0) // 2).unsqueeze(0), (cnt // 2).clamp(max=rows.shape[0] - 1).unsqueeze(0)
+        mid = 0.5 * (rows.gather(0, lo) + rows.gather(0, hi))[0]
+        out[s] = torch.where(cnt > 0, mid, torch.full_like(mid, float('nan')))
+    return out.float().contiguous()
+
+
+def _skeleton(name, init, track, bones, length, S):
+    """The bones as the HOST array the kernel takes, and length [S,Bn] float32 in the order of `ids`."""
+    bones = np.ascontiguousarray(np.asarray(bones, np.int64).reshape(-1, 2))
+    Bn = bones.shape[0]
+    if Bn > TRACK_MAX_BONES:
+        raise RuntimeError('%s: %d bones (at most XAS_TRACK_MAX_BONES = %d)' % (name, Bn, TRACK_MAX_BONES))
+    if length is None:
+        length = track_bone_lengths(init, track, None, bones)
+    length = torch.as_tensor(length).detach().to(device=init.device, dtype=torch.float32).contiguous()
+    if length.shape != (S, Bn):
+        raise RuntimeError('%s: length %s is not [S,Bn] = [%d,%d]' % (name, tuple(length.shape), S, Bn))
+    return (ctypes.c_int * max(2 * Bn, 1))(*bones.reshape(-1).tolist()), length, Bn
+
+
+def _own_workspace(name, ws, workspace):
+    """The caller's workspace in place of the fresh one `ws`, if it is given and holds at least as many bytes."""
+    if workspace is None:
+        return ws
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < ws.numel():
+        raise RuntimeError('%s: workspace must be a contiguous uint8 tensor of at least %d bytes (xas_track_skeleton_workspace_bytes), '
+                           'got %s of %d' % (name, ws.numel(), workspace.dtype, workspace.numel()))
+    return workspace
+
+
+def track_skeleton_linearise(points, pmat, init, track, frame, bones, length=None, anchor=None, info=None, views=None,
+                             weighted=False, huber_px=0.0, anchor_huber=TRACK_ANCHOR_HUBER, acc_w=TRACK_ACC_W,
+                             bone_w=TRACK_BONE_W, lam=0.0, workspace=None):
+    """One linearisation of track_skeleton_smooth's problem at the start with damping `lam` (xas_track_skeleton_linearise) ->
+    dict, float64, per-sample entries in the order given: g [N,K,3], hdiag [N,3K,3K], hoff [N,2], d [N,K,3] (the trial step),
+    C [S] and tracks [S]."""
+    name = 'track_skeleton_linearise'
+    raw_init, raw_track = init, torch.as_tensor(track)
+    points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S = _prepare(name, points, pmat, init, track, frame, views,
+                                                                                  'xas_track_skeleton_workspace_bytes')
+    anchor, info = _anchors(name, anchor, info, order, N, K)
+    host_bones, length, Bn = _skeleton(name, raw_init, raw_track, bones, length, S)
+    dev = points.device
+    ws = _own_workspace(name, ws, workspace)
+    g = torch.empty(N, K, 3, device=dev, dtype=torch.float64)
+    hdiag = torch.empty(N, 3 * K, 3 * K, device=dev, dtype=torch.float64)
+    hoff = torch.empty(N, 2, device=dev, dtype=torch.float64)
+    d = torch.empty(N, K, 3, device=dev, dtype=torch.float64)
+    C = torch.empty(S, device=dev, dtype=torch.float64)
+    call('xas_track_skeleton_linearise', ptr(points), ptr(pmat), ptr(init), ptr(views), ptr(anchor), ptr(info), host_bones,
+         ptr(length), table, ptr(frame), N, V, K, S, Bn, REFINE_WEIGHTED if weighted else 0, float(huber_px), float(anchor_huber),
+         float(acc_w), float(bone_w), float(lam), ptr(g), ptr(hdiag), ptr(hoff), ptr(d), ptr(C), ptr(ws))
+    return {'g': _scatter(order, g), 'hdiag': _scatter(order, hdiag), 'hoff': _scatter(order, hoff), 'd': _scatter(order, d),
+            'C': C, 'tracks': ids}
+
+
+def track_skeleton_smooth(points, pmat, init, track, frame, bones, length=None, anchor=None, info=None, views=None,
+                          weighted=False, huber_px=0.0, anchor_huber=TRACK_ANCHOR_HUBER, acc_w=TRACK_ACC_W, bone_w=TRACK_BONE_W,
+                          max_iter=30, want=('status', 'resid', 'bone', 'track_status', 'cost', 'trials'), workspace=None):
+    """track_anchor_smooth for all joints of a track at once, coupled in every frame (gap frames included) by the lengths of
+    the bones (xas_track_skeleton_smooth): bones [Bn,2] joint indices (bones_of), length [S,Bn] mm per track in ascending track
+    number, or None: track_bone_lengths of init; bone_w in px^2 per mm^2 (TRACK_BONE_W is an untuned guess).  Everything else,
+    the sorting by (track, frame) included, as track_anchor_smooth.  A (track, joint) with fewer than two data frames is fixed:
+    it leaves as init and its bones are switched off.
+    -> dict: xyzw [N,K,4]; tracks [S]; status [N,K] uint8, resid [N,K,2], bone [N,Bn,2] (the bone's length error in mm before
+    and after; NaN where it is not active), track_status [S] uint8 (SKELETON_TRACK_STATUS_NAMES), cost [S,2] float64, trials
+    [S] int32 as requested; length [S,Bn], the lengths used.  The semantics are those of include/xas_hip.h."""
+    name = 'track_skeleton_smooth'
+    raw_init, raw_track = init, torch.as_tensor(track)
+    points, pmat, init, views, frame, order, ids, table, ws, N, V, K, S = _prepare(name, points, pmat, init, track, frame, views,
+                                                                                  'xas_track_skeleton_workspace_bytes')
+    anchor, info = _anchors(name, anchor, info, order, N, K)
+    host_bones, length, Bn = _skeleton(name, raw_init, raw_track, bones, length, S)
+    dev = points.device
+    ws = _own_workspace(name, ws, workspace)
+    sorted_out = torch.empty(N, K, 4, device=dev)
+    per_sample, out = {}, {'tracks': ids, 'length': length}
+    if 'status' in want:
+        per_sample['status'] = torch.empty(N, K, device=dev, dtype=torch.uint8)
+    if 'resid' in want:
+        per_sample['resid'] = torch.empty(N, K, 2, device=dev)
+    if 'bone' in want:
+        per_sample['bone'] = torch.empty(N, Bn, 2, device=dev)
+    if 'track_status' in want:
+        out['track_status'] = torch.empty(S, device=dev, dtype=torch.uint8)
+    if 'cost' in want:
+        out['cost'] = torch.empty(S, 2, device=dev, dtype=torch.float64)
+    if 'trials' in want:
+        out['trials'] = torch.empty(S, device=dev, dtype=torch.int32)
+    call('xas_track_skeleton_smooth', ptr(points), ptr(pmat), ptr(init), ptr(views), ptr(anchor), ptr(info), host_bones,
+         ptr(length), table, ptr(frame), N, V, K, S, Bn, REFINE_WEIGHTED if weighted else 0, float(huber_px), float(anchor_huber),
+         float(acc_w), float(bone_w), int(max_iter), ptr(sorted_out), ptr(per_sample.get('status')), ptr(per_sample.get('resid')),
+         ptr(per_sample.get('bone')), ptr(out.get('track_status')), ptr(out.get('cost')), ptr(out.get('trials')), ptr(ws))
     out['xyzw'] = _scatter(order, sorted_out)
     for k, v in per_sample.items():
         out[k] = _scatter(order, v)
