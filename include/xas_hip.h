@@ -683,6 +683,56 @@ int xas_smpl_fit(const float* pose, const float* betas, const float* trans, cons
                  double* pose_out, double* betas_out, double* trans_out, double* joints_out, double* cost, int* iters,
                  unsigned char* status, void* workspace, void* stream);
 
+/* xas_smpl_fit over whole tracks (eval.py --fit-smpl --fit-shape track): ONE beta vector per track, pose and translation per
+ * frame.  The model arrays, targets, weights, priors and the init (pose, betas, trans: [N][72], [N][10], [N][3]) mean what they
+ * mean above.  track [N] int32 in [0, S) and frame [N] int32 (device) say which track a sample belongs to and where it stands
+ * in it; the samples may lie in any order in N.  A frame is USABLE by xas_smpl_fit's rule at its own init (>= 6 joints used and
+ * a finite cost there) if its track id is in [0, S); any other frame is PASSED THROUGH: it leaves as its init (pose, trans,
+ * joints = Y there, frame_cost = that cost twice, frame_status 2) and adds nothing to any track.
+ * UNKNOWNS of track s with usable frames F_s: y_t [75] = omega 3, t 3, theta 69 for every t in F_s, and beta_s [10].
+ * COST C_s = sum over t in F_s, ascending frame (a frame held twice: ascending sample index), of c(y_t, beta_s), c the COST above
+ * term for term, so the shape prior counts once per usable frame.  START: y_t from the init; beta_s the mean of the init betas
+ * over F_s, summed in that order in double.  A track of one frame is xas_smpl_fit's problem, and is solved bit for bit alike.
+ * SOLVER: one Levenberg-Marquardt per track with xas_smpl_fit's schedule: lambda = 1e-3, damping lambda diag(H) on every diagonal
+ * entry, a trial ACCEPTED if C_s at the trial is finite and strictly lower (lambda *= 0.1, CONVERGED if the largest |d| over all
+ * unknowns of the track is under XAS_SMPLFIT_STEP_TOL), otherwise and at a pivot that is not positive lambda *= 10; ends when
+ * converged, after max_iters trials or when lambda > 1e12.  So track_cost[1] <= track_cost[0], always.  The arrowhead system is
+ * solved by eliminating every frame's 75 unknowns (Cholesky of the frame's damped 85 x 85 matrix stopped after column 75) and
+ * summing the 10 x 10 Schur complements and reduced right-hand sides over F_s in the order above; no atomics.
+ * Outputs (double unless noted), every element written by every call: pose [N][72], trans [N][3], joints [N][18][3], frame_cost
+ * [N][2] = c at the track's start and at the result, frame_status [N] bytes (0 fitted, 2 passed through); track_betas [S][10]
+ * (a track without usable frame: the plain mean of the init betas of its samples in the order above, zeros if it has none),
+ * track_cost [S][2] = C_s at the start and at the result, track_trials [S] int32, track_status [S] bytes: 0 converged, 1 ran out
+ * of trials or lambda, 2 no usable frame.
+ * xas_smpl_fit_tracks_linearise: one trial at the given lambda >= 0 from the start: reduced [S][10][10] = the summed, damped
+ * Schur complement, rhs [S][10] with reduced . d_beta = rhs, the trial step d_y [N][75] (zeros for a frame passed through) and
+ * d_beta [S][10], track_cost [S] = C_s at the start.  A track without usable frame gives zeros; so does a track with a pivot
+ * that is not positive: in a frame's elimination the system and the step, in the reduced system the step.
+ * Argument errors return 1 before any launch; a track id outside [0, S) is one if `track` is host-visible memory (then it is read
+ * on the host), otherwise that frame is passed through.  N == 0 or S == 0 are valid.
+ * workspace: xas_smpl_fit_tracks_workspace_bytes(N, V, S) bytes, 16-byte aligned: the vertex-sized scratch exists once per
+ * workgroup of a bounded grid (min(N, 512) workgroups that stride over the frames), 61 936 bytes of state per frame whatever V.
+ * Set-up cost: a track's samples are found by one workgroup in a pass over N and ordered by ranking each against the others
+ * (T^2 comparisons for a track of T samples, nothing beside the trials at T = 256, not meant for one track of 1e5 frames).
+ * 5 launches to start, 4 per trial, all max_iters trials enqueued up front (a finished track does nothing in the later ones), no
+ * host synchronisation: a pure function of the inputs bit for bit, per track, whatever the order of the samples in N. */
+size_t xas_smpl_fit_tracks_workspace_bytes(int N, int V, int S);
+int xas_smpl_fit_tracks_linearise(const float* pose, const float* betas, const float* trans, const float* v_template,
+                                  const float* shapedirs, const float* posedirs, const float* j_regressor, const float* weights,
+                                  const int* parents, const float* h36m_regressor, const int* reg_verts, const int* reg_count,
+                                  const float* targets, const float* joint_w, const int* track, const int* frame,
+                                  float pose_prior, float shape_prior, int N, int V, int S, int center_idx, double lambda,
+                                  double* reduced, double* rhs, double* d_y, double* d_beta, double* track_cost, void* workspace,
+                                  void* stream);
+int xas_smpl_fit_tracks(const float* pose, const float* betas, const float* trans, const float* v_template,
+                        const float* shapedirs, const float* posedirs, const float* j_regressor, const float* weights,
+                        const int* parents, const float* h36m_regressor, const int* reg_verts, const int* reg_count,
+                        const float* targets, const float* joint_w, const int* track, const int* frame, float pose_prior,
+                        float shape_prior, int N, int V, int S, int center_idx, int max_iters, double* pose_out,
+                        double* trans_out, double* joints_out, double* frame_cost, unsigned char* frame_status,
+                        double* track_betas, double* track_cost, int* track_trials, unsigned char* track_status, void* workspace,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Fused multi-tensor Adam (train.py:257-264: betas (0.5, 0.999), eps 1e-8, no decay).
  * One launch updates a flat parameter arena: p, g, m, v are arenas of n floats.

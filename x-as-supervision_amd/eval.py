@@ -64,6 +64,14 @@ counts 1 / trace(cov), normalised to mean 1 per sample.  OUT.npz (`pose` [N,72],
 `joint_rms_mm`) is a bank that train.py --pseudo-online reads as it is; eval_result.txt gains one last line.  Unknown: how good
 the fits are on real detections (no checkpoint or dataset here), and the prior weights, which are untuned guesses.
 
+--fit-shape track (opt-in with --fit-smpl; model_params.fit_shape; one rank; without it exactly the calls above) keeps every
+batch's fit targets, weights and first-camera paths on the device and, after the loop, runs one fit_smpl_tracks over the whole
+set: tracks from tracks_of(paths, --fit-gap), ONE beta vector per track, pose and translation per frame, warm-started from the
+per-sample fits.  In OUT.npz `pose`, `betas` (each row its track's), `trans`, `cost`, `status` and `joint_rms_mm` then come from
+the track fit, and `betas_per_frame`, `track`, `frame`, `track_betas`, `track_status`, `track_trials` join; the FIT line gains
+the number of tracks and their mean length, joint RMS per frame -> per track and the mean within-track standard deviation of
+the per-frame betas.  There is no temporal prior on the pose.
+
 --calibrate OUT.npz (opt-in; model_params.calibrate; 2+ cameras, one rank) keeps every batch's triangulation inputs, final
 points and the views they used on the device and, after the loop, runs one bundle adjustment of the camera extrinsics per rig
 (xas_amd.ops_calib.calibrate_bundle).  OUT.npz holds the rigs' projection matrices (`keys`) and their corrections (`delta`:
@@ -271,6 +279,16 @@ class Eval:
             self.fit_pose_prior = float(mp.get('fit_pose_prior', ops_smplfit.POSE_PRIOR))      # untuned guesses, both
             self.fit_shape_prior = float(mp.get('fit_shape_prior', ops_smplfit.SHAPE_PRIOR))
             self.fit_rows = []                         # per batch: the host arrays of the file
+            self.fit_shape = mp.get('fit_shape') or 'frame'    # --fit-shape track: one beta vector per track, after the loop
+            if self.fit_shape not in ('frame', 'track'):
+                raise ValueError('fit_shape is frame or track, got {!r}'.format(self.fit_shape))
+            if self.fit_shape == 'track':
+                check_single_rank('fit_shape track solves over whole tracks: run it on one rank')
+                from xas_amd import ops_track
+                self.fit_gap = int(mp.get('fit_gap', ops_track.TRACK_MAX_GAP))
+                self.fit_track_rows = []               # per batch, on the device: targets, weights, usable joints, first-camera paths
+        elif (mp.get('fit_shape') or 'frame') != 'frame':
+            raise ValueError('fit_shape track is a mode of --fit-smpl: it needs fit_smpl (model_params.fit_smpl)')
         self.calibrate = mp.get('calibrate') or None   # --calibrate OUT.npz: bundle adjustment of the extrinsics over the whole set
         self.calibration = mp.get('calibration') or None   # --calibration IN.npz: every batch's cameras corrected by such a file
         if self.calibrate and self.calibration:
@@ -536,10 +554,11 @@ class Eval:
         save_npz(self.resolve_track, cols)
         return lines
 
-    def fit_batch(self, joints, bad, cov):
+    def fit_batch(self, joints, bad, cov, paths=None):
         """--fit-smpl on the final world joints [B,18,3] of a batch.  A joint's weight is 0 where it is not finite or `bad`
         [B,18] marks it (a triangulation that passed it through), else 1, or with `cov` [B,18,6] (xx xy xz yy yz zz, mm^2)
-        1 / trace(cov) normalised to mean 1 over the usable joints of the sample.  -> the file's rows, on the device."""
+        1 / trace(cov) normalised to mean 1 over the usable joints of the sample.  -> the file's rows, on the device.
+        With fit_shape track the batch's targets, weights and `paths` (the first camera's image paths, or None) are kept too."""
         from xas_amd import ops_smplfit
         ok = torch.isfinite(joints).all(dim=-1)
         if bad is not None:
@@ -554,6 +573,8 @@ class Eval:
                                  pose_prior=self.fit_pose_prior, shape_prior=self.fit_shape_prior)
         d2 = ((r['joints'] - torch.where(ok.unsqueeze(-1), joints.double(), r['joints'])) ** 2).sum(dim=-1)
         rms = (d2.sum(dim=1) / ok.double().sum(dim=1).clamp(min=1.0)).sqrt()
+        if self.fit_shape == 'track':                  # the per-sample fit is the warm start of write_fit_tracks
+            self.fit_track_rows.append({'targets': joints, 'weights': w, 'ok': ok, 'paths': None if paths is None else [str(p) for p in paths]})
         return {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
                 'fit_cost': r['cost'].float(), 'fit_status': r['status'], 'fit_joint_rms_mm': rms.float()}
 
@@ -563,19 +584,50 @@ class Eval:
         if row:
             self.fit_rows.append(row)
 
+    FIT_TRACKS_WORKSPACE_WARN = 1 << 30      # bytes: above this fit_tracks says what it is about to allocate
+
+    def fit_tracks(self, cols):
+        """--fit-shape track: one fit_smpl_tracks over the whole set, warm-started from the per-sample rows `cols`; the file's
+        columns of the track fit replace theirs and the new ones join.  -> the words the FIT line gains."""
+        from xas_amd import ops_smplfit, ops_track
+        targets, weights, ok, paths = (cat_rows(self.fit_track_rows, k) for k in ('targets', 'weights', 'ok', 'paths'))
+        dev, N = targets.device, targets.shape[0]
+        track, frame = ops_track.tracks_of(paths, self.fit_gap, count=N)
+        S = len(np.unique(track))
+        nbytes = ops_smplfit.tracks_workspace_bytes(N, self.smpl_layer.th_v_template.shape[-2], S)
+        if nbytes > self.FIT_TRACKS_WORKSPACE_WARN:
+            print('FIT tracks: the solver keeps its factor per frame, a workspace of {:.1f} GiB for {} frames'.format(nbytes / 2.0 ** 30, N), flush=True)
+        init = {k: torch.as_tensor(cols[k], device=dev) for k in ('pose', 'betas', 'trans')}
+        r = ops_smplfit.fit_smpl_tracks(targets, weights, track, frame, self.smpl_layer, self.h36m_regressor, init=init,
+                                        iters=self.fit_iters, pose_prior=self.fit_pose_prior, shape_prior=self.fit_shape_prior)
+        d2 = ((r['joints'] - torch.where(ok.unsqueeze(-1), targets.double(), r['joints'])) ** 2).sum(dim=-1)
+        rms = (d2.sum(dim=1) / ok.double().sum(dim=1).clamp(min=1.0)).sqrt()
+        per_frame, rms_frame = cols['betas'], cols['joint_rms_mm']
+        fitted = (r['status'] != ops_smplfit.STATUS_PASSED).cpu().numpy()
+        cols.update(pose=r['pose'].float().cpu().numpy(), betas=r['betas'].float().cpu().numpy(), trans=r['trans'].float().cpu().numpy(),
+                    cost=r['cost'].float().cpu().numpy(), status=r['status'].cpu().numpy(), joint_rms_mm=rms.float().cpu().numpy(),
+                    betas_per_frame=per_frame, track=r['track'].cpu().numpy(), frame=np.asarray(frame, np.int32),
+                    track_betas=r['track_betas'].float().cpu().numpy(), track_status=r['track_status'].cpu().numpy(),
+                    track_trials=r['track_trials'].cpu().numpy())
+        spread = [per_frame[(cols['track'] == s) & fitted].std(axis=0).mean() for s in range(S) if ((cols['track'] == s) & fitted).any()]
+        mean = lambda v: float(np.mean(v)) if len(v) else float('nan')
+        return ', shape per track: {} tracks of mean length {} (gap {}), joint RMS per frame {} -> per track {} mm, within-track std of the per-frame betas {}'.format(
+            S, N / max(S, 1), self.fit_gap, mean(rms_frame[fitted]), mean(cols['joint_rms_mm'][fitted]), mean(spread))
+
     def write_fit(self):
         """Writes the --fit-smpl file; passed-through samples are kept with their status.  -> the line of eval_result.txt."""
         from xas_amd import ops_smplfit
         shapes = {'pose': (0, 72), 'betas': (0, 10), 'trans': (0, 3), 'cost': (0, 2), 'status': (0,), 'joint_rms_mm': (0,)}
         cols = {k: (np.concatenate([r[k] for r in self.fit_rows]) if self.fit_rows else np.zeros(sh, np.uint8 if k == 'status' else np.float32))
                 for k, sh in shapes.items()}
+        words = self.fit_tracks(cols) if self.fit_shape == 'track' and self.fit_rows else ''
         save_npz(self.fit_smpl, cols)
         n = max(len(cols['status']), 1)
         fitted = cols['status'] != ops_smplfit.STATUS_PASSED
         rms = float(cols['joint_rms_mm'][fitted].mean()) if fitted.any() else float('nan')
         share = ' , '.join('{} {}'.format(name, float((cols['status'] == c).sum()) / n) for c, name in enumerate(ops_smplfit.STATUS_NAMES))
         return 'FIT smpl ({} trials, pose prior {}, shape prior {}): joint RMS {} mm; {}'.format(
-            self.fit_iters, self.fit_pose_prior, self.fit_shape_prior, rms, share)
+            self.fit_iters, self.fit_pose_prior, self.fit_shape_prior, rms, share) + words
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -784,14 +836,15 @@ class Eval:
                       'view': preds['view_' + m][..., :3].contiguous(), 'paths': None if paths is None else [str(p) for p in paths]}
         self.rt_rows.append(row)
 
-    def fit(self, t, preds, cams):
+    def fit(self, t, preds, cams, x):
         """--fit-smpl, after everything else, on the final world joints: the triangulated ones with their pass-through marks and
         covariance, or with one camera that view's selected hypothesis.  -> out: the fit_* rows of fit_batch, {} without the option."""
         if not self.fit_smpl:
             return {}
+        paths = x.get(cams[0] + '_img_path')       # read by fit_shape track alone
         if len(cams) > 1:
-            return self.fit_batch(preds['tri'][..., :3].contiguous(), t.bad, t.cov)
-        return self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None)
+            return self.fit_batch(preds['tri'][..., :3].contiguous(), t.bad, t.cov, paths)
+        return self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None, paths)
 
     @torch.no_grad()
     def eval_batch(self, x, mode='best', kps_by_cam=None):
@@ -809,7 +862,7 @@ class Eval:
         preds, errors = self.measure(s, t, x, gt, cams)
         out.update(errors)
         self.keep_track_rows(s, x, gt, preds, cams, mode)
-        out.update(self.fit(t, preds, cams))
+        out.update(self.fit(t, preds, cams, x))
         return out
 
     def eval(self, tb_log, record_table, count_table, record_3d_table, count_3d_table, record_3d_tri_table,
@@ -1035,6 +1088,22 @@ def mirror_fit_options(config, opt):
     mirror_options(config, opt, always=('fit_smpl', 'smpl_model', 'fit_iters'), given=('fit_pose_prior', 'fit_shape_prior'))
 
 
+CLI_FIT_SHAPE = (  # --fit-shape and its gap, parsed after CLI_SMOOTH_BONES (a table per option, as above)
+    ('--fit-shape', dict(default=None, choices=('frame', 'track'), dest='fit_shape',
+                         help='--fit-smpl: frame = betas per sample (the default); track = after the loop, one beta vector per '
+                              'track with pose and translation per frame, warm-started from the per-sample fits (needs one rank)')),
+    ('--fit-gap', dict(default=None, type=int, metavar='FRAMES', dest='fit_gap',
+                       help='--fit-shape track: consecutive frames of a sequence further apart start a new track')),
+)
+
+
+def mirror_fit_shape_options(config, opt):
+    """--fit-shape and --fit-gap as model_params keys (only if given: the gap's default is xas_amd.ops_track's)."""
+    if opt.fit_shape == 'track' and not opt.fit_smpl:
+        raise ValueError('--fit-shape track is a mode of --fit-smpl: it needs --fit-smpl')
+    mirror_options(config, opt, given=('fit_shape', 'fit_gap'))
+
+
 CLI_CALIB = (  # --calibrate / --calibration and their settings, parsed after CLI_FIT (a table per option, as above)
     ('--calibrate', dict(default=None, metavar='OUT.npz', dest='calibrate',
                          help='after everything above: bundle adjustment of the camera extrinsics over the whole set, per rig, '
@@ -1134,7 +1203,7 @@ def mirror_smooth_bones_options(config, opt):
 
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES + CLI_FIT_SHAPE:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -1147,6 +1216,7 @@ def main():
     mirror_resolve_track_options(config, opt)
     mirror_smooth_anchor_options(config, opt)
     mirror_smooth_bones_options(config, opt)
+    mirror_fit_shape_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

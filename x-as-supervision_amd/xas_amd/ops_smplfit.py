@@ -67,7 +67,7 @@ def default_init(targets, weights, smpl_layer, h36m_regressor):
     return {'pose': pose.float(), 'betas': torch.zeros(B, 10, device=dev), 'trans': t.float()}
 
 
-def _prepare(targets, weights, smpl_layer, h36m_regressor, init):
+def _prepare(targets, weights, smpl_layer, h36m_regressor, init, workspace=True):
     if targets.dim() != 3 or tuple(targets.shape[1:]) != (18, 3) or tuple(weights.shape) != (targets.shape[0], 18):
         raise RuntimeError('smpl fit: targets must be [B,18,3] and weights [B,18], got %s and %s'
                            % (tuple(targets.shape), tuple(weights.shape)))
@@ -85,12 +85,85 @@ def _prepare(targets, weights, smpl_layer, h36m_regressor, init):
     if tuple(pose.shape) != (B, 72) or tuple(betas.shape) != (B, 10) or tuple(trans.shape) != (B, 3):
         raise RuntimeError('smpl fit: init needs pose [B,72], betas [B,10] and trans [B,3]')
     rverts, rcount = compact_regressor(reg)
-    nbytes = query('xas_smpl_fit_workspace_bytes', B, V)
-    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    ws = None
+    if workspace:                                      # xas_smpl_fit's own; the track solver sizes another
+        nbytes = query('xas_smpl_fit_workspace_bytes', B, V)
+        ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
     head = (ptr(pose), ptr(betas), ptr(trans), *(ptr(t) for t in bufs), ptr(parents), ptr(reg), ptr(rverts), ptr(rcount),
             ptr(targets), ptr(weights))
     keep = (pose, betas, trans, bufs, parents, reg, rverts, rcount, targets, weights)
     return head, keep, ws, B, V, center, dev
+
+
+TRACK_STATUS_CONVERGED, TRACK_STATUS_LIMIT, TRACK_STATUS_NO_FRAME = 0, 1, 2
+TRACK_STATUS_NAMES = ('converged', 'trial limit', 'no usable frame')
+
+
+def _prepare_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, init):
+    """_prepare plus the track table: tracks renumbered 0..S-1 in ascending order of their id (as ops_track.track_bone_lengths
+    numbers them).  The one host read is S, the number of distinct ids."""
+    head, keep, _, N, V, center, dev = _prepare(targets, weights, smpl_layer, h36m_regressor, init, workspace=False)
+    track = torch.as_tensor(track).to(device=dev, dtype=torch.int64).reshape(-1)
+    frame = torch.as_tensor(frame).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if track.numel() != N or frame.numel() != N:
+        raise RuntimeError('smpl fit tracks: track and frame must hold one entry per sample (%d), got %d and %d'
+                           % (N, track.numel(), frame.numel()))
+    ids, inv = torch.unique(track, return_inverse=True)
+    S = int(ids.numel())
+    inv = inv.to(torch.int32).contiguous()
+    nbytes = query('xas_smpl_fit_tracks_workspace_bytes', N, V, S)
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    return head + (ptr(inv), ptr(frame)), keep + (inv, frame), ws, N, V, S, center, dev, ids
+
+
+def linearise_smpl_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, init=None, lam=1e-3,
+                          pose_prior=POSE_PRIOR, shape_prior=SHAPE_PRIOR, workspace=None):
+    """One trial of fit_smpl_tracks at the damping `lam` from the start (xas_smpl_fit_tracks_linearise) -> dict: reduced
+    [S,10,10], rhs [S,10], d_y [N,75], d_beta [S,10], cost [S] (float64), track_ids [S] (row s belongs to this id)."""
+    head, keep, ws, N, V, S, center, dev, ids = _prepare_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, init)
+    ws = _given_workspace(workspace, ws)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'reduced': f64(S, 10, 10), 'rhs': f64(S, 10), 'd_y': f64(N, 75), 'd_beta': f64(S, 10), 'cost': f64(S), 'track_ids': ids}
+    call('xas_smpl_fit_tracks_linearise', *head, float(pose_prior), float(shape_prior), N, V, S, center, float(lam),
+         ptr(out['reduced']), ptr(out['rhs']), ptr(out['d_y']), ptr(out['d_beta']), ptr(out['cost']), ptr(ws))
+    return out
+
+
+def _given_workspace(workspace, ws):
+    if workspace is None:
+        return ws
+    if workspace.dtype != torch.uint8 or workspace.numel() < ws.numel() or workspace.device != ws.device:
+        raise RuntimeError('smpl fit tracks: the workspace must be %d bytes (uint8) on %s' % (ws.numel(), ws.device))
+    return workspace
+
+
+def tracks_workspace_bytes(N, V, S):
+    return query('xas_smpl_fit_tracks_workspace_bytes', int(N), int(V), int(S))
+
+
+def fit_smpl_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, init=None, iters=30, pose_prior=POSE_PRIOR,
+                    shape_prior=SHAPE_PRIOR, workspace=None):
+    """fit_smpl with one beta vector per track (xas_smpl_fit_tracks; the semantics are those of include/xas_hip.h).  targets
+    [N,18,3], weights [N,18]; track [N] any integer ids, frame [N] integers (ops_track.tracks_of), the samples in any order.
+    -> dict: pose [N,72], betas [N,10] (each row its track's; a frame passed through keeps its init betas), trans [N,3],
+    joints [N,18,3], cost [N,2], all float64; status [N] uint8 (STATUS_CONVERGED = fitted, STATUS_PASSED); track [N] int32
+    (0..S-1, ascending id), track_ids [S], track_betas [S,10], track_cost [S,2] float64, track_trials [S] int32, track_status
+    [S] uint8 (TRACK_STATUS_*).  workspace: None, or a uint8 tensor of tracks_workspace_bytes to use."""
+    head, keep, ws, N, V, S, center, dev, ids = _prepare_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, init)
+    ws = _given_workspace(workspace, ws)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'pose': f64(N, 72), 'trans': f64(N, 3), 'joints': f64(N, 18, 3), 'cost': f64(N, 2),
+           'status': torch.empty(N, device=dev, dtype=torch.uint8), 'track_betas': f64(S, 10), 'track_cost': f64(S, 2),
+           'track_trials': torch.empty(S, device=dev, dtype=torch.int32), 'track_status': torch.empty(S, device=dev, dtype=torch.uint8)}
+    call('xas_smpl_fit_tracks', *head, float(pose_prior), float(shape_prior), N, V, S, center, int(iters), ptr(out['pose']),
+         ptr(out['trans']), ptr(out['joints']), ptr(out['cost']), ptr(out['status']), ptr(out['track_betas']),
+         ptr(out['track_cost']), ptr(out['track_trials']), ptr(out['track_status']), ptr(ws))
+    inv, init_betas = keep[-2], keep[1]
+    rows = out['track_betas'][inv.long()] if S else f64(N, 10)
+    fitted = (out['status'] != STATUS_PASSED).unsqueeze(1)
+    out['betas'] = torch.where(fitted, rows, init_betas.double())
+    out['track'], out['track_ids'] = inv, ids
+    return out
 
 
 def linearise_smpl(targets, weights, smpl_layer, h36m_regressor, init, pose_prior=POSE_PRIOR, shape_prior=SHAPE_PRIOR):
