@@ -733,6 +733,60 @@ int xas_smpl_fit_tracks(const float* pose, const float* betas, const float* tran
                         double* track_betas, double* track_cost, int* track_trials, unsigned char* track_status, void* workspace,
                         void* stream);
 
+/* xas_smpl_fit_tracks with an ACCELERATION PRIOR on pose and translation over the frames of a track (eval.py --fit-smpl --fit-shape
+ * track --fit-smooth).  Arguments, usable frames, start, outputs and limits are xas_smpl_fit_tracks', plus rot_w, trans_w >= 0,
+ * finite.  With both 0 the problem is xas_smpl_fit_tracks' (solved by another elimination order: equal within rounding, not in bits).
+ * COST of track s, its usable frames in xas_smpl_fit_tracks' order i = 0 .. T-1 with frame numbers f_i:
+ *   C_s = sum_i c(y_i, beta_s) + sum_{i=1..T-2} ws_i sum_{c<75} w_c (cm_i y_i-1,c + c0_i y_i,c + cp_i y_i+1,c)^2
+ * c as above; (cm, c0, cp, ws) the smoothers' stencil on the frame numbers (csrc/track_stencil.h: cm = 1 / (f_i - f_i-1), cp =
+ * 1 / (f_i+1 - f_i), c0 = -(cm + cp), ws = 2 / (f_i+1 - f_i-1)); w_c = rot_w for the 72 angles (omega at 0..2, theta at 6..74),
+ * trans_w for t at 3..5.  The squared residuals enter H = J^T J, g = J^T r and C like every other row, so the weights are mm^2 per
+ * rad^2 (per mm^2) per frame^-3 against the joint rows' mm^2; the rows are linear, their Gauss-Newton block is exact.  A track
+ * with fewer than three usable frames has no prior.  The prior acts on parameters: a difference of axis-angle vectors is not a
+ * geodesic distance.
+ * EQUAL FRAME NUMBERS: when rot_w + trans_w > 0, a usable frame whose frame number equals that of the usable frame before it in the
+ * track's order is PASSED THROUGH (frame_status 2, its init): the stencil would divide by zero.
+ * UNWRAPPING: omega and omega + 2 pi k omega / |omega| are one rotation but far apart for the prior.  When rot_w > 0 the set-up
+ * replaces, in track order, the root omega of each usable frame i >= 1 by the equivalent vector nearest the previous, already
+ * unwrapped, frame's: k = nearbyint((u . omega_i-1 - |omega_i|) / (2 pi)), u = omega_i / |omega_i|; |omega_i| = 0 is left alone.
+ * Output `pose` holds the unwrapped vectors.  The body pose is NOT unwrapped: its prior keeps it near 0.
+ * SOLVER: one Levenberg-Marquardt per track with xas_smpl_fit's schedule (lambda, damping lambda diag(H) with H including the
+ * prior's diagonal, acceptance, stop and status rules), so track_cost[1] <= track_cost[0], always.  The damped system is block-
+ * pentadiagonal (75 x 75 blocks; the off-diagonal blocks are hoff times diag(w)) with a 10-row border and a 10 x 10 corner.  A
+ * trial: frame kernels on xas_smpl_fit_tracks' bounded grid assemble H_i, g_i after an accepted trial and evaluate the data cost
+ * at the trial point; ONE WORKGROUP PER TRACK runs the block Cholesky in frame order (L_ii, L_i,i-1, L_i,i-2, the border row
+ * L_beta,i filled from both predecessors, the corner last), both substitutions, the prior's cost at the trial point and the
+ * decision.  6 launches to start, 4 per trial, all enqueued up front; no atomics, no host synchronisation, every sum in one
+ * order: a pure function of the inputs bit for bit, per track, whatever the order of the samples in N and the workspace's contents.
+ * Outputs: xas_smpl_fit_tracks'.  frame_cost [N][2] holds the DATA cost c of the frame alone, track_cost [S][2] the whole C_s
+ * with the prior: the frame costs of a track no longer sum to its track cost.
+ * xas_smpl_fit_tracks_smooth_linearise: one trial at the given lambda >= 0 from the (unwrapped) start.  Per sample: hdiag [N][75][75]
+ * the damped diagonal block of the body; hoff [N][2] with H_i,i-1 = hoff[.][0] diag(w) and H_i,i-2 = hoff[.][1] diag(w) towards the
+ * one and two usable frames before it in the track; border [N][10][75]; g_y [N][75] the gradient, prior included; d_y [N][75] the
+ * trial step.  Per track: corner [S][10][10] summed and damped; g_beta [S][10]; d_beta [S][10]; track_cost [S] = C_s at the start.
+ * The system solved is (blocks) d = -(g_y, g_beta).  Zeros for a frame passed through and a track without usable frame; zeros for
+ * the steps at a pivot that is not positive.
+ * workspace: xas_smpl_fit_tracks_smooth_workspace_bytes(N, V, S) bytes, 16-byte aligned: xas_smpl_fit_tracks' (61 936 bytes per
+ * frame) plus 98 432 bytes per frame for the factor's block row (L_ii packed, L_i,i-1, L_i,i-2 packed, the border row, the
+ * forward-substituted vector, the prior's diagonal and the gradient): 160 368 bytes per frame, about 330 MB for 2048 frames. */
+size_t xas_smpl_fit_tracks_smooth_workspace_bytes(int N, int V, int S);
+int xas_smpl_fit_tracks_smooth_linearise(const float* pose, const float* betas, const float* trans, const float* v_template,
+                                         const float* shapedirs, const float* posedirs, const float* j_regressor,
+                                         const float* weights, const int* parents, const float* h36m_regressor,
+                                         const int* reg_verts, const int* reg_count, const float* targets, const float* joint_w,
+                                         const int* track, const int* frame, float pose_prior, float shape_prior, double rot_w,
+                                         double trans_w, int N, int V, int S, int center_idx, double lambda, double* hdiag,
+                                         double* hoff, double* corner, double* border, double* g_y, double* g_beta, double* d_y,
+                                         double* d_beta, double* track_cost, void* workspace, void* stream);
+int xas_smpl_fit_tracks_smooth(const float* pose, const float* betas, const float* trans, const float* v_template,
+                               const float* shapedirs, const float* posedirs, const float* j_regressor, const float* weights,
+                               const int* parents, const float* h36m_regressor, const int* reg_verts, const int* reg_count,
+                               const float* targets, const float* joint_w, const int* track, const int* frame, float pose_prior,
+                               float shape_prior, double rot_w, double trans_w, int N, int V, int S, int center_idx,
+                               int max_iters, double* pose_out, double* trans_out, double* joints_out, double* frame_cost,
+                               unsigned char* frame_status, double* track_betas, double* track_cost, int* track_trials,
+                               unsigned char* track_status, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Fused multi-tensor Adam (train.py:257-264: betas (0.5, 0.999), eps 1e-8, no decay).
  * One launch updates a flat parameter arena: p, g, m, v are arenas of n floats.

@@ -12,6 +12,7 @@
              [--smooth OUT.npz --smooth-acc W --smooth-gap FRAMES --smooth-iters N]
              [--resolve-track OUT.npz --rt-vel W --rt-hyp W --rt-swap W --rt-gap FRAMES]
              [--smooth-data reproj|anchor --smooth-depth W --smooth-anchor-huber D]
+             [--fit-shape frame|track --fit-gap FRAMES --fit-smooth [W_ROT] --fit-smooth-trans W]
 
 One evaluation batch = the detector in eval mode on every camera, then ON THE DEVICE: left/right switch +
 hypothesis selection + 2-D error (one launch per camera), patch->world of every view, DLT triangulation of all
@@ -70,7 +71,15 @@ set: tracks from tracks_of(paths, --fit-gap), ONE beta vector per track, pose an
 per-sample fits.  In OUT.npz `pose`, `betas` (each row its track's), `trans`, `cost`, `status` and `joint_rms_mm` then come from
 the track fit, and `betas_per_frame`, `track`, `frame`, `track_betas`, `track_status`, `track_trials` join; the FIT line gains
 the number of tracks and their mean length, joint RMS per frame -> per track and the mean within-track standard deviation of
-the per-frame betas.  There is no temporal prior on the pose.
+the per-frame betas.  There is no temporal prior on the pose unless --fit-smooth asks for one.
+
+--fit-smooth [W_ROT] and --fit-smooth-trans W (opt-in with --fit-shape track; model_params.fit_smooth, fit_smooth_trans; without
+them exactly the calls above) make that one call fit_smpl_tracks_smooth: the same problem plus an acceleration prior on the 72
+angles (W_ROT, mm^2 per rad^2) and the translation (W) over the frames of a track, the root vectors unwrapped along it.
+OUT.npz gains `fit_smooth` [2] (the weights) and `joint_accel_mm` [N,3] (the norm of the second difference of the fitted joints
+over the frames, mean over the joints: of the per-frame fits, NaN (no unsmoothed track fit is run), of the result; NaN at a
+track's ends and at frames passed through); the FIT line ends with its mean before and after and the joint RMS before and after.
+Both weights are untuned guesses.
 
 --calibrate OUT.npz (opt-in; model_params.calibrate; 2+ cameras, one rank) keeps every batch's triangulation inputs, final
 points and the views they used on the device and, after the loop, runs one bundle adjustment of the camera extrinsics per rig
@@ -287,8 +296,18 @@ class Eval:
                 from xas_amd import ops_track
                 self.fit_gap = int(mp.get('fit_gap', ops_track.TRACK_MAX_GAP))
                 self.fit_track_rows = []               # per batch, on the device: targets, weights, usable joints, first-camera paths
+            # --fit-smooth: an acceleration prior on pose and translation over the frames of a track (None = off: today's calls)
+            self.fit_smooth = None
+            if mp.get('fit_smooth') is not None or mp.get('fit_smooth_trans') is not None:
+                if self.fit_shape != 'track':
+                    raise ValueError('fit_smooth is a mode of --fit-shape track: it needs fit_shape track (model_params.fit_shape)')
+                rot = ops_smplfit.FIT_SMOOTH_ROT if mp.get('fit_smooth') is None else float(mp['fit_smooth'])
+                trans = ops_smplfit.FIT_SMOOTH_TRANS if mp.get('fit_smooth_trans') is None else float(mp['fit_smooth_trans'])
+                self.fit_smooth = (rot, trans)
         elif (mp.get('fit_shape') or 'frame') != 'frame':
             raise ValueError('fit_shape track is a mode of --fit-smpl: it needs fit_smpl (model_params.fit_smpl)')
+        elif mp.get('fit_smooth') is not None or mp.get('fit_smooth_trans') is not None:
+            raise ValueError('fit_smooth is a mode of --fit-shape track: it needs fit_smpl (model_params.fit_smpl)')
         self.calibrate = mp.get('calibrate') or None   # --calibrate OUT.npz: bundle adjustment of the extrinsics over the whole set
         self.calibration = mp.get('calibration') or None   # --calibration IN.npz: every batch's cameras corrected by such a file
         if self.calibrate and self.calibration:
@@ -575,6 +594,8 @@ class Eval:
         rms = (d2.sum(dim=1) / ok.double().sum(dim=1).clamp(min=1.0)).sqrt()
         if self.fit_shape == 'track':                  # the per-sample fit is the warm start of write_fit_tracks
             self.fit_track_rows.append({'targets': joints, 'weights': w, 'ok': ok, 'paths': None if paths is None else [str(p) for p in paths]})
+            if self.fit_smooth:                        # the per-frame fits' joints: the `before` column of joint_accel_mm
+                self.fit_track_rows[-1]['joints'] = r['joints']
         return {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
                 'fit_cost': r['cost'].float(), 'fit_status': r['status'], 'fit_joint_rms_mm': rms.float()}
 
@@ -594,12 +615,18 @@ class Eval:
         dev, N = targets.device, targets.shape[0]
         track, frame = ops_track.tracks_of(paths, self.fit_gap, count=N)
         S = len(np.unique(track))
-        nbytes = ops_smplfit.tracks_workspace_bytes(N, self.smpl_layer.th_v_template.shape[-2], S)
+        sizer = ops_smplfit.tracks_smooth_workspace_bytes if self.fit_smooth else ops_smplfit.tracks_workspace_bytes
+        nbytes = sizer(N, self.smpl_layer.th_v_template.shape[-2], S)
         if nbytes > self.FIT_TRACKS_WORKSPACE_WARN:
             print('FIT tracks: the solver keeps its factor per frame, a workspace of {:.1f} GiB for {} frames'.format(nbytes / 2.0 ** 30, N), flush=True)
         init = {k: torch.as_tensor(cols[k], device=dev) for k in ('pose', 'betas', 'trans')}
-        r = ops_smplfit.fit_smpl_tracks(targets, weights, track, frame, self.smpl_layer, self.h36m_regressor, init=init,
-                                        iters=self.fit_iters, pose_prior=self.fit_pose_prior, shape_prior=self.fit_shape_prior)
+        if self.fit_smooth:
+            r = ops_smplfit.fit_smpl_tracks_smooth(targets, weights, track, frame, self.smpl_layer, self.h36m_regressor, init=init,
+                                                   iters=self.fit_iters, rot_w=self.fit_smooth[0], trans_w=self.fit_smooth[1],
+                                                   pose_prior=self.fit_pose_prior, shape_prior=self.fit_shape_prior)
+        else:
+            r = ops_smplfit.fit_smpl_tracks(targets, weights, track, frame, self.smpl_layer, self.h36m_regressor, init=init,
+                                            iters=self.fit_iters, pose_prior=self.fit_pose_prior, shape_prior=self.fit_shape_prior)
         d2 = ((r['joints'] - torch.where(ok.unsqueeze(-1), targets.double(), r['joints'])) ** 2).sum(dim=-1)
         rms = (d2.sum(dim=1) / ok.double().sum(dim=1).clamp(min=1.0)).sqrt()
         per_frame, rms_frame = cols['betas'], cols['joint_rms_mm']
@@ -611,8 +638,19 @@ class Eval:
                     track_trials=r['track_trials'].cpu().numpy())
         spread = [per_frame[(cols['track'] == s) & fitted].std(axis=0).mean() for s in range(S) if ((cols['track'] == s) & fitted).any()]
         mean = lambda v: float(np.mean(v)) if len(v) else float('nan')
+        if self.fit_smooth:
+            before = cat_rows(self.fit_track_rows, 'joints').cpu().numpy()
+            accel = np.stack([joint_accel_mm(before, cols['track'], cols['frame'], fitted), np.full(N, np.nan),
+                              joint_accel_mm(r['joints'].cpu().numpy(), cols['track'], cols['frame'], fitted)], axis=1)
+            cols.update(fit_smooth=np.asarray(self.fit_smooth, np.float64), joint_accel_mm=accel.astype(np.float32))
+            nanmean = lambda v: float(np.nanmean(v)) if np.isfinite(v).any() else float('nan')
+            smooth = ', smoothed over frames (weights {} {}): joint acceleration {} -> {} mm / frame^2, joint RMS {} -> {} mm'.format(
+                self.fit_smooth[0], self.fit_smooth[1], nanmean(accel[:, 0]), nanmean(accel[:, 2]), mean(rms_frame[fitted]),
+                mean(cols['joint_rms_mm'][fitted]))
+        else:
+            smooth = ''
         return ', shape per track: {} tracks of mean length {} (gap {}), joint RMS per frame {} -> per track {} mm, within-track std of the per-frame betas {}'.format(
-            S, N / max(S, 1), self.fit_gap, mean(rms_frame[fitted]), mean(cols['joint_rms_mm'][fitted]), mean(spread))
+            S, N / max(S, 1), self.fit_gap, mean(rms_frame[fitted]), mean(cols['joint_rms_mm'][fitted]), mean(spread)) + smooth
 
     def write_fit(self):
         """Writes the --fit-smpl file; passed-through samples are kept with their status.  -> the line of eval_result.txt."""
@@ -1104,6 +1142,40 @@ def mirror_fit_shape_options(config, opt):
     mirror_options(config, opt, given=('fit_shape', 'fit_gap'))
 
 
+CLI_FIT_SMOOTH = (  # --fit-smooth and its translation weight, parsed after CLI_FIT_SHAPE (a table per option, as above)
+    ('--fit-smooth', dict(default=None, nargs='?', const=True, type=float, metavar='W_ROT', dest='fit_smooth',
+                          help='--fit-shape track: an acceleration prior on pose and translation over the frames of a track; W_ROT '
+                               'weighs the 72 angles (mm^2 per rad^2; default xas_amd.ops_smplfit.FIT_SMOOTH_ROT)')),
+    ('--fit-smooth-trans', dict(default=None, type=float, metavar='W', dest='fit_smooth_trans',
+                                help='--fit-smooth: the weight of the translation (default xas_amd.ops_smplfit.FIT_SMOOTH_TRANS)')),
+)
+
+
+def mirror_fit_smooth_options(config, opt):
+    """--fit-smooth and --fit-smooth-trans as model_params keys (only if given; the bare flag takes the default weight)."""
+    if (opt.fit_smooth is not None or opt.fit_smooth_trans is not None) and opt.fit_shape != 'track':
+        raise ValueError('--fit-smooth is a mode of --fit-shape track: it needs --fit-shape track')
+    if opt.fit_smooth is True:
+        from xas_amd import ops_smplfit              # only with the flag
+        opt.fit_smooth = ops_smplfit.FIT_SMOOTH_ROT
+    mirror_options(config, opt, given=('fit_smooth', 'fit_smooth_trans'))
+
+
+def joint_accel_mm(joints, track, frame, fitted):
+    """--fit-smooth: per sample the norm of the acceleration stencil's second difference of joints [N,18,3] over the fitted
+    frames of its track in frame order, mean over the 18 joints; NaN at a track's ends and at frames passed through."""
+    out = np.full(len(track), np.nan)
+    for s in np.unique(track):
+        rows = np.nonzero((track == s) & fitted)[0]
+        rows = rows[np.argsort(frame[rows], kind='stable')]
+        f = frame[rows].astype(np.float64)
+        for k in range(1, len(rows) - 1):
+            h0, h1 = f[k] - f[k - 1], f[k + 1] - f[k]
+            q = joints[rows[k - 1]] / h0 - joints[rows[k]] * (1.0 / h0 + 1.0 / h1) + joints[rows[k + 1]] / h1
+            out[rows[k]] = np.linalg.norm(q, axis=-1).mean()
+    return out
+
+
 CLI_CALIB = (  # --calibrate / --calibration and their settings, parsed after CLI_FIT (a table per option, as above)
     ('--calibrate', dict(default=None, metavar='OUT.npz', dest='calibrate',
                          help='after everything above: bundle adjustment of the camera extrinsics over the whole set, per rig, '
@@ -1203,7 +1275,7 @@ def mirror_smooth_bones_options(config, opt):
 
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES + CLI_FIT_SHAPE:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES + CLI_FIT_SHAPE + CLI_FIT_SMOOTH:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -1217,6 +1289,7 @@ def main():
     mirror_smooth_anchor_options(config, opt)
     mirror_smooth_bones_options(config, opt)
     mirror_fit_shape_options(config, opt)
+    mirror_fit_smooth_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

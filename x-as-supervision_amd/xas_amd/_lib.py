@@ -158,6 +158,9 @@ SIGNATURES = {
     'xas_smpl_fit_tracks_workspace_bytes': ('iii', 'z'),
     'xas_smpl_fit_tracks_linearise': ('p' * 16 + 'ff' + 'iiii' + 'd' + 'ppppp' + 'pp', 'i'),
     'xas_smpl_fit_tracks': ('p' * 16 + 'ff' + 'iiiii' + 'p' * 9 + 'pp', 'i'),
+    'xas_smpl_fit_tracks_smooth_workspace_bytes': ('iii', 'z'),
+    'xas_smpl_fit_tracks_smooth_linearise': ('p' * 16 + 'ff' + 'dd' + 'iiii' + 'd' + 'p' * 9 + 'pp', 'i'),
+    'xas_smpl_fit_tracks_smooth': ('p' * 16 + 'ff' + 'dd' + 'iiiii' + 'p' * 9 + 'pp', 'i'),
     'xas_adam_step': ('pppplffffip', 'i'),
     'xas_grad_guard_workspace_bytes': ('l', 'z'),
     'xas_grad_guard': ('plfifffppp', 'i'),

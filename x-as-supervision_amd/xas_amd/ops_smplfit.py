@@ -166,6 +166,67 @@ def fit_smpl_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, 
     return out
 
 
+# Weights of the acceleration prior of fit_smpl_tracks_smooth on the 72 angles (mm^2 per rad^2) and on the translation: a second
+# difference of 0.01 rad, or of 1 mm, per frame^2 weighs like 1 mm of joint error.  UNTUNED GUESSES, as the priors above.
+FIT_SMOOTH_ROT = 1e4
+FIT_SMOOTH_TRANS = 1.0
+
+
+def _prepare_tracks_smooth(targets, weights, track, frame, smpl_layer, h36m_regressor, init, workspace):
+    head, keep, _, N, V, S, center, dev, ids = _prepare_tracks(targets, weights, track, frame, smpl_layer, h36m_regressor, init)
+    ws = torch.empty(max(tracks_smooth_workspace_bytes(N, V, S), 16), device=dev, dtype=torch.uint8) if workspace is None else None
+    if ws is None:
+        need = tracks_smooth_workspace_bytes(N, V, S)
+        if workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev:
+            raise RuntimeError('smpl fit tracks: the workspace must be %d bytes (uint8) on %s' % (need, dev))
+        ws = workspace
+    return head, keep, ws, N, V, S, center, dev, ids
+
+
+def tracks_smooth_workspace_bytes(N, V, S):
+    return query('xas_smpl_fit_tracks_smooth_workspace_bytes', int(N), int(V), int(S))
+
+
+def linearise_smpl_tracks_smooth(targets, weights, track, frame, smpl_layer, h36m_regressor, init=None, lam=1e-3,
+                                 rot_w=FIT_SMOOTH_ROT, trans_w=FIT_SMOOTH_TRANS, pose_prior=POSE_PRIOR, shape_prior=SHAPE_PRIOR,
+                                 workspace=None):
+    """One trial of fit_smpl_tracks_smooth at the damping `lam` from the start (xas_smpl_fit_tracks_smooth_linearise) -> dict:
+    hdiag [N,75,75], hoff [N,2], border [N,10,75], corner [S,10,10], g_y [N,75], g_beta [S,10], d_y [N,75], d_beta [S,10],
+    cost [S] (float64), track_ids [S]."""
+    head, keep, ws, N, V, S, center, dev, ids = _prepare_tracks_smooth(targets, weights, track, frame, smpl_layer, h36m_regressor,
+                                                                         init, workspace)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'hdiag': f64(N, 75, 75), 'hoff': f64(N, 2), 'corner': f64(S, 10, 10), 'border': f64(N, 10, 75), 'g_y': f64(N, 75),
+           'g_beta': f64(S, 10), 'd_y': f64(N, 75), 'd_beta': f64(S, 10), 'cost': f64(S), 'track_ids': ids}
+    call('xas_smpl_fit_tracks_smooth_linearise', *head, float(pose_prior), float(shape_prior), float(rot_w), float(trans_w), N, V, S,
+         center, float(lam), *(ptr(out[k]) for k in ('hdiag', 'hoff', 'corner', 'border', 'g_y', 'g_beta', 'd_y', 'd_beta', 'cost')),
+         ptr(ws))
+    return out
+
+
+def fit_smpl_tracks_smooth(targets, weights, track, frame, smpl_layer, h36m_regressor, init=None, iters=30, rot_w=FIT_SMOOTH_ROT,
+                           trans_w=FIT_SMOOTH_TRANS, pose_prior=POSE_PRIOR, shape_prior=SHAPE_PRIOR, workspace=None):
+    """fit_smpl_tracks with an acceleration prior on pose and translation over the frames of a track (xas_smpl_fit_tracks_smooth;
+    include/xas_hip.h).  The same dict as fit_smpl_tracks; `cost` [N,2] holds the data cost of a frame alone, `track_cost` the
+    whole cost with the prior, and `pose` the root vectors unwrapped along the track.  A usable frame that repeats the frame
+    number of the one before it in its track is passed through.  workspace: None, or tracks_smooth_workspace_bytes of uint8."""
+    head, keep, ws, N, V, S, center, dev, ids = _prepare_tracks_smooth(targets, weights, track, frame, smpl_layer, h36m_regressor,
+                                                                         init, workspace)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'pose': f64(N, 72), 'trans': f64(N, 3), 'joints': f64(N, 18, 3), 'cost': f64(N, 2),
+           'status': torch.empty(N, device=dev, dtype=torch.uint8), 'track_betas': f64(S, 10), 'track_cost': f64(S, 2),
+           'track_trials': torch.empty(S, device=dev, dtype=torch.int32), 'track_status': torch.empty(S, device=dev, dtype=torch.uint8)}
+    call('xas_smpl_fit_tracks_smooth', *head, float(pose_prior), float(shape_prior), float(rot_w), float(trans_w), N, V, S, center,
+         int(iters), ptr(out['pose']), ptr(out['trans']), ptr(out['joints']), ptr(out['cost']), ptr(out['status']),
+         ptr(out['track_betas']), ptr(out['track_cost']), ptr(out['track_trials']), ptr(out['track_status']), ptr(ws))
+    inv, init_betas = keep[-2], keep[1]
+    rows = out['track_betas'][inv.long()] if S else f64(N, 10)
+    fitted = (out['status'] != STATUS_PASSED).unsqueeze(1)
+    out['betas'] = torch.where(fitted, rows, init_betas.double())
+    out['track'], out['track_ids'] = inv, ids
+    return out
+
+
 def linearise_smpl(targets, weights, smpl_layer, h36m_regressor, init, pose_prior=POSE_PRIOR, shape_prior=SHAPE_PRIOR):
     """Residual r [B,133] and Jacobian J [B,133,85] (float64) at the parameters `init` (xas_smpl_fit_linearise); the unknowns
     are ordered omega 3, t 3, body pose 69, betas 10."""
