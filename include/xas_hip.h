@@ -683,6 +683,52 @@ int xas_smpl_fit(const float* pose, const float* betas, const float* trans, cons
                  double* pose_out, double* betas_out, double* trans_out, double* joints_out, double* cost, int* iters,
                  unsigned char* status, void* workspace, void* stream);
 
+/* xas_smpl_fit with the DATA TERM IN PIXELS, per camera (eval.py --fit-smpl --fit-data reproj; the reference has no counterpart).
+ * The model, the unknowns x [85], the init (pose, betas, trans), the model arrays, parents, h36m_regressor, reg_verts, reg_count,
+ * center_idx and the priors mean what they mean for xas_smpl_fit; there are no targets and no joint weights.  Instead a model
+ * joint Y_k(x) is held to what was measured:
+ *   points [B][C][18][3] fp32 = (u, v, weight) and P [B][C][3][4] fp32, xas_triangulate_refine's layout and meaning, 1 <= C <=
+ *   XAS_TRI_MAX_VIEWS; views [B][18] bytes or NULL; flags = 0 or XAS_REFINE_WEIGHTED; huber >= 0 finite (0 = squared);
+ *   anchor [B][18][3] fp32 mm and info [B][18][6] fp32 (xx xy xz yy yz zz), xas_track_anchor_smooth's, both NULL or both given;
+ *   anchor_huber >= 0 finite.
+ * WHICH OBSERVATIONS COUNT is decided once, at the init, and fixed for the whole fit.  View v counts for joint k if its weight
+ * is VALID (finite, > 0), it is in the joint's `views` byte (a zero byte, or views = NULL, stands for all valid views), u and v
+ * are finite and Y_k(init) lies in front of it (h_2 <= 0 is behind, as everywhere); a view behind the start is dropped for that
+ * joint.  An anchor counts if it is USABLE by xas_track_anchor_smooth's rule.  A joint is USED if it has at least one view or
+ * an anchor; a joint that is not used never reads its pixels, anchor or information into arithmetic (NaN there is legal).
+ * used [B][18] bytes, written by every call: the mask of the joint's views | 0x80 if it has an anchor.
+ * COST C(x), in px^2 (sigma^2 under XAS_REFINE_WEIGHTED), in double from the fp32 inputs: for the joints k ascending, at Y_k(x),
+ * xas_triangulate_refine's term over the joint's views ascending (the same scale rule, the same Huber loss) and then
+ * xas_track_anchor_smooth's anchor term (Huber anchor_huber of sqrt(max(e^T W e, 0))); then pose_prior theta_i^2, i ascending,
+ * and shape_prior beta_i^2, as xas_smpl_fit sums them.  Per joint the data reduce to a cost c_k, a 3x3 Gauss-Newton block A_k
+ * (the IRLS blocks w (ju ju^T + jv jv^T) of the views plus psi W of the anchor) and a gradient b_k; with Jy_k = dY_k / dx:
+ *   H = sum_k Jy_k^T A_k Jy_k + priors,   g = sum_k Jy_k^T b_k + priors   (k ascending; the priors as xas_smpl_fit's).
+ * xas_smpl_fit_views_linearise, at the init: H [B][85][85] full and symmetric in bits, undamped, priors in; g [B][85]; cost [B];
+ * joint_blocks [B][18][9] = A_k (xx xy xz yy yz zz) and b_k, zero for a joint not used; used.  No sample is passed through here.
+ * xas_smpl_fit_views: xas_smpl_fit's Levenberg-Marquardt rule for rule (lambda = 1e-3, damping lambda diag(H), x10 / x0.1,
+ * XAS_SMPLFIT_STEP_TOL, lambda > 1e12, 0 <= max_iters <= XAS_SMPLFIT_MAX_ITERS, the status codes, cost[1] <= cost[0]), with one
+ * addition: a trial that puts a used joint behind one of its views is rejected.  PASSED THROUGH by xas_smpl_fit's rule: fewer
+ * than 6 joints used, or a cost at the init that is not finite; the outputs then follow xas_smpl_fit's pass-through contract.
+ * Outputs: xas_smpl_fit's (pose, betas, trans, joints, cost [B][2], iters, status), and used.
+ * workspace: xas_smpl_fit_views_workspace_bytes(B, V) bytes, 16-byte aligned (xas_smpl_fit's layout; the joint blocks live in
+ * LDS).  B == 0 writes nothing.  One workgroup of 256 threads per sample and the whole LM in one launch, plus the joint-term
+ * launch; no atomics, no host synchronisation: a pure function of the inputs bit for bit, per sample, whatever the workspace held. */
+size_t xas_smpl_fit_views_workspace_bytes(int B, int V);
+int xas_smpl_fit_views_linearise(const float* pose, const float* betas, const float* trans, const float* v_template,
+                                 const float* shapedirs, const float* posedirs, const float* j_regressor, const float* weights,
+                                 const int* parents, const float* h36m_regressor, const int* reg_verts, const int* reg_count,
+                                 const float* points, const float* P, const unsigned char* views, const float* anchor,
+                                 const float* info, int flags, double huber, double anchor_huber, float pose_prior,
+                                 float shape_prior, int B, int V, int C, int center_idx, double* H, double* g, double* cost,
+                                 double* joint_blocks, unsigned char* used, void* workspace, void* stream);
+int xas_smpl_fit_views(const float* pose, const float* betas, const float* trans, const float* v_template, const float* shapedirs,
+                       const float* posedirs, const float* j_regressor, const float* weights, const int* parents,
+                       const float* h36m_regressor, const int* reg_verts, const int* reg_count, const float* points,
+                       const float* P, const unsigned char* views, const float* anchor, const float* info, int flags,
+                       double huber, double anchor_huber, float pose_prior, float shape_prior, int B, int V, int C,
+                       int center_idx, int max_iters, double* pose_out, double* betas_out, double* trans_out, double* joints_out,
+                       double* cost, int* iters, unsigned char* status, unsigned char* used, void* workspace, void* stream);
+
 /* xas_smpl_fit over whole tracks (eval.py --fit-smpl --fit-shape track): ONE beta vector per track, pose and translation per
  * frame.  The model arrays, targets, weights, priors and the init (pose, betas, trans: [N][72], [N][10], [N][3]) mean what they
  * mean above.  track [N] int32 in [0, S) and frame [N] int32 (device) say which track a sample belongs to and where it stands

@@ -1,4 +1,4 @@
-// What xas_smpl_fit (smplfit.hip) and xas_smpl_fit_tracks (smplfit_tracks.hip) share: the dual numbers, the two rotation maps,
+// What xas_smpl_fit (smplfit.hip), xas_smpl_fit_tracks (smplfit_tracks.hip) and xas_smpl_fit_views (smplfit_views.hip) share: the dual numbers, the two rotation maps,
 // the staging of a sample, the evaluation of a point with its vertex cache, the tangents, the assembly of H and g, the dense
 // solve, the joint-term launch and the argument checks.  smplfit.hip states how a point is evaluated and linearised.
 #pragma once
@@ -154,7 +154,7 @@ struct FitArgs {
   const int* parents;                                   // [24]
   const float* hreg;                                    // [17][V]
   const int *rverts, *rcount;                           // compacted vertex list [V] and its length (device), or both NULL = all
-  const float *tgt, *jw;                                // [B][18][3], [B][18]
+  const float *tgt, *jw;                                // [B][18][3], [B][18]; both NULL = weight 1 against a zero target
   double wp, wsh;
   int V, center;
   const double* jpre;                                   // j_regressor . v_template [24][3], j_regressor . shapedirs [24][3][10]
@@ -567,10 +567,10 @@ __device__ int fit_stage(FitShared& s, const FitArgs& a, int b) {
   }
   if (tid >= 128 && tid < 128 + 18) {
     const int k = tid - 128;
-    const float w = a.jw[(size_t)b * 18 + k];
-    const bool on = w > 0.f;                            // NaN and negative weights count as 0
+    const float w = a.jw ? a.jw[(size_t)b * 18 + k] : 1.f;   // no weights (smplfit_views.hip): s.sw = 1 and s.tgt = 0, so that
+    const bool on = w > 0.f;                            // s.r54 and s.m.J hold Y and dY/dx.  NaN and negative weights count as 0
     s.sw[k] = on ? sqrt((double)w) : 0.0;
-    for (int c = 0; c < 3; ++c) s.tgt[k * 3 + c] = on ? (double)a.tgt[((size_t)b * 18 + k) * 3 + c] : 0.0;
+    for (int c = 0; c < 3; ++c) s.tgt[k * 3 + c] = on && a.tgt ? (double)a.tgt[((size_t)b * 18 + k) * 3 + c] : 0.0;
   }
   if (tid >= 192 && tid < 192 + kJ) {
     const int i = tid - 192, p = a.parents[i];
@@ -609,10 +609,12 @@ size_t fit_sample_doubles(int V) { return (size_t)kT * kJ * 12 + (size_t)kCache 
 
 int fit_check(const char* who, const float* pose, const float* betas, const float* trans, const float* vt, const float* sd,
               const float* pd, const float* jreg, const float* skin, const int* parents, const float* hreg, const int* rverts,
-              const int* rcount, const float* tgt, const float* jw, float wp, float wsh, int B, int V, int center, void* ws) {
+              const int* rcount, const float* tgt, const float* jw, float wp, float wsh, int B, int V, int center, void* ws,
+              bool data = true) {                       // data = false: an entry point without targets and weights
   XAS_REQUIRE(B >= 0 && V >= 1, "%s: bad shape B=%d V=%d (B >= 0, V >= 1)", who, B, V);
-  XAS_REQUIRE(B == 0 || (pose && betas && trans && vt && sd && pd && jreg && skin && parents && hreg && tgt && jw && ws),
-              "%s: null buffer (parameters, the SMPL arrays, parents, the regressor, targets, weights and workspace are required)", who);
+  XAS_REQUIRE(B == 0 || (pose && betas && trans && vt && sd && pd && jreg && skin && parents && hreg && (!data || (tgt && jw)) && ws),
+              "%s: null buffer (parameters, the SMPL arrays, parents, the regressor%s and workspace are required)", who,
+              data ? ", targets, weights" : "");
   XAS_REQUIRE((rverts == nullptr) == (rcount == nullptr), "%s: the vertex list and its length come together (or both NULL)", who);
   XAS_REQUIRE(center >= -1 && center < kJ, "%s: center_idx=%d (needs -1 = none, or a joint < 24)", who, center);
   XAS_REQUIRE(wp >= 0.f && wp < INFINITY && wsh >= 0.f && wsh < INFINITY, "%s: priors %f, %f (need finite weights >= 0)", who,

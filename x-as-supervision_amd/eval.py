@@ -81,6 +81,17 @@ over the frames, mean over the joints: of the per-frame fits, NaN (no unsmoothed
 track's ends and at frames passed through); the FIT line ends with its mean before and after and the joint RMS before and after.
 Both weights are untuned guesses.
 
+--fit-data reproj (opt-in with --fit-smpl; model_params.fit_data; default joints = exactly the calls above, nothing new
+imported; not with --fit-shape track, not with --flip) fits the body to the DETECTIONS: per batch the joint fit runs as before
+and is the warm start, then xas_amd.ops_smplfit.fit_smpl_views holds every model joint to the pixels of the cameras that see it
+(the batch's triangulation inputs; --tri-weight spread scales the residuals, --tri-huber is Huber's delta, the robust inliers
+are the views) and to a 3-D anchor: with one camera the selected world point with information --smooth-depth along its ray,
+with more none unless --tri-volume ran (the fused point with the inverse of its covariance).  --fit-pose-prior and
+--fit-shape-prior, when given, apply to both fits; otherwise each has its own defaults.  OUT.npz stays a bank: `pose`, `betas`,
+`trans`, `cost` (px^2), `status` and `joint_rms_mm` come from the pixel fit; `fit_data`, `reproj_rms_px` [N,2] (at the warm
+start and at the result, over the observations used) and the warm start `pose_joints`, `betas_joints`, `trans_joints` join; the
+FIT line names the mode and the reprojection RMS before -> after.  Unknown: whether it helps on real detections, and every weight.
+
 --calibrate OUT.npz (opt-in; model_params.calibrate; 2+ cameras, one rank) keeps every batch's triangulation inputs, final
 points and the views they used on the device and, after the loop, runs one bundle adjustment of the camera extrinsics per rig
 (xas_amd.ops_calib.calibrate_bundle).  OUT.npz holds the rigs' projection matrices (`keys`) and their corrections (`delta`:
@@ -217,6 +228,12 @@ def masked_mean(errors, mask):
     return float(errors[mask].mean()) if bool(mask.any()) else float('nan')
 
 
+def full_covariance(c):
+    """[...,6] (xx xy xz yy yz zz, as the solvers write a covariance) -> [...,3,3]."""
+    return torch.stack([c[..., 0], c[..., 1], c[..., 2], c[..., 1], c[..., 3], c[..., 4], c[..., 2], c[..., 4], c[..., 5]],
+                       dim=-1).reshape(c.shape[:-1] + (3, 3))
+
+
 def homogeneous(point):
     """[...,3+] -> [...,4]: the first three coordinates and a one, the form the solvers take their start in."""
     return torch.cat([point[..., :3], torch.ones_like(point[..., :1])], dim=-1).contiguous()
@@ -279,6 +296,18 @@ class Eval:
         self.logits = None                         # volume only: the logits [B,K*D,D,D] of the latest detect()
         self.fit_smpl = mp.get('fit_smpl') or None     # --fit-smpl OUT.npz: SMPL parameters of the final world joints, a --pseudo-online bank
         if self.fit_smpl:
+            # --fit-data reproj: after the joint fit, the pixel fit from it (joints = today's calls, nothing new imported)
+            self.fit_data = mp.get('fit_data') or 'joints'
+            if self.fit_data not in ('joints', 'reproj'):
+                raise ValueError('fit_data is joints or reproj, got {!r}'.format(self.fit_data))
+            if self.fit_data == 'reproj':
+                if (mp.get('fit_shape') or 'frame') == 'track':
+                    raise ValueError('fit_data reproj fits every sample to its own detections; the track fits have no pixel term yet: '
+                                     '--fit-data reproj does not go with --fit-shape track')
+                if flip_test:
+                    raise ValueError('fit_data reproj reads the detections of the views as they were selected; with the flip test '
+                                     'that pairing is not wired up yet: --fit-data reproj does not go with --flip')
+                check_cameras(cam_id_list, 'fit_data reproj fits 1 to {} cameras; cam_id_list has {}', least=1)
             smpl = prepare_smpl(mp)                  # (Eval's signature is pinned: the model comes through model_params.smpl_model)
             if smpl[0] is None or smpl[1] is None:
                 raise ValueError('fit_smpl needs an SMPL layer and the H36M joint regressor (eval.py --smpl-model)')
@@ -288,6 +317,11 @@ class Eval:
             self.fit_pose_prior = float(mp.get('fit_pose_prior', ops_smplfit.POSE_PRIOR))      # untuned guesses, both
             self.fit_shape_prior = float(mp.get('fit_shape_prior', ops_smplfit.SHAPE_PRIOR))
             self.fit_rows = []                         # per batch: the host arrays of the file
+            if self.fit_data == 'reproj':
+                from xas_amd import ops_track          # only with the flag
+                self.fit_views_priors = (float(mp.get('fit_pose_prior', ops_smplfit.VIEWS_POSE_PRIOR)),      # untuned guesses, both
+                                         float(mp.get('fit_shape_prior', ops_smplfit.VIEWS_SHAPE_PRIOR)))
+                self.fit_depth = float(mp.get('smooth_depth', ops_track.TRACK_DEPTH_W))
             self.fit_shape = mp.get('fit_shape') or 'frame'    # --fit-shape track: one beta vector per track, after the loop
             if self.fit_shape not in ('frame', 'track'):
                 raise ValueError('fit_shape is frame or track, got {!r}'.format(self.fit_shape))
@@ -304,6 +338,8 @@ class Eval:
                 rot = ops_smplfit.FIT_SMOOTH_ROT if mp.get('fit_smooth') is None else float(mp['fit_smooth'])
                 trans = ops_smplfit.FIT_SMOOTH_TRANS if mp.get('fit_smooth_trans') is None else float(mp['fit_smooth_trans'])
                 self.fit_smooth = (rot, trans)
+        elif (mp.get('fit_data') or 'joints') != 'joints':
+            raise ValueError('fit_data reproj is a mode of --fit-smpl: it needs fit_smpl (model_params.fit_smpl)')
         elif (mp.get('fit_shape') or 'frame') != 'frame':
             raise ValueError('fit_shape track is a mode of --fit-smpl: it needs fit_smpl (model_params.fit_smpl)')
         elif mp.get('fit_smooth') is not None or mp.get('fit_smooth_trans') is not None:
@@ -573,11 +609,12 @@ class Eval:
         save_npz(self.resolve_track, cols)
         return lines
 
-    def fit_batch(self, joints, bad, cov, paths=None):
+    def fit_batch(self, joints, bad, cov, paths=None, views=None):
         """--fit-smpl on the final world joints [B,18,3] of a batch.  A joint's weight is 0 where it is not finite or `bad`
         [B,18] marks it (a triangulation that passed it through), else 1, or with `cov` [B,18,6] (xx xy xz yy yz zz, mm^2)
         1 / trace(cov) normalised to mean 1 over the usable joints of the sample.  -> the file's rows, on the device.
-        With fit_shape track the batch's targets, weights and `paths` (the first camera's image paths, or None) are kept too."""
+        With fit_shape track the batch's targets, weights and `paths` (the first camera's image paths, or None) are kept too.
+        With fit_data reproj that fit is the warm start of fit_batch_views on `views` (see there)."""
         from xas_amd import ops_smplfit
         ok = torch.isfinite(joints).all(dim=-1)
         if bad is not None:
@@ -596,8 +633,33 @@ class Eval:
             self.fit_track_rows.append({'targets': joints, 'weights': w, 'ok': ok, 'paths': None if paths is None else [str(p) for p in paths]})
             if self.fit_smooth:                        # the per-frame fits' joints: the `before` column of joint_accel_mm
                 self.fit_track_rows[-1]['joints'] = r['joints']
-        return {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
+        rows = {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
                 'fit_cost': r['cost'].float(), 'fit_status': r['status'], 'fit_joint_rms_mm': rms.float()}
+        if self.fit_data == 'reproj':
+            rows = self.fit_batch_views(rows, r, joints, ok, views)
+        return rows
+
+    def fit_batch_views(self, rows, warm, joints, ok, views):
+        """--fit-data reproj: fit_smpl_views on the batch's detections `views` = (points [B,V,K,3], P [B,V,3,4], inlier bytes
+        or None, anchor, info or None), warm-started from the joint fit `warm`.  -> the file's rows: the pixel fit's, the warm
+        start as *_joints, and reproj_rms_px [B,2] at the warm start and at the result over the observations used."""
+        from xas_amd import ops_smplfit
+        points, pmat, used, anchor, info = views
+        r = ops_smplfit.fit_smpl_views(points, pmat, self.smpl_layer, self.h36m_regressor, warm, views=used, anchor=anchor, info=info,
+                                       weighted=self.tri_weight == 'spread', huber=self.tri_huber, iters=self.fit_iters,
+                                       pose_prior=self.fit_views_priors[0], shape_prior=self.fit_views_priors[1])
+        bits = ((r['used'].unsqueeze(1).int() >> torch.arange(points.shape[1], device=points.device, dtype=torch.int32).view(1, -1, 1)) & 1).bool()
+
+        def rms_px(Y):                                 # [B,18,3] float64 -> [B] over the (view, joint) pairs used
+            h = torch.einsum('bvij,bkj->bvki', pmat.double()[..., :3], Y) + pmat.double()[..., 3].unsqueeze(2)
+            d2 = ((h[..., :2] / h[..., 2:] - points[..., :2].double()) ** 2).sum(-1)
+            return (torch.where(bits, d2, torch.zeros_like(d2)).sum(dim=(1, 2)) / bits.double().sum(dim=(1, 2)).clamp(min=1.0)).sqrt()
+        d2 = ((r['joints'] - torch.where(ok.unsqueeze(-1), joints.double(), r['joints'])) ** 2).sum(dim=-1)
+        rms = (d2.sum(dim=1) / ok.double().sum(dim=1).clamp(min=1.0)).sqrt()
+        return {'fit_pose': r['pose'].float(), 'fit_betas': r['betas'].float(), 'fit_trans': r['trans'].float(),
+                'fit_cost': r['cost'].float(), 'fit_status': r['status'], 'fit_joint_rms_mm': rms.float(),
+                'fit_pose_joints': rows['fit_pose'], 'fit_betas_joints': rows['fit_betas'], 'fit_trans_joints': rows['fit_trans'],
+                'fit_reproj_rms_px': torch.stack([rms_px(warm['joints']), rms_px(r['joints'])], dim=1).float()}
 
     def keep_fit_rows(self, host):
         """--fit-smpl: the fit_* entries of a batch's host arrays as one row of the file (none without the flag: no row)."""
@@ -659,6 +721,8 @@ class Eval:
         cols = {k: (np.concatenate([r[k] for r in self.fit_rows]) if self.fit_rows else np.zeros(sh, np.uint8 if k == 'status' else np.float32))
                 for k, sh in shapes.items()}
         words = self.fit_tracks(cols) if self.fit_shape == 'track' and self.fit_rows else ''
+        if self.fit_data == 'reproj':
+            return self.write_fit_views(cols)
         save_npz(self.fit_smpl, cols)
         n = max(len(cols['status']), 1)
         fitted = cols['status'] != ops_smplfit.STATUS_PASSED
@@ -666,6 +730,23 @@ class Eval:
         share = ' , '.join('{} {}'.format(name, float((cols['status'] == c).sum()) / n) for c, name in enumerate(ops_smplfit.STATUS_NAMES))
         return 'FIT smpl ({} trials, pose prior {}, shape prior {}): joint RMS {} mm; {}'.format(
             self.fit_iters, self.fit_pose_prior, self.fit_shape_prior, rms, share) + words
+
+    def write_fit_views(self, cols):
+        """--fit-data reproj: the file with the pixel fit's columns, `fit_data`, `reproj_rms_px` [N,2] and the warm start
+        (pose_joints, betas_joints, trans_joints).  -> the FIT line with the mode and the reprojection RMS."""
+        from xas_amd import ops_smplfit
+        more = {'pose_joints': (0, 72), 'betas_joints': (0, 10), 'trans_joints': (0, 3), 'reproj_rms_px': (0, 2)}
+        cols.update({k: (np.concatenate([r[k] for r in self.fit_rows]) if self.fit_rows else np.zeros(sh, np.float32)) for k, sh in more.items()})
+        cols['fit_data'] = np.asarray(self.fit_data)
+        save_npz(self.fit_smpl, cols)
+        n = max(len(cols['status']), 1)
+        fitted = cols['status'] != ops_smplfit.STATUS_PASSED
+        mean = lambda v: float(v[fitted].mean()) if fitted.any() else float('nan')
+        share = ' , '.join('{} {}'.format(name, float((cols['status'] == c).sum()) / n) for c, name in enumerate(ops_smplfit.STATUS_NAMES))
+        return ('FIT smpl reproj ({} trials, pose prior {}, shape prior {}; joint fit: {}, {}): reprojection RMS {} -> {} px, '
+                'joint RMS {} mm; {}').format(self.fit_iters, self.fit_views_priors[0], self.fit_views_priors[1], self.fit_pose_prior,
+                                              self.fit_shape_prior, mean(cols['reproj_rms_px'][:, 0]), mean(cols['reproj_rms_px'][:, 1]),
+                                              mean(cols['joint_rms_mm']), share)
 
     def detect(self, img):
         """Joints [B,Hy,K,3] of one camera's images: the detector's forward, or with flip_test its forward_flip (the head on
@@ -832,10 +913,7 @@ class Eval:
                 row['anchor'] = t.point[..., :3].contiguous()
                 if len(cams) > 1:
                     from xas_amd import ops_track
-                    c = t.cov
-                    cov = torch.stack([c[..., 0], c[..., 1], c[..., 2], c[..., 1], c[..., 3], c[..., 4], c[..., 2], c[..., 4], c[..., 5]],
-                                      dim=-1).reshape(c.shape[:-1] + (3, 3))
-                    row['info'] = ops_track.covariance_information(cov)
+                    row['info'] = ops_track.covariance_information(full_covariance(t.cov))
                     row['anchor'] = torch.where(t.bad.unsqueeze(-1), torch.full_like(row['anchor'], float('nan')), row['anchor'])
                     row['points'] = torch.cat([inputs[0][..., :2], torch.zeros_like(inputs[0][..., 2:])], dim=-1)
                     row['views'] = torch.zeros(t.bad.shape, dtype=torch.uint8, device=t.bad.device)
@@ -874,15 +952,34 @@ class Eval:
                       'view': preds['view_' + m][..., :3].contiguous(), 'paths': None if paths is None else [str(p) for p in paths]}
         self.rt_rows.append(row)
 
-    def fit(self, t, preds, cams, x):
+    def fit(self, t, s, preds, cams, x):
         """--fit-smpl, after everything else, on the final world joints: the triangulated ones with their pass-through marks and
         covariance, or with one camera that view's selected hypothesis.  -> out: the fit_* rows of fit_batch, {} without the option."""
         if not self.fit_smpl:
             return {}
         paths = x.get(cams[0] + '_img_path')       # read by fit_shape track alone
+        views = self.fit_views(t, s, preds, cams, x) if self.fit_data == 'reproj' else None
         if len(cams) > 1:
-            return self.fit_batch(preds['tri'][..., :3].contiguous(), t.bad, t.cov, paths)
-        return self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None, paths)
+            return self.fit_batch(preds['tri'][..., :3].contiguous(), t.bad, t.cov, paths, views)
+        return self.fit_batch(preds['view_' + cams[0]][..., :3].contiguous(), None, None, paths, views)
+
+    def fit_views(self, t, s, preds, cams, x):
+        """--fit-data reproj: what fit_smpl_views reads of a batch: the triangulation inputs (formed here where nothing was
+        triangulated), the robust inliers, and the anchors.  One camera: the selected world point with information along its
+        ray.  More: none, unless --tri-volume ran: then the fused point with the inverse of its covariance, NaN where the volume
+        passed the joint through."""
+        from xas_amd import ops_track
+        points, pmat = t.inputs if t.inputs is not None else triangulation_inputs(s.sel, x, self.cam_id_list, s.weights)
+        used = t.used if self.tri == 'robust' else None
+        anchor, info = None, None
+        if len(cams) == 1:
+            anchor = preds['view_' + cams[0]][..., :3].contiguous()
+            info = ops_track.ray_information(pmat[:, 0], anchor, self.fit_depth)
+        elif self.tri_volume:
+            info = ops_track.covariance_information(full_covariance(t.cov))
+            anchor = t.point[..., :3].contiguous()
+            anchor = torch.where(t.bad.unsqueeze(-1), torch.full_like(anchor, float('nan')), anchor)
+        return points, pmat, used, anchor, info
 
     @torch.no_grad()
     def eval_batch(self, x, mode='best', kps_by_cam=None):
@@ -900,7 +997,7 @@ class Eval:
         preds, errors = self.measure(s, t, x, gt, cams)
         out.update(errors)
         self.keep_track_rows(s, x, gt, preds, cams, mode)
-        out.update(self.fit(t, preds, cams, x))
+        out.update(self.fit(t, s, preds, cams, x))
         return out
 
     def eval(self, tb_log, record_table, count_table, record_3d_table, count_3d_table, record_3d_tri_table,
@@ -1142,6 +1239,26 @@ def mirror_fit_shape_options(config, opt):
     mirror_options(config, opt, given=('fit_shape', 'fit_gap'))
 
 
+CLI_FIT_DATA = (  # --fit-data, parsed after CLI_FIT_SMOOTH (a table per option, as above)
+    ('--fit-data', dict(default=None, choices=('joints', 'reproj'), dest='fit_data',
+                        help='--fit-smpl: joints = fit the final world joints in mm (the default); reproj = then, from that fit, fit '
+                             'the detections of every camera in pixels, with 3-D anchors where there is one (one camera: the '
+                             'selected point along its ray; --tri-volume: the fused point with its covariance)')),
+)
+
+
+def mirror_fit_data_options(config, opt):
+    """--fit-data as a model_params key (only if given)."""
+    if opt.fit_data == 'reproj':
+        if not opt.fit_smpl:
+            raise ValueError('--fit-data reproj is a mode of --fit-smpl: it needs --fit-smpl')
+        if opt.fit_shape == 'track':
+            raise ValueError('--fit-data reproj does not go with --fit-shape track: the track fits have no pixel term yet')
+        if opt.flip:
+            raise ValueError('--fit-data reproj does not go with --flip')
+    mirror_options(config, opt, given=('fit_data',))
+
+
 CLI_FIT_SMOOTH = (  # --fit-smooth and its translation weight, parsed after CLI_FIT_SHAPE (a table per option, as above)
     ('--fit-smooth', dict(default=None, nargs='?', const=True, type=float, metavar='W_ROT', dest='fit_smooth',
                           help='--fit-shape track: an acceleration prior on pose and translation over the frames of a track; W_ROT '
@@ -1275,7 +1392,7 @@ def mirror_smooth_bones_options(config, opt):
 
 def main():
     parser = ArgumentParser()
-    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES + CLI_FIT_SHAPE + CLI_FIT_SMOOTH:
+    for flag, kw in CLI + CLI_VOLUME + CLI_FIT + CLI_CALIB + CLI_SMOOTH + CLI_RESOLVE_TRACK + CLI_SMOOTH_ANCHOR + CLI_SMOOTH_BONES + CLI_FIT_SHAPE + CLI_FIT_SMOOTH + CLI_FIT_DATA:
         parser.add_argument(flag, **kw)
     opt = parser.parse_args()
     with open(opt.config) as f:
@@ -1290,6 +1407,7 @@ def main():
     mirror_smooth_bones_options(config, opt)
     mirror_fit_shape_options(config, opt)
     mirror_fit_smooth_options(config, opt)
+    mirror_fit_data_options(config, opt)
     if opt.batch_size:
         config['train_params']['batch_size'] = opt.batch_size
     if opt.checkpoint is None and not opt.synthetic:

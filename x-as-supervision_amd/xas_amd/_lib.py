@@ -155,6 +155,9 @@ SIGNATURES = {
     'xas_smpl_fit_workspace_bytes': ('ii', 'z'),
     'xas_smpl_fit_linearise': ('p' * 14 + 'ff' + 'iii' + 'ppp' + 'p', 'i'),
     'xas_smpl_fit': ('p' * 14 + 'ff' + 'iiii' + 'p' * 8 + 'p', 'i'),
+    'xas_smpl_fit_views_workspace_bytes': ('ii', 'z'),
+    'xas_smpl_fit_views_linearise': ('p' * 17 + 'i' + 'dd' + 'ff' + 'iiii' + 'ppppp' + 'pp', 'i'),
+    'xas_smpl_fit_views': ('p' * 17 + 'i' + 'dd' + 'ff' + 'iiiii' + 'p' * 8 + 'pp', 'i'),
     'xas_smpl_fit_tracks_workspace_bytes': ('iii', 'z'),
     'xas_smpl_fit_tracks_linearise': ('p' * 16 + 'ff' + 'iiii' + 'd' + 'ppppp' + 'pp', 'i'),
     'xas_smpl_fit_tracks': ('p' * 16 + 'ff' + 'iiiii' + 'p' * 9 + 'pp', 'i'),

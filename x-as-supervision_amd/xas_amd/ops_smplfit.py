@@ -251,3 +251,91 @@ def fit_smpl(targets, weights, smpl_layer, h36m_regressor, init=None, iters=30, 
          ptr(out['betas']), ptr(out['trans']), ptr(out['joints']), ptr(out['cost']), ptr(out['iters']), ptr(out['status']),
          ptr(ws))
     return out
+
+
+# ---- the data term in pixels (csrc/smplfit_views.hip, xas_smpl_fit_views) ------------------------------------------------------
+# Weights of the priors against px^2: the mm^2 priors above times 0.1, since roughly 0.3 px per mm (README) gives 0.09 px^2
+# per mm^2.  UNTUNED GUESSES, like them.
+VIEWS_POSE_PRIOR = 10.0
+VIEWS_SHAPE_PRIOR = 2.5
+USED_ANCHOR = 0x80                                     # the anchor's bit of `used`; the low bits are the joint's views
+
+
+def views_workspace_bytes(B, V):
+    return query('xas_smpl_fit_views_workspace_bytes', int(B), int(V))
+
+
+def _prepare_views(points, P, smpl_layer, h36m_regressor, init, views, anchor, info, weighted, huber, anchor_huber, workspace):
+    if anchor_huber is None:                           # the smoothers' default, read where it lives and only when a fit asks for it
+        from xas_amd.ops_track import TRACK_ANCHOR_HUBER as anchor_huber
+    if init is None:
+        raise RuntimeError('smpl fit views: init is required (dict(pose, betas, trans)): there is no start from pixels')
+    if points.dim() != 4 or tuple(points.shape[2:]) != (18, 3) or tuple(P.shape) != tuple(points.shape[:2]) + (3, 4):
+        raise RuntimeError('smpl fit views: points must be [B,C,18,3] and P [B,C,3,4], got %s and %s' % (tuple(points.shape), tuple(P.shape)))
+    if (anchor is None) != (info is None):
+        raise RuntimeError('smpl fit views: anchor and info come together')
+    dev, B, C = points.device, points.shape[0], points.shape[1]
+    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    points, P = f32(points), f32(P)
+    bufs, parents, center = _layer_arrays(smpl_layer, dev)
+    V = bufs[0].shape[0]
+    reg = f32(h36m_regressor)
+    if tuple(reg.shape) != (17, V):
+        raise RuntimeError('smpl fit views: h36m_regressor must be [17,%d], got %s' % (V, tuple(reg.shape)))
+    pose, betas, trans = (f32(init[k]) for k in ('pose', 'betas', 'trans'))
+    if tuple(pose.shape) != (B, 72) or tuple(betas.shape) != (B, 10) or tuple(trans.shape) != (B, 3):
+        raise RuntimeError('smpl fit views: init needs pose [B,72], betas [B,10] and trans [B,3]')
+    if views is not None:
+        views = views.detach().to(device=dev, dtype=torch.uint8).contiguous()
+        if tuple(views.shape) != (B, 18):
+            raise RuntimeError('smpl fit views: views must be [B,18] bytes, got %s' % (tuple(views.shape),))
+    if anchor is not None:
+        anchor, info = f32(anchor), f32(info)
+        if tuple(anchor.shape) != (B, 18, 3) or tuple(info.shape) != (B, 18, 6):
+            raise RuntimeError('smpl fit views: anchor must be [B,18,3] and info [B,18,6], got %s and %s'
+                               % (tuple(anchor.shape), tuple(info.shape)))
+    rverts, rcount = compact_regressor(reg)
+    need = max(views_workspace_bytes(B, V), 16)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev:
+        raise RuntimeError('smpl fit views: the workspace must be %d bytes (uint8) on %s' % (need, dev))
+    head = (ptr(pose), ptr(betas), ptr(trans), *(ptr(t) for t in bufs), ptr(parents), ptr(reg), ptr(rverts), ptr(rcount),
+            ptr(points), ptr(P), ptr(views), ptr(anchor), ptr(info), 1 if weighted else 0,      # 1 = XAS_REFINE_WEIGHTED
+            float(huber), float(anchor_huber))
+    keep = (pose, betas, trans, bufs, parents, reg, rverts, rcount, points, P, views, anchor, info)
+    return head, keep, workspace, B, V, C, center, dev
+
+
+def linearise_smpl_views(points, P, smpl_layer, h36m_regressor, init, views=None, anchor=None, info=None, weighted=False,
+                         huber=0.0, anchor_huber=None, pose_prior=VIEWS_POSE_PRIOR, shape_prior=VIEWS_SHAPE_PRIOR, workspace=None):
+    """The Gauss-Newton system of fit_smpl_views at `init` (xas_smpl_fit_views_linearise) -> dict: H [B,85,85] (symmetric,
+    undamped, priors in), g [B,85], cost [B], joint_blocks [B,18,9] = A_k (xx xy xz yy yz zz) and b_k, float64; used [B,18] uint8."""
+    head, keep, ws, B, V, C, center, dev = _prepare_views(points, P, smpl_layer, h36m_regressor, init, views, anchor, info, weighted,
+                                                          huber, anchor_huber, workspace)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'H': f64(B, 85, 85), 'g': f64(B, 85), 'cost': f64(B), 'joint_blocks': f64(B, 18, 9),
+           'used': torch.empty(B, 18, device=dev, dtype=torch.uint8)}
+    call('xas_smpl_fit_views_linearise', *head, float(pose_prior), float(shape_prior), B, V, C,
+         center, ptr(out['H']), ptr(out['g']), ptr(out['cost']), ptr(out['joint_blocks']), ptr(out['used']), ptr(ws))
+    return out
+
+
+def fit_smpl_views(points, P, smpl_layer, h36m_regressor, init, views=None, anchor=None, info=None, weighted=False, huber=0.0,
+                   anchor_huber=None, iters=30, pose_prior=VIEWS_POSE_PRIOR, shape_prior=VIEWS_SHAPE_PRIOR, workspace=None):
+    """fit_smpl with the data term in pixels (xas_smpl_fit_views; the semantics are those of include/xas_hip.h): points
+    [B,C,18,3] = (u, v, weight) and P [B,C,3,4] as ops_eval's refinement takes them, views [B,18] bytes or None, anchor
+    [B,18,3] mm with info [B,18,6] (ops_track.ray_information / covariance_information) or both None; weighted: a view's
+    residual is scaled by its weight; huber, anchor_huber (None = ops_track.TRACK_ANCHOR_HUBER): Huber's deltas, 0 = squared.
+    init: dict(pose, betas, trans), required.  -> fit_smpl's dict (cost in px^2) plus used [B,18] uint8: the views a joint
+    used | USED_ANCHOR."""
+    head, keep, ws, B, V, C, center, dev = _prepare_views(points, P, smpl_layer, h36m_regressor, init, views, anchor, info, weighted,
+                                                          huber, anchor_huber, workspace)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {'pose': f64(B, 72), 'betas': f64(B, 10), 'trans': f64(B, 3), 'joints': f64(B, 18, 3), 'cost': f64(B, 2),
+           'iters': torch.empty(B, device=dev, dtype=torch.int32), 'status': torch.empty(B, device=dev, dtype=torch.uint8),
+           'used': torch.empty(B, 18, device=dev, dtype=torch.uint8)}
+    call('xas_smpl_fit_views', *head, float(pose_prior), float(shape_prior), B, V, C, center,
+         int(iters), ptr(out['pose']), ptr(out['betas']), ptr(out['trans']), ptr(out['joints']), ptr(out['cost']), ptr(out['iters']),
+         ptr(out['status']), ptr(out['used']), ptr(ws))
+    return out
